@@ -1,7 +1,17 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the MI355X-native TTS hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload bigvgan|f5|indextts_f|indextts]
+    python bench.py --gpus N --steps K --warmup W [--workload bigvgan|f5|indextts_f|indextts] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps, the outputs of the last
+timed step when --dump-outputs is given, the result line (`roofline` null, no `cpu_baseline`, no `secondary_ms`).  `--full`
+adds everything else the bench measures, as separate passes after the timed steps: the event-timed per-kernel pass behind
+`roofline`, the host-array form of the step (`host_io_*`), the secondary workloads, the rocprofv3 --pmc passes
+(`roofline.traffic`) and the CPU baseline; `--no-secondary` / `--no-pmc` / `--no-cpu-baseline` leave parts of it out.
+
+--dump-outputs DIR: what the timed path returned in its last timed step, as DIR/<name>.npy in float32 (f5: `waveform`, the
+int16 samples (U, 1, T); with --gpus N > 1 every rank writes `waveform_rank<r>`).  The inputs are seeded: the same arguments
+give the same inputs on every run, so two builds can be compared output for output.
 
 Default workload = BASELINE.json's metric: F5-TTS NFE=32 end to end (preprocess -> 31 DiT evaluations with CFG ->
 Vocos + ISTFT -> int16), synthetic seeded weights, 6 s reference audio + ~15-word texts (N = 1126 frames), inputs
@@ -33,7 +43,8 @@ import time
 import numpy as np
 
 from bench_common import (ROOT, USER_OPTIONS, MFMA_F16_PEAK_TF, MFMA_F32_PEAK_TF, f5_flops_per_eval, merge_instantiations,
-                          dominant_kernel_roofline, bcast_device_blob, per_rank_times, max_over_ranks, f5_workload_name, emit, claim_stdout)
+                          dominant_kernel_roofline, bcast_device_blob, per_rank_times, max_over_ranks, f5_workload_name, emit, claim_stdout,
+                          synth_state_threaded, dump_outputs)
 
 
 def cpu_baseline_f5_run(cfg, st, audio, ids, N, noise, threads: int, evals):
@@ -113,12 +124,13 @@ class F5Bench:
         self.raw = None
         nparam = sum(int(np.prod(sh)) for _, sh, _ in W.f5_packed_spec(self.cfg))
         if rank == 0:
-            self.raw = W.synth_state(W.f5_spec(self.cfg), 9527)
+            self.raw = synth_state_threaded(W, W.f5_spec(self.cfg), 9527)
             self.blob_t = torch.from_numpy(W.pack_f5(self.cfg, self.raw)).to(dev)
         else:
             self.blob_t = torch.empty(nparam, dtype=torch.float32, device=dev)
         self.bcast_ms = 0.0
         self.dump_dir = None
+        self.last_output = None
         # one process per GPU: fail loudly if two ranks resolved to the same physical device (the plumbing test on a one-GPU box says so)
         from mi355tts.shard import assert_one_device_per_rank
         self.rank_devices = [f"{h}:{b}" for h, b in assert_one_device_per_rank(local, allow_shared=os.environ.get("MI355TTS_BENCH_ONE_GPU") == "1")]
@@ -134,7 +146,9 @@ class F5Bench:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, dtype: str, U: int, steps: int, warmup: int, f32_arithmetic=None):
+    def measure(self, dtype: str, U: int, steps: int, warmup: int, f32_arithmetic=None, detail=True, keep_output=False):
+        """`detail`: the event-timed per-kernel pass (-> roofline) and the host-array form of the step after the timed steps
+        (False in a plain run).  `keep_output`: the waveform of the last timed step, on the host, in self.last_output."""
         import dataclasses
         from mi355tts import _lib
         from mi355tts.f5 import F5Engine
@@ -164,22 +178,25 @@ class F5Bench:
             eng.synthesize_torch(t_audio, t_ids, N, noise=t_noise, out=out)
         self.barrier()
         dt = time.perf_counter() - t0
-        # roofline leg: ONE more pass with HIP events (on the engine's own stream) around every launch of the GEMM and
-        # attention families, attributed per kernel instantiation.  Events force the eager (un-graphed) launch path, so
-        # this pass is separate from the timed region and not part of `value`.
-        _lib.prof_reset()
-        _lib.prof_enable(["conv_gemm", "attn", "norm", "other"])
-        eng.synthesize_torch(t_audio, t_ids, N, noise=t_noise, out=out)
-        torch.cuda.synchronize()
-        _lib.prof_enable(())
-        kernels = _lib.prof_kernels()
+        self.last_output = out.cpu().numpy() if keep_output else None
+        kernels = []
+        if detail:
+            # roofline leg: ONE more pass with HIP events (on the engine's own stream) around every launch of the GEMM and
+            # attention families, attributed per kernel instantiation.  Events force the eager (un-graphed) launch path, so
+            # this pass is separate from the timed region and not part of `value`.
+            _lib.prof_reset()
+            _lib.prof_enable(["conv_gemm", "attn", "norm", "other"])
+            eng.synthesize_torch(t_audio, t_ids, N, noise=t_noise, out=out)
+            torch.cuda.synchronize()
+            _lib.prof_enable(())
+            kernels = _lib.prof_kernels()
         rank_dt = per_rank_times(torch, self.dist, self.world, dt, dev)
         dt = max_over_ranks(torch, self.dist, self.world, dt, dev)
         # the reference's own bracket (F5-TTS-ONNX-Inference.py:246-312: host int16 audio + ids in, int16 waveform on the host):
         # the same steps through the host-pointer form of the C-ABI (H2D of audio / ids / noise, D2H of the waveform inside).
         # Reported next to `value`, never as `value` (bench contract: inputs resident in HBM).
         host_ms = None
-        if self.world == 1:
+        if self.world == 1 and detail:
             eng.synthesize(audio, ids, N, noise=noise)
             th = time.perf_counter()
             for _ in range(steps):
@@ -220,7 +237,7 @@ class F5Bench:
             roof["instantiations"] = merged["instantiations"]
             roof["pmc_family"] = merged["pmc_family"]
         alg_flops = f5_flops_per_eval(cfg, N) * (cfg.nfe_step - 1) * U
-        ev_ms = sum(k["ms"] for k in kernels)
+        ev_ms = sum(k["ms"] for k in kernels) if detail else None
         res = {"value": self.world * audio_s * steps / dt, "ms_per_step": dt / steps * 1e3, "dtype": dtype,
                "rtf": dt / steps / audio_s, "utterances_per_gpu": U, "frames": N, "audio_seconds_per_step_per_gpu": audio_s,
                "end_to_end_TFLOP_per_step": alg_flops / 1e12, "end_to_end_TFLOP_per_s": alg_flops / (dt / steps) / 1e12,
@@ -243,11 +260,15 @@ def run_f5(args, world, rank, local, dev, dist, torch):
         fb.cfg_over["adaln_fold"] = False
     if args.adaln_fold:
         fb.cfg_over["adaln_fold"] = True
-    res, (audio, ids, N, noise) = fb.measure(args.dtype, args.batch, args.steps, args.warmup)
+    res, (audio, ids, N, noise) = fb.measure(args.dtype, args.batch, args.steps, args.warmup, detail=args.full,
+                                             keep_output=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"waveform" if world == 1 else f"waveform_rank{rank}": fb.last_output})
+        fb.last_output = None
     if fb.small:
         args.no_secondary = args.no_cpu_baseline = True
     secondary = {}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         import bench_detail
         secondary = bench_detail.f5_secondaries(torch, dist, fb, args, N, local, dev)
     del fb.blob_t
@@ -281,12 +302,12 @@ def run_f5(args, world, rank, local, dev, dist, torch):
     }
     if secondary:
         line["secondary"] = secondary
-    if world == 1 and not args.no_pmc and not fb.small and line["roofline"]:
+    if world == 1 and args.full and not args.no_pmc and not fb.small and line["roofline"]:
         import bench_detail
         tb, detail = bench_detail.pmc_traffic(line["roofline"]["kernel"], args.dtype, args.batch, family=line["roofline"].get("pmc_family"))
         line["roofline"]["traffic"] = tb
         line["roofline"]["traffic_detail"] = detail
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_f5(fb.cfg, fb.raw, audio[0], ids[0], N, noise[0], full=args.cpu_baseline_full, threads=args.cpu_threads)
     emit(line)
 
@@ -339,6 +360,11 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=128)
     ap.add_argument("--cpu-threads", type=int, default=None, help="f5: threads of the cpu_baseline leg (default 8 = the reference driver's MAX_THREADS)")
     ap.add_argument("--dump-dir", default=None, help="f5: every rank saves its int16 waveforms there (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel roofline pass, the host-array form, the "
+                         "secondary workloads, the rocprofv3 --pmc passes, the CPU baseline (off: set-up, warm-up, timed steps, line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy, float32 (at most 64 MiB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -15,6 +15,37 @@ MFMA_F16_PEAK_TF = 2500.0        # dense bf16/f16
 MFMA_F32_PEAK_TF = 157.3
 
 
+def synth_state_threaded(W, spec, seed: int = 9527):
+    """W.synth_state(spec, seed), the same arrays bit for bit (each tensor is still made by W.synth_tensor), with the tensors
+    drawn on a thread pool: numpy releases the GIL inside its array operations, and one thread takes ~25 s for the 337 M
+    DiT parameters, most of a plain run's set-up."""
+    from collections import OrderedDict
+    from concurrent.futures import ThreadPoolExecutor
+    threads = max(1, min(16, len(os.sched_getaffinity(0))))
+    with ThreadPoolExecutor(threads) as ex:
+        tensors = list(ex.map(lambda s: W.synth_tensor(seed, s[0], s[1], s[2]), spec))
+    return OrderedDict((name, t) for (name, _, _), t in zip(spec, tensors))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32 (int16 waveforms and int32 tokens are exact in it).  If the
+    set is over 64 MiB in all, each array is cut to the same fraction of its elements at fixed seeded positions (flat, sorted),
+    so two builds given the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    total = sum(int(np.asarray(a).size) * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, int(a.size * DUMP_LIMIT_BYTES // total))
+            idx = np.sort(np.random.default_rng(9527).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def f5_flops_per_eval(cfg, N: int) -> float:
     """Algorithmic FLOPs of one DiT CFG evaluation: tokens = 2N,
     MAC/token = depth*(4d^2 + 2*d*ff + 2*N*d) + (cat*d + 2*d*(d/g)*k + d*mel)."""

@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from bench_common import (ROOT, USER_OPTIONS, HBM_PEAK_GBS, MFMA_F16_PEAK_TF, MFMA_F32_PEAK_TF, dominant_kernel_roofline,
-                          bcast_device_blob, max_over_ranks, f5_workload_name, emit)
+                          bcast_device_blob, max_over_ranks, f5_workload_name, emit, synth_state_threaded, dump_outputs)
 
 
 def bigvgan_algorithmic_bytes(cfg, B: int, F: int, esz: int) -> float:
@@ -377,24 +377,29 @@ def run_indextts(args, world, rank, local, dev, dist, torch):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    # GPT leg alone (same state), then the roofline leg: one eager pass with HIP events around every GEMV / GEMM launch
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    gpt_leg()
-    torch.cuda.synchronize()
-    gpt_s = time.perf_counter() - t1
-    _lib.prof_reset()
-    _lib.prof_enable(["conv_gemm", "attn"])
-    gpt_leg()
-    torch.cuda.synchronize()
-    _lib.prof_enable(())
-    pg, pa = _lib.prof_get("conv_gemm"), _lib.prof_get("attn")
+    if args.dump_outputs:          # what the step returns: mel codes and latents of every sentence, the waveform of the last one
+        dump_outputs(args.dump_outputs, {(k if world == 1 else f"{k}_rank{rank}"): v.cpu().numpy() for k, v in
+                                         (("mel_codes", toks if NB == 1 else toks_b), ("latent", hid if NB == 1 else hid_b), ("waveform", wav))})
+    gpt_s = pg = pa = None
+    if args.full:
+        # GPT leg alone (same state), then the roofline leg: one eager pass with HIP events around every GEMV / GEMM launch
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        gpt_leg()
+        torch.cuda.synchronize()
+        gpt_s = time.perf_counter() - t1
+        _lib.prof_reset()
+        _lib.prof_enable(["conv_gemm", "attn"])
+        gpt_leg()
+        torch.cuda.synchronize()
+        _lib.prof_enable(())
+        pg, pa = _lib.prof_get("conv_gemm"), _lib.prof_get("attn")
     dt = max_over_ranks(torch, dist, world, dt, dev)
     if rank != 0:
         gpt.close(); voc.close(); cond_eng.close()
         return
     esz = 4 if args.dtype == "f32" else 2
-    achieved = pg["bytes"] / (pg["ms"] * 1e-3) / 1e9 if pg["ms"] > 0 else 0.0
+    achieved = (pg["bytes"] / (pg["ms"] * 1e-3) / 1e9 if pg["ms"] > 0 else 0.0) if pg else None
     wbytes = (gcfg.layers * 12 * gcfg.hidden * gcfg.hidden + gcfg.mel_codes * gcfg.hidden) * esz
     line = {
         "metric": "audio_seconds_per_second", "value": world * audio_s * args.steps / dt, "unit": "audio-s/s",
@@ -405,18 +410,19 @@ def run_indextts(args, world, rank, local, dev, dist, torch):
                                f"(Conformer / Perceiver / ECAPA) every step (BASELINE configs[4], all six graphs)",
                    "tokens": n_tok, "prompt_rows": P, "audio_seconds_per_step_per_gpu": audio_s,
                    "sentences_per_gpu": NB,
-                   "rtf": dt / args.steps / audio_s, "gpt_leg_ms": gpt_s * 1e3, "decode_tokens_per_s": NB * n_tok / gpt_s,
+                   "rtf": dt / args.steps / audio_s, "gpt_leg_ms": gpt_s * 1e3 if gpt_s else None,
+                   "decode_tokens_per_s": NB * n_tok / gpt_s if gpt_s else None,
                    "weight_bytes_streamed_per_token_GB": wbytes / 1e9,
-                   "decode_weight_stream_GBps": wbytes * n_tok / gpt_s / 1e9,
+                   "decode_weight_stream_GBps": wbytes * n_tok / gpt_s / 1e9 if gpt_s else None,
                    "weights": "synthetic seeded (510 M GPT + vocoder)", "weight_bcast_ms": bcast_ms},
         "roofline": {"bound": "hbm", "kernel": "gemv_kernel (decode-step linear layers: weights streamed once per token)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": None, "launches_per_step": pg["launches"], "avg_launch_ms": pg["ms"] / max(pg["launches"], 1),
                      "family_ms_per_step": pg["ms"], "attn_ms_per_step": pa["ms"],
                      "note": "event-timed in a separate eager pass (the timed region replays a hipGraph per token); the "
-                             "family also holds the prompt pass's 4 x 24 MFMA GEMM launches"},
+                             "family also holds the prompt pass's 4 x 24 MFMA GEMM launches"} if pg else None,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import gpt_np as O
         n_cpu = 6
         folds = [O.fold_layer(gcfg, graw, i) for i in range(gcfg.layers)]
@@ -438,9 +444,10 @@ def run_indextts(args, world, rank, local, dev, dist, torch):
     gpt.close(); voc.close(); cond_eng.close()
 
 
-def measure_bigvgan(torch, dist, world, rank, local, dev, dtype, B, F, steps, warmup, ixf):
+def measure_bigvgan(torch, dist, world, rank, local, dev, dtype, B, F, steps, warmup, ixf, detail=True, keep_output=False):
     """BigVGAN-v2 (BASELINE configs[0]/[1]) or IndexTTS graph F (`ixf`): one step = one vocoder pass over the batch, mel
-    resident in HBM.  Per-kernel HIP events are taken in a separate pass after the timed region."""
+    resident in HBM.  Per-kernel HIP events are taken in a separate pass after the timed region (`detail`; a plain run skips
+    it).  Returns (res, (cfg, state, the int16 waveform of the last timed step on the host if `keep_output`, else None))."""
     from mi355tts.config import BigVGANConfig
     from mi355tts import weights as W
     from mi355tts import _lib
@@ -450,7 +457,7 @@ def measure_bigvgan(torch, dist, world, rank, local, dev, dtype, B, F, steps, wa
     nparam = sum(int(np.prod(s)) for _, s, _ in spec)
     state = None
     if rank == 0:
-        state = W.synth_state(spec, 9527)
+        state = synth_state_threaded(W, spec, 9527)
         blob_t = torch.from_numpy(W.pack_bigvgan(cfg, state)).to(dev)
     else:
         blob_t = torch.empty(nparam, dtype=torch.float32, device=dev)
@@ -487,21 +494,24 @@ def measure_bigvgan(torch, dist, world, rank, local, dev, dtype, B, F, steps, wa
         step()
     barrier()
     dt = time.perf_counter() - t0
+    last = out.cpu().numpy() if keep_output else None
     dt = max_over_ranks(torch, dist, world, dt, dev)
-    # per-kernel durations: a separate pass after the timed region, with every launch on the engine's one stream — in the
-    # timed region the AMP blocks of a stage run on side streams (bigvgan_streams), where a launch's event-to-event time
-    # includes whatever ran beside it
-    _lib.set_option("bigvgan_streams", 1)
-    step()
-    _lib.prof_reset()
-    _lib.prof_enable(["conv_gemm", "aa_act", "conv_post"])
-    psteps = min(steps, 5)
-    for _ in range(psteps):
+    kernels, psteps = [], 0
+    if detail:
+        # per-kernel durations: a separate pass after the timed region, with every launch on the engine's one stream — in the
+        # timed region the AMP blocks of a stage run on side streams (bigvgan_streams), where a launch's event-to-event time
+        # includes whatever ran beside it
+        _lib.set_option("bigvgan_streams", 1)
         step()
-    torch.cuda.synchronize()
-    _lib.prof_enable(())
-    kernels = _lib.prof_kernels()
-    _lib.set_option("bigvgan_streams", USER_OPTIONS.get("bigvgan_streams", 3))       # (what the caller asked for with --option, else the default)
+        _lib.prof_reset()
+        _lib.prof_enable(["conv_gemm", "aa_act", "conv_post"])
+        psteps = min(steps, 5)
+        for _ in range(psteps):
+            step()
+        torch.cuda.synchronize()
+        _lib.prof_enable(())
+        kernels = _lib.prof_kernels()
+        _lib.set_option("bigvgan_streams", USER_OPTIONS.get("bigvgan_streams", 3))       # (what the caller asked for with --option, else the default)
     voc.close()
     esz = 4 if dtype == "f32" else 2
     alg = bigvgan_algorithmic_bytes(cfg, B, F, esz)
@@ -524,7 +534,7 @@ def measure_bigvgan(torch, dist, world, rank, local, dev, dtype, B, F, steps, wa
            "weight_bcast_ms": bcast_ms, "whole_forward_algorithmic_GB": alg / 1e9,
            "whole_forward_algorithmic_GBps": alg / (dt / steps) / 1e9,
            "whole_forward_frac_of_hbm_peak": alg / (dt / steps) / 1e9 / HBM_PEAK_GBS, "roofline": roof}
-    return res, (cfg, state)
+    return res, (cfg, state, last)
 
 
 def bigvgan_pmc(res, dtype: str, B: int):
@@ -588,7 +598,10 @@ def run_other(args, world, rank, local, dev, dist, torch):
     args.warmup = 3 if args.warmup is None else args.warmup
     args.dtype = "f16" if args.dtype is None else args.dtype
     B, F = (1, 126) if ixf else (8 if args.batch is None else args.batch, args.frames)
-    res, (cfg, state) = measure_bigvgan(torch, dist, world, rank, local, dev, args.dtype, B, F, args.steps, args.warmup, ixf)
+    res, (cfg, state, last) = measure_bigvgan(torch, dist, world, rank, local, dev, args.dtype, B, F, args.steps, args.warmup, ixf,
+                                              detail=args.full, keep_output=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"waveform" if world == 1 else f"waveform_rank{rank}": last})
     if rank != 0:
         return
     line = {"metric": "audio_seconds_per_second", "value": res["value"], "unit": "audio-s/s", "n_gpus": world,
@@ -597,12 +610,12 @@ def run_other(args, world, rank, local, dev, dist, torch):
             "config": {k: v for k, v in res.items() if k not in ("value", "ms_per_step", "dtype", "roofline")},
             "roofline": res["roofline"]}
     line["config"]["weights"] = "synthetic seeded (112.4 M params)"
-    if world == 1 and not args.no_pmc and not ixf:
+    if world == 1 and args.full and not args.no_pmc and not ixf:
         bigvgan_pmc(res, args.dtype, B)
         line["roofline"] = res["roofline"]
         for k in ("whole_forward_fabric_GB", "whole_forward_fabric_over_algorithmic"):
             if k in res:
                 line["config"][k] = res[k]
-    if world == 1 and not args.no_cpu_baseline and not ixf:
+    if world == 1 and args.full and not args.no_cpu_baseline and not ixf:
         line["cpu_baseline"] = cpu_baseline_bigvgan(cfg, state, args.cpu_frames)
     emit(line)

@@ -78,3 +78,39 @@ def test_non_finite_numbers_never_reach_the_line():
     c = C.compact_line(full)
     assert "rtf" not in c["config"] and "weight_bcast_ms" not in c["config"]
     json.dumps(c, allow_nan=False)
+
+
+def test_threaded_weight_synthesis_equals_synth_state():
+    """bench.py draws its seeded weights on a thread pool: the arrays must be W.synth_state's, bit for bit, in the same order."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "text-to-speech-tts-onnx_amd"))
+    from mi355tts.config import BigVGANConfig, F5Config
+    from mi355tts import weights as W
+    for spec in (W.f5_spec(F5Config.small()), W.bigvgan_spec(BigVGANConfig.small())):
+        a, b = C.synth_state_threaded(W, spec, 9527), W.synth_state(spec, 9527)
+        assert list(a) == list(b)
+        for k in a:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+
+
+def test_dump_outputs_writes_float32_and_caps_the_total(tmp_path, monkeypatch):
+    import numpy as np
+    wav = np.arange(-3000, 3000, dtype=np.int16).reshape(2, 1, 3000)
+    C.dump_outputs(str(tmp_path / "a"), {"waveform": wav})
+    got = np.load(tmp_path / "a" / "waveform.npy")
+    assert got.dtype == np.float32 and got.shape == wav.shape and np.array_equal(got, wav)
+    # over the limit: every array cut to the same fraction at fixed seeded positions, the same files on every call
+    monkeypatch.setattr(C, "DUMP_LIMIT_BYTES", 8000)
+    big = {"x": np.arange(4000, dtype=np.float64), "y": np.arange(1000, dtype=np.int32)}
+    C.dump_outputs(str(tmp_path / "b"), big)
+    C.dump_outputs(str(tmp_path / "c"), big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.dtype == y.dtype == np.float32 and (x.size + y.size) * 4 <= 8000 and x.size == 4 * y.size
+    assert np.all(np.diff(x) > 0) and np.array_equal(x, np.load(tmp_path / "c" / "x.npy"))
+
+
+def test_bench_options():
+    """--full (everything beside the headline figure) and --dump-outputs exist; a plain run is the default."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

@@ -35,7 +35,7 @@ def test_bench_two_ranks_on_one_gpu_equals_single_process(tmp_path):
                HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--batch", "3", "--dtype", "f32", "--dump-dir", str(tmp_path)]
+           "--batch", "3", "--dtype", "f32", "--dump-dir", str(tmp_path), "--dump-outputs", str(tmp_path / "outputs")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -46,6 +46,7 @@ def test_bench_two_ranks_on_one_gpu_equals_single_process(tmp_path):
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0 and line["dtype"] == "f32"
     assert "PLUMBING TEST ONLY" in line["config"]["workload"] and line["config"]["utterances_per_gpu"] == 3
     assert line["config"]["weight_bcast_ms"] > 0
+    assert line["roofline"] is None and "secondary_ms" not in line and "cpu_baseline" not in line      # a plain run: no extra passes
     # round 4: the job-level utterance list, the per-rank times behind the maximum, and which device every rank drove
     assert line["config"]["utterances_total"] == 6 and line["config"]["utterance_seeds"] == [9527, 9532]
     assert len(line["config"]["per_rank_ms"]) == 2 and max(line["config"]["per_rank_ms"]) == pytest.approx(line["ms_per_step"], rel=1e-9)
@@ -61,6 +62,8 @@ def test_bench_two_ranks_on_one_gpu_equals_single_process(tmp_path):
         audio, ids, N, noise = W.f5_synthetic_inputs(cfg, 3, rank, L=24000, first=3 * rank)      # the job-level list: rank r owns utterances 3 r .. 3 r + 2
         want = eng.synthesize(audio, ids, N, noise=noise)
         assert got.shape == want.shape and np.array_equal(got, want), rank
+        dumped = np.load(tmp_path / "outputs" / f"waveform_rank{rank}.npy")         # --dump-outputs: the last timed step, float32
+        assert dumped.dtype == np.float32 and np.array_equal(dumped, want.astype(np.float32)), rank
         assert np.sqrt(np.mean(want.astype(np.float64) ** 2)) > 100
     assert not np.array_equal(np.load(tmp_path / "f5_f32_u3_rank0.npy"), np.load(tmp_path / "f5_f32_u3_rank1.npy"))
     eng.close()
@@ -142,11 +145,17 @@ dist.destroy_process_group()
     assert r.returncode == 0 and "RCCL_OK nccl" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     env.pop("MASTER_PORT")
     env["MI355TTS_BENCH_SMALL"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--steps", "1", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--steps", "1", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "outputs")], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert line["n_gpus"] == 1 and line["config"]["collective_backend"] == "nccl" and line["config"]["weight_bcast_ms"] > 0
+    cfg = F5Config.small()
+    audio, ids, N, noise = W.f5_synthetic_inputs(cfg, 1, 0, L=24000)
+    eng = F5Engine(cfg, W.synth_state(W.f5_spec(cfg), 9527), dtype="f32")
+    want = eng.synthesize(audio, ids, N, noise=noise)
+    eng.close()
+    assert np.array_equal(np.load(tmp_path / "outputs" / "waveform.npy"), want.astype(np.float32))
 
 
 def test_two_ranks_on_one_device_are_refused_without_the_plumbing_switch():

@@ -2,7 +2,7 @@
 # same-box A/B of one environment switch: tools/dbg/ab_env.sh VAR=VALUE [bench args]   (base = without it)
 # prints ms_per_step and the per-kernel launch averages (the BENCH_DETAIL line bench.py writes to stderr)
 KV=$1; shift
-B="python bench.py --no-secondary --no-cpu-baseline --no-pmc $*"
+B="python bench.py --full --no-secondary --no-cpu-baseline --no-pmc $*"
 S='
 import json,sys
 ms=None; ks=[]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of one environment switch on the bf16 x 8 utterances line (configs[3] shard): tools/dbg/ab_env_u8.sh VAR=VALUE
 KV=$1; shift
-B="python bench.py --no-secondary --no-cpu-baseline --no-pmc --dtype bf16 --batch 8 --steps 4 --warmup 2 $*"
+B="python bench.py --full --no-secondary --no-cpu-baseline --no-pmc --dtype bf16 --batch 8 --steps 4 --warmup 2 $*"
 S='
 import json,sys
 ms=None; ks=[]

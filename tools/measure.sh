@@ -17,7 +17,7 @@ WHAT=${1:-bench}; shift || true
 O=$ROOT/gpurun_out/$ROUND/$WHAT; mkdir -p $O
 cd $ROOT
 B="python $ROOT/bench.py"
-Q="--no-secondary --no-cpu-baseline --no-pmc"
+Q="--full --no-secondary --no-cpu-baseline --no-pmc"
 R="rocprofv3 --kernel-trace --stats --output-format csv"
 # runb NAME [bench args]: stdout (the ONE compact line) -> $O/NAME.json, stderr -> $O/NAME.err, the full record -> $O/NAME_detail.json
 runb() { local n=$1; shift; rm -f $ROOT/bench_detail.json; timeout 1500 $B "$@" > $O/$n.json 2> $O/$n.err; [ -f $ROOT/bench_detail.json ] && cp $ROOT/bench_detail.json $O/${n}_detail.json; summary $O/$n.json; }
@@ -65,10 +65,10 @@ cpu-full)
     timeout 2400 $B --cpu-baseline-only --cpu-baseline-full > $O/cpu_baseline_full.json 2> $O/err.log; tail -c 300 $O/cpu_baseline_full.json ;;
 final)
     timeout 2700 python -m pytest tests -m gpu -q -x -rA --timeout 900 > $O/tests_gpu_rA.log 2>&1; tail -3 $O/tests_gpu_rA.log
-    runb bench_default --steps 20 --warmup 5
-    runb bench_bigvgan_f16_b8 --workload bigvgan
-    runb bench_indextts --workload indextts --no-cpu-baseline
-    MI355TTS_BENCH_BACKEND=gloo MI355TTS_BENCH_ONE_GPU=1 MI355TTS_BENCH_SMALL=1 runb bench_gpus2_selflaunch_plumbing --gpus 2 --steps 2 --warmup 1
+    runb bench_default --full --steps 20 --warmup 5
+    runb bench_bigvgan_f16_b8 --full --workload bigvgan
+    runb bench_indextts --full --workload indextts --no-cpu-baseline
+    MI355TTS_BENCH_BACKEND=gloo MI355TTS_BENCH_ONE_GPU=1 MI355TTS_BENCH_SMALL=1 runb bench_gpus2_selflaunch_plumbing --full --gpus 2 --steps 2 --warmup 1
     cd /tmp; export TMPDIR=/tmp
     timeout 600 $R -d $O/t_f5_f32_u1 -- $B $Q --steps 3 --warmup 2 2>/dev/null | tail -1 > $O/bench_f5_f32_under_rocprof.json
     timeout 600 $R -d $O/t_f5_bf16_u8 -- $B $Q --dtype bf16 --batch 8 --steps 2 --warmup 2 2>/dev/null | tail -1 > $O/bench_f5_bf16_u8_under_rocprof.json

@@ -490,12 +490,14 @@ def test_full_size_fp32_fused_producers_are_bit_neutral(full):
 
 # 1037 / 1152: the shortest and the longest utterance whose 2 N rows the exact-fit tiling takes in one round (>= 90 % of 16 x 144 rows);
 # 1153: one frame more, 17 row groups = 53 % of two rounds, back on the stream-K kernel
-@pytest.mark.parametrize("N", [701, 1015, 1037, 1152, 1153, 1280])
+# 1268: the reference's own zh.wav prompt length, on stream-K
+@pytest.mark.parametrize("N", [701, 1015, 1037, 1152, 1153, 1268, 1280])
 def test_full_size_fp32_other_lengths_default_forms_against_native(full, N):
     """The full-width DiT at frame counts other than the bench's 1126 — odd ones (K / V^T plane rows, the second batch item's
     rows and the last 128-row panel all start at odd offsets), one that fills whole panels — default arithmetic (fp16-pair
     linear layers, pre-split K / V^T, fp16-pair attention, pair-split position convolution) against the native fp32 MFMA
-    forms of the same engine, one evaluation and two utterances."""
+    forms of the same engine, one evaluation and two utterances; and both utterances against the fp32 oracle (the two engine
+    forms share the input embedding, position convolution, time MLP, AdaLN-final and proj_out, where a bug would cancel)."""
     from mi355tts import _lib
     cfg, raw, audio, ids, _, _ = full
     noise = np.stack([W.synth_normal(77 + u, "noise_n", (N, cfg.mel_dim)) for u in range(2)])
@@ -515,6 +517,14 @@ def test_full_size_fp32_other_lengths_default_forms_against_native(full, N):
     print(f"N = {N}: default forms against native fp32 MFMA, DiT evaluation: rel rms {e:.2e}")
     assert e < 3e-6, e
     assert rms(a[:2] - a1) / rms(a1) < 3e-6                    # one utterance alone: other tile counts, same values
+    st = W.fold_f5(cfg, raw)
+    t_emb = O.time_tables(cfg, st)[2][3]
+    cos, sin = O.rope_tables(N, cfg.dim_head)
+    for u in range(2):
+        ref = O.dit_forward(cfg, st, noise[u], cmt[u], cmtd[u], t_emb, cos, sin)
+        e_o = rms(a[2 * u:2 * u + 2] - ref) / rms(ref)
+        print(f"N = {N}: utterance {u}, default forms against the oracle: rel rms {e_o:.2e}")
+        assert e_o < 3.5e-6, (u, e_o)                           # achieved 1.09e-6 .. 1.13e-6 at every N
 
 
 @pytest.mark.parametrize("N", [1126, 333])

@@ -9,6 +9,8 @@ from mi355tts.config import F5Config
 from mi355tts import weights as W
 from oracle import f5_np as O
 
+import dit_oracle64 as D
+
 
 @pytest.fixture(scope="module")
 def g(golden_dir):
@@ -182,3 +184,64 @@ def test_bigvgan_type_mel_oracle_against_reference_fixture(golden_dir):
         assert got.shape == ref.shape and np.abs(got - ref)[m].max() < tol
     b = O.mel_basis_slaney()
     assert b.shape == (100, 513) and (b >= 0).all() and abs(float(b[50].sum() * (12000.0 / 512)) - 1.0) < 0.02     # slaney norm: unit-area triangles (a mid band spans many bins)
+
+
+# ---------------------------------------------------------------------------------------------
+# The float64 evaluation of the oracle (tests/dit_oracle64.py) that the GPU DiT tests measure against, and the bite of their gates
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mid1037():
+    """test_gpu_dit_tilings' mid-width config (dim 1024, two blocks) and its utterance 0 at N = 1037 (2074 rows: the exact-fit
+    tiling's partial last row group holds 58 live rows)."""
+    cfg = F5Config(depth=2, text_dim=64, text_num_embeds=40, conv_layers=1, vocos_dim=64, vocos_intermediate=128, vocos_layers=1,
+                   nfe_step=4)
+    st = W.fold_f5(cfg, W.synth_state(W.f5_spec(cfg), 7))
+    N = 1037
+    x = W.synth_normal(3, f"n{N}", (N, cfg.mel_dim))
+    c = W.synth_normal(14, f"c{N}", (N, cfg.mel_dim + cfg.text_dim), std=0.7)
+    cd = W.synth_normal(25, f"d{N}", (N, cfg.mel_dim + cfg.text_dim), std=0.7)
+    return cfg, st, D.widen(st), O.time_tables(cfg, st)[2][2], (x, c, cd)
+
+
+@pytest.fixture(scope="module")
+def ref1037(mid1037):
+    cfg, _, st64, t_emb, inp = mid1037
+    with pytest.MonkeyPatch.context() as mp:
+        return D.dit_forward64(mp, cfg, st64, *inp, t_emb)
+
+
+def test_float64_oracle_computes_the_fp32_oracle_function(mid1037, ref1037):
+    """F32 = float64 changes the rounding and nothing else: the fp32 oracle sits within 2e-6 rel RMS of it (measured 5.2e-7, and
+    6.6e-7 in its worst row — a third of what the fp32 engine achieves), and the module global is restored afterwards."""
+    cfg, st, _, t_emb, inp = mid1037
+    assert O.F32 is np.float32 and ref1037.dtype == np.float64 and ref1037.shape == (2, 1037, cfg.mel_dim)
+    cos, sin = O.rope_tables(1037, cfg.dim_head)
+    r32 = O.dit_forward(cfg, st, *inp, t_emb, cos, sin)
+    assert r32.dtype == np.float32
+    e_all, e_row = D.dit_errors(r32, ref1037)
+    assert e_all < 2e-6 and e_row < 4e-6, (e_all, e_row)
+    assert e_all > 1e-8                                     # really two different roundings
+    assert D.dit_gate_failures(r32, ref1037)[0] == set()
+
+
+def test_dit_gates_trip_on_injected_faults(mid1037, ref1037):
+    """The gates of the GPU DiT tests (dit_oracle64.F32_OVERALL_GATE / F32_ROW_GATE) applied to the float64 oracle against itself
+    with two faults of the kind a tiling bug makes, both confined to the last rows of the 2074-row GEMM."""
+    cfg, _, st64, t_emb, inp = mid1037
+    N = 1037
+    # RoPE one position off on the 58 rows of the partial last row group (positions 979 .. 1036 of both batch items)
+    cos, sin = D.rope64(N, cfg.dim_head, shift_from=N - 58)
+    with pytest.MonkeyPatch.context() as mp:
+        shifted = D.dit_forward64(mp, cfg, st64, *inp, t_emb, cos, sin)
+    bad, e_all, e_row = D.dit_gate_failures(shifted, ref1037)
+    assert bad == {"overall", "row"}, (e_all, e_row)        # measured 7.9e-4 overall, 3.2e-3 worst row
+    # The 16 rows of one last row block scaled by 1 + eps (a wrong LayerNorm statistic for one block).  Such a row's error is
+    # eps x rms(row) / rms(ref) ~ eps; the overall figure is eps x sqrt(16 / 2074) ~ 0.088 eps.  eps = 2 x the row gate trips the
+    # row gate with a factor of two to spare while the overall figure stays at 0.18 x the row gate (< 1/2 of the overall gate).
+    eps = 2 * D.F32_ROW_GATE
+    assert 0.088 * eps < 0.5 * D.F32_OVERALL_GATE
+    hurt = ref1037.copy()
+    hurt[1, N - 16:] *= 1 + eps
+    bad, e_all, e_row = D.dit_gate_failures(hurt, ref1037)
+    assert bad == {"row"}, (e_all, e_row)
+    assert e_row > 1.5 * D.F32_ROW_GATE and e_all < 0.5 * D.F32_OVERALL_GATE, (e_all, e_row)

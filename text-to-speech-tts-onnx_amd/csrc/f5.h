@@ -1,5 +1,7 @@
 // f5.h — F5-TTS engine object: DiT flow-matching sampler + text/mel front-end + Vocos/ISTFT back-end.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 #include "f5_kernels.h"
 
@@ -77,7 +79,9 @@ struct F5 {
     int np = 3;              // planes per operand of the panel-plane GEMMs, fixed when the weights are split (x3p_planes())
     ArithOverride arith;     // this engine's fp32 arithmetic: every call on the handle runs under ArithScope(arith)
     int arith_kind = ARITH_DEFAULT;
-    DevBuf Ap, Ap2;          // fp32 engines: the A operand of the big linear layers as panel planes (gemm_x3p.hip): dim / ff columns
+    DevBuf Ap, Ap2;          // fp32 engines: the A operand of the big linear layers as panel planes (gemm_x3p.hip): dim / ap2_cols() columns
+    // Ap2 also takes the input projection's rows (K = cat_ld()), which is wider than ff in the small configs
+    int ap2_cols() const { return std::max(cfg.ff(), cat_ld()); }
     // ---- AdaLN fold (dit_eval; gemm_epilogue.h) ----
     bool fold_built = false; // the load-time vectors exist (dim >= 1024, dim % 128 == 0, cfg.ln_fold != 0)
     DevBuf ApN;              // fp32 engines: x o (1 + scale) of the residual row as panel planes (16-bit engines: rows in Ub)

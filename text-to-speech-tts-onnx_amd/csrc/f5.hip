@@ -460,7 +460,7 @@ void F5::set_arith(int kind) {
     build_planes(&in_proj);
     if (ws_U > 0) {       // the activation planes are sized by the format
         const long rows = (long)2 * ws_U * ws_N;
-        Ap.ensure((size_t)x3p_bytes(rows, cfg.dim, np)); Ap2.ensure((size_t)x3p_bytes(rows, cfg.ff(), np)); ApN.ensure((size_t)x3p_bytes(rows, cfg.dim, np));
+        Ap.ensure((size_t)x3p_bytes(rows, cfg.dim, np)); Ap2.ensure((size_t)x3p_bytes(rows, ap2_cols(), np)); ApN.ensure((size_t)x3p_bytes(rows, cfg.dim, np));
     }
     MI_HIP(hipStreamSynchronize(stream));
 }
@@ -547,7 +547,7 @@ void F5::ensure_workspace(int U, int N) {
     }
     Hff.ensure(rows * c.ff() * es);
     if (dtype == MI_F32) {
-        Ap.ensure((size_t)x3p_bytes((long)rows, c.dim, np)); Ap2.ensure((size_t)x3p_bytes((long)rows, c.ff(), np));
+        Ap.ensure((size_t)x3p_bytes((long)rows, c.dim, np)); Ap2.ensure((size_t)x3p_bytes((long)rows, ap2_cols(), np));
         if (fold_built) ApN.ensure((size_t)x3p_bytes((long)rows, c.dim, np));
     }
     if (fold_built) { ln_stats.ensure((rows + 128) * (size_t)(c.dim / LN_BLK) * 2 * 4); if (dtype != MI_F32) ln_fin.ensure((rows + 128) * 8); }
@@ -582,9 +582,14 @@ void F5::gemm(int dt, const void* x, long xb, long xr, int K, const Lin& L, void
         g.B = 1; g.T_in = B * M; g.M = B * M;                      // (no per-item tile padding: 2252 rows -> 9 tiles, not 10)
     }
     if (dt == MI_F32 && L.w3p.p && g.B == 1 && Ap.p && gemm_x3p_enabled()) {
-        g.xp = K <= cfg.dim ? Ap.p : Ap2.p; g.w3p = L.w3p.p; g.np = np;
-        if (gemm_x3p_would_run(g)) x3p_split_rows((const float*)x, xr, const_cast<void*>(g.xp), g.M, K, stream, np, d_sat.as<int>());
-        else { g.xp = nullptr; g.w3p = nullptr; }
+        DevBuf& ab = K <= cfg.dim ? Ap : Ap2;                      // Ap holds dim columns, Ap2 ap2_cols() (ff, or the input projection's K)
+        g.xp = ab.p; g.w3p = L.w3p.p; g.np = np;
+        if (gemm_x3p_would_run(g)) {
+            MI_REQUIRE(x3p_bytes(g.M, K, np) <= (long)ab.bytes, "F5::gemm: the panel planes of the rows do not fit their buffer");
+            x3p_split_rows((const float*)x, xr, const_cast<void*>(g.xp), g.M, K, stream, np, d_sat.as<int>());
+        } else {
+            g.xp = nullptr; g.w3p = nullptr;
+        }
     }
     launch_conv_gemm(g, stream);
 }

@@ -7,6 +7,10 @@ session B, session C (decode), then the WAVEX write.  With no checkpoint on disk
 weights are the seeded synthetic ones — the output is noise-like audio, but every shape, dtype and call is the real one.
 
     python examples/f5_tts_infer.py --prompt prompt.wav --ref-text "..." --gen-text "..." --out generated.wav
+
+With --gen-text given more than once, every text becomes one request with its own max_duration (the reference's formula,
+mi355tts.text.max_duration) and all of them run in ONE ragged call (F5Engine.synthesize_ragged: one sampling loop for
+utterances of different lengths); the waveforms go to generated_0.wav, generated_1.wav, ...
 """
 import argparse
 import os
@@ -28,7 +32,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prompt", help="reference audio (RIFF/WAVE); default: a synthetic 3 s tone")
     ap.add_argument("--ref-text", default="the quick brown fox jumps over the lazy dog.")
-    ap.add_argument("--gen-text", default="pack my box with five dozen liquor jugs.")
+    ap.add_argument("--gen-text", action="append", help="text to speak; repeat for several requests in one ragged batch "
+                                                        "(default: one sentence)")
     ap.add_argument("--out", default="generated.wav")
     ap.add_argument("--models", help="directory holding F5_Preprocess / F5_Transformer / F5_Decode .mi355.json manifests")
     ap.add_argument("--dtype", default="bf16", choices=["f32", "f16", "bf16"])
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--seed", type=int, default=9527)
     ap.add_argument("--speed", type=float, default=1.0)
     a = ap.parse_args()
+    gen_texts = a.gen_text or ["pack my box with five dozen liquor jugs."]
 
     cfg = F5Config.small() if a.small else F5Config()
     tmp = None
@@ -65,8 +71,25 @@ def main():
     in_b, out_b = [i.name for i in sess_b.get_inputs()], [o.name for o in sess_b.get_outputs()]
     in_c, out_c = [i.name for i in sess_c.get_inputs()], [o.name for o in sess_c.get_outputs()]
 
-    ids = text.list_str_to_idx(text.convert_char_to_pinyin([a.ref_text + a.gen_text]), vocab)
-    max_duration = np.array([text.max_duration(audio.shape[-1], a.ref_text, a.gen_text, cfg.hop_length, a.speed)],
+    if len(gen_texts) > 1:           # several requests: one ragged call on the engine behind the sessions
+        eng = sess_a._eng
+        ids = [text.list_str_to_idx(text.convert_char_to_pinyin([a.ref_text + g]), vocab).reshape(-1) for g in gen_texts]
+        durs = [text.max_duration(audio.shape[-1], a.ref_text, g, cfg.hop_length, a.speed) for g in gen_texts]
+        t0 = time.time()
+        wavs = eng.synthesize_ragged([audio.reshape(-1)] * len(gen_texts), ids, durs, seed=a.seed)
+        dt = time.time() - t0
+        stem, ext = os.path.splitext(a.out)
+        for u, w in enumerate(wavs):
+            audio_io.write_wavex(f"{stem}_{u}{ext}", w.reshape(-1), cfg.sample_rate)
+        secs = sum(w.size for w in wavs) / cfg.sample_rate
+        print(f"{stem}_*{ext}: {len(wavs)} requests (max_duration {durs}), {secs:.2f} s of audio in {dt:.3f} s in one ragged call")
+        if tmp:
+            import shutil
+            shutil.rmtree(tmp, ignore_errors=True)
+        return
+
+    ids = text.list_str_to_idx(text.convert_char_to_pinyin([a.ref_text + gen_texts[0]]), vocab)
+    max_duration = np.array([text.max_duration(audio.shape[-1], a.ref_text, gen_texts[0], cfg.hop_length, a.speed)],
                             dtype=np.int64)
 
     t0 = time.time()

@@ -106,7 +106,8 @@ int         mi_conv_transpose1d(const float* x, int B, int Cin, int T, const flo
  * the q k scores to fp16 and multiplies them by attn_score_scale (= 100) in fp32 before the fp32 softmax.  `dtype` selects the DiT operand type (fp32 residual stream and
  * fp32 softmax/norm statistics always); the front end and the vocoder always run in fp32, like the
  * reference's CPU-pinned graphs A and C (F5-TTS-ONNX-Inference.py:173,214).
- * Batching extension: U utterances of equal max_duration N; tensors gain a leading U axis.        */
+ * Batching extension: U utterances of equal max_duration N; tensors gain a leading U axis (utterances of
+ * different lengths: mi_f5_synthesize_ragged).                                                        */
 int64_t     mi_f5_param_count(const int32_t* cfg_i, int n_i, const float* cfg_f, int n_f);
 mi_f5*      mi_f5_create(const int32_t* cfg_i, int n_i, const float* cfg_f, int n_f, const float* weights,
                          int64_t n_weights, int dtype, int device);
@@ -164,6 +165,23 @@ int         mi_f5_synthesize(mi_f5* h, int U, const int16_t* audio, int64_t L, c
 int         mi_f5_synthesize_mel(mi_f5* h, int U, const int16_t* audio, int64_t L, const int32_t* text_ids, int64_t T,
                                  int64_t max_duration, const float* noise_in, uint64_t seed, float* mel_out,
                                  int64_t* n_frames, int mem);
+
+/* Ragged batch: U utterances, each with its own prompt audio (audio_lens[u] samples), text (text_lens[u] ids) and
+ * max_duration N_u (max_durations[u]), through graph A, the sampling loop (one hipGraph) and graph C in one call.
+ * audio, text_ids and noise_in are the per-utterance arrays concatenated (noise_in: sum N_u x 100, or NULL to draw utterance
+ * u's noise with seed + u, as mi_f5_synthesize does); data arrays follow `mem`, the length arrays are always host int64.
+ * The loop runs on padded slabs of Nmax = max N_u rows (utterance u owns slab u; rows >= N_u stay zero and never reach a live
+ * row): each utterance gets the waveform it gets alone.  out receives the int16 waveforms concatenated, out_lens[u] =
+ * (N_u - R_u - 1) * hop with R_u the prompt's frames.  MI_EINVAL, with the handle still usable, for U < 1, N_u < R_u + 1,
+ * N_u < T_u, N_u > max_signal_length, out_cap below the sum of out_lens, or a text id out of range in any utterance.   */
+int         mi_f5_synthesize_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
+                                    const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed,
+                                    int16_t* out, int64_t out_cap, int64_t* out_lens, int mem);
+/* tests: one DiT evaluation of a ragged batch at grid index k.  noise (U, Nmax, 100), cat_mel_text(_drop) (U, Nmax, 612) in
+ * the padded layout (rows >= lens[u] are ignored), lens host int64 in [1, Nmax] -> pred (2U, Nmax, 100), cond branch first;
+ * only rows < lens[u] of items 2u, 2u + 1 are defined.                                                                  */
+int         mi_f5_dit_eval_ragged(mi_f5* h, int U, const int64_t* lens, const float* noise, const float* cat_mel_text,
+                                  const float* cat_mel_text_drop, int64_t Nmax, int k, float* pred, int mem);
 
 /* ---- IndexTTS acoustic GPT-2 (graphs B, C, E + the greedy decode loop) ------------------------------------------
  * Replaces ort_session_B / _C / _E of IndexTTS/Inference_IndexTTS_ONNX.py:619-675 and the loop at :745-783

@@ -58,6 +58,23 @@ namespace mi {
         bx_ = slot % (int)gridDim.x;                                                          \
     }
 
+// VARLEN (ragged F5 batches, padded slabs): item b = bh / H holds NL = lens[b / 2] live rows of its N (the CFG pair 2u, 2u + 1
+// shares utterance u's length); N stays the row stride of q / k / v / o, NL replaces it in every mask and loop bound.
+//   * keys >= NL are masked exactly like keys >= N: score -inf, their V^T values cleared before the P V product;
+//   * query rows in [NL, N) are stored as zeros (o and o_planes);
+//   * a query tile whose first row is >= NL is `dead`: it loads no stage; slice z = 0 stores its zero rows, the other
+//     slices return at once.  Every slice of a dead tile skips the merge, so no ticket of `cnt` is taken for it;
+//   * a live tile runs every slice and every slice takes its ticket.  A slice whose stages lie wholly past NL (st0 >= nstage
+//     after the clamp to ceil(NL / 64)) publishes the neutral partial m = -inf, l = 0, O = 0 — the empty slices attn_z_force
+//     makes — and the merge weighs it by 0 (the m == -inf test: no exp(-inf - (-inf))).  At least one slice of a live tile
+//     holds stage 0, so the merged l is > 0.  The last arriver resets the counter, so a completed launch leaves every
+//     counter at 0 for whatever length mix the next replay brings.
+// VARLEN = false: NL = N and dead = false are constants, the instantiations compile to the code they had without the switch.
+#define ATTN_VARLEN_PROLOGUE                                                                  \
+    const int NL = VARLEN ? lens[(bh / H) >> 1] : N;                                          \
+    const bool dead = VARLEN && (SPLIT2 ? bx_ * 64 : bx_ * 128) >= NL;                        \
+    if (dead && blockIdx.z != 0) return;
+
 // lane <-> lane ^ 32 exchange of the online softmax (row max, row sum: a query column lives in lanes l and l + 32) on
 // v_permlane32_swap instead of ds_bpermute (no LDS-crossbar round trip on the S -> max -> exp chain).  Two copies of the value
 // go in; the instruction leaves {own low | low} in one register and {high | own high} in the other, so their max / sum is the
@@ -71,10 +88,11 @@ __device__ __forceinline__ void xor32_pair(float v, float& a, float& b) {
 __device__ __forceinline__ float xor32_max(float v) { float a, b; xor32_pair(v, a, b); return fmaxf(a, b); }
 __device__ __forceinline__ float xor32_sum(float v) { float a, b; xor32_pair(v, a, b); return a + b; }
 
-template <typename T, bool SPLIT2 = false, bool X3S = false, bool REFH = false>
+template <typename T, bool SPLIT2 = false, bool X3S = false, bool REFH = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                    const T* __restrict__ v, T* __restrict__ o, int H, int N,
-                                                   float* __restrict__ ws, int* __restrict__ cnt, float sscale = 1.f, int xmap = 0) {
+                                                   float* __restrict__ ws, int* __restrict__ cnt, float sscale = 1.f, int xmap = 0,
+                                                   const int* __restrict__ lens = nullptr) {
     static_assert(!REFH || (sizeof(T) == 2 && !X3S), "REFH is the fp16 form");
     ATTN_XCD_MAP
     using MF = Mfma<T>;
@@ -92,6 +110,17 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hi = lane >> 5;
     const int bh = by_;
+    ATTN_VARLEN_PROLOGUE
+    if constexpr (VARLEN) {
+        if (dead) {          // slice 0 of a tile with no live query: its rows leave as zeros, and nothing below runs (no ticket)
+            const int r0 = SPLIT2 ? bx_ * 64 : bx_ * 128, r1 = min(r0 + (SPLIT2 ? 64 : 128), N);
+            constexpr int VPR = D * (int)sizeof(T) / 16;                // 16-byte vectors per row of one head
+            const int b = bh / H, h = bh - b * H;
+            for (int i = tid; i < (r1 - r0) * VPR; i += 256)
+                *reinterpret_cast<uint4*>(o + ((long)b * N + r0 + i / VPR) * H * D + h * D + (i % VPR) * (16 / (int)sizeof(T))) = make_uint4(0, 0, 0, 0);
+            return;
+        }
+    }
     const int q0 = SPLIT2 ? bx_ * 64 + (wave >> 1) * 32 : bx_ * 128 + wave * 32;
     const T* qb = q + (long)bh * N * D;
     const T* kb = k + (long)bh * N * D;
@@ -103,7 +132,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
     bf16x8 qf3[X3S ? 4 : 1][3];                            // X3S: Q[q][16 ks + 8 hi .. +8] as three bf16 pieces, pre-scaled by log2(e)
     if constexpr (X3S) {
         const int qr = q0 + lr;
-        const bool ok = qr < N;
+        const bool ok = qr < NL;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             float4 a = float4{0.f, 0.f, 0.f, 0.f}, b = a;
@@ -123,7 +152,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
         }
     } else {
         const int qr = q0 + lr;
-        const bool ok = qr < N;
+        const bool ok = qr < NL;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             // Q is pre-multiplied by log2(e): the softmax then needs v_exp_f32 (2^x) only, no expf expansion
@@ -147,13 +176,22 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
             const int vi = tid + i * 256;
             const int key = vi / (D / VEC), dv = vi - key * (D / VEC);
             uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
-            if (key0 + key < N) a = *reinterpret_cast<const uint4*>(kb + (long)(key0 + key) * D + dv * VEC);
+            if (key0 + key < NL) a = *reinterpret_cast<const uint4*>(kb + (long)(key0 + key) * D + dv * VEC);
             if constexpr (sizeof(T) == 4) {
-                if (key0 + key < N) b = *reinterpret_cast<const uint4*>(vb + (long)(key0 + key) * D + dv * VEC);
+                if (key0 + key < NL) b = *reinterpret_cast<const uint4*>(vb + (long)(key0 + key) * D + dv * VEC);
             } else {
                 // V arrives transposed from the QKV epilogue: row d = vi / 8, eight consecutive keys per vector
                 const int d = vi >> 3, kv = vi & 7;
-                if (key0 + kv * 8 < N) b = *reinterpret_cast<const uint4*>(vb + (long)d * vld + key0 + kv * 8);
+                if (key0 + kv * 8 < NL) b = *reinterpret_cast<const uint4*>(vb + (long)d * vld + key0 + kv * 8);
+                if constexpr (VARLEN) {       // keys [NL, N) are padding rows of the slab: clear their V^T values (16-bit halves)
+                    const int keep = NL - (key0 + kv * 8);
+                    if (keep > 0 && keep < 8) {
+                        unsigned w[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) w[e] &= (2 * e < keep ? 0x0000ffffu : 0u) | (2 * e + 1 < keep ? 0xffff0000u : 0u);
+                        b = make_uint4(w[0], w[1], w[2], w[3]);
+                    }
+                }
             }
             kreg[i] = a; vreg[i] = b;
         }
@@ -184,7 +222,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 
     // gridDim.z > 1 (SPLIT2 only): the 64-key stages are cut into gridDim.z contiguous slices, one workgroup each; the
     // slices of a query tile meet in `ws` and the LAST one to arrive merges them in slice order (see the end of the kernel)
-    const int nstage_all = (N + KT - 1) / KT;
+    const int nstage_all = (NL + KT - 1) / KT;
     const int st0 = SPLIT2 ? (int)((long)blockIdx.z * nstage_all / gridDim.z) : 0;
     const int nstage = SPLIT2 ? (int)((long)(blockIdx.z + 1) * nstage_all / gridDim.z) : nstage_all;
     if (st0 < nstage) {
@@ -238,11 +276,11 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
             // ---- online softmax (per lane = per query) -----------------------------------------
             // only the tile that straddles N needs the key >= N select (2 VALU issues per score, a third of the
             // softmax's VALU time when done on every tile): wave-uniform branch around it
-            if (key0 + 32 > N) {
+            if (key0 + 32 > NL) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= N) sacc[r] = -INFINITY;
+                    if (key >= NL) sacc[r] = -INFINITY;
                 }
             }
             float mloc = -INFINITY;
@@ -302,12 +340,12 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
             }
         };
         if constexpr (SPLIT2) {
-            if (st * KT + (wave & 1) * 32 < N) tile(wave & 1);           // this wave's half of the stage
+            if (st * KT + (wave & 1) * 32 < NL) tile(wave & 1);           // this wave's half of the stage
         } else {
 #pragma unroll
             for (int kt = 0; kt < KT / 32; ++kt) {
                 const int key0 = st * KT + kt * 32;
-                if (key0 < N) tile(kt);                                  // wave-uniform
+                if (key0 < NL) tile(kt);                                  // wave-uniform
             }
         }
         __syncthreads();
@@ -429,7 +467,10 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
     // ---- normalise + store o[b][n][h*64 + d] ---------------------------------------------------------
     const int qr = q0 + lr;
     if (qr < N) {
-        const float inv = 1.0f / l_run;
+        // VARLEN: rows >= NL leave as 0 x O (finite: zero for a dead tile, an average of live V rows otherwise) — a scale, not a
+        // select in front of the conversion, so that the live rows keep the uniform kernel's instruction forms (f16: multiply,
+        // then convert; a select in between made the compiler fuse them into one rounding elsewhere)
+        const float inv = VARLEN && qr >= NL ? 0.f : 1.0f / l_run;
         const int b = bh / H, h = bh - b * H;
         T* ob = o + ((long)b * N + qr) * H * D + h * D;
 #pragma unroll
@@ -470,12 +511,12 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 #define TSTAMP(v) do { } while (0)
 #define TACC(k, t1, t0) do { } while (0)
 #endif
-template <bool SPLIT2, bool KVP = false, int NP = 3>
+template <bool SPLIT2, bool KVP = false, int NP = 3, bool VARLEN = false>
 __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, float* __restrict__ o, int H, int N,
                                                        float* __restrict__ ws, int* __restrict__ cnt,
                                                        unsigned char* __restrict__ o_planes, int o_np, int xmap = 0,
-                                                       int cut1 = 0, int cut2 = 0, int cut3 = 0) {
+                                                       int cut1 = 0, int cut2 = 0, int cut3 = 0, const int* __restrict__ lens = nullptr) {
     ATTN_XCD_MAP
     // o_planes != null: the output leaves as gemm_x3p.hip panel planes of the [B * N][H * 64] matrix (the A operand of the O
     // projection), split here (o_np = 3 bf16 planes | 2 fp16 planes), instead of fp32 rows in o
@@ -492,6 +533,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hi = lane >> 5;
     const int bh = by_;
+    ATTN_VARLEN_PROLOGUE
     const int q0 = SPLIT2 ? bx_ * 64 + (wave >> 1) * 32 : bx_ * 128 + wave * 32;
     const float* qb = q + (long)bh * N * D;
     const float* kb = k + (long)bh * N * D;
@@ -532,7 +574,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     Frag qf3[4][NP];
     {
         const int qr = q0 + lr;
-        const bool ok = qr < N;
+        const bool ok = qr < NL;
         constexpr float L2E = 1.4426950408889634f;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -560,12 +602,12 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                 kpl[i] = *reinterpret_cast<const x3_u4*>(kpb + ((long)pl * vld + key0 + r) * D + c * 8);
                 vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * D + r) * vld + key0 + c * 8);
             }
-            if (key0 + KT > N) {
+            if (key0 + KT > NL) {
                 // last stage: the V^T values of keys >= N meet probabilities that are exactly zero, but 0 x NaN is NaN and
                 // the pad columns hold whatever the buffer held before (another layout, another mode): clear them here
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
-                    const int keep = N - (key0 + ((tid + i * 256) & 7) * 8);          // valid keys among this unit's eight
+                    const int keep = NL - (key0 + ((tid + i * 256) & 7) * 8);         // valid keys among this unit's eight
                     if (keep < 8) {
                         unsigned w[4] = {vpl[i].x, vpl[i].y, vpl[i].z, vpl[i].w};
 #pragma unroll
@@ -581,8 +623,14 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
             const int key = vi >> 4, dv = vi & 15;              // K: row key, floats 4 dv .. 4 dv + 3
             const int d = vi >> 4, kv = vi & 15;                // V^T: row d, keys key0 + 4 kv .. + 3
             float4 a = float4{0.f, 0.f, 0.f, 0.f}, b = a;
-            if (key0 + key < N) a = *reinterpret_cast<const float4*>(kb + (long)(key0 + key) * D + dv * 4);
-            if (key0 + kv * 4 < N) b = *reinterpret_cast<const float4*>(vb + (long)d * vld + key0 + kv * 4);
+            if (key0 + key < NL) a = *reinterpret_cast<const float4*>(kb + (long)(key0 + key) * D + dv * 4);
+            if (key0 + kv * 4 < NL) b = *reinterpret_cast<const float4*>(vb + (long)d * vld + key0 + kv * 4);
+            if constexpr (VARLEN) {           // keys [NL, N) are padding rows of the slab: clear their V^T values
+                const int keep = NL - (key0 + kv * 4);
+                if (keep < 2) b.y = 0.f;
+                if (keep < 3) b.z = 0.f;
+                if (keep < 4) b.w = 0.f;
+            }
             kreg[i] = a; vreg[i] = b;
         }
         }
@@ -623,7 +671,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     TSTAMP(tk_);
 #endif
 
-    const int nstage_all = (N + KT - 1) / KT;
+    const int nstage_all = dead ? 0 : (NL + KT - 1) / KT;
     // key slices (gridDim.z > 1): see the merge below.  cut1 > 0 (round 6): UNEVEN slices [0, cut1), [cut1, cut2), ... chosen by the
     // launcher so that the z-major dispatch order is longest-piece-first on the 3 x CUs slots (attn_pick_slices)
     int st0 = (int)((long)blockIdx.z * nstage_all / gridDim.z);
@@ -633,6 +681,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
         st0 = zz == 0 ? 0 : zz == 1 ? cut1 : zz == 2 ? cut2 : cut3;
         nstage = zz + 1 == ZZ ? nstage_all : zz == 0 ? cut1 : zz == 1 ? cut2 : cut3;
     }
+    if constexpr (VARLEN) { st0 = min(st0, nstage_all); nstage = min(nstage, nstage_all); }      // cuts are chosen for N stages
     if (st0 < nstage) {
         load_regs(st0 * KT);
         store_lds();
@@ -663,11 +712,11 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                     sacc = MF::mma(kf[0], qf3[ks][0], sacc);
                 }
             }
-            if (key0 + 32 > N) {
+            if (key0 + 32 > NL) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= N) sacc[r] = -INFINITY;
+                    if (key >= NL) sacc[r] = -INFINITY;
                 }
             }
             float mloc = -INFINITY;
@@ -746,12 +795,12 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
             TSTAMP(td_); TACC(2, td_, tc_);            // P split + V fragment reads + P V MFMAs (issued)
         };
         if constexpr (SPLIT2) {
-            if (st * KT + (wave & 1) * 32 < N) tile(wave & 1);
+            if (st * KT + (wave & 1) * 32 < NL) tile(wave & 1);
         } else {
 #pragma unroll
             for (int kt = 0; kt < KT / 32; ++kt) {
                 const int key0 = st * KT + kt * 32;
-                if (key0 < N) tile(kt);
+                if (key0 < NL) tile(kt);
             }
         }
         TSTAMP(ta_);
@@ -810,7 +859,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
         // does not depend on which one that is, resets the ticket counter (hipGraph replays find it at zero) and stores.
         // Nobody waits for anybody: there is no residency requirement. ---------------------------------------------------
         const int Z = (int)gridDim.z;
-        if (Z > 1) {
+        if (Z > 1 && !dead) {                                        // (a tile with no live query takes no ticket: see ATTN_VARLEN_PROLOGUE)
             const int z = (int)blockIdx.z;
             const int unit = (int)(by_ * gridDim.x + bx_);
             constexpr int SLOT = NG * (32 * 64 + 64 * 2);            // floats per (unit, slice)
@@ -885,7 +934,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     // ---- normalise + store o[b][n][h*64 + d] ---------------------------------------------------------
     const int qr = q0 + lr;
     if (qr < N) {
-        const float inv = 1.0f / l_run;
+        const float inv = VARLEN && qr >= NL ? 0.f : 1.0f / l_run;          // VARLEN: rows >= NL leave as zeros (see attn_kernel)
         const int b = bh / H, h = bh - b * H;
         float* ob = o + ((long)b * N + qr) * H * D + h * D;
         const long row = (long)b * N + qr;
@@ -1031,8 +1080,28 @@ static AttnSlices attn_pick_slices(long units, int S, int slots, int zmax) {
     return best;
 }
 
+// One launch of either kernel.  lens != nullptr: the VARLEN instantiation (ragged batch, ATTN_VARLEN_PROLOGUE); the grid, the
+// slices and every other argument are those of the uniform launch at the same N.
+template <bool SPLIT2, bool KVP, int NP>
+static void go_x3f(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int H, int N, float* ws, int* cnt,
+                   void* o_planes, int o_np, int xm, int c1, int c2, int c3, const int* lens) {
+    const float *qf = (const float*)q, *kf = (const float*)k, *vf = (const float*)v;
+    if (lens) prof_kernel_suffix(" + lengths");
+    if (lens) hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3, lens);
+    else hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3);
+}
+template <typename T, bool SPLIT2, bool X3S = false, bool REFH = false>
+static void go_attn(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int H, int N, float* ws, int* cnt,
+                    float sscale, int xm, const int* lens) {
+    const T *qt = (const T*)q, *kt = (const T*)k, *vt = (const T*)v;
+    if (lens) prof_kernel_suffix(" + lengths");
+    if (lens) hipLaunchKernelGGL((attn_kernel<T, SPLIT2, X3S, REFH, true>), grid, dim3(256), 0, s, qt, kt, vt, (T*)o, H, N, ws, cnt, sscale, xm, lens);
+    else hipLaunchKernelGGL((attn_kernel<T, SPLIT2, X3S, REFH>), grid, dim3(256), 0, s, qt, kt, vt, (T*)o, H, N, ws, cnt, sscale, xm);
+}
+
 void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
-                      float* ws, long ws_floats, int* cnt, long cnt_n, void* o_planes, int kv_planes, int o_np, float ref_fp16_scale) {
+                      float* ws, long ws_floats, int* cnt, long cnt_n, void* o_planes, int kv_planes, int o_np, float ref_fp16_scale,
+                      const int* lens) {
     MI_REQUIRE(ref_fp16_scale == 0.f || (dtype == MI_F16 && ref_fp16_scale > 0.f), "attention: the reference-fp16 score form needs f16 operands");
     MI_REQUIRE(o_np == 2 || o_np == 3, "attention: 2 or 3 output planes");
     MI_REQUIRE(!o_planes || attention_can_write_planes(N, BH, dtype), "attention: panel-plane output needs the fp32 split kernel");
@@ -1041,10 +1110,10 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
     MI_REQUIRE(BH % H == 0 && N > 0, "attention: bad shape");
     const double esz = (double)dtype_size(dtype);
     ProfScope ps(FAM_ATTN, s, 4.0 * BH * N * 64.0 * esz, 4.0 * BH * (double)N * N * 64.0);
-#define ATTN_LAUNCH(TT, SP, ...)                                                \
+#define ATTN_LAUNCH(TT, SP, GRID, SSCALE, XM)                                    \
     do {                                                                        \
         prof_set_kernel("attn_kernel<T, " #SP ">", type_label<TT>());           \
-        hipLaunchKernelGGL((attn_kernel<TT, SP>), __VA_ARGS__);                 \
+        go_attn<TT, SP>(GRID, s, q, k, v, o, H, N, ws, cnt, SSCALE, XM, lens);  \
     } while (0)
     attn_env_once();
     const int xm = (g_attn_xmap != 0 && BH % 8 == 0) ? 1 : 0;
@@ -1117,40 +1186,40 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
                     }
                 }
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs> + key slices", "", "");
-                hipLaunchKernelGGL((attn_x3f_kernel<false, true, 2>), dim3((N + 127) / 128, BH, sl.Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm,
-                                   sl.Z > 1 ? sl.cut[0] : 0, sl.cut[1], sl.cut[2]);
+                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH, sl.Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm,
+                                       sl.Z > 1 ? sl.cut[0] : 0, sl.cut[1], sl.cut[2], lens);
             } else if (opt_attn_x3() == 2) {
                 if (kv_planes == 2) {
                     prof_set_kernel("attn_x3f_kernel<true, pre-split K V, fp16 pairs>", "", "");
-                    hipLaunchKernelGGL((attn_x3f_kernel<true, true, 2>), dim3((N + 63) / 64, BH, Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm);
+                    go_x3f<true, true, 2>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens);
                 } else if (kv_planes) {
                     prof_set_kernel("attn_x3f_kernel<true, pre-split K V>", "", "");
-                    hipLaunchKernelGGL((attn_x3f_kernel<true, true>), dim3((N + 63) / 64, BH, Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np);
+                    go_x3f<true, true, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
                 } else {
                 prof_set_kernel("attn_x3f_kernel<true>", "", "");
-                hipLaunchKernelGGL((attn_x3f_kernel<true>), dim3((N + 63) / 64, BH, Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np);
+                go_x3f<true, false, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
                 }
             } else if (opt_attn_x3() == 1) {
                 prof_set_kernel("attn_kernel<float, true, x3>", "", "");
-                hipLaunchKernelGGL((attn_kernel<float, true, true>), dim3((N + 63) / 64, BH, Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt);
+                go_attn<float, true, true>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, 1.f, 0, lens);
             } else
-                ATTN_LAUNCH(float, true, dim3((N + 63) / 64, BH, Z), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt);
+                ATTN_LAUNCH(float, true, dim3((N + 63) / 64, BH, Z), 1.f, 0);
         } else if (opt_attn_x3() == 2) {
             if (kv_planes == 2) {
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs>", "", "");
-                hipLaunchKernelGGL((attn_x3f_kernel<false, true, 2>), dim3((N + 127) / 128, BH), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm);
+                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens);
             } else if (kv_planes) {
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V>", "", "");
-                hipLaunchKernelGGL((attn_x3f_kernel<false, true>), dim3((N + 127) / 128, BH), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np);
+                go_x3f<false, true, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
             } else {
             prof_set_kernel("attn_x3f_kernel<false>", "", "");
-            hipLaunchKernelGGL((attn_x3f_kernel<false>), dim3((N + 127) / 128, BH), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np);
+            go_x3f<false, false, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
             }
         } else if (opt_attn_x3() == 1) {
             prof_set_kernel("attn_kernel<float, false, x3>", "", "");
-            hipLaunchKernelGGL((attn_kernel<float, false, true>), dim3((N + 127) / 128, BH), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt);
+            go_attn<float, false, true>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, 1.f, 0, lens);
         } else
-            ATTN_LAUNCH(float, false, dim3((N + 127) / 128, BH), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, H, N, ws, cnt);
+            ATTN_LAUNCH(float, false, dim3((N + 127) / 128, BH), 1.f, 0);
     } else {
         // 16-bit: the same split below 512 workgroups (one utterance: attention 24.3 -> 21.1 ms per step; at two utterances,
         // 576 workgroups, the 128-query form is already balanced and shares each K / V stage among more waves)
@@ -1158,14 +1227,14 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
         const dim3 grid(sp ? (N + 63) / 64 : (N + 127) / 128, BH, sp ? pick_z(z16) : 1);
         if (dtype == MI_F16 && ref_fp16_scale != 0.f) {
             prof_set_kernel(sp ? "attn_kernel<T, true, reference-fp16 scores>" : "attn_kernel<T, false, reference-fp16 scores>", type_label<f16>());
-            if (sp) hipLaunchKernelGGL((attn_kernel<f16, true, false, true>), grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, H, N, ws, cnt, ref_fp16_scale);
-            else hipLaunchKernelGGL((attn_kernel<f16, false, false, true>), grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, H, N, ws, cnt, ref_fp16_scale);
+            if (sp) go_attn<f16, true, false, true>(grid, s, q, k, v, o, H, N, ws, cnt, ref_fp16_scale, 0, lens);
+            else go_attn<f16, false, false, true>(grid, s, q, k, v, o, H, N, ws, cnt, ref_fp16_scale, 0, lens);
         } else if (dtype == MI_F16) {
-            if (sp) ATTN_LAUNCH(f16, true, grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, H, N, ws, cnt, 1.f, xm);
-            else ATTN_LAUNCH(f16, false, grid, dim3(256), 0, s, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, H, N, ws, cnt, 1.f, xm);
+            if (sp) ATTN_LAUNCH(f16, true, grid, 1.f, xm);
+            else ATTN_LAUNCH(f16, false, grid, 1.f, xm);
         } else {
-            if (sp) ATTN_LAUNCH(bf16, true, grid, dim3(256), 0, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, H, N, ws, cnt, 1.f, xm);
-            else ATTN_LAUNCH(bf16, false, grid, dim3(256), 0, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, H, N, ws, cnt, 1.f, xm);
+            if (sp) ATTN_LAUNCH(bf16, true, grid, 1.f, xm);
+            else ATTN_LAUNCH(bf16, false, grid, 1.f, xm);
         }
     }
 #undef ATTN_LAUNCH

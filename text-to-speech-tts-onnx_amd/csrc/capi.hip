@@ -429,6 +429,85 @@ int mi_f5_synthesize_mel(mi_f5* h, int U, const int16_t* audio, int64_t L, const
     });
 }
 
+// ragged batches (F5::dit_eval with lengths): lengths are host int64, checked before anything reaches the device
+static std::vector<int> f5_lengths(const int64_t* lens, int U, int64_t lo, int64_t hi, const char* what) {
+    MI_REQUIRE(lens && U >= 1, what);
+    std::vector<int> v(U);
+    for (int u = 0; u < U; ++u) {
+        MI_REQUIRE(lens[u] >= lo && lens[u] <= hi, what);
+        v[u] = (int)lens[u];
+    }
+    return v;
+}
+
+int mi_f5_synthesize_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
+                            const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed, int16_t* out,
+                            int64_t out_cap, int64_t* out_lens, int mem) {
+    return guard([&] {
+        F5_CHECK(h, mem, "mi_f5_synthesize_ragged");
+        MI_REQUIRE(audio && text_ids && out && out_lens && U >= 1, "mi_f5_synthesize_ragged: bad arguments");
+        F5& e = *h->impl;
+        const F5Cfg& c = e.cfg;
+        std::vector<int> Ns = f5_lengths(max_durations, U, 1, c.max_len, "mi_f5_synthesize_ragged: max_durations must be in [1, max_signal_length]");
+        std::vector<int> Ts = f5_lengths(text_lens, U, 0, 1 << 20, "mi_f5_synthesize_ragged: bad text length");
+        std::vector<long> Ls(U);
+        std::vector<int> Rs(U);
+        const int mel_pad = c.mel_type == 1 ? (c.n_fft - c.hop) / 2 : c.n_fft / 2;
+        int64_t total = 0, ids = 0;
+        for (int u = 0; u < U; ++u) {
+            MI_REQUIRE(audio_lens && audio_lens[u] >= c.n_fft / 2 + 1 && audio_lens[u] > mel_pad && audio_lens[u] + 2 * mel_pad >= c.n_fft &&
+                       audio_lens[u] < (1L << 31), "mi_f5_synthesize_ragged: audio shorter than one STFT frame");
+            Ls[u] = (long)audio_lens[u];
+            const int R = e.ref_frames(Ls[u]);
+            MI_REQUIRE(Ns[u] >= R + 1 && Ns[u] >= Ts[u], "mi_f5_synthesize_ragged: max_duration must exceed the prompt's frames and cover the text");
+            total += (int64_t)(Ns[u] - R - 1) * c.hop;
+            ids += Ts[u];
+        }
+        MI_REQUIRE(total <= out_cap, "mi_f5_synthesize_ragged: out_cap is smaller than the sum of the waveform lengths");
+        if (mem == MI_HOST)
+            for (int64_t i = 0; i < ids; ++i)
+                MI_REQUIRE((int64_t)text_ids[i] + 1 >= 0 && (int64_t)text_ids[i] + 1 <= c.vocab, "mi_f5_synthesize_ragged: text id out of range");
+        const int Nmax = *std::max_element(Ns.begin(), Ns.end());
+        f5_run_checked(e, [&] {
+            e.preprocess_ragged(U, audio, Ls.data(), text_ids, Ts.data(), Ns.data(), Nmax, noise_in, seed, mem, Rs.data());
+            const int* lens = e.set_lengths(U, Ns.data());
+            e.build_cat_cond(U, Nmax);
+            e.steps(U, Nmax, 0, c.nfe - 1, lens);
+            int64_t off = 0;
+            for (int u = 0; u < U; ++u) {      // graph C per utterance, on its own frames of its slab
+                const long len = e.decode(e.d_noise.as<float>() + (size_t)u * Nmax * c.mel, 1, Ns[u], Rs[u], nullptr, e.v_outi.as<int16_t>());
+                copy_out(out + off, e.v_outi.p, (size_t)len * 2, mem, e.stream);
+                out_lens[u] = len;
+                off += len;
+            }
+            MI_HIP(hipStreamSynchronize(e.stream));
+        });
+        e.finish_call();
+    });
+}
+
+int mi_f5_dit_eval_ragged(mi_f5* h, int U, const int64_t* lens, const float* noise, const float* cmt, const float* cmtd, int64_t Nmax,
+                          int k, float* pred, int mem) {
+    return guard([&] {
+        F5_CHECK(h, mem, "mi_f5_dit_eval_ragged");
+        MI_REQUIRE(noise && cmt && cmtd && pred && U >= 1 && Nmax > 0 && Nmax <= h->impl->cfg.max_len, "mi_f5_dit_eval_ragged: bad arguments");
+        F5& e = *h->impl;
+        const int N = (int)Nmax;
+        std::vector<int> Ls = f5_lengths(lens, U, 1, N, "mi_f5_dit_eval_ragged: lengths must be in [1, Nmax]");
+        f5_run_checked(e, [&] {
+            e.load_cond(noise, cmt, cmtd, U, N, mem);
+            e.zero_pad_rows_cond(U, N, Ls.data());
+            const int* dl = e.set_lengths(U, Ls.data());
+            e.build_cat_cond(U, N);
+            e.dit_eval(U, N, k, dl);
+            MI_HIP(hipStreamSynchronize(e.stream));
+        });
+        copy_out(pred, e.pred_rows(U, N), (size_t)2 * U * N * e.cfg.mel * 4, mem, e.stream);
+        MI_HIP(hipStreamSynchronize(e.stream));
+        e.finish_call();
+    });
+}
+
 int mi_f5_stft(mi_f5* h, const int16_t* audio, int64_t L, float* spec, int mem) {
     return guard([&] {
         F5_CHECK(h, mem, "mi_f5_stft");

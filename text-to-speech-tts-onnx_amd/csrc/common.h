@@ -114,6 +114,7 @@ enum { FAM_CONV_GEMM = 0, FAM_AA = 1, FAM_CONV_POST = 2, FAM_ATTN = 3, FAM_NORM 
 // rocprofv3 --kernel-trace shows for it); the enclosing ProfScope files its elapsed time under that name.  No-op unless
 // profiling is on.
 void prof_set_kernel(const char* expr, const char* t = nullptr, const char* to = nullptr);
+void prof_kernel_suffix(const char* sfx);     // appends to the name prof_set_kernel set last (e.g. a variant of the same launch)
 template <typename T> inline const char* type_label();
 template <> inline const char* type_label<float>() { return "float"; }
 template <> inline const char* type_label<f16>() { return "_Float16"; }

@@ -62,14 +62,14 @@ struct F5 {
     struct VBlock { DevBuf dw_w, dw_b, n_w, n_b; Lin pw1, pw2; };
     std::vector<VBlock> vblocks;
 
-    // ---- HIP graphs of the sampling loop, keyed by (U, N, k0, nsteps) ----
+    // ---- HIP graphs of the sampling loop, keyed by (U, N, k0, nsteps, ragged) ----
     struct GraphEntry { hipGraphExec_t exec = nullptr; int uses = 0; };
     std::map<std::vector<int>, GraphEntry> graphs;
     bool use_graph = true;          // MI355TTS_NO_GRAPH=1 disables
     long graph_epoch = 0;           // option_epoch() the cached graphs were captured under
     void drop_graphs();
     void recover();          // after an error on this handle: drain the stream, drop graphs, re-zero the hand-off flags / tickets
-    void steps_eager(int U, int N, int k0, int nsteps);
+    void steps_eager(int U, int N, int k0, int nsteps, const int* lens = nullptr);
 
     // ---- workspace ----
     SkWorkspace sk;          // stream-K partial-tile slots of this handle's stream
@@ -112,8 +112,19 @@ struct F5 {
     void check_text_ids();
     void load_cond(const float* noise, const float* cmt, const float* cmtd, int U, int N, int mem);
     void build_cat_cond(int U, int N);
-    void dit_eval(int U, int N, int k);                 // pred <- DiT(noise, cond, t_k)
-    void steps(int U, int N, int k0, int nsteps);       // Euler/CFG updates k0 .. k0+nsteps-1 (in d_noise)
+    // lens (device, int32 [U], nullptr = every utterance N rows): a ragged batch in padded slabs — utterance u is live in rows
+    // [0, lens[u]) of slab u (CFG items 2u, 2u + 1); the padded rows must come in zero and stay finite (see dit_eval)
+    void dit_eval(int U, int N, int k, const int* lens = nullptr);             // pred <- DiT(noise, cond, t_k)
+    void steps(int U, int N, int k0, int nsteps, const int* lens = nullptr);   // Euler/CFG updates k0 .. k0+nsteps-1 (in d_noise)
+    // ---- ragged batches: U utterances with their own prompt, text and max_duration, as slabs of Nmax = max N_u rows ----
+    DevBuf d_len;                    // int32 [U]: the live rows of each slab, uploaded before the loop (never captured)
+    std::vector<int> h_len;
+    int ref_frames(long L) const;    // mel frames of a prompt of L samples (the front end's R)
+    const int* set_lengths(int U, const int* lens);                            // -> d_len (asynchronous on `stream`)
+    void zero_pad_rows_cond(int U, int Nmax, const int* lens);                 // rows >= lens[u] of d_noise / d_cmt / d_cmtd slab u <- 0
+    // preprocess per utterance into slab u at its own N_u (zero-filled to Nmax); audio / text_ids / noise_in concatenated
+    void preprocess_ragged(int U, const int16_t* audio, const long* L, const int32_t* text_ids, const int* T, const int* Ns, int Nmax,
+                           const float* noise_in, uint64_t seed, int mem, int* R);
     long decode(const float* denoised_dev, int U, int N, int R, float* out_f, int16_t* out_i);  // device outputs
 };
 

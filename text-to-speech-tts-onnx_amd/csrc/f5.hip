@@ -742,7 +742,15 @@ void F5::build_cat_cond(int U, int N) {
         }
 }
 
-void F5::dit_eval(int U, int N, int k) {
+// lens != nullptr (ragged batch, padded slabs): every layer runs on the 2 U N rows as in the uniform case (each GEMM, norm and
+// the AdaLN fold is row-local, RoPE restarts at every slab), and the lengths enter in three places only:
+//   * the position convolution (k = 31) would carry padded rows into live ones near the end of a slab: its inputs (hin, c1)
+//     are zeroed in rows >= lens[u], the zero padding the reference sees at the end of the sequence;
+//   * attention masks keys >= lens[u] and writes zero rows for queries >= lens[u] (attention.hip, VARLEN);
+//   * the caller's update (launch_cfg_update_len) keeps the padded noise rows at zero.
+// The padded rows still pass through the GEMMs: they are finite (zero inputs) and deterministic, so the fp16 range watch never
+// sees them.  Every host-side choice depends on (U, N) alone: one captured graph serves every length mix.
+void F5::dit_eval(int U, int N, int k, const int* lens) {
     const F5Cfg& c = cfg;
     MI_REQUIRE(k >= 0 && k < c.nfe, "f5: time step out of range");
     hipStream_t s = stream;
@@ -754,6 +762,8 @@ void F5::dit_eval(int U, int N, int k) {
     gemm(dtype, cat.p, (long)N * ld, ld, ld, in_proj, h32.p, MI_F32, (long)N * d, d, B, N);
     const void* hin = h32.p;
     if (dtype != MI_F32) { launch_copy2d(h32.as<float>(), d, hT.p, d, rows, d, dtype, s); hin = hT.p; }
+    const long row_bytes = (long)d * (long)dtype_size(dtype);
+    if (lens) launch_zero_pad_rows(const_cast<void*>(hin), row_bytes, B, N, lens, 2, s);
     {
         ConvGemm g;
         g.dtype = dtype; g.x = hin; g.w = gconv1.w.p; g.bias = gconv1.b.as<float>(); g.out = c1.p;
@@ -761,6 +771,7 @@ void F5::dit_eval(int U, int N, int k) {
         g.x_bstride = (long)N * d; g.x_rstride = d; g.x_goff = d / c.pos_g; g.out_bstride = (long)N * d; g.out_rstride = d;
         g.act = ACT_MISH; g.sat = d_sat.as<int>(); g.gcp_w = gconv1.w3p.p;
         launch_conv_gemm(g, s);
+        if (lens) launch_zero_pad_rows(c1.p, row_bytes, B, N, lens, 2, s);
         g.x = c1.p; g.w = gconv2.w.p; g.bias = gconv2.b.as<float>(); g.out = X.p; g.out_dtype = MI_F32; g.res = h32.p; g.gcp_w = gconv2.w3p.p;
         launch_conv_gemm(g, s);
     }
@@ -834,7 +845,7 @@ void F5::dit_eval(int U, int N, int k) {
                 launch_conv_gemm(g, s);
             }
             launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             f32 ? Ap.p : nullptr, kvp ? kvp_fmt : 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f);
+                             f32 ? Ap.p : nullptr, kvp ? kvp_fmt : 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens);
             {
                 ConvGemm g = lin(bk.o, d, MI_F32, X.p);
                 g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d;
@@ -873,7 +884,7 @@ void F5::dit_eval(int U, int N, int k) {
                 launch_conv_gemm(g, s);
             }
             launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             Ap.p, kvp ? kvp_fmt : 0, np, 0.f);
+                             Ap.p, kvp ? kvp_fmt : 0, np, 0.f, lens);
             {
                 ConvGemm g = lin(bk.o, d, MI_F32, X.p);
                 g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d; with_planes(g, bk.o, Ap.p);
@@ -903,7 +914,7 @@ void F5::dit_eval(int U, int N, int k) {
             launch_conv_gemm(g, s);
         }
         launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                         nullptr, 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f);
+                         nullptr, 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens);
         gemm(dtype, Ob.p, (long)N * d, d, d, bk.o, X.p, MI_F32, (long)N * d, d, B, N, ACT_NONE, X.p, m + 2 * d);
         launch_rownorm(NORM_LN_MOD, X.as<float>(), Ub.p, dtype, m + 4 * d, m + 3 * d, rows, d, 1e-6f, s);
         gemm(dtype, Ub.p, (long)N * d, d, d, bk.ff1, Hff.p, dtype, (long)N * ff, ff, B, N, ACT_GELU_TANH);
@@ -929,10 +940,14 @@ const float* F5::pred_rows(int U, int N) {
     return pred_sum.as<float>();
 }
 
-void F5::steps_eager(int U, int N, int k0, int nsteps) {
+void F5::steps_eager(int U, int N, int k0, int nsteps, const int* lens) {
     for (int k = k0; k < k0 + nsteps; ++k) {
-        dit_eval(U, N, k);
-        launch_cfg_update(d_noise.as<float>(), pred.as<float>(), U, N, cfg.mel, cfg.cfg_strength, delta_t.as<float>(), k, stream, proj_parts);
+        dit_eval(U, N, k, lens);
+        if (lens)
+            launch_cfg_update_len(d_noise.as<float>(), pred.as<float>(), U, N, cfg.mel, cfg.cfg_strength, delta_t.as<float>(), k, lens, stream,
+                                  proj_parts);
+        else
+            launch_cfg_update(d_noise.as<float>(), pred.as<float>(), U, N, cfg.mel, cfg.cfg_strength, delta_t.as<float>(), k, stream, proj_parts);
     }
 }
 
@@ -964,18 +979,20 @@ void F5::recover() {
 
 // The reference drives 31 host round trips (F5-TTS-ONNX-Inference.py:291-304).  Here the whole loop is ~5000 kernel
 // launches on one stream with every operand resident in HBM; from the second use of a shape on it is captured once
-// into a hipGraph and replayed, which removes the per-launch host cost (launch-bound at batch 1).
-void F5::steps(int U, int N, int k0, int nsteps) {
+// into a hipGraph and replayed, which removes the per-launch host cost (launch-bound at batch 1).  A ragged batch (lens != nullptr,
+// always d_len) has graphs of its own, keyed like the uniform ones: the lengths are read from d_len when the graph runs.
+void F5::steps(int U, int N, int k0, int nsteps, const int* lens) {
     MI_REQUIRE(k0 >= 0 && nsteps >= 0 && k0 + nsteps <= cfg.nfe - 1, "f5: step range exceeds the NFE grid");
-    if (!use_graph || prof_mask() != 0 || nsteps < 2) { steps_eager(U, N, k0, nsteps); return; }
+    MI_REQUIRE(!lens || lens == d_len.p, "f5: ragged steps read the handle's length table");
+    if (!use_graph || prof_mask() != 0 || nsteps < 2) { steps_eager(U, N, k0, nsteps, lens); return; }
     if (graph_epoch != option_epoch()) { drop_graphs(); graph_epoch = option_epoch(); }
-    GraphEntry& e = graphs[{U, N, k0, nsteps}];
+    GraphEntry& e = graphs[{U, N, k0, nsteps, lens ? 1 : 0}];
     if (e.exec) { MI_HIP(hipGraphLaunch(e.exec, stream)); return; }
-    if (e.uses++ == 0) { steps_eager(U, N, k0, nsteps); return; }      // first use: eager (also warms one-time allocations)
+    if (e.uses++ == 0) { steps_eager(U, N, k0, nsteps, lens); return; }      // first use: eager (also warms one-time allocations)
     hipGraph_t graph = nullptr;
     MI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     try {
-        steps_eager(U, N, k0, nsteps);
+        steps_eager(U, N, k0, nsteps, lens);
     } catch (...) {
         (void)hipStreamEndCapture(stream, &graph);
         if (graph) (void)hipGraphDestroy(graph);
@@ -984,8 +1001,59 @@ void F5::steps(int U, int N, int k0, int nsteps) {
     MI_HIP(hipStreamEndCapture(stream, &graph));
     hipError_t err = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
-    if (err != hipSuccess) { e.exec = nullptr; use_graph = false; steps_eager(U, N, k0, nsteps); return; }
+    if (err != hipSuccess) { e.exec = nullptr; use_graph = false; steps_eager(U, N, k0, nsteps, lens); return; }
     MI_HIP(hipGraphLaunch(e.exec, stream));
+}
+
+int F5::ref_frames(long L) const {
+    const int mel_pad = cfg.mel_type == 1 ? (cfg.n_fft - cfg.hop) / 2 : cfg.n_fft / 2;      // as preprocess()
+    return (int)((L + 2 * mel_pad - cfg.n_fft) / cfg.hop) + 1;
+}
+
+const int* F5::set_lengths(int U, const int* lens) {
+    h_len.assign(lens, lens + U);               // member: outlives the asynchronous copy
+    if ((size_t)U * 4 > d_len.bytes) { drop_graphs(); d_len.ensure((size_t)std::max(U, 8) * 4); }      // captured graphs hold d_len.p
+    MI_HIP(hipMemcpyAsync(d_len.p, h_len.data(), (size_t)U * 4, hipMemcpyHostToDevice, stream));
+    return d_len.as<int>();
+}
+
+void F5::zero_pad_rows_cond(int U, int Nmax, const int* lens) {
+    const size_t cd = cfg.cond_dim(), M = cfg.mel;
+    for (int u = 0; u < U; ++u) {
+        const size_t n = (size_t)lens[u], pad = (size_t)(Nmax - lens[u]);
+        if (pad == 0) continue;
+        MI_HIP(hipMemsetAsync(d_noise.as<float>() + ((size_t)u * Nmax + n) * M, 0, pad * M * 4, stream));
+        MI_HIP(hipMemsetAsync(d_cmt.as<float>() + ((size_t)u * Nmax + n) * cd, 0, pad * cd * 4, stream));
+        MI_HIP(hipMemsetAsync(d_cmtd.as<float>() + ((size_t)u * Nmax + n) * cd, 0, pad * cd * 4, stream));
+    }
+}
+
+// Graph A per utterance (the front end is ~1 ms an utterance, not the hot path): preprocess() writes utterance u as a batch of one
+// at rows [0, N_u) of slab 0, from where it is copied to slab u.  The utterances go last to first, so slab 0's own run comes last
+// and nothing overwrites a slab that is already filled; the padded rows are cleared at the end.  The stream is drained after
+// each utterance: preprocess() reuses its temporaries and the host noise buffer, and a text id the device rejects is reported for
+// the utterance that holds it.
+void F5::preprocess_ragged(int U, const int16_t* audio, const long* L, const int32_t* text_ids, const int* T, const int* Ns, int Nmax,
+                           const float* noise_in, uint64_t seed, int mem, int* R) {
+    const size_t M = cfg.mel, cd = cfg.cond_dim();
+    MI_HIP(hipSetDevice(device));
+    ensure_workspace(U, Nmax);
+    std::vector<long> a_off(U + 1, 0), t_off(U + 1, 0), n_off(U + 1, 0);
+    for (int u = 0; u < U; ++u) { a_off[u + 1] = a_off[u] + L[u]; t_off[u + 1] = t_off[u] + T[u]; n_off[u + 1] = n_off[u] + Ns[u]; }
+    const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+    for (int u = U - 1; u >= 0; --u) {
+        const int N = Ns[u];
+        R[u] = preprocess(1, audio + a_off[u], L[u], text_ids + t_off[u], T[u], N, noise_in ? noise_in + (size_t)n_off[u] * M : nullptr,
+                          seed + (uint64_t)u, mem);
+        if (u > 0) {
+            MI_HIP(hipMemcpyAsync(d_noise.as<float>() + (size_t)u * Nmax * M, d_noise.p, (size_t)N * M * 4, d2d, stream));
+            MI_HIP(hipMemcpyAsync(d_cmt.as<float>() + (size_t)u * Nmax * cd, d_cmt.p, (size_t)N * cd * 4, d2d, stream));
+            MI_HIP(hipMemcpyAsync(d_cmtd.as<float>() + (size_t)u * Nmax * cd, d_cmtd.p, (size_t)N * cd * 4, d2d, stream));
+        }
+        MI_HIP(hipStreamSynchronize(stream));
+        check_text_ids();
+    }
+    zero_pad_rows_cond(U, Nmax, Ns);
 }
 
 long F5::decode(const float* den, int U, int N, int R, float* out_f, int16_t* out_i) {

@@ -35,6 +35,11 @@ void launch_istft_ola(const float* frames, const float* wsi, int U, int F, int n
                       int16_t* out_i, hipStream_t s);
 void launch_cat_noise(const float* noise, void* cat, int U, int N, int M, int ldc, int dtype, hipStream_t s);
 void launch_cfg_update(float* noise, const float* pred, int U, int N, int M, float cfg, const float* dt, int k, hipStream_t s, int parts = 1);
+// ragged batches (padded slabs of N rows, utterance u live in rows [0, len[u])): the same update, 0 in rows >= len[u]
+void launch_cfg_update_len(float* noise, const float* pred, int U, int N, int M, float cfg, const float* dt, int k, const int* len,
+                           hipStream_t s, int parts = 1);
+// x [items][N][row_bytes]: rows >= len[item / per] set to zero (16-byte stores; row_bytes % 16 == 0)
+void launch_zero_pad_rows(void* x, long row_bytes, int items, int N, const int* len, int per, hipStream_t s);
 void launch_sum_parts(const float* in, float* out, long rows, int M, int parts, hipStream_t s);
 
 // attention.hip: softmax_fp32(q k^T) v, no mask, no scale (q/k are pre-scaled): modules.py:467
@@ -45,7 +50,7 @@ void launch_sum_parts(const float* in, float* out, long rows, int M, int parts, 
 // counter per tile); without them every query tile is one workgroup
 void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
                       float* ws = nullptr, long ws_floats = 0, int* cnt = nullptr, long cnt_n = 0, void* o_planes = nullptr,
-                      int kv_planes = 0, int o_np = 3, float ref_fp16_scale = 0.f);
+                      int kv_planes = 0, int o_np = 3, float ref_fp16_scale = 0.f, const int* lens = nullptr);
 // ref_fp16_scale (f16 engines; 0 = off): the score rounding points of the reference's fp16-transformer export — q k scores
 // rounded to fp16, then x ref_fp16_scale (= 100, undoing the extra x0.1 folded into q and k) in fp32 (F5/fp16/modules.py:467)
 // kv_planes (fp32 engines, both products split): k and v are the pre-split bf16 planes the QKV epilogue wrote (ConvGemm::kv_planes:

@@ -637,6 +637,47 @@ void launch_cfg_update(float* noise, const float* pred, int U, int N, int M, flo
     MI_HIP(hipGetLastError());
 }
 
+// cfg_update_kernel for a ragged batch: utterance u is live in rows [0, len[u]) of its N-row slab; its padded rows stay zero
+__global__ __launch_bounds__(256) void cfg_update_len_kernel(float* __restrict__ noise, const float* __restrict__ pred,
+                                                             long NM, int M, int parts, long total, float cfg, const float* __restrict__ dt,
+                                                             int k, const int* __restrict__ len) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long u = i / NM, r = i - u * NM;
+    const long n = r / M; const int m = (int)(r - n * M);
+    if (n >= len[u]) { noise[i] = 0.f; return; }
+    const float* c = pred + ((2 * u) * NM + n * M) * parts + m;
+    const float* un = c + NM * parts;
+    float pc = c[0], pu = un[0];
+    for (int q = 1; q < parts; ++q) { pc += c[(long)q * M]; pu += un[(long)q * M]; }
+    noise[i] += (pc + (pc - pu) * cfg) * dt[k];
+}
+void launch_cfg_update_len(float* noise, const float* pred, int U, int N, int M, float cfg, const float* dt, int k, const int* len,
+                           hipStream_t s, int parts) {
+    const long total = (long)U * N * M;
+    hipLaunchKernelGGL(cfg_update_len_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, noise, pred, (long)N * M, M, parts,
+                       total, cfg, dt, k, len);
+    MI_HIP(hipGetLastError());
+}
+
+// Padded rows of a ragged batch (F5::dit_eval with lengths): x [items][N][row_bytes], rows [len[item / per], N) of every item set to
+// zero.  One workgroup per 8 rows of an item; the ones over live rows only return (the lengths live on the device: one launch
+// serves every length mix of a captured graph).
+__global__ __launch_bounds__(256) void zero_pad_rows_kernel(uint4* __restrict__ x, int row_vec, int N, const int* __restrict__ len, int per) {
+    const int item = (int)blockIdx.y, r0 = (int)blockIdx.x * 8;
+    const int live = len[item / per];
+    if (r0 + 8 <= live) return;
+    const int first = r0 > live ? r0 : live, last = r0 + 8 < N ? r0 + 8 : N;
+    uint4* base = x + (long)item * N * row_vec;
+    for (long i = (long)first * row_vec + threadIdx.x; i < (long)last * row_vec; i += 256) base[i] = make_uint4(0, 0, 0, 0);
+}
+void launch_zero_pad_rows(void* x, long row_bytes, int items, int N, const int* len, int per, hipStream_t s) {
+    MI_REQUIRE(row_bytes % 16 == 0 && items > 0 && N > 0 && per > 0, "zero_pad_rows: bad shape");
+    hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((N + 7) / 8), (unsigned)items), dim3(256), 0, s, (uint4*)x, (int)(row_bytes / 16),
+                       N, len, per);
+    MI_HIP(hipGetLastError());
+}
+
 // out[row][m] = sum over the slices of in[row][q][m], in slice order (the export of F5::pred_rows)
 __global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ in, float* __restrict__ out, long total, int M, int parts) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

@@ -104,6 +104,12 @@ void prof_set_kernel(const char* expr, const char* t, const char* to) {
     std::lock_guard<std::mutex> lk(g_pm);
     g_cur_kernel = &g_kstat.emplace(n, KStat{}).first->first;
 }
+void prof_kernel_suffix(const char* sfx) {
+    if (!g_prof_mask || !g_cur_kernel) return;
+    const std::string n = *g_cur_kernel + sfx;
+    std::lock_guard<std::mutex> lk(g_pm);
+    g_cur_kernel = &g_kstat.emplace(n, KStat{}).first->first;
+}
 
 ProfScope::ProfScope(int family, hipStream_t stream, double bytes, double flops) : fam(family), s(stream) {
     on = (g_prof_mask >> fam) & 1u;

@@ -24,6 +24,32 @@ def _p(a):
     return None if a is None else a.ctypes.data
 
 
+def ragged_layout(cfg: F5Config, audio_lens, text_lens, max_durations):
+    """Host-side plan of a ragged batch (F5Engine.synthesize_ragged): per utterance the prompt's frames R_u
+    (cfg.ref_frames), the generated frames F_u = N_u - R_u and the waveform length (N_u - R_u - 1) * hop, and the slab
+    height Nmax = max N_u.  Raises ValueError for inputs the engine would refuse, before the GPU is touched."""
+    L = [int(x) for x in audio_lens]
+    T = [int(x) for x in text_lens]
+    N = [int(x) for x in max_durations]
+    if not L or len(T) != len(L) or len(N) != len(L):
+        raise ValueError("ragged batch: audio_lens, text_lens and max_durations need one entry per utterance (at least one)")
+    R, F, out = [], [], []
+    for u, (l, t, n) in enumerate(zip(L, T, N)):
+        if l < cfg.n_fft // 2 + 1 or cfg.ref_frames(l) < 1:
+            raise ValueError(f"utterance {u}: prompt audio of {l} samples is shorter than one STFT frame")
+        if t < 0:
+            raise ValueError(f"utterance {u}: negative text length")
+        r = cfg.ref_frames(l)
+        if n < r + 1:
+            raise ValueError(f"utterance {u}: max_duration {n} leaves no generated frame after {r} prompt frames")
+        if n < t:
+            raise ValueError(f"utterance {u}: max_duration {n} is shorter than the text ({t} ids)")
+        if n > cfg.max_signal_length:
+            raise ValueError(f"utterance {u}: max_duration {n} exceeds max_signal_length {cfg.max_signal_length}")
+        R.append(r); F.append(n - r); out.append((n - r - 1) * cfg.hop_length)
+    return R, F, out, max(N)
+
+
 class F5Engine:
     def __init__(self, cfg: F5Config, state: Optional[dict] = None, *, blob: Optional[np.ndarray] = None,
                  blob_device=None, dtype: str = "f32", device: int = 0):
@@ -235,6 +261,60 @@ class F5Engine:
                    "mi_f5_synthesize")
         assert ln.value == n
         return out
+
+    def synthesize_ragged(self, audios, text_ids, max_durations, noise=None, seed: int = 9527):
+        """U utterances of different lengths in one sampling loop: audios[u] int16 (L_u,), text_ids[u] (T_u,), max_durations[u]
+        = N_u, noise None or a list of (N_u, 100) -> list of int16 (1, (N_u - R_u - 1) * hop), each the waveform `synthesize`
+        gives for that utterance alone (noise None: utterance u draws with seed + u, as in the uniform batch)."""
+        cfg = self.cfg
+        audios = [np.ascontiguousarray(np.asarray(a).reshape(-1)) for a in audios]
+        if any(a.dtype != np.int16 for a in audios):
+            raise ValueError("audio must be int16")
+        ids = [np.ascontiguousarray(np.asarray(t).reshape(-1), dtype=np.int32) for t in text_ids]
+        if len(ids) != len(audios) or len(max_durations) != len(audios):
+            raise ValueError("audios / text_ids / max_durations batch mismatch")
+        _, _, out_lens, _ = ragged_layout(cfg, [a.size for a in audios], [t.size for t in ids], max_durations)
+        U = len(audios)
+        N = [int(n) for n in max_durations]
+        if noise is not None:
+            if len(noise) != U:
+                raise ValueError("noise: one (N_u, 100) array per utterance")
+            noise = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(N[u], cfg.mel_dim) for u, x in enumerate(noise)]))
+        a = np.ascontiguousarray(np.concatenate(audios))
+        t = np.ascontiguousarray(np.concatenate(ids)) if sum(x.size for x in ids) else np.zeros(1, np.int32)
+        al = np.asarray([x.size for x in audios], np.int64)
+        tl = np.asarray([x.size for x in ids], np.int64)
+        nl = np.asarray(N, np.int64)
+        out = np.empty(max(sum(out_lens), 1), np.int16)
+        lens = np.zeros(U, np.int64)
+        _lib.check(_lib.load().mi_f5_synthesize_ragged(self._h, U, a.ctypes.data, al.ctypes.data, t.ctypes.data, tl.ctypes.data,
+                                                       nl.ctypes.data, _p(noise), seed, out.ctypes.data, out.size, lens.ctypes.data,
+                                                       _lib.MI_HOST), "mi_f5_synthesize_ragged")
+        assert list(lens) == out_lens, (list(lens), out_lens)
+        offs = np.concatenate([[0], np.cumsum(out_lens)])
+        return [out[offs[u]:offs[u + 1]].reshape(1, -1).copy() for u in range(U)]
+
+    def dit_eval_ragged(self, noises, cmts, cmtds, k: int):
+        """One DiT evaluation of a ragged batch: noises[u] (N_u, 100), cmts[u] / cmtds[u] (N_u, 612) -> list of (2, N_u, 100)
+        (cond branch first).  Padded into (U, max N_u, .) slabs on the way in, stripped on the way out."""
+        cfg = self.cfg
+        U = len(noises)
+        if U < 1 or len(cmts) != U or len(cmtds) != U:
+            raise ValueError("noises / cmts / cmtds batch mismatch")
+        N = [int(np.asarray(x).shape[0]) for x in noises]
+        Nmax, cd = max(N), cfg.mel_dim + cfg.text_dim
+        x = np.zeros((U, Nmax, cfg.mel_dim), np.float32)
+        c = np.zeros((U, Nmax, cd), np.float32)
+        d = np.zeros((U, Nmax, cd), np.float32)
+        for u in range(U):
+            x[u, :N[u]] = np.asarray(noises[u], np.float32).reshape(N[u], cfg.mel_dim)
+            c[u, :N[u]] = np.asarray(cmts[u], np.float32).reshape(N[u], cd)
+            d[u, :N[u]] = np.asarray(cmtds[u], np.float32).reshape(N[u], cd)
+        lens = np.asarray(N, np.int64)
+        pred = np.empty((2 * U, Nmax, cfg.mel_dim), np.float32)
+        _lib.check(_lib.load().mi_f5_dit_eval_ragged(self._h, U, lens.ctypes.data, x.ctypes.data, c.ctypes.data, d.ctypes.data, Nmax, k,
+                                                     pred.ctypes.data, _lib.MI_HOST), "mi_f5_dit_eval_ragged")
+        return [pred[2 * u:2 * u + 2, :N[u]].copy() for u in range(U)]
 
     def synthesize_mel(self, audio, text_ids, max_duration, noise=None, seed: int = 9527):
         """A -> loop, generated frames as a vocoder mel: float32 (U, 100, N - R), channels first — what

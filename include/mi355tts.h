@@ -79,6 +79,19 @@ int         mi_bigvgan_forward_f32(mi_bigvgan* h, const float* mel, int B, int f
  * bigvgan_cond_layer_speaker_embedding, concatenated (n_conds floats).  out: int16 (1,1,(T_codes-2)*hop+30).            */
 int         mi_bigvgan_forward_latent(mi_bigvgan* h, const float* latent, int T_codes, const float* conds, int64_t n_conds,
                                       int16_t* out, float* out_f32, int mem);
+/* Ragged batch: B items of different lengths in one forward.  frames[b] = F_b (host int64); mel = the items' (num_mels, F_b)
+ * channels-first arrays concatenated.  out_i16 (and out_f32 when not NULL) receive the waveforms concatenated, out_lens[b] =
+ * F_b * hop + 30; data arrays follow `mem`.  The batch runs as padded slabs of Fmax = max F_b frames; every layer stores zeros
+ * past an item's live rows, so item b gets the waveform a forward of it alone gives.  MI_EINVAL, with the handle still usable,
+ * for B < 1, F_b < 1, Fmax past the uniform path's limit, out_cap below the sum of out_lens, or a graph-F handle.           */
+int         mi_bigvgan_forward_ragged(mi_bigvgan* h, int B, const float* mel, const int64_t* frames, int16_t* out_i16,
+                                      float* out_f32, int64_t out_cap, int64_t* out_lens, int mem);
+/* ... and IndexTTS graph F for B sentences of one speaker: latent = the items' (t_codes[b], gpt_dim) rows concatenated (the last
+ * two rows of each are dropped, like mi_bigvgan_forward_latent; t_codes[b] >= 3, host int64); one conditioning vector for all
+ * items, in the layout of mi_bigvgan_forward_latent.  out_lens[b] = (t_codes[b] - 2) * hop + 30.                            */
+int         mi_bigvgan_forward_latent_ragged(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, const float* conds,
+                                             int64_t n_conds, int16_t* out_i16, float* out_f32, int64_t out_cap, int64_t* out_lens,
+                                             int mem);
 /* unit-level entry (tests): one anti-aliased SnakeBeta Activation1d on x (B,C,T) fp32
  * channels-first host memory; post!=0 selects the pad-15 variant (out T+30).                   */
 int         mi_aa_activation1d(const float* x, int B, int C, int T, const float* alpha_log,
@@ -177,6 +190,12 @@ int         mi_f5_synthesize_mel(mi_f5* h, int U, const int16_t* audio, int64_t 
 int         mi_f5_synthesize_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
                                     const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed,
                                     int16_t* out, int64_t out_cap, int64_t* out_lens, int mem);
+/* The same ragged batch handed on as mels for a vocoder engine: utterance u's generated frames [R_u, N_u) leave as (100, N_u - R_u)
+ * fp32 channels first, concatenated in mel_out (mel_cap floats) — exactly the `mel` of mi_bigvgan_forward_ragged, whose frames
+ * are n_frames[u] = N_u - R_u (host int64).  Inputs and checks as mi_f5_synthesize_ragged.                                   */
+int         mi_f5_synthesize_mel_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
+                                        const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed,
+                                        float* mel_out, int64_t mel_cap, int64_t* n_frames, int mem);
 /* tests: one DiT evaluation of a ragged batch at grid index k.  noise (U, Nmax, 100), cat_mel_text(_drop) (U, Nmax, 612) in
  * the padded layout (rows >= lens[u] are ignored), lens host int64 in [1, Nmax] -> pred (2U, Nmax, 100), cond branch first;
  * only rows < lens[u] of items 2u, 2u + 1 are defined.                                                                  */

@@ -65,11 +65,14 @@ const float* aa_filter_host() {
     return g_taps;
 }
 
-template <typename T, int R>
+// LENS (ragged batches): item b holds Tb = lens[b] * len_mul + len_add live input rows (zeros after them, slab of Tlen rows); its
+// output rows >= Tb + 2 * shift are stored as zeros and a tile wholly past them loads and computes nothing
+template <typename T, int R, bool LENS = false>
 __global__ __launch_bounds__(256) void aa_act_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                      const float* __restrict__ alpha,
                                                      const float* __restrict__ inv_beta, int Tlen, int C, int CT,
-                                                     int TT, int shift, int ext) {
+                                                     int TT, int shift, int ext, const int* lens = nullptr, int len_mul = 1,
+                                                     int len_add = 0) {
     constexpr int VEC = 16 / (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     T* xs = reinterpret_cast<T*>(lds_raw);                // (TT+10) x CT  raw input (16-byte copies, no bank conflicts)
@@ -83,15 +86,26 @@ __global__ __launch_bounds__(256) void aa_act_kernel(const T* __restrict__ x, T*
     const int mp0 = o0 - shift;               // centred index m' of the first output row
     const T* xb = x + (long)b * Tlen * C;
     T* yb = y + (long)b * Tout * C;
+    const int cvn = CT / VEC;
+    int Tb = Tlen;
+    if constexpr (LENS) {
+        Tb = __builtin_amdgcn_readfirstlane(lens[b] * len_mul + len_add);
+        if (o0 >= Tb + 2 * shift) {           // workgroup-uniform: a dead tile stores its zeros only
+            for (int v = tid; v < TT * cvn; v += 256) {
+                const int row = v / cvn, cv = v - row * cvn;
+                if (o0 + row < Tout) *reinterpret_cast<uint4*>(yb + (long)(o0 + row) * C + c0 + cv * VEC) = make_uint4(0, 0, 0, 0);
+            }
+            return;
+        }
+    }
 
     // ---- stage x rows [mp0-5, mp0+TT+5) ------------------------------------------------------
-    const int cvn = CT / VEC;
     const int nvec = (TT + 10) * cvn;
     for (int v = tid; v < nvec; v += 256) {
         const int row = v / cvn, cv = v - row * cvn;
         const int t = mp0 - 5 + row;
         uint4 raw = make_uint4(0, 0, 0, 0);
-        if (t >= 0 && t < Tlen) raw = *reinterpret_cast<const uint4*>(xb + (long)t * C + c0 + cv * VEC);
+        if (t >= 0 && t < Tb) raw = *reinterpret_cast<const uint4*>(xb + (long)t * C + c0 + cv * VEC);
         *reinterpret_cast<uint4*>(xs + row * CT + cv * VEC) = raw;
     }
     __syncthreads();
@@ -99,7 +113,7 @@ __global__ __launch_bounds__(256) void aa_act_kernel(const T* __restrict__ x, T*
     // ---- sliding-window compute (aa_math.h) ------------------------------------------------------
     constexpr bool FAST = sizeof(T) == 2;           // 16-bit storage: v_sin_f32; fp32 parity path: libm sinf
     const AATaps tp = aa_make_taps(c_h);
-    const int lo = -ext, hi = 2 * Tlen + ext;
+    const int lo = -ext, hi = 2 * Tb + ext;
     const bool edge = (2 * (mp0 - 3) - 1 < lo) || (2 * (mp0 + TT + 3) >= hi);      // block-uniform
     // two adjacent channels per work item (CT is even): one LDS access moves a channel pair, and the packed FMAs of
     // aa_math.h carry the pair in their two halves
@@ -134,9 +148,11 @@ __global__ __launch_bounds__(256) void aa_act_kernel(const T* __restrict__ x, T*
     for (int v = tid; v < nout; v += 256) {
         const int row = v / cvn, cv = v - row * cvn;
         const int o = o0 + row;
-        if (o < Tout)
-            *reinterpret_cast<uint4*>(yb + (long)o * C + c0 + cv * VEC) =
-                *reinterpret_cast<const uint4*>(ys + row * CT + cv * VEC);
+        if (o < Tout) {
+            uint4 val = *reinterpret_cast<const uint4*>(ys + row * CT + cv * VEC);
+            if constexpr (LENS) if (o >= Tb + 2 * shift) val = make_uint4(0, 0, 0, 0);
+            *reinterpret_cast<uint4*>(yb + (long)o * C + c0 + cv * VEC) = val;
+        }
     }
 }
 
@@ -151,10 +167,12 @@ __global__ __launch_bounds__(256) void aa_act_kernel(const T* __restrict__ x, T*
 // -----------------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void aa_lds_void;
 
-template <typename T, int R>
+// LENS: as aa_act_kernel.  A dead tile (wholly past its item's live rows) gets no DMA and no compute, only its zero stores.
+template <typename T, int R, bool LENS = false>
 __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ alpha,
                                                           const float* __restrict__ inv_beta, int Tlen, int C, int CT, int TT,
-                                                          int shift, int ext, int ntt, int nct, int ntiles, int xsp) {
+                                                          int shift, int ext, int ntt, int nct, int ntiles, int xsp,
+                                                          const int* lens = nullptr, int len_mul = 1, int len_add = 0) {
     constexpr int VEC = 16 / (int)sizeof(T);
     static_assert(sizeof(T) == 2, "16-bit storage");
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_raw[];
@@ -189,10 +207,30 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
         }
 #endif
     };
+    // LENS: live input rows of a tile's item (workgroup-uniform), and whether the tile lies wholly past its live output rows
+    auto live_in = [&](int b) -> int { return LENS ? __builtin_amdgcn_readfirstlane(lens[b] * len_mul + len_add) : Tlen; };
+    auto dead = [&](int t) -> bool {
+        if constexpr (!LENS) return false;
+        int o0, c0, b;
+        decode(t, o0, c0, b);
+        return o0 >= live_in(b) + 2 * shift;
+    };
     auto store = [&](int t) {
         int o0, c0, b;
         decode(t, o0, c0, b);
         T* yb = y + (long)b * Tout * C;
+        if constexpr (LENS) {
+            const int tob = live_in(b) + 2 * shift;
+            for (int v = tid; v < nout; v += 256) {
+                const int row = v / cvn, cv = v - row * cvn;
+                const int o = o0 + row;
+                if (o < Tout) {
+                    const uint4 val = o < tob ? *reinterpret_cast<const uint4*>(ys + row * CT + cv * VEC) : make_uint4(0, 0, 0, 0);
+                    *reinterpret_cast<uint4*>(yb + (long)o * C + c0 + cv * VEC) = val;
+                }
+            }
+            return;
+        }
         for (int v = tid; v < nout; v += 256) {
             const int row = v / cvn, cv = v - row * cvn;
             const int o = o0 + row;
@@ -203,18 +241,22 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
 
     int t = blockIdx.x;
     if (t >= ntiles) return;
-    dma(t, 0);
+    if (!dead(t)) dma(t, 0);
     int buf = 0, tprev = -1;
     for (; t < ntiles; t += gridDim.x) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this tile's rows have landed (this wave's share); the stores before them too
         __syncthreads();
         if (tprev >= 0) store(tprev);                         // the previous tile leaves while this one is computed
         __syncthreads();                                      // ys is free again
-        if (t + (int)gridDim.x < ntiles) dma(t + gridDim.x, buf ^ 1);      // that buffer's tile was computed before the first barrier
+        if (t + (int)gridDim.x < ntiles && !dead(t + gridDim.x)) dma(t + gridDim.x, buf ^ 1);      // that buffer's tile was computed before the first barrier
         int o0, c0, b;
         decode(t, o0, c0, b);
+        if constexpr (LENS) {
+            if (o0 >= live_in(b) + 2 * shift) { tprev = t; buf ^= 1; continue; }      // dead: store() writes its zeros
+        }
         const int mp0 = o0 - shift;
-        const bool edge = (2 * (mp0 - 3) - 1 < lo) || (2 * (mp0 + TT + 3) >= hi);      // workgroup-uniform
+        const int hi_b = LENS ? 2 * live_in(b) + ext : hi;
+        const bool edge = (2 * (mp0 - 3) - 1 < lo) || (2 * (mp0 + TT + 3) >= hi_b);      // workgroup-uniform
         const T* xs = xs0 + buf * xsp;
         for (int it = tid; it < nitems; it += 256) {
             const int run = it / CP, c = 2 * (it - run * CP);
@@ -233,8 +275,8 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
                     pr.a = from_f32<T>(v.x); pr.b = from_f32<T>(v.y);
                     *reinterpret_cast<Pair*>(ys + (ml + r) * CT + c) = pr;
                 };
-                if (edge) aa_run_stream<R, true, true>(ld, st, tp, al, ib, mp0 + ml, lo, hi);
-                else aa_run_stream<R, true, false>(ld, st, tp, al, ib, mp0 + ml, lo, hi);
+                if (edge) aa_run_stream<R, true, true>(ld, st, tp, al, ib, mp0 + ml, lo, hi_b);
+                else aa_run_stream<R, true, false>(ld, st, tp, al, ib, mp0 + ml, lo, hi_b);
                 continue;
             }
             aa_f2 xv[R + 10], acc[R];
@@ -243,8 +285,8 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
                 const Pair pr = *reinterpret_cast<const Pair*>(xs + (ml + j) * CT + c);
                 xv[j] = aa_f2{to_f32(pr.a), to_f32(pr.b)};
             }
-            if (edge) aa_run<R, true, true>(xv, acc, tp, al, ib, mp0 + ml, lo, hi);
-            else aa_run<R, true, false>(xv, acc, tp, al, ib, mp0 + ml, lo, hi);
+            if (edge) aa_run<R, true, true>(xv, acc, tp, al, ib, mp0 + ml, lo, hi_b);
+            else aa_run<R, true, false>(xv, acc, tp, al, ib, mp0 + ml, lo, hi_b);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 Pair pr;
@@ -313,7 +355,15 @@ static void launch_t(const AAAct& p, hipStream_t s) {
             if (per_cu >= 1 && lds2 <= 64 * 1024 && ntiles < 0x7fffffffL) {
                 const int grid_p = (int)std::min<long>(ntiles, (long)cus * per_cu);
                 prof_set_kernel("aa_act_pipe_kernel<T>", type_label<T>());
-                if (RP == 16)
+                if (p.lens) {
+                    prof_kernel_suffix(" + lengths");
+                    if (RP == 16)
+                        hipLaunchKernelGGL((aa_act_pipe_kernel<T, 16, true>), dim3(grid_p), dim3(256), lds2, s, (const T*)p.x, (T*)p.y, p.alpha,
+                                           p.inv_beta, p.T, p.C, CT, TT, shift, ext, ntt, nct, (int)ntiles, xsp, p.lens, p.len_mul, p.len_add);
+                    else
+                        hipLaunchKernelGGL((aa_act_pipe_kernel<T, 8, true>), dim3(grid_p), dim3(256), lds2, s, (const T*)p.x, (T*)p.y, p.alpha,
+                                           p.inv_beta, p.T, p.C, CT, TT, shift, ext, ntt, nct, (int)ntiles, xsp, p.lens, p.len_mul, p.len_add);
+                } else if (RP == 16)
                     hipLaunchKernelGGL((aa_act_pipe_kernel<T, 16>), dim3(grid_p), dim3(256), lds2, s, (const T*)p.x, (T*)p.y, p.alpha, p.inv_beta,
                                        p.T, p.C, CT, TT, shift, ext, ntt, nct, (int)ntiles, xsp);
                 else
@@ -325,8 +375,13 @@ static void launch_t(const AAAct& p, hipStream_t s) {
         }
     }
     prof_set_kernel("aa_act_kernel<T>", type_label<T>());
-    hipLaunchKernelGGL((aa_act_kernel<T, R>), grid, dim3(256), lds, s, (const T*)p.x, (T*)p.y, p.alpha, p.inv_beta,
-                       p.T, p.C, CT, TT, shift, ext);
+    if (p.lens) {
+        prof_kernel_suffix(" + lengths");
+        hipLaunchKernelGGL((aa_act_kernel<T, R, true>), grid, dim3(256), lds, s, (const T*)p.x, (T*)p.y, p.alpha, p.inv_beta,
+                           p.T, p.C, CT, TT, shift, ext, p.lens, p.len_mul, p.len_add);
+    } else
+        hipLaunchKernelGGL((aa_act_kernel<T, R>), grid, dim3(256), lds, s, (const T*)p.x, (T*)p.y, p.alpha, p.inv_beta,
+                           p.T, p.C, CT, TT, shift, ext);
     MI_HIP(hipGetLastError());
 }
 

@@ -32,9 +32,12 @@ struct AAConvDev {
     float alpha; int accumulate;
     int w_off;    // element offset of the weight ring inside the LDS block (0: aliases the dead raw-input region)
     int dbg;      // tuning: bit0 skip AA math, bit1 skip MFMA loop, bit2 skip epilogue global traffic
+    const int* lens; int len_mul, len_add;      // ragged batches (LENS kernels): item b has lens[b] * len_mul + len_add live rows
 };
 
-template <typename T, int BM, int TN>
+// LENS (ragged batches): rows >= Tb (item b's live rows; zeros in the input) are the conv's zero padding and are stored as zeros;
+// a tile wholly past Tb loads and computes nothing
+template <typename T, int BM, int TN, bool LENS = false>
 __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
     using MF = Mfma<T>;
     constexpr int KP = MF::KP;
@@ -51,6 +54,19 @@ __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
     const int m0 = blockIdx.x * BM;
     const int C = p.C, S = p.S;
     const T* xb = (const T*)p.x + (long)b * p.T * C;
+    int Tb = p.T;
+    if constexpr (LENS) {
+        Tb = __builtin_amdgcn_readfirstlane(p.lens[b] * p.len_mul + p.len_add);
+        if (m0 >= Tb) {                                              // workgroup-uniform: a dead tile stores its zeros only
+            const int cvn = C / VEC;
+            T* ob = (T*)p.out + (long)b * p.T * C;
+            for (int v = tid; v < BM * cvn; v += 256) {
+                const int row = v / cvn, cv = v - row * cvn;
+                if (m0 + row < p.T) *reinterpret_cast<uint4*>(ob + (long)(m0 + row) * C + cv * VEC) = make_uint4(0, 0, 0, 0);
+            }
+            return;
+        }
+    }
 
     // ---- 1. stage x rows [m0 - halo - 5, ...) ---------------------------------------------------------
     {
@@ -60,7 +76,7 @@ __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
             const int row = v / cvn, cv = v - row * cvn;
             const int t = t_base + row;
             uint4 raw = make_uint4(0, 0, 0, 0);
-            if (t >= 0 && t < p.T) raw = *reinterpret_cast<const uint4*>(xb + (long)t * C + cv * VEC);
+            if (t >= 0 && t < Tb) raw = *reinterpret_cast<const uint4*>(xb + (long)t * C + cv * VEC);
             *reinterpret_cast<uint4*>(XS + row * C + cv * VEC) = raw;
         }
     }
@@ -71,7 +87,7 @@ __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
         const AATaps tp = aa_make_taps(c_h_fused);
         const int runs = (p.rows_act + R - 1) / R;
         const int t_act0 = m0 - p.halo;                              // global time of activated row 0
-        const int hi2 = 2 * p.T;
+        const int hi2 = 2 * Tb;
         const bool edge = (2 * (t_act0 - 3) - 1 < 0) || (2 * (t_act0 + runs * R + 3) >= hi2);
         // two adjacent channels per work item: every LDS access moves a channel PAIR (the 2-byte-per-lane version was
         // bound by LDS instruction issue, not by the FIR math)
@@ -105,7 +121,7 @@ __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
                 const int row = ml + r;
                 if (row < p.rows_act) {
                     const int t = mp + r;
-                    const bool in = t >= 0 && t < p.T;
+                    const bool in = t >= 0 && t < Tb;
                     Pair pr;
                     pr.a = from_f32<T>(in ? o[r].x : 0.f); pr.b = from_f32<T>(in ? o[r].y : 0.f);
                     *reinterpret_cast<Pair*>(AS + row * S + c) = pr;
@@ -246,7 +262,9 @@ __global__ __launch_bounds__(256) void aa_conv_kernel(const AAConvDev p) {
             T ov[VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) ov[e] = from_f32<T>(o[e]);
-            *reinterpret_cast<uint4*>(ob + gi) = *reinterpret_cast<const uint4*>(ov);
+            uint4 val = *reinterpret_cast<const uint4*>(ov);
+            if constexpr (LENS) if (t >= Tb) val = make_uint4(0, 0, 0, 0);
+            *reinterpret_cast<uint4*>(ob + gi) = val;
         }
     }
 }
@@ -264,6 +282,7 @@ static void launch_t(const AAConv& q, hipStream_t s) {
     d.S = ((q.C / 8) & 1) ? q.C : q.C + 8;             // S/8 odd => conflict-free ds_read_b128 fragment rows
     if (sizeof(T) == 4) d.S = (q.C % 2 == 0) ? q.C + 1 : q.C;   // fp32 fragments are ds_read_b32: odd dword stride
     d.alpha = q.alpha; d.accumulate = q.accumulate;
+    d.lens = q.lens; d.len_mul = q.len_mul; d.len_add = q.len_add;
     { const char* e = std::getenv("MI355TTS_AACONV_DBG"); d.dbg = e ? std::atoi(e) : 0; }
     const int BM = q.C <= 48 ? 256 : 128;
     d.rows_act = BM + 2 * d.halo;
@@ -300,10 +319,11 @@ static void launch_t(const AAConv& q, hipStream_t s) {
                  2.0 * q.B * (double)q.T * q.C * d.K + 60.0 * q.B * (double)q.T * q.C);
 #define LAUNCH(BMv, TNv)                                                                                         \
     do {                                                                                                         \
-        auto kfn = aa_conv_kernel<T, BMv, TNv>;                                                                  \
+        auto kfn = q.lens ? aa_conv_kernel<T, BMv, TNv, true> : aa_conv_kernel<T, BMv, TNv>;                     \
         /* the opt-in is per DEVICE and cheap: set whenever needed (a process-wide flag would skip device 1) */ \
         if (lds > 64 * 1024) MI_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
         prof_set_kernel("aa_conv_kernel<T, " #BMv ", " #TNv ">", type_label<T>());                                \
+        if (q.lens) prof_kernel_suffix(" + lengths");                                                            \
         hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, d);                                                     \
     } while (0)
     if (BM == 256) { if (TN == 1) LAUNCH(256, 1); else LAUNCH(256, 2); }

@@ -52,9 +52,21 @@ struct BigVGAN {
     int fused_max_c = 96;
     bool use_fused = true;     // MI355TTS_NO_FUSED_AA=1 selects the unfused AA + conv path (A/B and debugging)
     void run(const float* mel, int B, int F, float* out_f32, int16_t* out_i16, int mem);
+    // ragged batches (padded slabs of Fmax frames, item b live in its first frames[b]): mel = the items' (num_mels, frames[b])
+    // arrays concatenated; the waveforms (frames[b] * hop + 30 samples each) leave concatenated in the same order
+    void run_ragged(const float* mel, int B, const int* frames, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
+    // ... and graph F: latent = the items' (T_codes[b], num_mels) rows concatenated, one conditioning vector for all items
+    void run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
+                           int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
     // IndexTTS graph F: latent (T_codes, num_mels) channels-last fp32, conds = [cond_0 .. cond_{n_up-1}, cond_pre] concatenated
     void run_latent(const float* latent, int T_codes, const float* conds, long n_conds, float* out_f32, int16_t* out_i16, int mem);
     void body(const void* x0, int B, int F, const float* const* cond_ptrs, float* out_f32, int16_t* out_i16, int mem);
+    // lengths of the current ragged call (null: uniform): d_frames = F_b per item; every launch of body() gets the table with
+    // the (mul, add) of its resolution; conv_post writes item b from sample d_out_offs[b] of the output (total samples)
+    const int* ln = nullptr; int ln_mul = 1;
+    DevBuf d_frames, d_in_offs, d_out_offs;
+    const long* out_offs = nullptr; long out_total = 0;
+    std::vector<long> ragged_tables(int B, const int* frames, long extra_rows);   // checks + uploads; returns the output offsets
     long total_cond() const;
     DevBuf ln_w, ln_b, d_latent;
 };

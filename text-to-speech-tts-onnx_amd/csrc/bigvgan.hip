@@ -13,6 +13,7 @@
 #include "common.h"
 #include "bigvgan.h"
 #include "f5_kernels.h"
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 
@@ -218,6 +219,7 @@ void BigVGAN::conv(const ConvW& cw, const void* x, void* out, int B, int T, int 
     p.B = B; p.T_in = T; p.M = T; p.N = Cout; p.Cin = Cin; p.taps = k; p.dil = dil; p.pad = (k * dil - dil) / 2;
     p.x_bstride = (long)T * Cin; p.x_rstride = Cin; p.out_bstride = (long)T * Cout; p.out_rstride = Cout;
     p.alpha = alpha; p.accumulate = accumulate;
+    p.lens = ln; p.len_mul = ln_mul;
     launch_conv_gemm(p, ls ? ls : stream);
 }
 
@@ -227,6 +229,7 @@ void BigVGAN::aa_conv(const SnakeP& sp, const ConvW& cw, const void* x, void* ou
     a.dtype = dtype; a.x = x; a.w = cw.w.p; a.bias = cw.b.as<float>(); a.snake_alpha = sp.alpha.as<float>();
     a.snake_inv_beta = sp.inv_beta.as<float>(); a.out = out; a.res = res; a.B = B; a.T = T; a.C = C; a.k = k; a.dil = dil;
     a.alpha = alpha; a.accumulate = accumulate;
+    a.lens = ln; a.len_mul = ln_mul;
     launch_aa_conv(a, ls ? ls : stream);
 }
 
@@ -234,6 +237,7 @@ void BigVGAN::aa(const SnakeP& sp, const void* x, void* y, int B, int T, int C, 
     AAAct a;
     a.dtype = dtype; a.x = x; a.y = y; a.alpha = sp.alpha.as<float>(); a.inv_beta = sp.inv_beta.as<float>();
     a.B = B; a.T = T; a.C = C; a.post = post;
+    a.lens = ln; a.len_mul = ln_mul;
     launch_aa_act(a, ls ? ls : stream);
 }
 
@@ -289,6 +293,102 @@ void BigVGAN::run_latent(const float* latent, int T_codes, const float* conds, l
     body(bT1.p, 1, F, ptrs.data(), out_f32, out_i16, mem);
 }
 
+// Ragged batches: item b owns slab b of Fmax frames at every layer and every launch gets the frame table with the
+// (mul, add) of its resolution, so that each buffer a layer writes holds exact zeros in the rows past the item's live rows
+// (F_b * prod(rates[0..i]) inside stage i, F_b * hop + 30 after the post activation).  The next layer's zero padding then sees
+// what a solo run sees at the item's end, and stale workspace never reaches a live row.  Host decisions depend on (B, Fmax) only.
+std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_rows) {
+    std::vector<long> in_offs(B), out_offs(B + 1, 0);
+    long acc = 0;
+    for (int b = 0; b < B; ++b) {
+        in_offs[b] = acc;
+        acc += frames[b] + extra_rows;
+        out_offs[b + 1] = out_offs[b] + (long)frames[b] * cfg.hop + 30;
+    }
+    d_frames.ensure((size_t)B * 4); d_in_offs.ensure((size_t)B * 8); d_out_offs.ensure((size_t)B * 8);
+    MI_HIP(hipMemcpyAsync(d_frames.p, frames, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(d_in_offs.p, in_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(d_out_offs.p, out_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipStreamSynchronize(stream));                // the host tables are temporaries
+    return out_offs;
+}
+
+void BigVGAN::run_ragged(const float* mel, int B, const int* frames, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens,
+                         int mem) {
+    MI_REQUIRE(mel && frames && out_lens && B > 0, "bigvgan_forward_ragged: bad arguments");
+    MI_REQUIRE(out_f32 || out_i16, "bigvgan_forward_ragged: no output buffer");
+    MI_REQUIRE(!cfg.pre_ln && !cfg.cond, "bigvgan_forward_ragged: this handle is an IndexTTS graph-F vocoder, use mi_bigvgan_forward_latent_ragged");
+    int Fmax = 0;
+    long total = 0, mel_frames = 0;
+    for (int b = 0; b < B; ++b) {
+        MI_REQUIRE(frames[b] >= 1, "bigvgan_forward_ragged: every item needs at least one frame");
+        Fmax = std::max(Fmax, frames[b]);
+        mel_frames += frames[b];
+        total += (long)frames[b] * cfg.hop + 30;
+    }
+    MI_REQUIRE((long)Fmax * cfg.hop < (1L << 30), "bigvgan_forward_ragged: too many frames");
+    MI_REQUIRE(total <= out_cap, "bigvgan_forward_ragged: out_cap is smaller than the sum of the waveform lengths");
+    MI_HIP(hipSetDevice(device));
+    ensure_workspace(B, Fmax);
+    const std::vector<long> offs = ragged_tables(B, frames, 0);
+    const float* dmel = mel;
+    if (mem == MI_HOST) {
+        MI_HIP(hipMemcpyAsync(d_mel.p, mel, (size_t)mel_frames * cfg.num_mels * 4, hipMemcpyHostToDevice, stream));
+        dmel = d_mel.as<float>();
+    }
+    launch_ncl_to_nlc_len(dmel, bT1.p, B, cfg.num_mels, Fmax, mel_pad, dtype, d_frames.as<int>(), d_in_offs.as<long>(), stream);
+    ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total;
+    try {
+        body(bT1.p, B, Fmax, nullptr, out_f32, out_i16, mem);
+    } catch (...) { ln = nullptr; out_offs = nullptr; throw; }
+    ln = nullptr; out_offs = nullptr;
+    for (int b = 0; b < B; ++b) out_lens[b] = offs[b + 1] - offs[b];
+}
+
+void BigVGAN::run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
+                                int16_t* out_i16, long out_cap, int64_t* out_lens, int mem) {
+    MI_REQUIRE(cfg.pre_ln && cfg.cond, "bigvgan_forward_latent_ragged: handle was not created with the IndexTTS graph-F flags");
+    MI_REQUIRE(latent && T_codes && conds && out_lens && B > 0 && (out_f32 || out_i16), "bigvgan_forward_latent_ragged: bad arguments");
+    MI_REQUIRE(n_conds == total_cond(), "bigvgan_forward_latent_ragged: conditioning vector length");
+    MI_REQUIRE(mel_pad == cfg.num_mels, "bigvgan_forward_latent_ragged: the latent width must be a multiple of the 16-byte vector");
+    std::vector<int> F(B);
+    int Fmax = 0;
+    long total = 0, rows = 0;
+    for (int b = 0; b < B; ++b) {
+        MI_REQUIRE(T_codes[b] >= 3, "bigvgan_forward_latent_ragged: every item needs >= 3 latent rows");
+        F[b] = T_codes[b] - 2;                           // the reference drops the last two latent rows
+        Fmax = std::max(Fmax, F[b]);
+        rows += T_codes[b];
+        total += (long)F[b] * cfg.hop + 30;
+    }
+    MI_REQUIRE((long)Fmax * cfg.hop < (1L << 30), "bigvgan_forward_latent_ragged: too many frames");
+    MI_REQUIRE(total <= out_cap, "bigvgan_forward_latent_ragged: out_cap is smaller than the sum of the waveform lengths");
+    MI_HIP(hipSetDevice(device));
+    ensure_workspace(B, Fmax);
+    std::vector<float> hc((size_t)n_conds);
+    if (mem == MI_HOST) std::memcpy(hc.data(), conds, (size_t)n_conds * 4);
+    else MI_HIP(hipMemcpy(hc.data(), conds, (size_t)n_conds * 4, hipMemcpyDeviceToHost));
+    std::vector<const float*> ptrs(cfg.n_up + 1);
+    long off = 0;
+    for (int i = 0; i < cfg.n_up; ++i) { ptrs[i] = hc.data() + off; off += cfg.c0 >> (i + 1); }
+    ptrs[cfg.n_up] = hc.data() + off;
+    const std::vector<long> offs = ragged_tables(B, F.data(), 2);      // latent rows of item b start at sum of T_codes before it
+    const float* dl = latent;
+    if (mem == MI_HOST) {
+        d_latent.ensure((size_t)rows * cfg.num_mels * 4);
+        MI_HIP(hipMemcpyAsync(d_latent.p, latent, (size_t)rows * cfg.num_mels * 4, hipMemcpyHostToDevice, stream));
+        dl = d_latent.as<float>();
+    }
+    launch_rownorm_len(NORM_LN_AFFINE, dl, bT1.p, dtype, ln_w.as<float>(), ln_b.as<float>(), B, Fmax, cfg.num_mels, 1e-5f,
+                       d_frames.as<int>(), d_in_offs.as<long>(), stream);
+    ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total;
+    try {
+        body(bT1.p, B, Fmax, ptrs.data(), out_f32, out_i16, mem);
+    } catch (...) { ln = nullptr; out_offs = nullptr; throw; }
+    ln = nullptr; out_offs = nullptr;
+    for (int b = 0; b < B; ++b) out_lens[b] = offs[b + 1] - offs[b];
+}
+
 static void eff_bias(ConvW& cw, const float* cond, hipStream_t s) {
     std::vector<float> e(cw.hb);
     for (size_t i = 0; i < e.size(); ++i) e[i] += cond[i];
@@ -301,6 +401,8 @@ static void eff_bias(ConvW& cw, const float* cond, hipStream_t s) {
 void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float* out_f32, int16_t* out_i16, int mem) {
     const long Tout = (long)F * cfg.hop + 30;
     ls = nullptr;
+    const int* lens = ln;                 // ragged call: every launch below carries the frame table (ln_mul = its resolution)
+    ln_mul = 1;
     DevBuf* IN = &bIN;     // holds the running stage input/output
     DevBuf* X = &bX;
     {
@@ -310,6 +412,7 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
         p.dtype = dtype; p.x = x0; p.w = pre.w.p; p.bias = bias; p.out = IN->p;
         p.B = B; p.T_in = F; p.M = F; p.N = cfg.c0; p.Cin = mel_pad; p.taps = 7; p.dil = 1; p.pad = 3;
         p.x_bstride = (long)F * mel_pad; p.x_rstride = mel_pad; p.out_bstride = (long)F * cfg.c0; p.out_rstride = cfg.c0;
+        p.lens = lens;
         launch_conv_gemm(p, stream);
     }
     int T = F;
@@ -326,6 +429,8 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
             p.B = B; p.T_in = T; p.M = T + taps - 1; p.N = st.u * C; p.Cin = st.cin; p.taps = taps; p.dil = 1; p.pad = taps - 1;
             p.x_bstride = (long)T * st.cin; p.x_rstride = st.cin; p.out_bstride = (long)Tn * C; p.out_rstride = C;
             p.epi = EPI_CONVT; p.u = st.u; p.Cout = C; p.padT = (st.k - st.u) / 2; p.T_out = Tn;
+            ln_mul *= st.u;               // stage i's resolution: F_b * prod(rates[0..i])
+            p.lens = lens; p.len_mul = ln_mul;
             launch_conv_gemm(p, stream);
         }
         // AMP blocks: XS(=IN) = 1/3 * sum_j block_j(X).  The blocks only meet in X (read) and in IN (block 0 writes it, blocks
@@ -384,13 +489,16 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
         T = Tn;
     }
     const int cl = cfg.c0 >> cfg.n_up;
-    aa(post_act, IN->p, bT1.p, B, T, cl, 1);
+    aa(post_act, IN->p, bT1.p, B, T, cl, 1);          // ragged: live rows F_b * hop in, + 30 out
     float* of = out_f32 ? (mem == MI_DEVICE ? out_f32 : d_out_f32.as<float>()) : nullptr;
     int16_t* oi = out_i16 ? (mem == MI_DEVICE ? out_i16 : d_out_i16.as<int16_t>()) : nullptr;
-    launch_conv_post(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, stream);
+    const long n_out = lens ? out_total : (long)B * Tout;
+    if (lens) launch_conv_post_len(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, lens, cfg.hop, 30,
+                                   out_offs, stream);
+    else launch_conv_post(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, stream);
     if (mem == MI_HOST) {
-        if (out_f32) MI_HIP(hipMemcpyAsync(out_f32, of, (size_t)B * Tout * 4, hipMemcpyDeviceToHost, stream));
-        if (out_i16) MI_HIP(hipMemcpyAsync(out_i16, oi, (size_t)B * Tout * 2, hipMemcpyDeviceToHost, stream));
+        if (out_f32) MI_HIP(hipMemcpyAsync(out_f32, of, (size_t)n_out * 4, hipMemcpyDeviceToHost, stream));
+        if (out_i16) MI_HIP(hipMemcpyAsync(out_i16, oi, (size_t)n_out * 2, hipMemcpyDeviceToHost, stream));
     }
     MI_HIP(hipStreamSynchronize(stream));
 }

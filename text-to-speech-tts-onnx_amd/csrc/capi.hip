@@ -167,6 +167,41 @@ int mi_bigvgan_forward_latent(mi_bigvgan* h, const float* latent, int T_codes, c
     });
 }
 
+// ragged batches: lengths are host int64, checked before anything reaches the device (the handle stays usable)
+static std::vector<int> bigvgan_lengths(const int64_t* lens, int B, int64_t lo, const char* what) {
+    MI_REQUIRE(lens && B >= 1, what);
+    std::vector<int> v(B);
+    for (int b = 0; b < B; ++b) {
+        MI_REQUIRE(lens[b] >= lo && lens[b] < (1L << 30), what);
+        v[b] = (int)lens[b];
+    }
+    return v;
+}
+
+int mi_bigvgan_forward_ragged(mi_bigvgan* h, int B, const float* mel, const int64_t* frames, int16_t* out_i16, float* out_f32,
+                              int64_t out_cap, int64_t* out_lens, int mem) {
+    return guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_bigvgan_forward_ragged: null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_bigvgan_forward_ragged: bad mem kind");
+        MI_REQUIRE(out_i16, "mi_bigvgan_forward_ragged: null out_i16");
+        const std::vector<int> F = bigvgan_lengths(frames, B, 1, "mi_bigvgan_forward_ragged: B >= 1 items of >= 1 frames");
+        h->impl->run_ragged(mel, B, F.data(), out_f32, out_i16, (long)out_cap, out_lens, mem);
+    });
+}
+
+int mi_bigvgan_forward_latent_ragged(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, const float* conds,
+                                     int64_t n_conds, int16_t* out_i16, float* out_f32, int64_t out_cap, int64_t* out_lens, int mem) {
+    return guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_bigvgan_forward_latent_ragged: null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_bigvgan_forward_latent_ragged: bad mem kind");
+        MI_REQUIRE(out_i16, "mi_bigvgan_forward_latent_ragged: null out_i16");
+        const std::vector<int> T = bigvgan_lengths(t_codes, B, 3, "mi_bigvgan_forward_latent_ragged: B >= 1 items of >= 3 latent rows");
+        h->impl->run_latent_ragged(latent, B, T.data(), conds, (long)n_conds, out_f32, out_i16, (long)out_cap, out_lens, mem);
+    });
+}
+
 int mi_aa_activation1d(const float* x, int B, int C, int T, const float* alpha_log, const float* beta_log,
                        int logscale, int post, int dtype, float* y) {
     return guard([&] {
@@ -440,6 +475,42 @@ static std::vector<int> f5_lengths(const int64_t* lens, int U, int64_t lo, int64
     return v;
 }
 
+// The host plan of a ragged batch (mi_f5_synthesize_ragged / mi_f5_synthesize_mel_ragged: the same inputs and checks): lengths,
+// prompt frames R_u, text ids, all checked before anything reaches the device.  `name` prefixes the messages.
+struct F5RaggedPlan { std::vector<int> Ns, Ts, Rs; std::vector<long> Ls; int Nmax = 0; };
+static F5RaggedPlan f5_ragged_plan(F5& e, int U, const int64_t* audio_lens, const int32_t* text_ids, const int64_t* text_lens,
+                                   const int64_t* max_durations, int mem, const std::string& name) {
+    const F5Cfg& c = e.cfg;
+    F5RaggedPlan pl;
+    pl.Ns = f5_lengths(max_durations, U, 1, c.max_len, (name + ": max_durations must be in [1, max_signal_length]").c_str());
+    pl.Ts = f5_lengths(text_lens, U, 0, 1 << 20, (name + ": bad text length").c_str());
+    pl.Ls.resize(U); pl.Rs.resize(U);
+    const int mel_pad = c.mel_type == 1 ? (c.n_fft - c.hop) / 2 : c.n_fft / 2;
+    int64_t ids = 0;
+    for (int u = 0; u < U; ++u) {
+        MI_REQUIRE(audio_lens && audio_lens[u] >= c.n_fft / 2 + 1 && audio_lens[u] > mel_pad && audio_lens[u] + 2 * mel_pad >= c.n_fft &&
+                   audio_lens[u] < (1L << 31), name + ": audio shorter than one STFT frame");
+        pl.Ls[u] = (long)audio_lens[u];
+        pl.Rs[u] = e.ref_frames(pl.Ls[u]);
+        MI_REQUIRE(pl.Ns[u] >= pl.Rs[u] + 1 && pl.Ns[u] >= pl.Ts[u], name + ": max_duration must exceed the prompt's frames and cover the text");
+        ids += pl.Ts[u];
+    }
+    if (mem == MI_HOST)
+        for (int64_t i = 0; i < ids; ++i)
+            MI_REQUIRE((int64_t)text_ids[i] + 1 >= 0 && (int64_t)text_ids[i] + 1 <= c.vocab, name + ": text id out of range");
+    pl.Nmax = *std::max_element(pl.Ns.begin(), pl.Ns.end());
+    return pl;
+}
+
+// ... and its front end + sampling loop (inside f5_run_checked): the U slabs of d_noise hold the final latents afterwards
+static void f5_ragged_loop(F5& e, int U, const int16_t* audio, const int32_t* text_ids, const float* noise_in, uint64_t seed, int mem,
+                           F5RaggedPlan& pl) {
+    e.preprocess_ragged(U, audio, pl.Ls.data(), text_ids, pl.Ts.data(), pl.Ns.data(), pl.Nmax, noise_in, seed, mem, pl.Rs.data());
+    const int* lens = e.set_lengths(U, pl.Ns.data());
+    e.build_cat_cond(U, pl.Nmax);
+    e.steps(U, pl.Nmax, 0, e.cfg.nfe - 1, lens);
+}
+
 int mi_f5_synthesize_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
                             const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed, int16_t* out,
                             int64_t out_cap, int64_t* out_lens, int mem) {
@@ -448,38 +519,51 @@ int mi_f5_synthesize_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t
         MI_REQUIRE(audio && text_ids && out && out_lens && U >= 1, "mi_f5_synthesize_ragged: bad arguments");
         F5& e = *h->impl;
         const F5Cfg& c = e.cfg;
-        std::vector<int> Ns = f5_lengths(max_durations, U, 1, c.max_len, "mi_f5_synthesize_ragged: max_durations must be in [1, max_signal_length]");
-        std::vector<int> Ts = f5_lengths(text_lens, U, 0, 1 << 20, "mi_f5_synthesize_ragged: bad text length");
-        std::vector<long> Ls(U);
-        std::vector<int> Rs(U);
-        const int mel_pad = c.mel_type == 1 ? (c.n_fft - c.hop) / 2 : c.n_fft / 2;
-        int64_t total = 0, ids = 0;
-        for (int u = 0; u < U; ++u) {
-            MI_REQUIRE(audio_lens && audio_lens[u] >= c.n_fft / 2 + 1 && audio_lens[u] > mel_pad && audio_lens[u] + 2 * mel_pad >= c.n_fft &&
-                       audio_lens[u] < (1L << 31), "mi_f5_synthesize_ragged: audio shorter than one STFT frame");
-            Ls[u] = (long)audio_lens[u];
-            const int R = e.ref_frames(Ls[u]);
-            MI_REQUIRE(Ns[u] >= R + 1 && Ns[u] >= Ts[u], "mi_f5_synthesize_ragged: max_duration must exceed the prompt's frames and cover the text");
-            total += (int64_t)(Ns[u] - R - 1) * c.hop;
-            ids += Ts[u];
-        }
+        F5RaggedPlan pl = f5_ragged_plan(e, U, audio_lens, text_ids, text_lens, max_durations, mem, "mi_f5_synthesize_ragged");
+        int64_t total = 0;
+        for (int u = 0; u < U; ++u) total += (int64_t)(pl.Ns[u] - pl.Rs[u] - 1) * c.hop;
         MI_REQUIRE(total <= out_cap, "mi_f5_synthesize_ragged: out_cap is smaller than the sum of the waveform lengths");
-        if (mem == MI_HOST)
-            for (int64_t i = 0; i < ids; ++i)
-                MI_REQUIRE((int64_t)text_ids[i] + 1 >= 0 && (int64_t)text_ids[i] + 1 <= c.vocab, "mi_f5_synthesize_ragged: text id out of range");
-        const int Nmax = *std::max_element(Ns.begin(), Ns.end());
         f5_run_checked(e, [&] {
-            e.preprocess_ragged(U, audio, Ls.data(), text_ids, Ts.data(), Ns.data(), Nmax, noise_in, seed, mem, Rs.data());
-            const int* lens = e.set_lengths(U, Ns.data());
-            e.build_cat_cond(U, Nmax);
-            e.steps(U, Nmax, 0, c.nfe - 1, lens);
+            f5_ragged_loop(e, U, audio, text_ids, noise_in, seed, mem, pl);
             int64_t off = 0;
             for (int u = 0; u < U; ++u) {      // graph C per utterance, on its own frames of its slab
-                const long len = e.decode(e.d_noise.as<float>() + (size_t)u * Nmax * c.mel, 1, Ns[u], Rs[u], nullptr, e.v_outi.as<int16_t>());
+                const long len = e.decode(e.d_noise.as<float>() + (size_t)u * pl.Nmax * c.mel, 1, pl.Ns[u], pl.Rs[u], nullptr,
+                                          e.v_outi.as<int16_t>());
                 copy_out(out + off, e.v_outi.p, (size_t)len * 2, mem, e.stream);
                 out_lens[u] = len;
                 off += len;
             }
+            MI_HIP(hipStreamSynchronize(e.stream));
+        });
+        e.finish_call();
+    });
+}
+
+// mi_f5_synthesize_ragged up to the end of the loop, then utterance u's frames [R_u, N_u) of its slab as (100, N_u - R_u) channels first
+int mi_f5_synthesize_mel_ragged(mi_f5* h, int U, const int16_t* audio, const int64_t* audio_lens, const int32_t* text_ids,
+                                const int64_t* text_lens, const int64_t* max_durations, const float* noise_in, uint64_t seed, float* mel_out,
+                                int64_t mel_cap, int64_t* n_frames, int mem) {
+    return guard([&] {
+        F5_CHECK(h, mem, "mi_f5_synthesize_mel_ragged");
+        MI_REQUIRE(audio && text_ids && mel_out && n_frames && U >= 1, "mi_f5_synthesize_mel_ragged: bad arguments");
+        F5& e = *h->impl;
+        const F5Cfg& c = e.cfg;
+        F5RaggedPlan pl = f5_ragged_plan(e, U, audio_lens, text_ids, text_lens, max_durations, mem, "mi_f5_synthesize_mel_ragged");
+        int64_t total = 0;
+        for (int u = 0; u < U; ++u) total += (int64_t)(pl.Ns[u] - pl.Rs[u]) * c.mel;
+        MI_REQUIRE(total <= mel_cap, "mi_f5_synthesize_mel_ragged: mel_cap is smaller than the sum of the mels");
+        f5_run_checked(e, [&] {
+            f5_ragged_loop(e, U, audio, text_ids, noise_in, seed, mem, pl);
+            float* dst = mel_out;
+            if (mem == MI_HOST) { e.v_outf.ensure((size_t)total * 4); dst = e.v_outf.as<float>(); }
+            int64_t off = 0;
+            for (int u = 0; u < U; ++u) {
+                const int F = pl.Ns[u] - pl.Rs[u];
+                launch_nlc_to_ncl(e.d_noise.as<float>() + ((size_t)u * pl.Nmax + pl.Rs[u]) * c.mel, dst + off, 1, c.mel, F, MI_F32, e.stream);
+                n_frames[u] = F;
+                off += (int64_t)F * c.mel;
+            }
+            if (mem == MI_HOST) copy_out(mel_out, dst, (size_t)total * 4, mem, e.stream);
             MI_HIP(hipStreamSynchronize(e.stream));
         });
         e.finish_call();

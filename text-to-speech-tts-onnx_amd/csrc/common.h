@@ -191,6 +191,9 @@ struct ConvGemm {
     int ln_final = 0;             // consumer: ln_stats_in holds FINISHED (rstd, mean * rstd) per row, [row][2] (launch_ln_finalize), not partials
     // fp16-pair producers: *sat |= 1 when an operand met the fp16 range limit (|a| >= 65504, inf, nan) while being split
     int* sat = nullptr;
+    // ragged batches (padded slabs, BigVGAN::run_ragged): output rows >= lens[b] * len_mul + len_add of item b are stored as
+    // zeros and tiles wholly past them skip their main loop; lens is a device table of B ints (null: every row is live)
+    const int* lens = nullptr; int len_mul = 1, len_add = 0;
 };
 constexpr int LN_BLK = 32;        // columns per partial-statistics block of the AdaLN fold
 void launch_conv_gemm(const ConvGemm& p, hipStream_t s);
@@ -264,6 +267,9 @@ struct AAAct {
     const float* inv_beta = nullptr;   // 1/(exp(beta_log)+1e-9)    [C]
     int B = 1, T = 0, C = 0;
     int post = 0;                      // 1: pad-15 variant, output rows T+30
+    // ragged batches: item b holds lens[b] * len_mul + len_add input rows (zeros after them); its output rows past
+    // that count (+ 30 with post) are stored as zeros (null: every row is live)
+    const int* lens = nullptr; int len_mul = 1, len_add = 0;
 };
 void launch_aa_act(const AAAct& p, hipStream_t s);
 const float* aa_filter_host();         // the 12 kaiser-sinc taps
@@ -277,6 +283,7 @@ struct AAConv {
     void* out = nullptr; const void* res = nullptr;
     int B = 1, T = 0, C = 0, k = 3, dil = 1;
     float alpha = 1.f; int accumulate = 0;
+    const int* lens = nullptr; int len_mul = 1, len_add = 0;   // ragged batches, as AAAct
 };
 void launch_aa_conv(const AAConv& p, hipStream_t s);
 bool aa_conv_set_option(const char* key, long v);
@@ -287,10 +294,17 @@ bool gemm_x3_enabled();
 // layout helpers (elementwise.hip)
 // (B,C,T) fp32 channels-first -> (B,T,Cpad) dtype channels-last (zero padded channels)
 void launch_ncl_to_nlc(const float* x, void* y, int B, int C, int T, int Cpad, int dtype, hipStream_t s);
+// ragged batches: item b's (C, lens[b]) channels-first array starts at x + C * offs[b] (host-built device tables); it becomes
+// slab b of (B, T, Cpad), rows >= lens[b] zero
+void launch_ncl_to_nlc_len(const float* x, void* y, int B, int C, int T, int Cpad, int dtype, const int* lens, const long* offs,
+                           hipStream_t s);
 // (B,T,C) dtype channels-last -> (B,C,T) fp32 channels-first
 void launch_nlc_to_ncl(const void* x, float* y, int B, int C, int T, int dtype, hipStream_t s);
 // conv_post: (B,T,C) -> tanh/clamp -> float (B,T) and/or int16 (B,T)
 void launch_conv_post(const void* x, const float* w /*[7][C]*/, float bias, int B, int T, int C, int dtype,
                       int use_tanh, float* out_f32, int16_t* out_i16, hipStream_t s);
+// ragged batches: item b has lens[b] * len_mul + len_add output samples, written from out + offs[b] (the items concatenated)
+void launch_conv_post_len(const void* x, const float* w, float bias, int B, int T, int C, int dtype, int use_tanh, float* out_f32,
+                          int16_t* out_i16, const int* lens, int len_mul, int len_add, const long* offs, hipStream_t s);
 
 }  // namespace mi

@@ -8,6 +8,9 @@ enum { NORM_LN_MOD = 0, NORM_LN_AFFINE = 1, NORM_L2 = 2 };
 // x fp32 [rows][D] -> y (out_dtype) ; LN_MOD: LN(x)*(1+a)+b ; LN_AFFINE: LN(x)*a+b ; L2: a*x/||x||+b
 void launch_rownorm(int mode, const float* x, void* y, int out_dtype, const float* a, const float* b, long rows, int D,
                     float eps, hipStream_t s);
+// ragged batches: items x Fmax rows out; row t of item i normalises x row offs[i] + t, rows t >= lens[i] are zeros (device tables)
+void launch_rownorm_len(int mode, const float* x, void* y, int out_dtype, const float* a, const float* b, int items, int Fmax, int D,
+                        float eps, const int* lens, const long* offs, hipStream_t s);
 // LN_MOD with the result as gemm_x3p.hip panel planes (three-way bf16 split of the fp32 value) instead of fp32 rows
 void launch_rownorm_x3p(const float* x, void* planes, const float* a, const float* b, long rows, int D, float eps, hipStream_t s,
                         int np = 3, int* sat = nullptr);       // sat: range watch of the fp16-pair split (x3_split.h)

@@ -21,14 +21,33 @@ namespace mi {
 // -----------------------------------------------------------------------------------------------
 // row norm: one 64-lane wave per row, row cached in registers (D <= 64*4*MAXV), two-pass statistics
 // -----------------------------------------------------------------------------------------------
-template <typename TO, int MAXV>
+// LENS (ragged batches): rows = items x Fmax slab rows; row t of item i reads x row offs[i] + t and is written as zeros when
+// t >= lens[i] (wave-uniform: one row per wave)
+template <typename TO, int MAXV, bool LENS = false>
 __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ x, TO* __restrict__ y,
                                                       const float* __restrict__ a, const float* __restrict__ b,
-                                                      long rows, int D, int mode, float eps) {
+                                                      long rows, int D, int mode, float eps, const int* lens = nullptr,
+                                                      const long* offs = nullptr, int Fmax = 0) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* xr = x + row * D;
+    if constexpr (LENS) {
+        const int it = __builtin_amdgcn_readfirstlane((int)(row / Fmax)), t = (int)(row - (long)it * Fmax);
+        if (t >= __builtin_amdgcn_readfirstlane(lens[it])) {
+            TO* yz = y + row * D;
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i) {
+                const int c = (i * 64 + lane) * 4;
+                if (c < D) {
+                    if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(yz + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    else *reinterpret_cast<uint2*>(yz + c) = make_uint2(0, 0);
+                }
+            }
+            return;
+        }
+        xr = x + (offs[it] + t) * D;
+    }
     float4 v[MAXV], av[MAXV], bv[MAXV];
     float s = 0.f;
 #pragma unroll
@@ -308,6 +327,25 @@ void launch_rownorm(int mode, const float* x, void* y, int out_dtype, const floa
     ProfScope ps(FAM_NORM, s, (double)rows * D * (4.0 + (double)dtype_size(out_dtype)), 8.0 * rows * D);
 #define RN(TO, MV) hipLaunchKernelGGL((rownorm_kernel<TO, MV>), grid, dim3(256), 0, s, x, (TO*)y, a, b, rows, D, mode, eps)
     const int mv = D <= 256 ? 1 : D <= 512 ? 2 : D <= 1024 ? 4 : 8;
+    if (out_dtype == MI_F32) { if (mv == 1) RN(float, 1); else if (mv == 2) RN(float, 2); else if (mv == 4) RN(float, 4); else RN(float, 8); }
+    else if (out_dtype == MI_F16) { if (mv == 1) RN(f16, 1); else if (mv == 2) RN(f16, 2); else if (mv == 4) RN(f16, 4); else RN(f16, 8); }
+    else { if (mv == 1) RN(bf16, 1); else if (mv == 2) RN(bf16, 2); else if (mv == 4) RN(bf16, 4); else RN(bf16, 8); }
+#undef RN
+    MI_HIP(hipGetLastError());
+}
+
+void launch_rownorm_len(int mode, const float* x, void* y, int out_dtype, const float* a, const float* b, int items, int Fmax, int D,
+                        float eps, const int* lens, const long* offs, hipStream_t s) {
+    MI_REQUIRE(D % 4 == 0 && D <= 2048 && items > 0 && Fmax > 0, "rownorm: D must be a multiple of 4 and <= 2048");
+    const long rows = (long)items * Fmax;
+    dim3 grid((unsigned)((rows + 3) / 4));
+    ProfScope ps(FAM_NORM, s, (double)rows * D * (4.0 + (double)dtype_size(out_dtype)), 8.0 * rows * D);
+    const int mv = D <= 256 ? 1 : D <= 512 ? 2 : D <= 1024 ? 4 : 8;
+    const char* tl = out_dtype == MI_F32 ? "float" : out_dtype == MI_F16 ? "_Float16" : "__bf16";
+    const std::string nm = std::string("rownorm_kernel<T, ") + std::to_string(mv) + ">";
+    prof_set_kernel(nm.c_str(), tl);
+    prof_kernel_suffix(" + lengths");
+#define RN(TO, MV) hipLaunchKernelGGL((rownorm_kernel<TO, MV, true>), grid, dim3(256), 0, s, x, (TO*)y, a, b, rows, D, mode, eps, lens, offs, Fmax)
     if (out_dtype == MI_F32) { if (mv == 1) RN(float, 1); else if (mv == 2) RN(float, 2); else if (mv == 4) RN(float, 4); else RN(float, 8); }
     else if (out_dtype == MI_F16) { if (mv == 1) RN(f16, 1); else if (mv == 2) RN(f16, 2); else if (mv == 4) RN(f16, 4); else RN(f16, 8); }
     else { if (mv == 1) RN(bf16, 1); else if (mv == 2) RN(bf16, 2); else if (mv == 4) RN(bf16, 4); else RN(bf16, 8); }

@@ -28,7 +28,8 @@
 
 namespace mi {
 
-template <typename T, typename TO, int BM, int BN, int WGM, int WGN, int KC>
+// LENS (ragged batches, ConvGemmDev::lens): rows past item b's length leave as zeros; a tile wholly past it loads nothing
+template <typename T, typename TO, int BM, int BN, int WGM, int WGN, int KC, bool LENS = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmDev p) {
     using MF = Mfma<T>;
     constexpr int KP = MF::KP;
@@ -123,6 +124,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmDev p) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    int vb = 0;
+    if constexpr (LENS) {
+        vb = gemm_live_rows(p, b);
+        if (gemm_tile_dead(p, m0, vb)) {                   // workgroup-uniform: the zeros only
+            gemm_epilogue<TO, TM, TN, WM, WN, true>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
+            return;
+        }
+    }
     load_regs(0);
     store_lds();
     __syncthreads();
@@ -150,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmDev p) 
         }
     }
 
-    gemm_epilogue<TO, TM, TN, WM, WN>(acc, p, m0, n0, b, g, wm, wn, lr, lk);
+    gemm_epilogue<TO, TM, TN, WM, WN, LENS>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -169,10 +178,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmDev p) 
 // and every 16-deep k-step is three v_mfma_f32_32x32x16_f16 on two accumulator sets instead of eight v_mfma_f32_32x32x2_f32 —
 // the arithmetic of gemm_x3p.hip for shapes its panel planes do not cover (the grouped k = 31 position convolution of the
 // DiT, N = 64 per group): 512 matrix-core cycles per chunk become 96, the split costs ~290 VALU cycles.
-template <typename T, typename TO, bool LEPI, int NST = 2, int BT = 128, bool PAIRS = false>
+// LENS: as conv_gemm_kernel (direct epilogue only)
+template <typename T, typename TO, bool LEPI, int NST = 2, int BT = 128, bool PAIRS = false, bool LENS = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev p) {
     using MF = Mfma<T>;
     static_assert(!PAIRS || (sizeof(T) == 4 && NST == 2), "PAIRS: the fp32 two-buffer loop");
+    static_assert(!LENS || (!LEPI && !PAIRS), "LENS: direct epilogue, plain products");
     // a tile row is always 128 bytes = eight 16-byte k-vectors: 64 halfs / bf16s or 32 floats per K chunk
     constexpr int VEC = 16 / (int)sizeof(T), KC = 8 * VEC;
     // BT = 128: the 128x128 tile (64x64 per wave).  BT = 64: 64x64 tiles (32x32 per wave) for fp32 problems with too few
@@ -286,6 +297,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accb[i][j][r] = 0.f;
+    }
+    int vb = 0;
+    if constexpr (LENS) {
+        vb = gemm_live_rows(p, b);
+        if (gemm_tile_dead(p, m0, vb)) {                   // workgroup-uniform: no DMA, no main loop, the zeros only
+            gemm_epilogue<TO, TM, TN, WM, WN, true>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
+            return;
+        }
     }
     int tap = 0, c0 = 0;
     const int ntaps = p.K / p.Cin;
@@ -500,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
         }
         gemm_epilogue_lds<TO, TM, TN, WM, WN>(acc, p, m0, n0, b, g, wm, wn, lr, lk, stage);
     } else {
-        gemm_epilogue<TO, TM, TN, WM, WN>(acc, p, m0, n0, b, g, wm, wn, lr, lk);
+        gemm_epilogue<TO, TM, TN, WM, WN, LENS>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
     }
 }
 
@@ -564,7 +583,22 @@ static bool buf_ok(const ConvGemmDev& d, int esz = 2) {
     return g_buf && d.Cin % (128 / esz) == 0 && a_bytes + (long)512 * d.x_rstride * esz < 0x7fff0000L && b_bytes < 0x7fff0000L;
 }
 
-template <typename T, typename TO>
+// a launch of dispatch_tiles: K is the uniform instantiation, KL the same tile with the lengths switch (LENS), which the
+// profiler files under K's name + " + lengths"
+#define MI_LAUNCH_LN(K, KL, T_, TO_, grid, blk, lds, s, ...)                                            \
+    do {                                                                                               \
+        if constexpr (LENS) {                                                                          \
+            mi::prof_set_kernel(#K, mi::type_label<T_>(), mi::type_label<TO_>());                      \
+            mi::prof_kernel_suffix(" + lengths");                                                      \
+            hipLaunchKernelGGL(KL, grid, blk, lds, s, __VA_ARGS__);                                    \
+        } else {                                                                                       \
+            MI_LAUNCH(K, T_, TO_, grid, blk, lds, s, __VA_ARGS__);                                     \
+        }                                                                                              \
+    } while (0)
+
+// LENS: ragged batches (ConvGemmDev::lens) — only the kernels with the direct epilogue take them; the planner's choice of tile is the
+// uniform one, so (B, M) alone decides it
+template <typename T, typename TO, bool LENS>
 static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
     constexpr int KC = sizeof(T) == 4 ? 16 : 64;
     dim3 blk(256);
@@ -573,7 +607,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
     if (d.N <= 32) {
         no_fold();
         dim3 grid((d.M + 255) / 256, (d.N + 31) / 32, B * d.G);
-        MI_LAUNCH((conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC>), T, TO, grid, blk, 0, s, d);
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC>), (conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC, true>), T, TO, grid, blk, 0, s, d);
     } else if (d.N <= 64) {
         no_fold();
         {
@@ -588,21 +622,21 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                 dim3 g2(e.RT * e.Tn, d.G);
                 if constexpr (sizeof(T) == 4) {
                     // fp32 with many taps (the DiT's grouped k = 31 position convolution): operands as fp16 pairs split in registers
-                    if (opt_x3() != 0 && opt_n64_pairs() != 0 && d.K / d.Cin >= 8 && d.Cin % 32 == 0) {
+                    if (!LENS && opt_x3() != 0 && opt_n64_pairs() != 0 && d.K / d.Cin >= 8 && d.Cin % 32 == 0) {
                         if (e.lds_epi) { prof_set_kernel("conv_gemm_dma_kernel<float, float, true, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, true, 2, 64, true>), g2, blk, 0, s, e); }
                         else { prof_set_kernel("conv_gemm_dma_kernel<float, float, false, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, false, 2, 64, true>), g2, blk, 0, s, e); }
                         MI_HIP(hipGetLastError());
                         return;
                     }
                 }
-                if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false, 2, 64>), T, TO, g2, blk, 0, s, e);
+                if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
+                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
                 MI_HIP(hipGetLastError());
                 return;
             }
         }
         dim3 grid((d.M + 127) / 128, (d.N + 63) / 64, B * d.G);
-        MI_LAUNCH((conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC>), T, TO, grid, blk, 0, s, d);
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
     } else {
         dim3 grid((d.M + 127) / 128, (d.N + 127) / 128, B * d.G);
         // a launch that carries the AdaLN fold (gemm_ln_fold_ok said yes) skips the 16-bit kernels without fold epilogues (dma3<192 |
@@ -612,7 +646,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
         if constexpr (sizeof(T) == 2) {
             // many row tiles (a batch of utterances): the 8-wave 256x256 eight-phase main loop
             const long tiles256 = (long)((d.M + 255) / 256) * ((d.N + 255) / 256);
-            if (g_ph8 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % 64 == 0 && d.pad == 0 && d.N % 64 == 0 && buf_ok(d, 2) &&
+            if (!LENS && g_ph8 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % 64 == 0 && d.pad == 0 && d.N % 64 == 0 && buf_ok(d, 2) &&
                 d.lds_epi && (d.epi == EPI_PLAIN || d.epi == EPI_QKV_ROPE) && tiles256 >= g_ph8_min_tiles) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = e.Tm; e.RC = (int)g_ph8_order;
@@ -622,13 +656,13 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
         }
         if constexpr (sizeof(T) == 4) {
             const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-            if (d.xp && d.w3p && B == 1) {                      // both kept only when x3p_eligible() said yes (launch_conv_gemm)
+            if (!LENS && d.xp && d.w3p && B == 1) {                      // both kept only when x3p_eligible() said yes (launch_conv_gemm)
                 ConvGemmDev e = d;
                 e.x = d.xp; e.w3 = d.w3p;
                 launch_linear_x3p(e, s);
                 return;
             }
-            if (d.w3 && B == 1 && tiles >= 64) {                // d.w3 is only kept when x3_eligible() said yes (launch_conv_gemm)
+            if (!LENS && d.w3 && B == 1 && tiles >= 64) {                // d.w3 is only kept when x3_eligible() said yes (launch_conv_gemm)
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
                 e.RC = 0;       // row tiles fastest: neighbouring ranges share the weight planes, the heavier operand here (24 of the 40 KB per chunk): 62.9 -> 61.0 us
@@ -642,7 +676,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
             // plain linear layer (one tap, one group, one M axis, whole K chunks): stream-K over persistent workgroups
             constexpr int KCB = 128 / (int)sizeof(T);
             const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-            if (!(sizeof(T) == 2 && fold) && g_sk >= (sizeof(T) == 4 ? 1 : 2) && d.sk_ws && d.sk_slots >= 256 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % KCB == 0 &&
+            if (!LENS && !(sizeof(T) == 2 && fold) && g_sk >= (sizeof(T) == 4 ? 1 : 2) && d.sk_ws && d.sk_slots >= 256 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % KCB == 0 &&
                 (d.epi == EPI_PLAIN || (d.epi == EPI_QKV_ROPE && (sizeof(T) == 2 || g_sk_qkv32))) && buf_ok(d, (int)sizeof(T)) && d.M > 128 && tiles >= g_sk_min_tiles && tiles <= g_sk_max_tiles && d.pad == 0) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
@@ -661,7 +695,13 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
             // the CUs idle for the whole launch, 256 tiles of 256x192 fill the chip): compare rounds x tile width
             const long rt256 = (long)B * ((d.M + 255) / 256);
             const long rounds192 = (rt256 * (d.N / 192) + 255) / 256, rounds256 = (rt256 * ((d.N + 255) / 256) + 255) / 256;
-            const bool n192_wins = d.N % 256 != 0 || (d.K > g_k_min && rounds192 * 192 < rounds256 * 256);
+            bool n192_wins = d.N % 256 != 0 || (d.K > g_k_min && rounds192 * 192 < rounds256 * 256);
+            // LENS: there is no 256x256 instantiation with lengths (its epilogue would spill: the uniform one already spills 108
+            // VGPRs).  Where the uniform plan takes that tile below, a ragged launch takes the 256x192 tile when N allows and the
+            // 256x128 one otherwise — still a choice of (B, M) alone
+            const bool big256 = g_use_dma3 && g_big_tiles && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > g_k_min && buf_ok(d) &&
+                                rt256 * ((d.N + 255) / 256) >= g_big_min && (((d.N + 255) / 256) * 256 - d.N) * 4 <= d.N;
+            if (LENS && big256) n192_wins = true;
             if (!fold && g_use_dma3 && g_n192 && buf_ok(d) && d.K % d.Cin == 0 && d.M > 128 && d.N % 192 == 0 && n192_wins &&
                 d.K >= 576 && (long)B * ((d.M + 255) / 256) * (d.N / 192) >= g_n192_min) {
                 // N = 192 / 384 (BigVGAN stages 2 and 1): a 192-wide tile has no padded columns (128-wide tiles waste 25 %
@@ -680,7 +720,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                 const long blocks_256x128 = (long)B * ((d.M + 255) / 256) * ((d.N + 127) / 128);
                 const long blocks_256x256 = (long)B * ((d.M + 255) / 256) * ((d.N + 255) / 256);
                 const int n_waste_256 = ((d.N + 255) / 256) * 256 - d.N;
-                if (g_big_tiles && buf_ok(d) && blocks_256x256 >= g_big_min && n_waste_256 * 4 <= d.N) {
+                if (!LENS && g_big_tiles && buf_ok(d) && blocks_256x256 >= g_big_min && n_waste_256 * 4 <= d.N) {
                     // every CU busy for >= 2 rounds: the tile with the fewest DMA bytes per flop
                     e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = B * e.Tm;
                     no_fold();
@@ -710,18 +750,18 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                     // tiles, FF1, the doubled DMA bytes per flop already cost more than the balance gains)
                     e.Tm = (d.M + 63) / 64; e.Tn = (d.N + 63) / 64; e.RT = B * e.Tm; e.RC = 0;
                     dim3 g2(e.RT * e.Tn, d.G);
-                    if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                    else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false, 2, 64>), T, TO, g2, blk, 0, s, e);
+                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
+                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
                     MI_HIP(hipGetLastError());
                     return;
                 }
                 if (g_ring4 && (long)g1.x * g1.y <= g_ring4_max && nchunks >= 6) {
                     // at most one workgroup per CU: the four-stage ring hides the DMA round trip that the two-buffer
                     // loop exposes when a CU has no second workgroup to switch to
-                    if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 4>), T, TO, g1, blk, 0, s, e);
-                    else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false, 4>), T, TO, g1, blk, 0, s, e);
-                } else if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
-                else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false>), T, TO, g1, blk, 0, s, e);
+                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 4>), T, TO, g1, blk, 0, s, e);
+                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 4>), (conv_gemm_dma_kernel<T, TO, false, 4, 128, false, true>), T, TO, g1, blk, 0, s, e);
+                } else if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
+                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false>), (conv_gemm_dma_kernel<T, TO, false, 2, 128, false, true>), T, TO, g1, blk, 0, s, e);
                 MI_HIP(hipGetLastError());
                 return;
             }
@@ -739,20 +779,20 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                     // balance the chip (O projection 144 -> 576 workgroups: makespan 3 quarter-tiles instead of 4)
                     e.Tm = (d.M + 63) / 64; e.Tn = (d.N + 63) / 64; e.RT = B * e.Tm; e.RC = 0;
                     dim3 g2(e.RT * e.Tn, d.G);
-                    if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                    else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false, 2, 64>), T, TO, g2, blk, 0, s, e);
+                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
+                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
                     MI_HIP(hipGetLastError());
                     return;
                 }
                 dim3 g1(e.RC > 0 ? 8 * e.RC * e.Tn : e.RT * e.Tn, d.G);
-                if (e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
-                else MI_LAUNCH((conv_gemm_dma_kernel<T, TO, false>), T, TO, g1, blk, 0, s, e);
+                if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
+                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false>), (conv_gemm_dma_kernel<T, TO, false, 2, 128, false, true>), T, TO, g1, blk, 0, s, e);
                 MI_HIP(hipGetLastError());
                 return;
             }
         }
         no_fold();
-        MI_LAUNCH((conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC>), T, TO, grid, blk, 0, s, d);
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
     }
     MI_HIP(hipGetLastError());
 }
@@ -864,7 +904,7 @@ bool gemm_ln_fold_ok(const ConvGemm& p) {
 
 void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     ConvGemm p = p_in;
-    if (p.B > 1 && p.taps == 1 && p.G == 1 && p.pad == 0 && p.epi == EPI_PLAIN && p.M == p.T_in && p.gate_bstride == 0 &&
+    if (!p.lens && p.B > 1 && p.taps == 1 && p.G == 1 && p.pad == 0 && p.epi == EPI_PLAIN && p.M == p.T_in && p.gate_bstride == 0 &&
         p.x_bstride == (long)p.M * p.x_rstride && p.out_bstride == (long)p.M * p.out_rstride) {
         p.T_in = p.M = p.B * p.M; p.B = 1;          // one-tap GEMM over contiguous batch items: a single M axis
     }
@@ -878,7 +918,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     const bool split_plain = p.epi == EPI_PLAIN && p.gate_bstride == 0 && !p.out_planes && !p.accumulate;
     const bool split_qkv = p.epi == EPI_QKV_ROPE && p.rows_per_item >= 32 && !p.kv_planes && p.m_off == 0;   // the epilogue indexes
                                                       // tokens from the flattened row: the second launch carries its row offset (m_off)
-    if (g_row_split != 0 && g_ph8 != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
+    if (!p.lens && g_row_split != 0 && g_ph8 != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
         (split_plain || split_qkv) && p.M == p.T_in && p.N % 256 == 0 && !p.xp) {
         int dev = 0, cus = 256;
         MI_HIP(hipGetDevice(&dev));
@@ -947,6 +987,11 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     d.ln_scale = p.ln_scale; d.ln_out = p.ln_out; d.ln_stats_out = p.ln_stats_out; d.ln_out_np = p.ln_out_np;
     d.ln_stats_in = p.ln_stats_in; d.ln_p = p.ln_p; d.ln_c = p.ln_c; d.ln_dim = p.ln_dim; d.ln_eps = p.ln_eps; d.ln_final = p.ln_final;
     d.sat = p.sat;
+    d.lens = p.lens; d.len_mul = p.len_mul; d.len_add = p.len_add;
+    if (p.lens)
+        MI_REQUIRE((p.epi == EPI_PLAIN || p.epi == EPI_CONVT) && !p.ln_stats_in && !p.ln_stats_out && !p.out_planes && !p.xp && !p.w3 &&
+                       !p.gcp_w && p.G == 1 && !p.gate,
+                   "conv_gemm: a launch with lengths is a plain or ConvTranspose1d convolution over padded slabs");
     if (p.ln_stats_in || p.ln_stats_out) {
         MI_REQUIRE(!(p.ln_stats_in && p.ln_stats_out), "conv_gemm: a launch is the producer OR the consumer of the AdaLN fold");
         MI_REQUIRE(p.B == 1 && p.G == 1 && p.taps == 1 && p.alpha == 1.f && !p.accumulate && p.gate_bstride == 0 && p.N % 64 == 0,
@@ -1009,7 +1054,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
         // of rows) and every tap re-fetched its rows from the fabric (PMC: 341 MB per launch against 100 MB algorithmic);
         // consecutive taps now re-read the same rows x 64 channels.  fp32 accumulation: only the summation order changes.
         // (A run-time switch between the two orders cost 12 % by itself, so the order is fixed.)
-        d.lds_epi = lds_epi_for(p, odt, use_x3) ? 1 : 0;
+        d.lds_epi = (!p.lens && lds_epi_for(p, odt, use_x3)) ? 1 : 0;     // the LENS kernels have the direct epilogue only
     }
     if (p.ln_stats_in || p.ln_stats_out)
         MI_REQUIRE(d.lds_epi && (p.dtype != MI_F32 || use_x3p), "conv_gemm: the AdaLN fold lives in the LDS-staged epilogues of linear_x3p / linear_ph8 / conv_gemm_dma (gemm_ln_fold_ok)");
@@ -1030,17 +1075,24 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     ProfScope ps(FAM_CONV_GEMM, s, bytes, flops);
 
     // fp32 grouped convolutions with 64 channels per group and >= 8 taps (the DiT's position convolution): gconv_pairs.hip
-    if (p.dtype == MI_F32 && opt_x3() != 0 && opt_n64_pairs() != 0 && opt_gconv() != 0 && g_use_dma && launch_gconv_pairs(p, s)) return;
+    if (!p.lens && p.dtype == MI_F32 && opt_x3() != 0 && opt_n64_pairs() != 0 && opt_gconv() != 0 && g_use_dma && launch_gconv_pairs(p, s)) return;
     // ... and the same shape on the 16-bit engines, weights as LDS images built at load: gconv16.hip
-    if (p.dtype != MI_F32 && p.gcp_w && g_use_dma && launch_gconv16(p, s)) return;
+    if (!p.lens && p.dtype != MI_F32 && p.gcp_w && g_use_dma && launch_gconv16(p, s)) return;
+    if (p.lens) {
+        MI_REQUIRE(odt == p.dtype, "conv_gemm: a launch with lengths writes the engine dtype");
+        if (p.dtype == MI_F32) dispatch_tiles<float, float, true>(d, p.B, s);
+        else if (p.dtype == MI_F16) dispatch_tiles<f16, f16, true>(d, p.B, s);
+        else dispatch_tiles<bf16, bf16, true>(d, p.B, s);
+        return;
+    }
     if (p.dtype == MI_F32) {
-        dispatch_tiles<float, float>(d, p.B, s);
+        dispatch_tiles<float, float, false>(d, p.B, s);
     } else if (p.dtype == MI_F16) {
-        if (odt == MI_F32) dispatch_tiles<f16, float>(d, p.B, s);
-        else dispatch_tiles<f16, f16>(d, p.B, s);
+        if (odt == MI_F32) dispatch_tiles<f16, float, false>(d, p.B, s);
+        else dispatch_tiles<f16, f16, false>(d, p.B, s);
     } else {
-        if (odt == MI_F32) dispatch_tiles<bf16, float>(d, p.B, s);
-        else dispatch_tiles<bf16, bf16>(d, p.B, s);
+        if (odt == MI_F32) dispatch_tiles<bf16, float, false>(d, p.B, s);
+        else dispatch_tiles<bf16, bf16, false>(d, p.B, s);
     }
 }
 

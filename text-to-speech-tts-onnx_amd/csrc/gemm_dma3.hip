@@ -3,6 +3,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
+#include <type_traits>
 
 namespace mi {
 
@@ -16,7 +17,8 @@ namespace mi {
 // Swizzle: slot = kv ^ ((row >> 1) & 7): rows of equal parity inside every ds_read_b128 lane group get eight
 // distinct slots => conflict-free fragment reads.
 // ---------------------------------------------------------------------------------------------------
-template <typename T, typename TO, int BM, int BN, int WM, int WN, int NST, bool BUF = false>
+// LENS (ragged batches, ConvGemmDev::lens): rows past item b's length leave as zeros; a tile wholly past it loads nothing
+template <typename T, typename TO, int BM, int BN, int WM, int WN, int NST, bool BUF = false, bool LENS = false>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_kernel(const ConvGemmDev p) {
     using MF = Mfma<T>;
     // two configurations: 256x128 tile / 64x64 per wave / 3-stage ring (default) and 256x256 tile / 128x64 per wave /
@@ -132,6 +134,14 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    int vb = 0;
+    if constexpr (LENS) {
+        vb = gemm_live_rows(p, b);
+        if (gemm_tile_dead(p, m0, vb)) {                   // workgroup-uniform: no DMA, no main loop, the zeros only
+            gemm_epilogue<TO, TM, TN, WM, WN, true>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
+            return;
+        }
+    }
     int itap = 0, ic0 = 0;                                        // cursor of the NEXT chunk to issue
     const int ntaps = p.K / p.Cin;
     auto advance = [&]() { if (++itap >= ntaps) { itap = 0; ic0 += KC; } };   // K order = (channel chunk, tap)
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
             mmas(1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        gemm_epilogue<TO, TM, TN, WM, WN>(acc, p, m0, n0, b, g, wm, wn, lr, lk);
+        gemm_epilogue<TO, TM, TN, WM, WN, LENS>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
         return;
     }
     int st = 0;
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
         __builtin_amdgcn_s_barrier();
         if (++st == NST) st = 0;
     }
-    gemm_epilogue<TO, TM, TN, WM, WN>(acc, p, m0, n0, b, g, wm, wn, lr, lk);
+    gemm_epilogue<TO, TM, TN, WM, WN, LENS>(acc, p, m0, n0, b, g, wm, wn, lr, lk, vb);
 }
 
 // bn = 192: 256x192 tile / 64x96 per wave / 2 stages ; bn = 256: 256x256 / 128x64 / 2 stages (both with buffer-descriptor
@@ -255,6 +265,21 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
 template <typename T, typename TO>
 void launch_conv_gemm_dma3(const ConvGemmDev& e, int bn, hipStream_t s) {
     const dim3 grid(e.RC == 2 ? 8 * ((e.RT * e.Tn + 7) / 8) : e.RT * e.Tn, e.G);
+    if constexpr (std::is_same<T, TO>::value) if (e.lens) {
+        // ragged batches: the same tiles with the lengths switch, named as the uniform ones + " + lengths"
+        if (bn == 192) {
+            prof_set_kernel("conv_gemm_dma3_kernel<T, TO, 256, 192, 64, 96, 2, true>", type_label<T>(), type_label<TO>());
+            prof_kernel_suffix(" + lengths");
+            hipLaunchKernelGGL((conv_gemm_dma3_kernel<T, TO, 256, 192, 64, 96, 2, true, true>), grid, dim3(512), 0, s, e);
+        } else {
+            // no 256x256 tile with lengths: dispatch_tiles sends those launches to 256x192 / 256x128
+            MI_REQUIRE(bn == 128, "conv_gemm_dma3: no 256x256 tile with lengths");
+            prof_set_kernel("conv_gemm_dma3_kernel<T, TO, 256, 128, 64, 64, 3>", type_label<T>(), type_label<TO>());
+            prof_kernel_suffix(" + lengths");
+            hipLaunchKernelGGL((conv_gemm_dma3_kernel<T, TO, 256, 128, 64, 64, 3, false, true>), grid, dim3(512), 0, s, e);
+        }
+        return;
+    }
     if (bn == 192) MI_LAUNCH((conv_gemm_dma3_kernel<T, TO, 256, 192, 64, 96, 2, true>), T, TO, grid, dim3(512), 0, s, e);
     else if (bn == 256) MI_LAUNCH((conv_gemm_dma3_kernel<T, TO, 256, 256, 128, 64, 2, true>), T, TO, grid, dim3(512), 0, s, e);
     else MI_LAUNCH((conv_gemm_dma3_kernel<T, TO, 256, 128, 64, 64, 3>), T, TO, grid, dim3(512), 0, s, e);

@@ -51,6 +51,7 @@ struct ConvGemmDev {
     const float* ln_stats_in = nullptr; const float* ln_p = nullptr; const float* ln_c = nullptr; int ln_dim = 0; float ln_eps = 0.f;
     int ln_final = 0;                            // ln_stats_in = finished (rstd, mean * rstd) per row instead of partial sums
     int* sat = nullptr;                          // fp16-pair producers raise bit 0 when an operand met the fp16 range limit
+    const int* lens = nullptr; int len_mul = 1, len_add = 0;   // ragged batches (ConvGemm::lens): the LENS instantiations only
 };
 
 // Shared epilogue: 32x32 accumulator tiles -> bias / activation / gate / residual / alpha / accumulate -> HBM,
@@ -85,10 +86,12 @@ __device__ __forceinline__ void act16(float (&v)[16]) {
     }
 }
 
-template <typename TO, int TM, int TN, int WM, int WN>
+// LENS (ragged batches, ConvGemmDev::lens): output rows >= vb (item b's live rows) are stored as zeros and read no residual /
+// accumulate operand; vb is wave-uniform.  EPI_PLAIN / EPI_CONVT only.
+template <typename TO, int TM, int TN, int WM, int WN, bool LENS = false>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int m0, int n0, int b, int g,
-                                              int wm, int wn, int lr, int lk) {
-    if (p.epi == EPI_QKV_ROPE) {
+                                              int wm, int wn, int lr, int lk, int vb = 0) {
+    if (!LENS && p.epi == EPI_QKV_ROPE) {
         // fused bias + interleaved-pair RoPE + head scatter (AttnProcessor, modules.py:459-466, 421-438):
         //   column n -> (which = q|k|v, head, d) ; q,k: z*cos + rot(z)*sin with rot(z)[2j] = -z[2j+1],
         //   rot(z)[2j+1] = z[2j] (the pair partner lives in lane^1 of the accumulator tile) ;
@@ -146,6 +149,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvG
         else col = g * p.N + nc;
         const float bv = p.bias ? p.bias[col] : 0.f;
         const float gv = p.gate ? p.gate[(long)b * p.gate_bstride + col] : 1.f;
+        // LENS: M rows m < mlim of this column are live (output row m, or m * u + ph - padT for the ConvTranspose1d map, < vb)
+        int mlim = 0;
+        if constexpr (LENS) mlim = p.epi == EPI_CONVT ? (vb + p.padT - ph + p.u - 1) / p.u : vb;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int mb = m0 + wm * WM + i * 32 + 4 * lk;
@@ -158,6 +164,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvG
                 if (p.epi == EPI_CONVT) { row = (long)m * p.u + ph - p.padT; o = o && row >= 0 && row < p.T_out; }
                 return (o ? row : 0) * p.out_rstride + col;
             };
+            auto live = [&](int r) -> bool { return mb + (r & 3) + 8 * (r >> 2) < mlim; };     // LENS: item b's live rows
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = acc[i][j][r] + bv;
             switch (p.act) {                                  // wave-uniform, once per tile
@@ -171,19 +178,40 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvG
             for (int r = 0; r < 16; ++r) v[r] *= gv;
             if (resp) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { bool o; const long ix = row_of(r, o); v[r] += o ? to_f32(resp[ix]) : 0.f; }
+                for (int r = 0; r < 16; ++r) {
+                    bool o; const long ix = row_of(r, o);
+                    if constexpr (LENS) o = o && live(r);
+                    v[r] += o ? to_f32(resp[ix]) : 0.f;
+                }
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] *= p.alpha;
             if (p.accumulate) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { bool o; const long ix = row_of(r, o); v[r] += o ? to_f32(outp[ix]) : 0.f; }
+                for (int r = 0; r < 16; ++r) {
+                    bool o; const long ix = row_of(r, o);
+                    if constexpr (LENS) o = o && live(r);
+                    v[r] += o ? to_f32(outp[ix]) : 0.f;
+                }
+            }
+            if constexpr (LENS) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) if (!live(r)) v[r] = 0.f;
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) { bool o; const long ix = row_of(r, o); if (o) outp[ix] = from_f32<TO>(v[r]); }
             __builtin_amdgcn_sched_barrier(0);                // keep one tile's addresses live at a time
         }
     }
+}
+
+// LENS kernels: item b's live output rows, and whether the tile whose first M row is m0 lies wholly past them (its lowest output
+// row: m0, or m0 * u - padT for the ConvTranspose1d map).  The length is one scalar load per workgroup.
+__device__ __forceinline__ int gemm_live_rows(const ConvGemmDev& p, int b) {
+    return __builtin_amdgcn_readfirstlane(p.lens[b] * p.len_mul + p.len_add);
+}
+__device__ __forceinline__ bool gemm_tile_dead(const ConvGemmDev& p, int m0, int vb) {
+    return (p.epi == EPI_CONVT ? m0 * p.u - p.padT : m0) >= vb;
 }
 
 // LDS-staged epilogue for the DMA kernels (EPI_PLAIN / EPI_CONVT): the accumulator layout gives every lane ONE output

@@ -108,6 +108,12 @@ def load() -> C.CDLL:
     L.mi_f5_synthesize_ragged.restype = C.c_int
     L.mi_f5_dit_eval_ragged.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int]
     L.mi_f5_dit_eval_ragged.restype = C.c_int
+    L.mi_f5_synthesize_mel_ragged.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_int64, vp, C.c_int]
+    L.mi_f5_synthesize_mel_ragged.restype = C.c_int
+    L.mi_bigvgan_forward_ragged.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int64, vp, C.c_int]
+    L.mi_bigvgan_forward_ragged.restype = C.c_int
+    L.mi_bigvgan_forward_latent_ragged.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int]
+    L.mi_bigvgan_forward_latent_ragged.restype = C.c_int
     L.mi_indextts_cond_param_count.argtypes = [C.POINTER(C.c_int32), C.c_int]; L.mi_indextts_cond_param_count.restype = C.c_int64
     L.mi_indextts_cond_create.argtypes = [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int]
     L.mi_indextts_cond_create.restype = vp

@@ -16,6 +16,29 @@ from .config import BigVGANConfig
 from .weights import pack_bigvgan
 
 
+def ragged_layout(cfg: BigVGANConfig, frames, latent: bool = False):
+    """Host-side plan of a ragged batch (BigVGANVocoder.run_ragged / run_latent_ragged): per item the frames F_b, the offset of
+    its input in the concatenated input (frames for mels, latent rows for graph F), its waveform length F_b * hop + 30 and
+    offset in the concatenated output, and the slab height Fmax = max F_b.  `frames` are the mel frames, or with latent=True
+    the latent rows T_b (F_b = T_b - 2, the reference drops the last two).  Raises ValueError for inputs the engine would
+    refuse, before the GPU is touched.  Returns (F, in_offs, out_lens, out_offs, Fmax)."""
+    n = [int(x) for x in frames]
+    if not n:
+        raise ValueError("ragged batch: at least one item")
+    lo = 3 if latent else 1
+    for b, x in enumerate(n):
+        if x < lo:
+            raise ValueError(f"item {b}: {x} {'latent rows' if latent else 'frames'}, needs >= {lo}")
+    F = [x - 2 for x in n] if latent else n
+    Fmax = max(F)
+    if Fmax * cfg.hop >= 1 << 30:
+        raise ValueError(f"ragged batch: {Fmax} frames exceed the vocoder's limit")
+    in_offs = [int(v) for v in np.concatenate([[0], np.cumsum(n)[:-1]])]
+    out_lens = [f * cfg.hop + 30 for f in F]
+    out_offs = [int(v) for v in np.concatenate([[0], np.cumsum(out_lens)[:-1]])]
+    return F, in_offs, out_lens, out_offs, Fmax
+
+
 class BigVGANVocoder:
     def __init__(self, cfg: BigVGANConfig, state: Optional[dict] = None, *, blob: Optional[np.ndarray] = None,
                  blob_device=None, dtype: str = "f32", device: int = 0):
@@ -97,6 +120,93 @@ class BigVGANVocoder:
                    "mi_bigvgan_forward")
         return out
 
+    # ---- ragged batches: items of different lengths in one forward ------------------------------------------
+    def run_ragged(self, mels, return_float: bool = False):
+        """mels: list of (num_mels, F_b) arrays -> list of int16 (1, 1, F_b * hop + 30), each the waveform ``run`` gives for
+        that item alone (with return_float: also the float waveforms, as a second list)."""
+        cfg = self.cfg
+        mels = [np.asarray(m) for m in mels]
+        for b, m in enumerate(mels):
+            if m.ndim != 2 or m.shape[0] != cfg.num_mels:
+                raise ValueError(f"item {b}: mel must be ({cfg.num_mels}, F), got {m.shape}")
+        F, _, out_lens, out_offs, _ = ragged_layout(cfg, [m.shape[1] for m in mels])
+        x = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(m, np.float32).reshape(-1) for m in mels]))
+        n = sum(out_lens)
+        out = np.empty(n, np.int16)
+        outf = np.empty(n, np.float32) if return_float else None
+        fr = np.asarray(F, np.int64)
+        lens = np.zeros(len(F), np.int64)
+        _lib.check(_lib.load().mi_bigvgan_forward_ragged(self._h, len(F), x.ctypes.data, fr.ctypes.data, out.ctypes.data,
+                                                         None if outf is None else outf.ctypes.data, n, lens.ctypes.data,
+                                                         _lib.MI_HOST), "mi_bigvgan_forward_ragged")
+        assert list(lens) == out_lens, (list(lens), out_lens)
+        wav = [out[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        if return_float:
+            return wav, [outf[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        return wav
+
+    def run_ragged_torch(self, mel_cat, frames, out=None):
+        """Device-resident run_ragged: mel_cat = the items' (num_mels, F_b) mels concatenated (float32 CUDA tensor, e.g. from
+        ``F5Engine.synthesize_mel_ragged_torch``), frames = the host list F_b.  Returns (wav_cat, out_lens): the int16 waveforms
+        concatenated in one CUDA tensor and their lengths."""
+        import torch
+        cfg = self.cfg
+        F, _, out_lens, _, _ = ragged_layout(cfg, frames)
+        if not (mel_cat.is_cuda and mel_cat.dtype == torch.float32 and mel_cat.is_contiguous()):
+            raise ValueError("mel_cat must be a contiguous float32 tensor on the GPU")
+        if mel_cat.numel() < sum(F) * cfg.num_mels:
+            raise ValueError("mel_cat holds fewer than sum(frames) * num_mels values")
+        n = sum(out_lens)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int16, device=mel_cat.device)
+        assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous()
+        fr = np.asarray(F, np.int64)
+        lens = np.zeros(len(F), np.int64)
+        torch.cuda.current_stream(mel_cat.device).synchronize()
+        _lib.check(_lib.load().mi_bigvgan_forward_ragged(self._h, len(F), mel_cat.data_ptr(), fr.ctypes.data, out.data_ptr(), None,
+                                                         out.numel(), lens.ctypes.data, _lib.MI_DEVICE), "mi_bigvgan_forward_ragged")
+        return out, [int(v) for v in lens]
+
+    def run_latent_ragged(self, latents, conds, return_float: bool = False):
+        """IndexTTS graph F for B sentences of one speaker: latents = list of (T_b >= 3, gpt_dim) arrays, conds as in
+        ``run_latent`` (shared by all items) -> list of int16 (1, 1, (T_b - 2) * hop + 30)."""
+        cfg = self.cfg
+        if not (cfg.pre_layernorm and cfg.speaker_cond):
+            raise ValueError("this vocoder was not created from an IndexTTS graph-F config")
+        latents = [np.asarray(x) for x in latents]
+        for b, x in enumerate(latents):
+            if x.ndim != 2 or x.shape[1] != cfg.num_mels:
+                raise ValueError(f"item {b}: latent must be (T_codes, {cfg.num_mels}), got {x.shape}")
+        _, _, out_lens, out_offs, _ = ragged_layout(cfg, [x.shape[0] for x in latents], latent=True)
+        flat = self._flat_conds(conds)
+        x = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(v, np.float32) for v in latents]))
+        tc = np.asarray([v.shape[0] for v in latents], np.int64)
+        n = sum(out_lens)
+        out = np.empty(n, np.int16)
+        outf = np.empty(n, np.float32) if return_float else None
+        lens = np.zeros(len(latents), np.int64)
+        _lib.check(_lib.load().mi_bigvgan_forward_latent_ragged(self._h, len(latents), x.ctypes.data, tc.ctypes.data, flat.ctypes.data,
+                                                                flat.size, out.ctypes.data, None if outf is None else outf.ctypes.data,
+                                                                n, lens.ctypes.data, _lib.MI_HOST), "mi_bigvgan_forward_latent_ragged")
+        assert list(lens) == out_lens, (list(lens), out_lens)
+        wav = [out[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        if return_float:
+            return wav, [outf[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        return wav
+
+    def _flat_conds(self, conds):
+        cfg = self.cfg
+        want = [cfg.stage_channels(i) for i in range(cfg.num_upsamples)] + [cfg.upsample_initial_channel]
+        if len(conds) != len(want):
+            raise ValueError(f"expected {len(want)} conditioning vectors")
+        flat = []
+        for c, n in zip(conds, want):
+            c = np.asarray(c, dtype=np.float32).reshape(-1)
+            if c.size != n:
+                raise ValueError(f"conditioning vector has {c.size} values, expected {n}")
+            flat.append(c)
+        return np.ascontiguousarray(np.concatenate(flat))
+
     # ---- IndexTTS graph F: latent + speaker conditioning in, waveform out ------------------------------------
     def run_latent(self, latent: np.ndarray, conds, return_float: bool = False):
         """latent (T_codes, gpt_dim) float32 ('save_hidden_state'); conds = [save_bigvgan_conds_0..n-1,
@@ -107,16 +217,7 @@ class BigVGANVocoder:
         latent = np.ascontiguousarray(latent, dtype=np.float32)
         if latent.ndim != 2 or latent.shape[1] != cfg.num_mels or latent.shape[0] < 3:
             raise ValueError(f"save_hidden_state must be (T_codes >= 3, {cfg.num_mels}), got {latent.shape}")
-        want = [cfg.stage_channels(i) for i in range(cfg.num_upsamples)] + [cfg.upsample_initial_channel]
-        if len(conds) != len(want):
-            raise ValueError(f"expected {len(want)} conditioning vectors")
-        flat = []
-        for c, n in zip(conds, want):
-            c = np.asarray(c, dtype=np.float32).reshape(-1)
-            if c.size != n:
-                raise ValueError(f"conditioning vector has {c.size} values, expected {n}")
-            flat.append(c)
-        flat = np.ascontiguousarray(np.concatenate(flat))
+        flat = self._flat_conds(conds)
         T = latent.shape[0]
         n = (T - 2) * cfg.hop + 30
         out = np.empty((1, 1, n), np.int16)

@@ -362,6 +362,67 @@ class F5Engine:
                                                     C.byref(nf), _lib.MI_DEVICE), "mi_f5_synthesize_mel")
         return out
 
+    def synthesize_mel_ragged(self, audios, text_ids, max_durations, noise=None, seed: int = 9527):
+        """synthesize_ragged up to the end of the loop, the generated frames as vocoder mels: a list of float32 (100, F_u),
+        F_u = N_u - R_u, each what ``synthesize_mel`` gives for that utterance alone — ``BigVGANVocoder.run_ragged`` takes the
+        list as it is."""
+        cfg = self.cfg
+        audios = [np.ascontiguousarray(np.asarray(a).reshape(-1)) for a in audios]
+        if any(a.dtype != np.int16 for a in audios):
+            raise ValueError("audio must be int16")
+        ids = [np.ascontiguousarray(np.asarray(t).reshape(-1), dtype=np.int32) for t in text_ids]
+        if len(ids) != len(audios) or len(max_durations) != len(audios):
+            raise ValueError("audios / text_ids / max_durations batch mismatch")
+        _, F, _, _ = ragged_layout(cfg, [a.size for a in audios], [t.size for t in ids], max_durations)
+        U = len(audios)
+        N = [int(n) for n in max_durations]
+        if noise is not None:
+            if len(noise) != U:
+                raise ValueError("noise: one (N_u, 100) array per utterance")
+            noise = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(N[u], cfg.mel_dim) for u, x in enumerate(noise)]))
+        a = np.ascontiguousarray(np.concatenate(audios))
+        t = np.ascontiguousarray(np.concatenate(ids)) if sum(x.size for x in ids) else np.zeros(1, np.int32)
+        al = np.asarray([x.size for x in audios], np.int64)
+        tl = np.asarray([x.size for x in ids], np.int64)
+        nl = np.asarray(N, np.int64)
+        mel = np.empty(sum(F) * cfg.mel_dim, np.float32)
+        nf = np.zeros(U, np.int64)
+        _lib.check(_lib.load().mi_f5_synthesize_mel_ragged(self._h, U, a.ctypes.data, al.ctypes.data, t.ctypes.data, tl.ctypes.data,
+                                                           nl.ctypes.data, _p(noise), seed, mel.ctypes.data, mel.size, nf.ctypes.data,
+                                                           _lib.MI_HOST), "mi_f5_synthesize_mel_ragged")
+        assert list(nf) == F, (list(nf), F)
+        offs = np.concatenate([[0], np.cumsum(F)]) * cfg.mel_dim
+        return [mel[offs[u]:offs[u + 1]].reshape(cfg.mel_dim, F[u]).copy() for u in range(U)]
+
+    def synthesize_mel_ragged_torch(self, audio, audio_lens, text_ids, text_lens, max_durations, noise=None, seed: int = 9527,
+                                    out=None):
+        """Device-resident synthesize_mel_ragged: audio / text_ids (/ noise) are the per-utterance CUDA tensors concatenated
+        (int16 / int32 / float32), the length lists host ints.  Returns (mel_cat, frames): float32 CUDA tensor of the (100, F_u)
+        mels concatenated, and the list F_u — the arguments of ``BigVGANVocoder.run_ragged_torch``."""
+        import torch
+        cfg = self.cfg
+        _, F, _, _ = ragged_layout(cfg, audio_lens, text_lens, max_durations)
+        U = len(F)
+        total = sum(F) * cfg.mel_dim
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=audio.device)
+        assert audio.is_cuda and audio.dtype == torch.int16 and audio.is_contiguous()
+        assert text_ids.is_cuda and text_ids.dtype == torch.int32 and text_ids.is_contiguous()
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+        al = np.asarray([int(x) for x in audio_lens], np.int64)
+        tl = np.asarray([int(x) for x in text_lens], np.int64)
+        nl = np.asarray([int(x) for x in max_durations], np.int64)
+        nf = np.zeros(U, np.int64)
+        torch.cuda.current_stream(audio.device).synchronize()
+        _lib.check(_lib.load().mi_f5_synthesize_mel_ragged(self._h, U, audio.data_ptr(), al.ctypes.data, text_ids.data_ptr(), tl.ctypes.data,
+                                                           nl.ctypes.data, None if noise is None else noise.data_ptr(), seed,
+                                                           out.data_ptr(), out.numel(), nf.ctypes.data, _lib.MI_DEVICE),
+                   "mi_f5_synthesize_mel_ragged")
+        assert list(nf) == F, (list(nf), F)
+        return out, F
+
     def synthesize_torch(self, audio, text_ids, max_duration, noise=None, seed: int = 9527, out=None):
         """Device-resident variant: torch int16 (U,L) / int32 (U,T) / float32 (U,N,100) CUDA tensors."""
         import torch

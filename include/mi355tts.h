@@ -272,7 +272,12 @@ void        mi_indextts_cond_destroy(mi_cond* h);
 int         mi_indextts_cond_run(mi_cond* h, const int16_t* audio, int64_t L, float* conds, float* conds_latent, float* mel,
                                  int mem);
 
-/* Process-wide tuning / A-B switches (tools, tests).  Thread safety: every entry point that DISPATCHES KERNELS (create / run / step /
+/* Process-wide tuning / A-B switches (tools, tests), one table (csrc/options.h).  Precedence, for every key: the default, then the
+ * environment variable of the key where it has one (the whole table is read ONCE, at the process's first call into the library),
+ * then mi_set_option.  mi_get_option reports what the process runs with.  Out-of-range values: the "attn_*" keys,
+ * "bigvgan_streams" (1..3) and "gemm_ph8_split_max" (1..4) clamp; "gemm_f32_planes" / "attn_f32_planes" take 2 or 3 and the call
+ * fails otherwise (mi_last_error names the key, the value stays); on/off keys store value != 0; the rest store the value as given.
+ * Thread safety: every entry point that DISPATCHES KERNELS (create / run / step /
  * generate / forward ...) holds the shared side of one reader-writer lock for its duration and mi_set_option the exclusive side — a
  * change waits for the calls in flight on other threads (under sustained concurrent inference that wait is unbounded: the lock
  * prefers readers; set options before serving) and is seen as a whole by the calls that start after it; it never alters the dispatch
@@ -305,6 +310,8 @@ int         mi_indextts_cond_run(mi_cond* h, const int16_t* audio, int64_t L, fl
  * "gemm_f32_n64_dma", "gemm_n64_dma16", "attn_z_max", "attn_z16_max",
  * "aa_conv_deterministic".  Changing an option invalidates the hipGraphs captured by existing handles.   */
 int         mi_set_option(const char* key, int64_t value);
+/* The current value of a mi_set_option key into *value (no GPU needed).  Fails for an unknown key or a null pointer. */
+int         mi_get_option(const char* key, int64_t* value);
 /* PCI bus id of HIP device `device` ("0000:05:00.0") into buf: multi-rank launchers use it to check that every rank drives its
  * own GPU (mi355tts/shard.py assert_one_device_per_rank).  No reference counterpart (the reference is single-device).   */
 int         mi_device_pci_bus_id(int device, char* buf, int cap);

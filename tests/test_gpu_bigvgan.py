@@ -264,6 +264,7 @@ def test_amp_blocks_on_side_streams_are_bit_identical(full_state, dtype, B, F):
     cfg, st = full_state
     v = BV.BigVGANVocoder(cfg, st, dtype=dtype)
     mel = _mel(B, F, seed=23)
+    saved = _lib.get_option("bigvgan_streams")
     try:
         _lib.set_option("bigvgan_streams", 1)
         ref = v.run(mel)
@@ -272,7 +273,7 @@ def test_amp_blocks_on_side_streams_are_bit_identical(full_state, dtype, B, F):
             _lib.set_option("bigvgan_streams", ns)
             assert np.array_equal(v.run(mel), ref), ns
     finally:
-        _lib.set_option("bigvgan_streams", 3)
+        _lib.set_option("bigvgan_streams", saved)
         v.close()
 
 
@@ -331,16 +332,17 @@ def test_bad_inputs_raise(small_voc):
 # every tile configuration of the 16-bit LDS-DMA GEMM, forced at test sizes (they normally engage
 # only when the launch fills the chip) and compared with the oracle
 # ---------------------------------------------------------------------------------------------
-_DEFAULTS = {"gemm_big_tile_min": 160, "gemm_n192_min": 160, "gemm_mid_tile_min": 160, "gemm_dma3_k_min": 2048,
-             "gemm_use_dma3": 1, "gemm_use_dma": 1, "gemm_big_tiles": 1, "gemm_n192": 1, "gemm_f32_dma": 1, "gemm_ring4": 1, "gemm_ring4_max": 256, "gemm_buf": 1, "gemm_f32_small": 1, "gemm_f32_small_max": 1024, "gemm_small16_max": 256, "gemm_sk": 1, "gemm_sk_stages": 0, "gemm_ph8": 1, "gemm_ph8_min_tiles": 200, "gemm_ph8_order": 1, "gemm_ph8_split_max": 2, "gemm_ph8_split_min_nk": 24, "gemm_f32_x3": 1,
-             "gemm_f32_x3p": 1, "gemm_x3p_grid": 0, "gemm_x3p_noalign": 0, "gemm_f32_planes": 2, "gemm_f32_n64_pairs": 1}
-
-
 @pytest.fixture
 def gemm_options():
+    """set_option for a test; every key it set goes back to the value it had before."""
     from mi355tts import _lib
-    yield _lib.set_option
-    for k, v in _DEFAULTS.items():
+    saved = {}
+
+    def set_option(key, value):
+        saved.setdefault(key, _lib.get_option(key))
+        _lib.set_option(key, value)
+    yield set_option
+    for k, v in saved.items():
         _lib.set_option(k, v)
 
 
@@ -386,9 +388,8 @@ def test_stream_k_linear_vs_oracle(gemm_options, dtype, tol, stages, Ci, Co, T, 
     order by the owner of the tile's first chunk.  Ragged M / N tails, every ring depth, partial tiles of 2..many pieces, and
     bit-identical results from run to run (the fix-up order is fixed).  The last two shapes have more tiles than persistent
     workgroups (288 / 320 tiles)."""
-    from mi355tts import _lib
-    _lib.set_option("gemm_sk", 2)
-    _lib.set_option("gemm_sk_stages", stages)
+    gemm_options("gemm_sk", 2)
+    gemm_options("gemm_sk_stages", stages)
     x = W.synth_normal(1, f"skx{Ci}{T}", (B, Ci, T))
     w = W.synth_normal(2, f"skw{Ci}{Co}", (Co, Ci, 1), std=1.0 / np.sqrt(Ci))
     b = W.synth_normal(3, "skb", (Co,), std=0.1)
@@ -400,7 +401,7 @@ def test_stream_k_linear_vs_oracle(gemm_options, dtype, tol, stages, Ci, Co, T, 
     else:
         assert rms(y - ref) / rms(ref) < tol
     assert np.array_equal(y, BV.conv1d(x, w, b, dtype=dtype))
-    _lib.set_option("gemm_sk", 0)
+    gemm_options("gemm_sk", 0)
     y0 = BV.conv1d(x, w, b, dtype=dtype)                    # one tile per workgroup: same products, other summation split
     if dtype == "f32":
         np.testing.assert_allclose(y, y0, atol=3e-5, rtol=1e-5)

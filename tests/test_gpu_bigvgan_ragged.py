@@ -174,6 +174,7 @@ def test_stale_workspace(full_state, vocs, dtype):
 def test_stream_modes_bit_identical(vocs):
     mels = [_mel(F, 60 + b) for b, F in enumerate((24, 11, 3))]
     v = vocs["f16"]
+    saved = _lib.get_option("bigvgan_streams")
     try:
         _lib.set_option("bigvgan_streams", 1)
         ref = v.run_ragged(mels)
@@ -182,7 +183,7 @@ def test_stream_modes_bit_identical(vocs):
             out = v.run_ragged(mels)
             assert all(np.array_equal(a, b) for a, b in zip(out, ref)), ns
     finally:
-        _lib.set_option("bigvgan_streams", 3)
+        _lib.set_option("bigvgan_streams", saved)
 
 
 def test_full_size_reference_fixture(full_state, vocs, golden_dir):

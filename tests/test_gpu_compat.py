@@ -390,6 +390,7 @@ def test_set_option_while_other_threads_run_calls():
     mels = [W.synth_normal(70 + i, "mel", (1, cfg.num_mels, 64 + 16 * i), std=1.0) for i in range(4)]
     want = [engs[0].run(m) for m in mels]
     errs, done, flips = [], threading.Event(), [0]
+    saved = _lib.get_option("bigvgan_streams")
 
     def work(eng):
         try:
@@ -413,7 +414,7 @@ def test_set_option_while_other_threads_run_calls():
     [t.start() for t in th]; tf.start()
     [t.join(300) for t in th]
     done.set(); tf.join(60)
-    _lib.set_option("bigvgan_streams", 3)
+    _lib.set_option("bigvgan_streams", saved)
     assert not any(t.is_alive() for t in th) and not tf.is_alive(), "dead-lock"
     assert not errs, errs[:3]
     assert flips[0] >= 3

@@ -19,8 +19,6 @@ from oracle import f5_np as O
 
 pytestmark = pytest.mark.gpu
 
-ATTN_SPLIT_DEFAULT = 2          # mi_set_option("attn_split"): the library default (attention.hip g_attn_split)
-
 
 def rms(a):
     return float(np.sqrt(np.mean(np.square(np.asarray(a, dtype=np.float64)))))
@@ -201,6 +199,7 @@ def test_attention_xcd_aware_workgroup_map_is_bit_neutral(dtype):
     cfg = F5Config(dim=256, depth=1, heads=4, dim_head=64, text_dim=64, text_num_embeds=40, conv_layers=1,
                    pos_conv_groups=4, vocos_dim=64, vocos_intermediate=128, vocos_layers=1, nfe_step=4)
     eng = F5Engine(cfg, W.synth_state(W.f5_spec(cfg), 7), dtype=dtype)
+    saved = {k: _lib.get_option(k) for k in ("attn_xcd_map",)}
     try:
         for U, N in ((1, 130), (2, 257), (1, 700)):
             noise = W.synth_normal(3, f"n{N}", (U, N, cfg.mel_dim))
@@ -212,7 +211,8 @@ def test_attention_xcd_aware_workgroup_map_is_bit_neutral(dtype):
             got = eng.dit_eval(noise, cmt, cmtd, 1)
             assert np.isfinite(ref).all() and np.array_equal(got, ref), (dtype, U, N)
     finally:
-        _lib.set_option("attn_xcd_map", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
 
 
@@ -227,6 +227,7 @@ def test_fp32_attention_split_products_match_native():
     st = W.fold_f5(cfg, raw)
     eng = F5Engine(cfg, raw, dtype="f32")
     tables = O.time_tables(cfg, st)
+    saved = {k: _lib.get_option(k) for k in ("attn_f32_x3", "attn_split")}
     try:
         for N in (67, 257, 700):
             noise = W.synth_normal(3, f"n{N}", (N, cfg.mel_dim))
@@ -244,8 +245,8 @@ def test_fp32_attention_split_products_match_native():
                     assert np.array_equal(got[x3], eng.dit_eval(noise[None], cmt[None], cmtd[None], 1))
                 assert np.abs(got[1] - got[0]).max() < 5e-5 and np.abs(got[2] - got[0]).max() < 5e-5
     finally:
-        _lib.set_option("attn_f32_x3", 2)
-        _lib.set_option("attn_split", ATTN_SPLIT_DEFAULT)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
 
 
@@ -261,6 +262,7 @@ def test_attention_uneven_key_slices_longest_first():
     st = W.fold_f5(cfg, raw)
     eng = F5Engine(cfg, raw, dtype="f32")
     tables = O.time_tables(cfg, st)
+    saved = {k: _lib.get_option(k) for k in ("attn_lpt",)}
     try:
         for N in (257, 700, 1126):
             noise = W.synth_normal(3, f"n{N}", (N, cfg.mel_dim))
@@ -277,7 +279,8 @@ def test_attention_uneven_key_slices_longest_first():
             np.testing.assert_allclose(a, ref, atol=3e-4)
             assert np.abs(a - even).max() < 1e-4, N
     finally:
-        _lib.set_option("attn_lpt", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
 
 
@@ -288,6 +291,7 @@ def test_attention_key_slices_agree(dtype, tol, split):
     split = 1: 64-query workgroups whose wave pairs share the keys; 2 (fp32 pairs kernel): 128-query workgroups, four
     32-query groups per slice."""
     from mi355tts import _lib
+    saved = {k: _lib.get_option(k) for k in ("attn_z_force", "attn_split")}
     _lib.set_option("attn_split", split)
     cfg = F5Config(dim=256, depth=1, heads=4, dim_head=64, text_dim=64, text_num_embeds=40, conv_layers=1,
                    pos_conv_groups=4, vocos_dim=64, vocos_intermediate=128, vocos_layers=1, nfe_step=4)
@@ -316,8 +320,8 @@ def test_attention_key_slices_agree(dtype, tol, split):
             for a in outs[1:]:
                 assert np.abs(a - outs[0]).max() < (1e-4 if dtype == "f32" else 0.1)
     finally:
-        _lib.set_option("attn_z_force", 0)
-        _lib.set_option("attn_split", ATTN_SPLIT_DEFAULT)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
 
 
@@ -468,6 +472,7 @@ def test_full_size_fp32_fused_producers_are_bit_neutral(full):
     from mi355tts import _lib
     cfg, raw, audio, ids, N, noise = full
     eng = F5Engine(cfg, raw, dtype="f32")
+    saved = {k: _lib.get_option(k) for k in ("attn_kv_planes", "attn_f32_planes")}
     try:
         for U in (1, 3):
             o = [eng.preprocess(audio[u].reshape(1, 1, -1), ids[u].reshape(1, -1), np.array([N]), noise=noise[u]) for u in range(U)]
@@ -484,7 +489,8 @@ def test_full_size_fp32_fused_producers_are_bit_neutral(full):
             print(f"U={U}: DiT evaluation, fp16-pair attention against three-plane attention: rel rms {e:.2e}")
             assert e < 2e-6 and not np.array_equal(pairs, a), e
     finally:
-        _lib.set_option("attn_kv_planes", 1); _lib.set_option("attn_f32_planes", 2)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
 
 
@@ -502,6 +508,7 @@ def test_full_size_fp32_other_lengths_default_forms_against_native(full, N):
     cfg, raw, audio, ids, _, _ = full
     noise = np.stack([W.synth_normal(77 + u, "noise_n", (N, cfg.mel_dim)) for u in range(2)])
     eng = F5Engine(cfg, raw, dtype="f32")
+    saved = {k: _lib.get_option(k) for k in ("gemm_f32_x3", "attn_f32_x3", "gemm_f32_n64_pairs")}
     try:
         o = [eng.preprocess(audio[u].reshape(1, 1, -1), ids[u].reshape(1, -1), np.array([N]), noise=noise[u]) for u in range(2)]
         cmt = np.concatenate([x["cat_mel_text"] for x in o]); cmtd = np.concatenate([x["cat_mel_text_drop"] for x in o])
@@ -510,7 +517,8 @@ def test_full_size_fp32_other_lengths_default_forms_against_native(full, N):
         _lib.set_option("gemm_f32_x3", 0); _lib.set_option("attn_f32_x3", 0); _lib.set_option("gemm_f32_n64_pairs", 0)
         b = eng.dit_eval(noise, cmt, cmtd, 3)
     finally:
-        _lib.set_option("gemm_f32_x3", 1); _lib.set_option("attn_f32_x3", 2); _lib.set_option("gemm_f32_n64_pairs", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
     assert a.shape == (4, N, cfg.mel_dim) and np.isfinite(a).all()
     e = rms(a - b) / rms(b)
@@ -538,6 +546,7 @@ def test_fp32_position_convolution_weights_split_at_load(full, N):
     noise = np.stack([W.synth_normal(31 + u, "noise_gc", (N, cfg.mel_dim)) for u in range(2)])
     eng = F5Engine(cfg, raw, dtype="f32")
     outs, kernels = {}, {}
+    saved = {k: _lib.get_option(k) for k in ("gconv_two_taps",)}
     try:
         o = [eng.preprocess(audio[u].reshape(1, 1, -1)[..., :24000 * 2], ids[u].reshape(1, -1)[:, :40], np.array([N]), noise=noise[u]) for u in range(2)]
         cmt = np.concatenate([x["cat_mel_text"] for x in o]); cmtd = np.concatenate([x["cat_mel_text_drop"] for x in o])
@@ -551,7 +560,8 @@ def test_fp32_position_convolution_weights_split_at_load(full, N):
             kernels[on] = [k["kernel"] for k in _lib.prof_kernels()]
         assert eng.info()["saturation_events"] == 0
     finally:
-        _lib.set_option("gconv_two_taps", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
     assert any("gconv_pairs2_kernel" in k for k in kernels[1]) and not any("gconv_pairs2_kernel" in k for k in kernels[0]), kernels
     assert any("gconv_pairs_kernel" in k for k in kernels[0]), kernels[0]
@@ -572,6 +582,7 @@ def test_two_fp32_handles_on_two_threads_stream_k_and_exact_fit(full, x3d):
     cfg, raw, audio, ids, _, _ = full
     N = 1126
     engs = [F5Engine(cfg, raw, dtype="f32") for _ in range(2)]
+    saved = {k: _lib.get_option(k) for k in ("gemm_x3d",)}
     _lib.set_option("gemm_x3d", x3d)
     try:
         inputs = []
@@ -606,7 +617,8 @@ def test_two_fp32_handles_on_two_threads_stream_k_and_exact_fit(full, x3d):
                 assert np.array_equal(a, b)
             assert engs[j].info()["saturation_events"] == 0
     finally:
-        _lib.set_option("gemm_x3d", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         for e in engs: e.close()
 
 
@@ -650,6 +662,7 @@ def test_16bit_position_convolution_from_weight_images(full, dtype, tol):
     noise = np.stack([W.synth_normal(71 + u, "noise_g16", (N, cfg.mel_dim)) for u in range(2)])
     eng = F5Engine(cfg, raw, dtype=dtype)
     outs, kernels = {}, {}
+    saved = {k: _lib.get_option(k) for k in ("gconv16",)}
     try:
         o = [eng.preprocess(audio[u].reshape(1, 1, -1)[..., :96000], ids[u].reshape(1, -1), np.array([N]), noise=noise[u]) for u in range(2)]
         cmt = np.concatenate([x["cat_mel_text"] for x in o]); cmtd = np.concatenate([x["cat_mel_text_drop"] for x in o])
@@ -662,7 +675,8 @@ def test_16bit_position_convolution_from_weight_images(full, dtype, tol):
                 _lib.prof_enable(())
             kernels[on] = [k["kernel"] for k in _lib.prof_kernels()]
     finally:
-        _lib.set_option("gconv16", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
     assert any("gconv16_kernel" in k for k in kernels[1]) and not any("gconv16_kernel" in k for k in kernels[0]), kernels
     e = rms(outs[1] - outs[0]) / rms(outs[0])

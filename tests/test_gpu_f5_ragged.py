@@ -26,7 +26,7 @@ from dit_oracle64 import F32_OVERALL_GATE, F32_ROW_GATE, dit_errors, dit_forward
 pytestmark = pytest.mark.gpu
 
 K_EVAL = 2
-ATTN_SPLIT_DEFAULT = 2          # the library default of "attn_split" (attention.hip g_attn_split)
+ATTN_SPLIT_DEFAULT = 2          # "attn_split" of the fp32 128-query kernel (the library default; pinned in tests/test_options.py)
 LONG = (701, 1037, 1153)        # the exact-fit tiling's boundaries (test_gpu_dit_tilings) as one batch
 SHORT = (67, 130, 257)          # one to five 64-key stages: forced key slices run wholly past the short utterances
 
@@ -150,14 +150,15 @@ def test_key_slices_past_an_utterance_publish_the_neutral_partial(mid, split, z,
     cfg, raw = mid[0], mid[1]
     x, c, d, refs = _batch(mid, lengths)
     eng = F5Engine(cfg, raw, dtype="f32")
+    saved = {k: _lib.get_option(k) for k in ("attn_z_force", "attn_split")}
     try:
         _lib.set_option("attn_split", split)
         _lib.set_option("attn_z_force", z)
         a = eng.dit_eval_ragged(x, c, d, K_EVAL)
         b = eng.dit_eval_ragged(x, c, d, K_EVAL)
     finally:
-        _lib.set_option("attn_z_force", 0)
-        _lib.set_option("attn_split", ATTN_SPLIT_DEFAULT)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
         eng.close()
     for u in range(len(lengths)):
         assert np.array_equal(a[u], b[u]), u

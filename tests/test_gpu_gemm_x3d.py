@@ -27,6 +27,7 @@ def test_exact_fit_linear_against_float64_and_stream_k(T, Cin, Cout):
     x, w, b, ref = _case(T, Cin, Cout, 7)
     scale = np.abs(ref).max()
     outs = {}
+    saved = {k: _lib.get_option(k) for k in ("gemm_x3d",)}
     try:
         for on in (1, 0):
             _lib.set_option("gemm_x3d", on)
@@ -35,7 +36,8 @@ def test_exact_fit_linear_against_float64_and_stream_k(T, Cin, Cout):
             assert np.array_equal(y, bigvgan.conv1d(x, w, b, dtype="f32")[0].astype(np.float64))    # run to run
             outs[on] = y
     finally:
-        _lib.set_option("gemm_x3d", 1)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
     assert np.abs(outs[1] - outs[0]).max() / scale < 1e-6
 
 
@@ -43,6 +45,7 @@ def test_exact_fit_threshold_option():
     """gemm_x3d_min_eff: the planner takes the kernel from that share of useful tile area; at 100 nothing qualifies (every shape
     pays the 144-row rounding) and the results are the stream-K kernel's, bit for bit."""
     x, w, b, ref = _case(2252, 1024, 1024, 11)
+    saved = {k: _lib.get_option(k) for k in ("gemm_x3d", "gemm_x3d_min_eff")}
     try:
         _lib.set_option("gemm_x3d", 0)
         sk = bigvgan.conv1d(x, w, b, dtype="f32")
@@ -53,5 +56,5 @@ def test_exact_fit_threshold_option():
         fit = bigvgan.conv1d(x, w, b, dtype="f32")
         assert not np.array_equal(fit, sk) and np.abs(fit[0].astype(np.float64) - ref).max() / np.abs(ref).max() < 1e-6
     finally:
-        _lib.set_option("gemm_x3d", 1)
-        _lib.set_option("gemm_x3d_min_eff", 90)
+        for k, v in saved.items():
+            _lib.set_option(k, v)

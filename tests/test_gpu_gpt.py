@@ -358,6 +358,7 @@ def test_generate_batch_matrix_core_path(dtype, tol, nb):
     """16-bit engines with >= 9 sentences (threshold lowered to 3 here) run the decode-step linears as v_mfma_f32_16x16x32 skinny GEMMs (hidden 256 and
     320: one and five 64-wide K blocks per wave; inner 1280 takes the 8-way K split).  Checked against the oracle fed with
     the engine's own tokens."""
+    saved = _lib.get_option("gpt_mfma_min")
     _lib.set_option("gpt_mfma_min", 3)
     for hidden, heads, inner in ((256, 4, 1024), (320, 5, 2560)):
         cfg = IndexGPTConfig(hidden=hidden, layers=2, heads=heads, inner=inner, mel_codes=301, text_tokens=64, max_mel_pos=80,
@@ -376,7 +377,7 @@ def test_generate_batch_matrix_core_path(dtype, tol, nb):
             for k, t in enumerate(toks):
                 assert ologits[k, t] >= ologits[k].max() - 6 * tol, (b, k)
         e.close()
-    _lib.set_option("gpt_mfma_min", 9)
+    _lib.set_option("gpt_mfma_min", saved)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -20,7 +20,6 @@
 #include "common.h"
 #include "aa_math.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace mi {
 
@@ -315,8 +314,7 @@ static void launch_t(const AAAct& p, hipStream_t s) {
             if (p.C % cand == 0 && cand % VEC == 0) { CT = cand; break; }
         MI_REQUIRE(CT > 0, "aa_act: unsupported channel count");
     }
-    static int tt_elems = 0;                                // tile size in elements (rows x channels); tuning: MI355TTS_AA_TILE
-    if (!tt_elems) { const char* e = std::getenv("MI355TTS_AA_TILE"); tt_elems = e ? std::atoi(e) : 8192; }
+    const int tt_elems = (int)opt(OPT_AA_TILE);             // tile size in elements (rows x channels); tuning: MI355TTS_AA_TILE
     int TT = (tt_elems / CT) / R * R;
     if (TT < R) TT = R;
     if (TT > 512) TT = 512;
@@ -328,11 +326,11 @@ static void launch_t(const AAAct& p, hipStream_t s) {
     const double flops = (double)p.B * p.C * Tout * 60.0;
     ProfScope ps(FAM_AA, s, bytes, flops);
     if constexpr (sizeof(T) == 2) {
-        static const bool pipe = [] { const char* e = std::getenv("MI355TTS_AA_PIPE"); return !(e && e[0] == '0'); }();
+        const bool pipe = opt(OPT_AA_PIPE) != 0;
         const long in_bytes = (long)p.T * p.C * (long)sizeof(T);
         // outputs per work item of the pipelined kernel: 16 in the streaming form (aa_run_stream: 135 VGPRs; 21 / 16 instead of 13 / 8
         // up-sampler + snake evaluations per output: 44.2 -> 41.4 us per launch, bit-identical; MI355TTS_AA_R=8: the A/B switch)
-        static const int run_len = [] { const char* e = std::getenv("MI355TTS_AA_R"); return e ? std::atoi(e) : 16; }();
+        const int run_len = (int)opt(OPT_AA_R);
         const int RP = run_len == 8 ? 8 : 16;
         if (pipe && in_bytes < 0x7fff0000L) {
             // persistent workgroups walking tiles, input by LDS-DMA one tile ahead (aa_act_pipe_kernel)

@@ -12,19 +12,15 @@
 //   3. implicit-GEMM on MFMA: A fragments are read from the LDS tile at row offsets tap*dilation (im2col
 //      never exists), B fragments (weights [co][tap][ci]) stream from L2
 //   4. accumulators -> LDS (fp32) -> coalesced epilogue (bias, residual, alpha, accumulate) -> HBM
-#include <atomic>
 #include "common.h"
 #include "mfma.h"
 #include "aa_math.h"
-#include <cstdlib>
 
 namespace mi {
 
 extern __constant__ float c_h_fused[12];
 __constant__ float c_h_fused[12];
 
-static std::atomic<long> g_aa_lds_min = -1;        // > 80 KB: one workgroup per CU (a diagnostic since round 3), see launch_t
-bool aa_conv_set_option(const char*, long) { return false; }      // (round 4: "aa_conv_deterministic" removed — the default has been bit-reproducible since round 3; MI355TTS_AACONV_LDS_MIN stays as the diagnostic)
 
 struct AAConvDev {
     const void* x; const void* w; const float* bias; const float* alpha_s; const float* inv_beta; void* out; const void* res;
@@ -283,7 +279,7 @@ static void launch_t(const AAConv& q, hipStream_t s) {
     if (sizeof(T) == 4) d.S = (q.C % 2 == 0) ? q.C + 1 : q.C;   // fp32 fragments are ds_read_b32: odd dword stride
     d.alpha = q.alpha; d.accumulate = q.accumulate;
     d.lens = q.lens; d.len_mul = q.len_mul; d.len_add = q.len_add;
-    { const char* e = std::getenv("MI355TTS_AACONV_DBG"); d.dbg = e ? std::atoi(e) : 0; }
+    d.dbg = (int)env_int("MI355TTS_AACONV_DBG", 0);
     const int BM = q.C <= 48 ? 256 : 128;
     d.rows_act = BM + 2 * d.halo;
     d.rows_x = (d.rows_act + 15) / 16 * 16 + 10;
@@ -308,10 +304,7 @@ static void launch_t(const AAConv& q, hipStream_t s) {
     // source a whole aligned pair): 0 of 119 runs differ with two workgroups per CU, and tests/test_gpu_bigvgan.py asserts
     // array_equal across batch items and runs in the default mode.  The one-workgroup-per-CU policy stays as a diagnostic:
     // MI355TTS_AACONV_LDS_MIN=83968 (+19 % forward time).
-    {
-        if (g_aa_lds_min < 0) { const char* e = std::getenv("MI355TTS_AACONV_LDS_MIN"); g_aa_lds_min = e ? std::atol(e) : 0; }
-        if (sizeof(T) == 2) lds = std::max(lds, (size_t)g_aa_lds_min);
-    }
+    if (sizeof(T) == 2) lds = std::max(lds, (size_t)opt(OPT_AACONV_LDS_MIN));
     MI_REQUIRE(lds <= 160 * 1024, "aa_conv: tile does not fit LDS");
     dim3 grid((q.T + BM - 1) / BM, q.B);
     const double E = (double)q.B * q.T * q.C * sizeof(T);

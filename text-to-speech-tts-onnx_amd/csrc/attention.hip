@@ -17,7 +17,6 @@
 //   fp32 : v_mfma_f32_32x32x2_f32 (exact fp32 products, K = 2 keys per instruction)
 //   f16/bf16 : v_mfma_f32_32x32x16 — V is staged transposed ([d][key]) so that the 8 keys a lane feeds
 //                 per instruction are two contiguous 8-byte LDS reads.
-#include <atomic>
 #include "common.h"
 #include <functional>
 #include <map>
@@ -25,7 +24,6 @@
 #include "mfma.h"
 #include "f5_kernels.h"
 #include "x3_split.h"
-#include <cstdlib>
 #include <type_traits>
 #include <string>
 #include <algorithm>
@@ -967,62 +965,24 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     }
 }
 
-// key slices of the SPLIT2 form: at most g_attn_zmax for fp32, g_attn_z16 for 16-bit operands (1 = off: no gain measured)
 // fp32 attention: 0 = native fp32 MFMA ; 1 = q.k as exact bf16 splits (attn_kernel X3S) ; 2 = both products (attn_x3f_kernel;
 // V then arrives transposed like in the 16-bit engines: attention_v_ld() tells the QKV epilogue)
-static std::atomic<int> g_attn_x3 = 2;
-static std::atomic<int> g_attn_np = 2;                                // format of the pre-split K / V^T (and of Q / P inside the kernel): 2 fp16 pairs | 3 bf16 planes
-static std::atomic<int> g_attn_split = 2;                             // small grids: 1 = 64-query workgroups with the keys split between wave pairs (+ key slices) ; 2 = fp32 pairs kernel: 128-query workgroups + key slices
-static std::atomic<int> g_attn_zmax = 4, g_attn_z16 = 1, g_attn_zforce = 0;      // zforce (tests): exactly that many slices, even empty ones
-static std::atomic<int> g_attn_xmap = 1;                              // XCD-aware (query tile, head) map of the workgroup ids (A/B: attn_xcd_map; -1 % per launch, bit-neutral)
-static std::atomic<int> g_attn_lpt = 1;                               // fp32 128-query kernel: uneven key slices, longest first (A/B: attn_lpt)
-static std::atomic<int> g_attn_kvp = 1;                               // fp32, both products split: K / V^T pre-split by the QKV epilogue (A/B: attn_kv_planes)
-// The MI355TTS_ATTN_* environment overrides are read ONCE, before the first use of any of the globals above by ANY of the
-// three entry points: F5::dit_eval asks attention_v_ld() for the V layout of the QKV epilogue before the first
-// launch_attention() of the process, and a lazy read inside launch_attention() made that first block write V transposed
-// for a kernel that then read it untransposed.  mi_set_option() applied later overrides the environment.
-static inline int opt_attn_x3() { const int o = arith_tls().attn_x3; return o >= 0 ? o : (int)g_attn_x3; }      // the engine's arithmetic first (ArithScope, common.h)
-static inline int opt_attn_np() { const int o = arith_tls().attn_np; return (o == 2 || o == 3) ? o : (int)g_attn_np; }
-static void attn_env_once() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char* e = std::getenv("MI355TTS_ATTN_NO_SPLIT"); if (e && e[0] == '1') g_attn_split = 0;
-        if (const char* z = std::getenv("MI355TTS_ATTN_Z")) g_attn_zmax = std::max(1, std::min(4, std::atoi(z)));
-        if (const char* z = std::getenv("MI355TTS_ATTN_X3")) g_attn_x3 = std::max(0, std::min(2, std::atoi(z)));
-        if (const char* z = std::getenv("MI355TTS_ATTN_Z16")) g_attn_z16 = std::max(1, std::min(4, std::atoi(z)));
-        if (const char* z = std::getenv("MI355TTS_ATTN_KVP")) g_attn_kvp = std::atoi(z) != 0;
-        if (const char* z = std::getenv("MI355TTS_ATTN_LPT")) g_attn_lpt = std::atoi(z) != 0;
-        if (const char* z = std::getenv("MI355TTS_ATTN_PLANES")) g_attn_np = std::atoi(z) == 3 ? 3 : 2;
-    });
-}
+// (The MI355TTS_ATTN_* variables are part of the one read of the option table, options.h: F5::dit_eval asks attention_v_ld() for the V
+// layout of the QKV epilogue before the first launch_attention() of the process, and a lazy read inside launch_attention() once made
+// that first block write V transposed for a kernel that then read it untransposed.)
+static inline int opt_attn_x3() { const int o = arith_tls().attn_x3; return o >= 0 ? o : (int)opt(OPT_ATTN_F32_X3); }      // the engine's arithmetic first (ArithScope, common.h)
+static inline int opt_attn_np() { const int o = arith_tls().attn_np; return (o == 2 || o == 3) ? o : (int)opt(OPT_ATTN_F32_PLANES); }
 long attention_v_ld(int N, int dtype) {
-    attn_env_once();
     return (dtype == MI_F32 && opt_attn_x3() != 2) ? 0 : (long)((N + 7) / 8 * 8);
 }
-bool attn_set_option(const char* key, long v) {
-    attn_env_once();
-    const std::string k(key);
-    if (k == "attn_f32_x3") g_attn_x3 = (int)std::max(0L, std::min(2L, v));
-    else if (k == "attn_split") g_attn_split = (int)std::max(0L, std::min(2L, v));
-    else if (k == "attn_xcd_map") g_attn_xmap = v != 0;
-    else if (k == "attn_kv_planes") g_attn_kvp = v != 0;
-    else if (k == "attn_lpt") g_attn_lpt = v != 0;
-    else if (k == "attn_f32_planes") { if (v != 2 && v != 3) return false; g_attn_np = (int)v; }
-    else if (k == "attn_z_force") g_attn_zforce = (int)std::max(0L, std::min(4L, v));
-    else return false;
-    return true;
-}
-
 bool attention_takes_kv_planes(int N, int BH, int dtype) {
-    attn_env_once();
     (void)N; (void)BH;
-    return dtype == MI_F32 && opt_attn_x3() == 2 && g_attn_kvp != 0;
+    return dtype == MI_F32 && opt_attn_x3() == 2 && opt(OPT_ATTN_KV_PLANES) != 0;
 }
 
-int attention_kv_planes_format() { attn_env_once(); return opt_attn_np(); }
+int attention_kv_planes_format() { return opt_attn_np(); }
 
 bool attention_can_write_planes(int N, int BH, int dtype) {
-    attn_env_once();
     (void)N; (void)BH;
     return dtype == MI_F32 && opt_attn_x3() == 2;
 }
@@ -1115,9 +1075,8 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
         prof_set_kernel("attn_kernel<T, " #SP ">", type_label<TT>());           \
         go_attn<TT, SP>(GRID, s, q, k, v, o, H, N, ws, cnt, SSCALE, XM, lens);  \
     } while (0)
-    attn_env_once();
-    const int xm = (g_attn_xmap != 0 && BH % 8 == 0) ? 1 : 0;
-    const int zmax = g_attn_zmax;
+    const int xm = (opt(OPT_ATTN_XCD_MAP) != 0 && BH % 8 == 0) ? 1 : 0;
+    const int zmax = opt(OPT_ATTN_Z);
     // key slices for the SPLIT2 form (see attn_kernel): makespan(Z) = ceil(units * Z / CUs) / Z in units of one unsliced
     // workgroup, + 6 % per extra slice for the prologue and the merge (measured, fp32, one utterance = 576 units:
     // Z = 1 / 2 / 3 / 4 -> 135 / 122 / 121 / 126 us in round 2; 62.1 / 58.8 / 60.8 / 60.7 us with the fp16-pair kernel of
@@ -1133,8 +1092,8 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
             if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
             cus = cu_count[dev & 15];
         }
-        if (g_attn_zforce > 0)
-            return (ws && cnt && units * g_attn_zforce * slot <= ws_floats && units <= cnt_n) ? (int)g_attn_zforce : 1;
+        if (opt(OPT_ATTN_Z_FORCE) > 0)
+            return (ws && cnt && units * opt(OPT_ATTN_Z_FORCE) * slot <= ws_floats && units <= cnt_n) ? (int)opt(OPT_ATTN_Z_FORCE) : 1;
         int Z = 1;
         double best = 1e30;
         const int zm = dtype == MI_F32 ? zmax : std::min(zmax, zlimit16);
@@ -1145,21 +1104,21 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
         }
         return Z;
     };
-    const int z16 = g_attn_z16;
+    const int z16 = opt(OPT_ATTN_Z16);
     if (dtype == MI_F32) {
         // few 128-query workgroups (one or two utterances): halve them along the keys, see attn_kernel — or (attn_split = 2, the
         // default for the pre-split fp16-pair kernel, round 4) keep the 128-query workgroups, whose four waves share every K / V
         // stage and multiply two tiles per barrier pair, and cut only the key range into slices: 288 x 3 workgroups for one
         // utterance, 56.3 against 60.0 us per launch on the same box (step 177.8 -> 174.3 ms)
-        if (g_attn_split && (long)((N + 127) / 128) * BH < 1024 && N >= 64) {
+        if (opt(OPT_ATTN_SPLIT) && (long)((N + 127) / 128) * BH < 1024 && N >= 64) {
             // ... and cut the key range into Z slices when that evens out the workgroups per CU
-            const bool wide = g_attn_split == 2 && opt_attn_x3() == 2 && kv_planes == 2;
+            const bool wide = opt(OPT_ATTN_SPLIT) == 2 && opt_attn_x3() == 2 && kv_planes == 2;
             const int Z = pick_z(1, wide);
             if (wide) {
                 // uneven slices, longest first (attn_pick_slices): cached per (N, BH)
                 AttnSlices sl;
                 sl.Z = Z;
-                if (g_attn_lpt && g_attn_zforce == 0 && Z >= 1 && ws && cnt) {
+                if (opt(OPT_ATTN_LPT) && opt(OPT_ATTN_Z_FORCE) == 0 && Z >= 1 && ws && cnt) {
                     static std::mutex mu;
                     static std::map<std::pair<int, int>, AttnSlices> cache;
                     std::lock_guard<std::mutex> lk(mu);
@@ -1171,14 +1130,14 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
                         hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cus = pr.multiProcessorCount;
                         const long units = (long)((N + 127) / 128) * BH;
                         const long slot = 4 * (32 * 64 + 64 * 2);
-                        int zm = std::min((int)g_attn_zmax, 4);
+                        int zm = std::min((int)opt(OPT_ATTN_Z), 4);
                         while (zm > 1 && (units * zm * slot > ws_floats || units > cnt_n)) --zm;
                         it = cache.emplace(key, attn_pick_slices(units, (N + 63) / 64, 3 * cus, zm)).first;
                     }
                     sl = it->second;
-                    if (const char* e = std::getenv("MI355TTS_ATTN_CUTS")) {          // experiments: "7,14" = slices of stages [0,7) [7,14) [14,S)
-                        const int S = (N + 63) / 64;
-                        int c[3] = {S, S, S}, n = std::sscanf(e, "%d,%d,%d", &c[0], &c[1], &c[2]);
+                    if (const AttnCuts& e = opt_attn_cuts(); e.n) {          // experiments: MI355TTS_ATTN_CUTS
+                        const int S = (N + 63) / 64, n = e.n;
+                        const int* c = e.c;
                         const long units = (long)((N + 127) / 128) * BH;
                         if (n >= 1 && c[0] > 0 && c[0] < S && units * (n + 1) * 4 * (32 * 64 + 64 * 2) <= ws_floats && units <= cnt_n) {
                             sl.Z = n + 1; sl.cut[0] = c[0]; sl.cut[1] = n >= 2 ? c[1] : S; sl.cut[2] = n >= 3 ? c[2] : S;
@@ -1223,7 +1182,7 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
     } else {
         // 16-bit: the same split below 512 workgroups (one utterance: attention 24.3 -> 21.1 ms per step; at two utterances,
         // 576 workgroups, the 128-query form is already balanced and shares each K / V stage among more waves)
-        const bool sp = g_attn_split && (long)((N + 127) / 128) * BH < 512 && N >= 64;
+        const bool sp = opt(OPT_ATTN_SPLIT) && (long)((N + 127) / 128) * BH < 512 && N >= 64;
         const dim3 grid(sp ? (N + 63) / 64 : (N + 127) / 128, BH, sp ? pick_z(z16) : 1);
         if (dtype == MI_F16 && ref_fp16_scale != 0.f) {
             prof_set_kernel(sp ? "attn_kernel<T, true, reference-fp16 scores>" : "attn_kernel<T, false, reference-fp16 scores>", type_label<f16>());

@@ -80,7 +80,6 @@ void unit_conv1d(const float* x, int B, int Cin, int T, const float* w, const fl
 void unit_conv_transpose1d(const float* x, int B, int Cin, int T, const float* w, const float* bias, int Cout, int k,
                            int stride, int padding, int dtype, float* y);
 
-bool bigvgan_set_option(const char* key, long v);   // "bigvgan_streams"
 
 // runtime.hip
 const std::string& last_error();

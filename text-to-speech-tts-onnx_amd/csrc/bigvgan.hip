@@ -14,8 +14,6 @@
 #include "bigvgan.h"
 #include "f5_kernels.h"
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 
 namespace mi {
 
@@ -104,8 +102,8 @@ BigVGAN::BigVGAN(const BigVGANCfg& g, const float* w, int64_t nw, int dt, int de
     MI_REQUIRE(nw == bigvgan_param_count(g), "bigvgan: weight blob size does not match the config");
     MI_HIP(hipSetDevice(dev));
     MI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (const char* e = std::getenv("MI355TTS_NO_FUSED_AA")) use_fused = !(e[0] == '1');
-    if (const char* e = std::getenv("MI355TTS_FUSED_MAX_C")) fused_max_c = std::atoi(e);
+    use_fused = !env_first_is("MI355TTS_NO_FUSED_AA", '1');
+    fused_max_c = (int)env_int("MI355TTS_FUSED_MAX_C", fused_max_c);
     const int vec = 16 / (int)dtype_size(dt);
     MI_REQUIRE((g.c0 >> g.n_up) % vec == 0, "bigvgan: last-stage channels must be a multiple of the 16-byte vector");
     mel_pad = round_up(g.num_mels, vec);
@@ -179,13 +177,6 @@ BigVGAN::~BigVGAN() {
 // the stages whose AMP halves are separate AA and conv launches (C > 96) on side streams; 3 = every stage.
 // fp16, mel (8,100,512), same box (tools/r3/bigvgan_streams_ab.py, profiles/r3/s6_bigvgan_streams_ab.txt): 16.8 / 16.2 / 16.07 ms per
 // forward for 1 / 2 / 3, waveforms identical bit for bit.
-static std::atomic<long> g_bigvgan_streams = 3;
-bool bigvgan_set_option(const char* key, long v) {
-    if (std::string(key) != "bigvgan_streams") return false;
-    g_bigvgan_streams = std::max(1L, std::min(3L, v));
-    return true;
-}
-
 void BigVGAN::ensure_side(int n) {
     MI_REQUIRE(n <= MAX_SIDE, "bigvgan: more resblock kernels than side streams");
     if (!ev_x) MI_HIP(hipEventCreateWithFlags(&ev_x, hipEventDisableTiming));
@@ -440,7 +431,7 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
         // bit for bit.  What it buys: the AA launches (VALU / HBM) of one block run beside the conv GEMM (matrix cores, one
         // workgroup per CU with LDS and registers to spare) of another.
         const bool fused = use_fused && C <= fused_max_c;
-        const long ns = g_bigvgan_streams;
+        const long ns = opt(OPT_BIGVGAN_STREAMS);
         const int nside = (cfg.n_kernels > 1 && cfg.n_kernels - 1 <= MAX_SIDE && (ns >= 3 || (ns == 2 && !fused))) ? cfg.n_kernels - 1 : 0;
         if (nside) {
             ensure_side(nside);
@@ -448,7 +439,7 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
             for (int j = 0; j < nside; ++j) MI_HIP(hipStreamWaitEvent(side[j], ev_x, 0));
         }
         std::vector<const void*> curs(cfg.n_kernels, X->p);
-        static const bool dbg_sync = [] { const char* e = std::getenv("MI355TTS_BV_SYNC"); return e && e[0] == '1'; }();
+        const bool dbg_sync = opt(OPT_BV_SYNC) != 0;
         // issue order: dilation-major with side streams (every block has its own scratch), block-major on one stream (the
         // blocks share T1 / T2 / P / Q there)
         const int n_it = cfg.n_dil * cfg.n_kernels;

@@ -4,7 +4,6 @@
 #include "f5.h"
 #include "gpt.h"
 #include "cond.h"
-#include <cstdlib>
 #include <algorithm>
 #include <mutex>
 #include <exception>
@@ -23,6 +22,7 @@ struct mi_cond { Cond* impl; std::mutex mu; };
 // different handles may be driven from different threads holds with mi_set_option in the picture).
 template <typename F> static int guard(F&& f, bool exclusive = false) {
     try {
+        options_init();           // the process's first C-ABI call reads the environment into the option table (options.h)
         std::shared_lock<std::shared_mutex> rd(option_lock(), std::defer_lock);
         std::unique_lock<std::shared_mutex> wr(option_lock(), std::defer_lock);
         if (exclusive) wr.lock(); else rd.lock();
@@ -904,11 +904,10 @@ int mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int di
         auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; };
         for (auto& v : hx) v = rnd();
         for (auto& v : hw) v = rnd() * 0.1f;
-        if (const char* z = std::getenv("MI355TTS_BENCH_ZERO")) if (z[0] == '1') { std::fill(hx.begin(), hx.end(), 0.f); std::fill(hw.begin(), hw.end(), 0.f); }   // data-dependent power / clock check
+        if (env_first_is("MI355TTS_BENCH_ZERO", '1')) { std::fill(hx.begin(), hx.end(), 0.f); std::fill(hw.begin(), hw.end(), 0.f); }   // data-dependent power / clock check
         // MI355TTS_BENCH_WSETS=n: cycle through n copies of the weights (n * bytes > 256 MiB MALL => every launch
         // streams cold weights from HBM, like consecutive layers of a real model)
-        int nsets = 1;
-        if (const char* e = std::getenv("MI355TTS_BENCH_WSETS")) nsets = std::max(1, std::atoi(e));
+        const int nsets = std::max(1, (int)env_int("MI355TTS_BENCH_WSETS", 1));
         upload_as(x, hx.data(), nx, dtype, s); upload_as(w, hw.data(), nw, dtype, s); upload_f32(bias, hb.data(), N, s);
         DevBuf wsets;
         if (nsets > 1) {
@@ -1001,10 +1000,18 @@ int mi_indextts_cond_run(mi_cond* h, const int16_t* audio, int64_t L, float* con
 int mi_set_option(const char* key, int64_t value) {
     return guard([&] {
         MI_REQUIRE(key != nullptr, "mi_set_option: null key");
-        MI_REQUIRE(gemm_set_option(key, (long)value) || gpt_set_option(key, (long)value) || aa_conv_set_option(key, (long)value) ||
-                       attn_set_option(key, (long)value) || bigvgan_set_option(key, (long)value), "mi_set_option: unknown key");
+        if (!options_set(key, (long)value)) throw Error(MI_EINVAL, std::string("mi_set_option: unknown key ") + key);
         option_epoch_bump();
     }, /*exclusive=*/true);
+}
+
+int mi_get_option(const char* key, int64_t* value) {
+    return guard([&] {
+        MI_REQUIRE(key != nullptr && value != nullptr, "mi_get_option: null key or value");
+        long v = 0;
+        if (!options_get(key, &v)) throw Error(MI_EINVAL, std::string("mi_get_option: unknown key ") + key);
+        *value = v;
+    });
 }
 
 int mi_device_pci_bus_id(int device, char* buf, int cap) {

@@ -13,6 +13,7 @@
 #include <shared_mutex>
 
 #include "../../include/mi355tts.h"
+#include "options.h"
 
 namespace mi {
 
@@ -24,11 +25,6 @@ struct Error : std::runtime_error {
     Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 void set_last_error(const std::string& m);
-// bumped by every mi_set_option: handles drop their captured hipGraphs when it moved (a graph bakes the dispatch in)
-long option_epoch();
-void option_epoch_bump();
-// shared: every C-ABI call; exclusive: mi_set_option (capi.hip guard)
-std::shared_mutex& option_lock();
 
 #define MI_HIP(expr)                                                                              \
     do {                                                                                          \
@@ -232,7 +228,6 @@ struct SkWorkspace {
     bool tripped() const;            // the spin watchdog of a stream-K fix-up gave up (last flag word, gemm_x3p.hip): synchronous 4-byte read
     void attach(ConvGemm& g) const { g.sk_ws = ws.as<float>(); g.sk_flags = flags.as<int>(); g.sk_slots = slots; }
 };
-bool gemm_set_option(const char* key, long v);
 
 // How an fp32 engine forms its fp32 products on the matrix cores — a property of the ENGINE, not of the process (VERDICT r3
 // weak #1: an fp16-pair engine and a native-fp32 engine must be able to coexist).  The launchers read the process-wide
@@ -286,8 +281,6 @@ struct AAConv {
     const int* lens = nullptr; int len_mul = 1, len_add = 0;   // ragged batches, as AAAct
 };
 void launch_aa_conv(const AAConv& p, hipStream_t s);
-bool aa_conv_set_option(const char* key, long v);
-bool attn_set_option(const char* key, long v);
 void split3_planes(const float* w, void* planes, long n, hipStream_t s);   // gemm_x3.hip
 bool gemm_x3_enabled();
 

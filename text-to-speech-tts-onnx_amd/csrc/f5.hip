@@ -12,7 +12,6 @@
 // modulation for all (step, block) pairs, RoPE tables, STFT / mel / ISTFT bases.
 // Batching: U utterances of equal length N are laid out as batch 2U (2u = cond, 2u+1 = uncond).
 #include "f5.h"
-#include <cstdlib>
 
 namespace mi {
 
@@ -91,15 +90,12 @@ F5::F5(const F5Cfg& c, const float* w, int64_t nw, int dt, int dev, int mem) : c
     MI_REQUIRE(nw == f5_param_count(c), "f5: weight blob size does not match the config");
     MI_HIP(hipSetDevice(dev));
     MI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (const char* e = std::getenv("MI355TTS_NO_GRAPH")) use_graph = !(e[0] == '1');
+    use_graph = !env_first_is("MI355TTS_NO_GRAPH", '1');
     hipStream_t s = stream;
     d_sat.ensure(64);
     MI_HIP(hipMemsetAsync(d_sat.p, 0, 64, s));
     const int d = c.dim, td = c.text_dim, ff = c.ff(), ti = td * c.conv_mult, cin = c.cat_dim();
-    {
-        const char* e = std::getenv("MI355TTS_CAT_PAD");
-        if (dt == MI_F32 && !(e && e[0] == '0')) cat_pad = rup(cin, 64) - cin;
-    }
+    if (dt == MI_F32 && !env_first_is("MI355TTS_CAT_PAD", '0')) cat_pad = rup(cin, 64) - cin;
     const float* p = w;
     auto take = [&](size_t n) { const float* r = p; p += n; return r; };          // blob ranges (host or device memory)
     BlobReader R(mem, s);
@@ -281,8 +277,7 @@ F5::F5(const F5Cfg& c, const float* w, int64_t nw, int dt, int dev, int mem) : c
         const float* pw = take((size_t)c.mel * d); const float* pb = take(c.mel);
         put_lin(R, proj_out, pw, pb, c.mel, d, dt);
         {
-            const char* e = std::getenv("MI355TTS_PROJ_PARTS");
-            const int parts = e ? std::atoi(e) : 4;
+            const int parts = (int)env_int("MI355TTS_PROJ_PARTS", 4);
             if (dt == MI_F32 && parts > 1 && parts <= 8 && d % (parts * 32) == 0) {
                 proj_parts = parts;
                 const int kq = d / parts;

@@ -16,8 +16,6 @@
 #include "gemm_epilogue.h"
 #include "mfma.h"
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 
 namespace mi {
 
@@ -175,13 +173,11 @@ __global__ __launch_bounds__(512, 2) void gconv16_kernel(const GConv16Dev p) {
     }
 }
 
-static std::atomic<bool> g_gconv16{[] { const char* e = std::getenv("MI355TTS_GCONV16"); return !(e && e[0] == '0'); }()};
-void gconv16_set_option(long v) { g_gconv16 = v != 0; }
 
 // true: launched.  false: not this kernel's shape (the caller goes on to its other kernels).
 bool launch_gconv16(const ConvGemm& p, hipStream_t s) {
     const int odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
-    if (!g_gconv16 || !p.gcp_w || (p.dtype != MI_F16 && p.dtype != MI_BF16) || (odt != p.dtype && odt != MI_F32)) return false;
+    if (!opt(OPT_GCONV16) || !p.gcp_w || (p.dtype != MI_F16 && p.dtype != MI_BF16) || (odt != p.dtype && odt != MI_F32)) return false;
     if (p.N != GC16_C || p.Cin != GC16_C || p.taps < 8 || p.taps > 127 || p.dil != 1) return false;
     if (p.epi != EPI_PLAIN || p.gate || p.accumulate || p.alpha != 1.f || p.out_planes || p.xp || p.ln_stats_in || p.ln_stats_out) return false;
     const int ev = odt == MI_F32 ? 4 : 4;          // output rows are written four values at a time (16 | 8 bytes)

@@ -21,8 +21,6 @@
 #include "gemm_epilogue.h"
 #include "mfma.h"
 #include "x3_split.h"
-#include <atomic>
-#include <cstdlib>
 
 namespace mi {
 
@@ -349,8 +347,6 @@ __global__ __launch_bounds__(512, 1) void gconv_pairs2_kernel(const GConvPairsDe
 }
 
 // option gconv_two_taps (mi_set_option; MI355TTS_GCONV2=0 at start-up): 0 = the per-launch split kernel even when the planes exist (A/B, tests)
-static std::atomic<bool> g_two_taps{[] { const char* e = std::getenv("MI355TTS_GCONV2"); return !(e && e[0] == '0'); }()};
-void gconv_pairs_set_option(long v) { g_two_taps = v != 0; }
 
 // true: launched.  false: not this kernel's shape (the caller goes on to its other kernels).
 bool launch_gconv_pairs(const ConvGemm& p, hipStream_t s) {
@@ -391,7 +387,7 @@ bool launch_gconv_pairs(const ConvGemm& p, hipStream_t s) {
         prof_set_kernel("gconv_pairs_kernel<" #BMv "> (fp32 grouped conv, fp16 pairs split once per workgroup)", "", "");      \
         hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, d);                                                                  \
     } while (0)
-    if (p.gcp_w && g_two_taps) {
+    if (p.gcp_w && opt(OPT_GCONV_TWO_TAPS)) {
         // weights pre-split at load (gconv_pairs_split_weights): 192 rows, eight waves, two taps in flight
         constexpr int BM2 = 192;
         const int ra = BM2 + p.taps - 1;

@@ -19,12 +19,10 @@
 // fp32 accumulate always.  4 waves per workgroup, each owning a (WM x WN) sub-tile of 32x32 MFMA
 // tiles.  K is streamed in KC-wide chunks: global -> registers (next chunk, issued before the
 // MFMAs of the current one) -> LDS -> fragments.
-#include <atomic>
 #include "common.h"
 #include <mutex>
 #include "mfma.h"
 #include "gemm_epilogue.h"
-#include <cstdlib>
 
 namespace mi {
 
@@ -523,29 +521,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
     }
 }
 
-static std::atomic<bool> g_use_dma = true, g_xcd_order = false, g_use_dma3 = true, g_big_tiles = true;
-static std::atomic<long> g_big_min = 160, g_n192_min = 160, g_mid_min = 160, g_k_min = 2048;
-static std::atomic<bool> g_n192 = true, g_f32_dma = true, g_ring4 = true, g_f32_small = true;
-static std::atomic<long> g_f32_small_max = 1024, g_small16_max = 256, g_f32_n64_dma = 1, g_n64_dma16 = 0;      // 16-bit: neutral (455 vs 457 ms at 8 utterances), off
-static std::atomic<long> g_ring4_max = 256;
-// stream-K (gemm_sk.hip): 0 off ; 1 fp32 linear layers ; 2 also 16-bit ; g_sk_stages: ring depth override (0 = automatic) ;
-// g_sk_max_tiles: only launches with at most this many 128x128 tiles (beyond that one tile per workgroup balances by itself)
-static std::atomic<long> g_sk = 1, g_sk_stages = 0, g_sk_max_tiles = 2048, g_sk_order = -1;
-static std::atomic<long> g_sk_min_tiles = 64;      // plain stream-K linear layers: at least this many 128x128 tiles ("gemm_sk_min_tiles")
-// whole tiles first, stream-K for the remainder only: measured SLOWER on the fp32 DiT layers (FF1 / FF2, 288 tiles: 87.0 vs
-// 83.7 us per launch — the remainder's eight-piece fix-ups cost more than the aligned K walk of the first phase gains): opt-in
-// fp32 linear layers as six exact bf16 x bf16 partial products (gemm_x3.hip) when the caller supplies the weight planes
-static std::atomic<long> g_x3 = 1;
-// ... with both operands as panel planes (gemm_x3p.hip, round 3) when the caller supplies them
-static std::atomic<long> g_x3p = 1;
-static std::atomic<long> g_f32_gconv = 1;         // ... and, when the shape allows, with each operand split once per workgroup (gconv_pairs.hip)
+// stream-K linear layers: at least g_sk_min_tiles 128x128 tiles, at most g_sk_max_tiles (beyond that one tile per workgroup balances by itself)
+static constexpr long g_sk_min_tiles = 64, g_sk_max_tiles = 2048;
 bool launch_gconv_pairs(const ConvGemm& p, hipStream_t s);
-void gconv_pairs_set_option(long v);
 bool launch_gconv16(const ConvGemm& p, hipStream_t s);
-void gconv16_set_option(long v);
-static std::atomic<long> g_f32_n64_pairs = 1;     // fp32 N = 64 convolutions with >= 8 taps: fp16 pairs split in registers (conv_gemm_dma_kernel PAIRS)
-// number format of the panel planes built from now on: 3 = three bf16 planes (six products), 2 = fp16 {hi, lo} planes (three products)
-static std::atomic<long> g_x3p_np = 0;          // 0: not set by mi_set_option -> MI355TTS_F32_PLANES, else 2
 // The engine's arithmetic (ArithScope, common.h) overrides the process-wide options for the calling thread
 ArithOverride& arith_tls() { static thread_local ArithOverride a; return a; }
 ArithOverride arith_for(int kind) {
@@ -555,32 +534,23 @@ ArithOverride arith_for(int kind) {
     else if (kind == ARITH_BF16X3) { a.gemm_x3 = 1; a.gemm_x3p = 1; a.planes = 3; a.n64_pairs = 0; a.gconv = 0; a.attn_x3 = 2; a.attn_np = 3; }
     return a;
 }
-static inline long opt_x3() { const int o = arith_tls().gemm_x3; return o >= 0 ? o : (long)g_x3; }
-static inline long opt_x3p() { const int o = arith_tls().gemm_x3p; return o >= 0 ? o : (long)g_x3p; }
-static inline long opt_n64_pairs() { const int o = arith_tls().n64_pairs; return o >= 0 ? o : (long)g_f32_n64_pairs; }
-static inline long opt_gconv() { const int o = arith_tls().gconv; return o >= 0 ? o : (long)g_f32_gconv; }
+static inline long opt_x3() { const int o = arith_tls().gemm_x3; return o >= 0 ? o : opt(OPT_GEMM_F32_X3); }
+static inline long opt_x3p() { const int o = arith_tls().gemm_x3p; return o >= 0 ? o : opt(OPT_GEMM_F32_X3P); }
+static inline long opt_n64_pairs() { const int o = arith_tls().n64_pairs; return o >= 0 ? o : opt(OPT_GEMM_F32_N64_PAIRS); }
+static inline long opt_gconv() { const int o = arith_tls().gconv; return o >= 0 ? o : opt(OPT_GEMM_F32_GCONV); }
 bool gemm_x3_enabled() { return opt_x3() != 0; }
 int x3p_planes() {
     const int o = arith_tls().planes;
     if (o == 2 || o == 3) return o;
-    if (g_x3p_np == 2 || g_x3p_np == 3) return (int)g_x3p_np;
-    static const int env = [] { const char* e = std::getenv("MI355TTS_F32_PLANES"); return e ? std::atoi(e) : 0; }();
-    return env == 3 ? 3 : 2;
+    return (int)opt(OPT_GEMM_F32_PLANES);
 }
 bool gemm_x3p_enabled() { return opt_x3() != 0 && opt_x3p() != 0; }
-// fp32 QKV + RoPE: its scatter epilogue is slow and in a persistent launch every workgroup runs it at the same time at the
-// end (in-model 184 us against 138 us for the 64x64 tiles, whose epilogues overlap other workgroups' main loops): off
-static std::atomic<long> g_sk_qkv32 = 0;
-// 256x256 eight-phase kernel (gemm_ph8.hip) for 16-bit linear layers with at least g_ph8_min_tiles tiles of 256x256
-static std::atomic<long> g_ph8 = 1, g_ph8_min_tiles = 200, g_ph8_order = 1;
-static std::atomic<long> g_row_split = 1;          // rows beyond the last whole round of 256x256 tiles as a second launch (launch_conv_gemm)
 static DevBuf g_zero_page[16];
 
 // buffer-descriptor DMA (BUF kernels): whole 64-deep chunks only, and every byte offset must fit the 32-bit range check
-static std::atomic<bool> g_buf = true;
 static bool buf_ok(const ConvGemmDev& d, int esz = 2) {
     const long a_bytes = (((long)d.T_in - 1) * d.x_rstride + d.Cin) * esz, b_bytes = (long)d.N * d.K * esz;
-    return g_buf && d.Cin % (128 / esz) == 0 && a_bytes + (long)512 * d.x_rstride * esz < 0x7fff0000L && b_bytes < 0x7fff0000L;
+    return opt(OPT_GEMM_BUF) && d.Cin % (128 / esz) == 0 && a_bytes + (long)512 * d.x_rstride * esz < 0x7fff0000L && b_bytes < 0x7fff0000L;
 }
 
 // a launch of dispatch_tiles: K is the uniform instantiation, KL the same tile with the lengths switch (LENS), which the
@@ -614,8 +584,8 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
             // N = 64 per group (the DiT position convolution: k = 31, 16 groups of 64 channels): 64x64 tiles of the LDS-DMA kernel
             // instead of the register-staged 128x64 one (fp32: 186 -> 120 us per launch)
             constexpr int VEC_ = 16 / (int)sizeof(T);
-            const long lim = sizeof(T) == 4 ? g_f32_n64_dma : g_n64_dma16;
-            if (lim && d.N == 64 && g_use_dma && (sizeof(T) != 4 || g_f32_dma) && d.Cin % VEC_ == 0 && d.K % d.Cin == 0) {
+            const long lim = sizeof(T) == 4 ? opt(OPT_GEMM_F32_N64_DMA) : opt(OPT_GEMM_N64_DMA16);
+            if (lim && d.N == 64 && opt(OPT_GEMM_USE_DMA) && (sizeof(T) != 4 || opt(OPT_GEMM_F32_DMA)) && d.Cin % VEC_ == 0 && d.K % d.Cin == 0) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 63) / 64; e.Tn = 1; e.RT = B * e.Tm; e.RC = 0;
                 e.use_buf = buf_ok(d, (int)sizeof(T));
@@ -646,10 +616,10 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
         if constexpr (sizeof(T) == 2) {
             // many row tiles (a batch of utterances): the 8-wave 256x256 eight-phase main loop
             const long tiles256 = (long)((d.M + 255) / 256) * ((d.N + 255) / 256);
-            if (!LENS && g_ph8 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % 64 == 0 && d.pad == 0 && d.N % 64 == 0 && buf_ok(d, 2) &&
-                d.lds_epi && (d.epi == EPI_PLAIN || d.epi == EPI_QKV_ROPE) && tiles256 >= g_ph8_min_tiles) {
+            if (!LENS && opt(OPT_GEMM_PH8) && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % 64 == 0 && d.pad == 0 && d.N % 64 == 0 && buf_ok(d, 2) &&
+                d.lds_epi && (d.epi == EPI_PLAIN || d.epi == EPI_QKV_ROPE) && tiles256 >= opt(OPT_GEMM_PH8_MIN_TILES)) {
                 ConvGemmDev e = d;
-                e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = e.Tm; e.RC = (int)g_ph8_order;
+                e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = e.Tm; e.RC = (int)opt(OPT_GEMM_PH8_ORDER);
                 launch_linear_ph8<T, TO>(e, s);
                 return;
             }
@@ -666,7 +636,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
                 e.RC = 0;       // row tiles fastest: neighbouring ranges share the weight planes, the heavier operand here (24 of the 40 KB per chunk): 62.9 -> 61.0 us
-                if (g_sk_order >= 0) e.RC = (int)g_sk_order;
+                if (opt(OPT_GEMM_SK_ORDER) >= 0) e.RC = (int)opt(OPT_GEMM_SK_ORDER);
                 no_fold();
                 launch_linear_x3(e, s);
                 return;
@@ -676,15 +646,15 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
             // plain linear layer (one tap, one group, one M axis, whole K chunks): stream-K over persistent workgroups
             constexpr int KCB = 128 / (int)sizeof(T);
             const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-            if (!LENS && !(sizeof(T) == 2 && fold) && g_sk >= (sizeof(T) == 4 ? 1 : 2) && d.sk_ws && d.sk_slots >= 256 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % KCB == 0 &&
-                (d.epi == EPI_PLAIN || (d.epi == EPI_QKV_ROPE && (sizeof(T) == 2 || g_sk_qkv32))) && buf_ok(d, (int)sizeof(T)) && d.M > 128 && tiles >= g_sk_min_tiles && tiles <= g_sk_max_tiles && d.pad == 0) {
+            if (!LENS && !(sizeof(T) == 2 && fold) && opt(OPT_GEMM_SK) >= (sizeof(T) == 4 ? 1 : 2) && d.sk_ws && d.sk_slots >= 256 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % KCB == 0 &&
+                (d.epi == EPI_PLAIN || (d.epi == EPI_QKV_ROPE && (sizeof(T) == 2 || opt(OPT_GEMM_SK_QKV32)))) && buf_ok(d, (int)sizeof(T)) && d.M > 128 && tiles >= g_sk_min_tiles && tiles <= g_sk_max_tiles && d.pad == 0) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
                 e.RC = d.M <= d.N ? 0 : 1;      // per-XCD groups: whole weight panels (x re-read 8x) when x is the smaller operand, else whole row tiles
-                if (g_sk_order >= 0) e.RC = (int)g_sk_order;
+                if (opt(OPT_GEMM_SK_ORDER) >= 0) e.RC = (int)opt(OPT_GEMM_SK_ORDER);
                 e.tail_tiles = 0;
                 no_fold();
-                launch_linear_sk<T, TO>(e, (int)g_sk_stages, s);
+                launch_linear_sk<T, TO>(e, (int)opt(OPT_GEMM_SK_STAGES), s);
                 return;
             }
         }
@@ -695,15 +665,15 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
             // the CUs idle for the whole launch, 256 tiles of 256x192 fill the chip): compare rounds x tile width
             const long rt256 = (long)B * ((d.M + 255) / 256);
             const long rounds192 = (rt256 * (d.N / 192) + 255) / 256, rounds256 = (rt256 * ((d.N + 255) / 256) + 255) / 256;
-            bool n192_wins = d.N % 256 != 0 || (d.K > g_k_min && rounds192 * 192 < rounds256 * 256);
+            bool n192_wins = d.N % 256 != 0 || (d.K > opt(OPT_GEMM_DMA3_K_MIN) && rounds192 * 192 < rounds256 * 256);
             // LENS: there is no 256x256 instantiation with lengths (its epilogue would spill: the uniform one already spills 108
             // VGPRs).  Where the uniform plan takes that tile below, a ragged launch takes the 256x192 tile when N allows and the
             // 256x128 one otherwise — still a choice of (B, M) alone
-            const bool big256 = g_use_dma3 && g_big_tiles && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > g_k_min && buf_ok(d) &&
-                                rt256 * ((d.N + 255) / 256) >= g_big_min && (((d.N + 255) / 256) * 256 - d.N) * 4 <= d.N;
+            const bool big256 = opt(OPT_GEMM_USE_DMA3) && opt(OPT_GEMM_BIG_TILES) && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > opt(OPT_GEMM_DMA3_K_MIN) && buf_ok(d) &&
+                                rt256 * ((d.N + 255) / 256) >= opt(OPT_GEMM_BIG_TILE_MIN) && (((d.N + 255) / 256) * 256 - d.N) * 4 <= d.N;
             if (LENS && big256) n192_wins = true;
-            if (!fold && g_use_dma3 && g_n192 && buf_ok(d) && d.K % d.Cin == 0 && d.M > 128 && d.N % 192 == 0 && n192_wins &&
-                d.K >= 576 && (long)B * ((d.M + 255) / 256) * (d.N / 192) >= g_n192_min) {
+            if (!fold && opt(OPT_GEMM_USE_DMA3) && opt(OPT_GEMM_N192) && buf_ok(d) && d.K % d.Cin == 0 && d.M > 128 && d.N % 192 == 0 && n192_wins &&
+                d.K >= 576 && (long)B * ((d.M + 255) / 256) * (d.N / 192) >= opt(OPT_GEMM_N192_MIN)) {
                 // N = 192 / 384 (BigVGAN stages 2 and 1): a 192-wide tile has no padded columns (128-wide tiles waste 25 %
                 // of the MFMAs and DMA bytes at N = 192) and the fewest DMA bytes per useful flop after 256x256
                 ConvGemmDev e = d;
@@ -713,14 +683,14 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                 MI_HIP(hipGetLastError());
                 return;
             }
-            if (!fold && g_use_dma3 && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > g_k_min) {
+            if (!fold && opt(OPT_GEMM_USE_DMA3) && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > opt(OPT_GEMM_DMA3_K_MIN)) {
                 ConvGemmDev e = d;
                 e.RC = 0;
                 const long blocks_128 = (long)B * ((d.M + 127) / 128) * ((d.N + 127) / 128);
                 const long blocks_256x128 = (long)B * ((d.M + 255) / 256) * ((d.N + 127) / 128);
                 const long blocks_256x256 = (long)B * ((d.M + 255) / 256) * ((d.N + 255) / 256);
                 const int n_waste_256 = ((d.N + 255) / 256) * 256 - d.N;
-                if (!LENS && g_big_tiles && buf_ok(d) && blocks_256x256 >= g_big_min && n_waste_256 * 4 <= d.N) {
+                if (!LENS && opt(OPT_GEMM_BIG_TILES) && buf_ok(d) && blocks_256x256 >= opt(OPT_GEMM_BIG_TILE_MIN) && n_waste_256 * 4 <= d.N) {
                     // every CU busy for >= 2 rounds: the tile with the fewest DMA bytes per flop
                     e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = B * e.Tm;
                     no_fold();
@@ -728,7 +698,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                     MI_HIP(hipGetLastError());
                     return;
                 }
-                if (blocks_256x128 >= g_mid_min || blocks_128 < blocks_256x128 + 32) {
+                if (blocks_256x128 >= opt(OPT_GEMM_MID_TILE_MIN) || blocks_128 < blocks_256x128 + 32) {
                     e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
                     no_fold();
                     launch_conv_gemm_dma3<T, TO>(e, 128, s);
@@ -737,14 +707,14 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                 }
                 // few tiles: fall through to the 128x128 kernel so that more CUs pull data
             }
-            if (g_use_dma && d.Cin % 8 == 0 && d.K % d.Cin == 0) {
+            if (opt(OPT_GEMM_USE_DMA) && d.Cin % 8 == 0 && d.K % d.Cin == 0) {
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
-                e.RC = g_xcd_order ? (e.RT + 7) / 8 : 0;
+                e.RC = opt(OPT_GEMM_XCD_ORDER) ? (e.RT + 7) / 8 : 0;
                 e.use_buf = buf_ok(d, 2);
                 dim3 g1(e.RC > 0 ? 8 * e.RC * e.Tn : e.RT * e.Tn, d.G);
                 const int nchunks = (d.K / d.Cin) * ((d.Cin + 63) / 64);
-                if (d.epi == EPI_PLAIN && (long)g1.x * g1.y <= g_small16_max) {
+                if (d.epi == EPI_PLAIN && (long)g1.x * g1.y <= opt(OPT_GEMM_SMALL16_MAX)) {
                     // at most one 128x128 tile per CU (the O / FF2 projections of one utterance: 144 tiles): 64x64 tiles put
                     // four times as many, shorter workgroups on ALL CUs (O 15.6 -> 12.1 us, FF2 24.6 -> 21.4 us; with 288
                     // tiles, FF1, the doubled DMA bytes per flop already cost more than the balance gains)
@@ -755,7 +725,7 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
                     MI_HIP(hipGetLastError());
                     return;
                 }
-                if (g_ring4 && (long)g1.x * g1.y <= g_ring4_max && nchunks >= 6) {
+                if (opt(OPT_GEMM_RING4) && (long)g1.x * g1.y <= opt(OPT_GEMM_RING4_MAX) && nchunks >= 6) {
                     // at most one workgroup per CU: the four-stage ring hides the DMA round trip that the two-buffer
                     // loop exposes when a CU has no second workgroup to switch to
                     if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 4>), T, TO, g1, blk, 0, s, e);
@@ -768,13 +738,13 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
         }
         if constexpr (sizeof(T) == 4) {
             // fp32: the same 128x128 LDS-DMA kernel with 32-float K chunks (MFMA-bound: 8x the MFMA cycles per DMA byte)
-            if (g_use_dma && g_f32_dma && d.Cin % 4 == 0 && d.K % d.Cin == 0) {
+            if (opt(OPT_GEMM_USE_DMA) && opt(OPT_GEMM_F32_DMA) && d.Cin % 4 == 0 && d.K % d.Cin == 0) {
                 no_fold();
                 ConvGemmDev e = d;
                 e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
-                e.RC = g_xcd_order ? (e.RT + 7) / 8 : 0;
+                e.RC = opt(OPT_GEMM_XCD_ORDER) ? (e.RT + 7) / 8 : 0;
                 e.use_buf = buf_ok(d, 4);
-                if (g_f32_small && (long)e.RT * e.Tn * d.G < g_f32_small_max) {
+                if (opt(OPT_GEMM_F32_SMALL) && (long)e.RT * e.Tn * d.G < opt(OPT_GEMM_F32_SMALL_MAX)) {
                     // fewer than a few 128x128 tiles per CU (one utterance: 144 / 288 / 432 tiles on 256 CUs): 64x64 tiles
                     // balance the chip (O projection 144 -> 576 workgroups: makespan 3 quarter-tiles instead of 4)
                     e.Tm = (d.M + 63) / 64; e.Tn = (d.N + 63) / 64; e.RT = B * e.Tm; e.RC = 0;
@@ -797,47 +767,6 @@ static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
     MI_HIP(hipGetLastError());
 }
 
-// test / tuning hook: force a tile configuration regardless of problem size
-bool gemm_set_option(const char* key, long v) {
-    const std::string k(key);
-    if (k == "gemm_big_tile_min") g_big_min = v;
-    else if (k == "gemm_n192_min") g_n192_min = v;
-    else if (k == "gemm_mid_tile_min") g_mid_min = v;
-    else if (k == "gemm_dma3_k_min") g_k_min = v;
-    else if (k == "gemm_use_dma3") g_use_dma3 = v != 0;
-    else if (k == "gemm_use_dma") g_use_dma = v != 0;
-    else if (k == "gemm_big_tiles") g_big_tiles = v != 0;
-    else if (k == "gemm_n192") g_n192 = v != 0;
-    else if (k == "gconv_two_taps") gconv_pairs_set_option(v);
-    else if (k == "gconv16") gconv16_set_option(v);
-    else if (k == "gemm_f32_dma") g_f32_dma = v != 0;
-    else if (k == "gemm_ring4") g_ring4 = v != 0;
-    else if (k == "gemm_buf") g_buf = v != 0;
-    else if (k == "gemm_f32_small") g_f32_small = v != 0;
-    else if (k == "gemm_f32_small_max") g_f32_small_max = v;
-    else if (k == "gemm_small16_max") g_small16_max = v;
-    else if (k == "gemm_ring4_max") g_ring4_max = v;
-    else if (k == "gemm_sk") g_sk = v;
-    else if (k == "gemm_sk_stages") g_sk_stages = v;
-    else if (k == "gemm_f32_x3") g_x3 = v;
-    else if (k == "gemm_f32_x3p") g_x3p = v;
-    else if (k == "gemm_f32_n64_pairs") g_f32_n64_pairs = v;
-    else if (k == "gemm_f32_gconv") g_f32_gconv = v;
-    else if (k == "gemm_f32_planes") { if (v != 2 && v != 3) return false; g_x3p_np = v; }
-    else if (k == "gemm_x3p_noalign") x3p_set_option(0, v);
-    else if (k == "gemm_x3p_grid") x3p_set_option(1, v);
-    else if (k == "gemm_x3d") x3d_set_option(0, v);
-    else if (k == "gemm_x3d_min_eff") x3d_set_option(1, v);
-    else if (k == "gemm_ph8") g_ph8 = v;
-    else if (k == "gemm_ph8_min_tiles") g_ph8_min_tiles = v;
-    else if (k == "gemm_row_split") g_row_split = v;
-    else if (k == "gemm_ph8_order") g_ph8_order = v;
-    else if (k == "gemm_ph8_split_max") ph8_set_split_max(v);               // (test hooks of the split-tail instantiation)
-    else if (k == "gemm_ph8_split_min_nk") ph8_set_split_min_nk(v);
-    else return false;
-    return true;
-}
-
 // the bf16x3 kernel (gemm_x3.hip) takes this launch: decided ONCE here, because the epilogue kind depends on it
 static bool x3_eligible(const ConvGemm& p) {
     if (!opt_x3() || !p.w3 || p.dtype != MI_F32 || (p.out_dtype >= 0 && p.out_dtype != MI_F32)) return false;
@@ -848,7 +777,7 @@ static bool x3_eligible(const ConvGemm& p) {
     const long tiles = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
     if (tiles < 64 || tiles > g_sk_max_tiles) return false;
     const long a_bytes = (((long)p.T_in - 1) * p.x_rstride + p.Cin) * 4, b_bytes = (long)3 * p.N * p.Cin * 2;
-    return g_buf && a_bytes + (long)512 * p.x_rstride * 4 < 0x7fff0000L && b_bytes < 0x7fff0000L;
+    return opt(OPT_GEMM_BUF) && a_bytes + (long)512 * p.x_rstride * 4 < 0x7fff0000L && b_bytes < 0x7fff0000L;
 }
 
 // ... and the panel-plane form of it (gemm_x3p.hip): whole 128-column weight panels, whole 32-deep chunks
@@ -866,9 +795,7 @@ bool gemm_x3p_would_run(const ConvGemm& p) { return x3p_eligible(p) && p.B == 1 
 
 // outputs leave through the LDS-staged, 16-byte-store epilogues (decided once per launch: the kernels instantiate either kind)
 static bool lds_epi_for(const ConvGemm& p, int odt, bool use_x3) {
-    static int no_lds_epi = -1;
-    if (no_lds_epi < 0) { const char* q = std::getenv("MI355TTS_NO_LDS_EPI"); no_lds_epi = (q && q[0] == '1') ? 1 : 0; }
-    if (no_lds_epi) return false;
+    if (!opt(OPT_GEMM_LDS_EPI)) return false;
     const int ch = 16 / (int)dtype_size(odt);
     // measured: +8-14 % on the K = 1024 DiT linears in the 2-blocks-per-CU 128x128 kernel, a loss on the conv shapes
     // (N <= 768) and in the one-block-per-CU 8-wave kernels, so it is used for wide linear layers only
@@ -897,8 +824,8 @@ bool gemm_ln_fold_ok(const ConvGemm& p) {
     if (p.B != 1 || p.G != 1 || p.taps != 1 || p.pad != 0 || p.alpha != 1.f || p.accumulate || p.gate_bstride != 0 || p.N % 64 != 0 || p.M <= 128) return false;
     if (p.epi != EPI_PLAIN && p.epi != EPI_QKV_ROPE) return false;
     if (p.dtype == MI_F32) return gemm_x3p_would_run(p) && lds_epi_for(p, odt, true);
-    if (!lds_epi_for(p, odt, false) || !g_use_dma || p.Cin % 64 != 0 || p.N <= 64) return false;
-    if (g_use_dma3 && p.Cin > g_k_min) return false;                    // K > 2048: the 256-row dma3 kernels are the faster choice (a preference, not a constraint: dispatch_tiles keeps fold launches off the kernels without fold epilogues)
+    if (!lds_epi_for(p, odt, false) || !opt(OPT_GEMM_USE_DMA) || p.Cin % 64 != 0 || p.N <= 64) return false;
+    if (opt(OPT_GEMM_USE_DMA3) && p.Cin > opt(OPT_GEMM_DMA3_K_MIN)) return false;                    // K > 2048: the 256-row dma3 kernels are the faster choice (a preference, not a constraint: dispatch_tiles keeps fold launches off the kernels without fold epilogues)
     return true;
 }
 
@@ -918,7 +845,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     const bool split_plain = p.epi == EPI_PLAIN && p.gate_bstride == 0 && !p.out_planes && !p.accumulate;
     const bool split_qkv = p.epi == EPI_QKV_ROPE && p.rows_per_item >= 32 && !p.kv_planes && p.m_off == 0;   // the epilogue indexes
                                                       // tokens from the flattened row: the second launch carries its row offset (m_off)
-    if (!p.lens && g_row_split != 0 && g_ph8 != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
+    if (!p.lens && opt(OPT_GEMM_ROW_SPLIT) != 0 && opt(OPT_GEMM_PH8) != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
         (split_plain || split_qkv) && p.M == p.T_in && p.N % 256 == 0 && !p.xp) {
         int dev = 0, cus = 256;
         MI_HIP(hipGetDevice(&dev));
@@ -934,7 +861,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
         const long r = (p.M / 256) / rstep * rstep;               // N = 1024 / 2048 / 3072 on 256 CUs: multiples of 64 / 32 / 64
         const long rem = p.M - 256 * r;
         const long rem_tiles = (rem + 255) / 256 * ntn;
-        if (r >= 1 && rem > 0 && rem_tiles * 2 < cus && r * ntn >= g_ph8_min_tiles) {
+        if (r >= 1 && rem > 0 && rem_tiles * 2 < cus && r * ntn >= opt(OPT_GEMM_PH8_MIN_TILES)) {
             ConvGemm a = p, b = p;
             a.M = a.T_in = (int)(256 * r);
             b.M = b.T_in = (int)rem;
@@ -1009,35 +936,6 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     d.tail_tiles = 0; d.tail_split = 1;
     d.use_buf = 0;
     {
-        static std::once_flag env_once;      // handles on different threads may launch concurrently
-        std::call_once(env_once, [] { const char* e = std::getenv("MI355TTS_NO_DMA_GEMM"); g_use_dma = !(e && e[0] == '1');
-            const char* x = std::getenv("MI355TTS_XCD_ORDER"); g_xcd_order = x && x[0] == '1';
-            const char* y = std::getenv("MI355TTS_NO_DMA3_GEMM"); g_use_dma3 = !(y && y[0] == '1');
-            const char* z = std::getenv("MI355TTS_NO_BIG_TILES"); g_big_tiles = !(z && z[0] == '1');
-            if (const char* m = std::getenv("MI355TTS_BIG_TILE_MIN")) g_big_min = std::atol(m);
-            if (const char* m = std::getenv("MI355TTS_DMA3_K_MIN")) g_k_min = std::atol(m);
-            if (const char* n = std::getenv("MI355TTS_NO_N192")) g_n192 = !(n[0] == '1');
-            if (const char* n = std::getenv("MI355TTS_NO_RING4")) g_ring4 = !(n[0] == '1');
-            if (const char* n = std::getenv("MI355TTS_NO_BUF")) g_buf = !(n[0] == '1');
-            if (const char* n = std::getenv("MI355TTS_NO_F32_SMALL")) g_f32_small = !(n[0] == '1');
-            if (const char* n = std::getenv("MI355TTS_F32_SMALL_MAX")) g_f32_small_max = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_F32_N64_DMA")) g_f32_n64_dma = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_N64_DMA16")) g_n64_dma16 = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_SMALL16_MAX")) g_small16_max = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_RING4_MAX")) g_ring4_max = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_SK")) g_sk = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_SK_STAGES")) g_sk_stages = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_SK_ORDER")) g_sk_order = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_F32_X3")) g_x3 = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_F32_X3P")) g_x3p = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_X3P_NOALIGN")) x3p_set_option(0, std::atol(n));
-            if (const char* n = std::getenv("MI355TTS_X3P_GRID")) x3p_set_option(1, std::atol(n));
-            if (const char* n = std::getenv("MI355TTS_SK_QKV32")) g_sk_qkv32 = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_PH8")) g_ph8 = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_PH8_MIN")) g_ph8_min_tiles = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_PH8_ORDER")) g_ph8_order = std::atol(n);
-            if (const char* n = std::getenv("MI355TTS_PH8_SPLIT")) ph8_set_split_max(std::atol(n));
-        });
         int dev = 0;
         MI_HIP(hipGetDevice(&dev));
         {
@@ -1047,8 +945,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
             if (!z.p) { z.ensure(4096); MI_HIP(hipMemset(z.p, 0, 4096)); MI_HIP(hipDeviceSynchronize()); }
             d.zero = z.p;
         }
-        const char* dm = std::getenv("MI355TTS_GEMM_DBG");
-        d.dbg = dm ? std::atoi(dm) : 0;
+        d.dbg = (int)env_int("MI355TTS_GEMM_DBG", 0);
         // K-loop order of the DMA kernels is (channel chunk, tap), not (tap, channel chunk): sweeping all Cin channels
         // of a block's rows once per tap overflowed the 4 MiB XCD L2 between taps at C = 384 (32 resident blocks x 196 KB
         // of rows) and every tap re-fetched its rows from the fabric (PMC: 341 MB per launch against 100 MB algorithmic);
@@ -1075,9 +972,9 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     ProfScope ps(FAM_CONV_GEMM, s, bytes, flops);
 
     // fp32 grouped convolutions with 64 channels per group and >= 8 taps (the DiT's position convolution): gconv_pairs.hip
-    if (!p.lens && p.dtype == MI_F32 && opt_x3() != 0 && opt_n64_pairs() != 0 && opt_gconv() != 0 && g_use_dma && launch_gconv_pairs(p, s)) return;
+    if (!p.lens && p.dtype == MI_F32 && opt_x3() != 0 && opt_n64_pairs() != 0 && opt_gconv() != 0 && opt(OPT_GEMM_USE_DMA) && launch_gconv_pairs(p, s)) return;
     // ... and the same shape on the 16-bit engines, weights as LDS images built at load: gconv16.hip
-    if (!p.lens && p.dtype != MI_F32 && p.gcp_w && g_use_dma && launch_gconv16(p, s)) return;
+    if (!p.lens && p.dtype != MI_F32 && p.gcp_w && opt(OPT_GEMM_USE_DMA) && launch_gconv16(p, s)) return;
     if (p.lens) {
         MI_REQUIRE(odt == p.dtype, "conv_gemm: a launch with lengths writes the engine dtype");
         if (p.dtype == MI_F32) dispatch_tiles<float, float, true>(d, p.B, s);

@@ -842,13 +842,9 @@ void launch_linear_x3(const ConvGemmDev& e, hipStream_t s);
 // gemm_ph8.hip: 256x256 eight-phase kernel for 16-bit linear layers with many row tiles
 template <typename T, typename TO> void launch_linear_ph8(const ConvGemmDev& e, hipStream_t s);
 void launch_linear_x3p(const ConvGemmDev& e, hipStream_t s);
-void x3p_set_option(int which, long v);
 // gemm_x3d.hip: exact-fit data-parallel form of linear_x3p (np = 2) — taken by launch_linear_x3p when x3d_plan finds a tiling
 bool x3d_plan(const ConvGemmDev& e, int cus, int& tw, int& rgn, int& cgn, int& band);
 void launch_linear_x3d(const ConvGemmDev& e, int tw, int rgn, int cgn, int band, hipStream_t s);
-void x3d_set_option(int which, long v);
-void ph8_set_split_max(long v);
-void ph8_set_split_min_nk(long v);
 
 
 }  // namespace mi

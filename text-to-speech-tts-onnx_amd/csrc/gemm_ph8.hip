@@ -34,7 +34,6 @@
 //
 // The DMA instructions are issued from inline asm (see gemm_sk.hip: hipcc drains vmcnt in front of a ds_read that follows
 // a builtin LDS-DMA).  Epilogues: the shared LDS-staged ones (gemm_epilogue.h) on the wave's contiguous 128x64 tile.
-#include <atomic>
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
@@ -327,9 +326,6 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
 #endif
 }
 
-static std::atomic<long> g_ph8_split_max = 2, g_ph8_split_min_nk = 24;      // measured: a gain only for the K = 2048 layer (FF2, 32 K tiles), two slices
-void ph8_set_split_min_nk(long v) { g_ph8_split_min_nk = v; }
-void ph8_set_split_max(long v) { g_ph8_split_max = v < 1 ? 1 : v > 4 ? 4 : v; }       // the kernel's fix-up is unrolled for at most 4 slices
 
 template <typename T, typename TO>
 void launch_linear_ph8(const ConvGemmDev& e_in, hipStream_t s) {
@@ -342,12 +338,12 @@ void launch_linear_ph8(const ConvGemmDev& e_in, hipStream_t s) {
         cus = cu_count[dev & 15];
     }
     const int T_all = e.Tm * e.Tn, nk = e.K / 64;
-    // split tail: the largest S (<= g_ph8_split_max) with S * rem workgroups on the chip at once, >= 4 K tiles per slice and
+    // split tail: the largest S (<= gemm_ph8_split_max) with S * rem workgroups on the chip at once, >= 4 K tiles per slice and
     // (S - 1) * rem slabs of 256 KB in the workspace; worth it only when the tail round is mostly empty
     const int rem = T_all % cus;
     int S = 1;
-    if (T_all > cus && rem > 0 && rem * 2 <= cus && e.sk_ws && e.sk_flags && nk >= g_ph8_split_min_nk) {
-        for (int c = 2; c <= (int)g_ph8_split_max; ++c)
+    if (T_all > cus && rem > 0 && rem * 2 <= cus && e.sk_ws && e.sk_flags && nk >= opt(OPT_GEMM_PH8_SPLIT_MIN_NK)) {
+        for (int c = 2; c <= (int)opt(OPT_GEMM_PH8_SPLIT_MAX); ++c)
             if (rem * c <= cus && nk / c >= 4 && (long)rem * (c - 1) * 4 <= e.sk_slots) S = c;
     }
     e.tail_tiles = S > 1 ? rem : 0;

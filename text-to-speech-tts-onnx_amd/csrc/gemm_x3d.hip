@@ -27,12 +27,10 @@
 // pieces of a step ride on the MFMAs of phase 1 two (TW = 128: three) steps ahead.
 // Epilogue: the tile is staged in LDS as 32 x 64 blocks in the 32x32 accumulator layout's order, each wave takes blocks and
 // runs gemm_epilogue.h's per-role epilogues unchanged (QKV + RoPE + V^T | FF1 planes + GELU | gated residual + AdaLN fold).
-#include <atomic>
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
 #include "x3_split.h"
-#include <cstdlib>
 #include <type_traits>
 #include <algorithm>
 
@@ -353,18 +351,10 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
 #endif
 }
 
-static std::atomic<long> g_x3d = 1, g_x3d_min_eff = 90;       // options gemm_x3d (0 off, 1 automatic), gemm_x3d_min_eff (per cent of useful tile area)
-void x3d_set_option(int which, long v) { if (which == 0) g_x3d = v; else g_x3d_min_eff = v; }
 
 // Does an exact-fit tiling exist for this launch?  tw: tile width, rgn x cgn tiles, band: row groups per band of the tile order.
 bool x3d_plan(const ConvGemmDev& e, int cus, int& tw, int& rgn, int& cgn, int& band) {
-    static int env_read = 0;
-    if (!env_read) {
-        env_read = 1;
-        if (const char* s = std::getenv("MI355TTS_X3D")) g_x3d = std::atol(s);
-        if (const char* s = std::getenv("MI355TTS_X3D_MIN_EFF")) g_x3d_min_eff = std::atol(s);
-    }
-    if (!g_x3d || e.np != 2 || !e.lds_epi || e.K % 32 != 0 || cus < 8) return false;
+    if (!opt(OPT_GEMM_X3D) || e.np != 2 || !e.lds_epi || e.K % 32 != 0 || cus < 8) return false;
     const int nch = e.K / 32;
     double best = 0.0; int btw = 0;
     for (int w : {192, 128, 64}) {
@@ -376,7 +366,7 @@ bool x3d_plan(const ConvGemmDev& e, int cus, int& tw, int& rgn, int& cgn, int& b
         const double eff = (double)e.M * e.N / ((double)rounds * cus * 144.0 * w);
         if (eff > best + 1e-9) { best = eff; btw = w; }         // ties: the wider tile (fewer L2 -> LDS bytes per flop)
     }
-    if (!btw || best * 100.0 < (double)g_x3d_min_eff) return false;
+    if (!btw || best * 100.0 < (double)opt(OPT_GEMM_X3D_MIN_EFF)) return false;
     tw = btw; rgn = (e.M + 143) / 144; cgn = e.N / btw;
     // band height a: an XCD's 32 consecutive tiles span a row groups x 32 / a column groups; fabric bytes ~ a * 144 + (32 / a) * tw rows
     int ba = 1; double bc = 1e300;

@@ -37,13 +37,11 @@
 //    CYCLICALLY from a per-tile start chunk chosen so that all workgroups of the launch are at the same physical chunk at
 //    the same time (ranges still differ by (range length mod chunks-per-tile) for their tail pieces): the workgroups of an
 //    XCD that share a row or weight panel request the same 24 KB within a few chunk times of each other.
-#include <atomic>
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
 #include "x3_split.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace mi {
 
@@ -476,8 +474,6 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
 #endif
 }
 
-static std::atomic<long> g_x3p_noalign = 0, g_x3p_grid = 0;       // A/B switches: 1 = no cyclic K alignment ; grid: 0 = automatic, else GR (1, 2, 4, 8)
-void x3p_set_option(int which, long v) { if (which == 0) g_x3p_noalign = v; else g_x3p_grid = v; }
 
 void launch_linear_x3p(const ConvGemmDev& e_in, hipStream_t s) {
     ConvGemmDev e = e_in;
@@ -500,20 +496,20 @@ void launch_linear_x3p(const ConvGemmDev& e_in, hipStream_t s) {
     int best = 1; double best_cost = 1e300;
     for (int gr = 1; gr <= 8; gr *= 2) {
         const int gc = 8 / gr;
-        if (g_x3p_grid && gr != g_x3p_grid) continue;
+        if (opt(OPT_GEMM_X3P_GRID) && gr != opt(OPT_GEMM_X3P_GRID)) continue;
         long worst = 0, least = 1L << 60;
         for (int a = 0; a < gr; ++a)
             for (int b = 0; b < gc; ++b) {
                 const long t = ((long)(a + 1) * e.Tm / gr - (long)a * e.Tm / gr) * ((long)(b + 1) * e.Tn / gc - (long)b * e.Tn / gc);
                 worst = std::max(worst, t); least = std::min(least, t);
             }
-        if (least == 0 && !g_x3p_grid) continue;
+        if (least == 0 && !opt(OPT_GEMM_X3P_GRID)) continue;
         const double traffic = (double)gc * e.M + (double)gr * e.N;       // x K x 6 bytes, common factor dropped
         const double cost = (double)worst * 1e9 + traffic;
         if (cost < best_cost) { best_cost = cost; best = gr; }
     }
     e.RT = best; e.RC = 8 / best;
-    e.tail_tiles = (int)g_x3p_noalign;
+    e.tail_tiles = (int)opt(OPT_GEMM_X3P_NOALIGN);
     const int P = std::min(cus, e.sk_slots - 8) & ~7;          // the LAST flag word is the watchdog's error word (SkWorkspace::tripped)
     const dim3 grid(P);
     MI_REQUIRE(e.np == 2 || e.np == 3, "linear_x3p: 2 or 3 planes per operand");

@@ -13,19 +13,11 @@
 // argument: it is captured once and replayed.  A decode step is a chain of weight-streaming GEMVs (HBM-bound:
 // every weight byte is read once per token), so the GEMV kernel is a plain coalesced 16-byte-per-lane dot product,
 // not an MFMA tile; the prompt pass (ids_len rows at once) goes through the MFMA implicit-GEMM kernel instead.
-#include <atomic>
 #include "gpt.h"
 #include "mfma.h"
 #include "wave_reduce.h"
-#include <cstdlib>
 
 namespace mi {
-
-static std::atomic<long> g_gpt_mfma_min = 9;
-bool gpt_set_option(const char* key, long v) {
-    if (std::string(key) == "gpt_mfma_min") { g_gpt_mfma_min = v; return true; }
-    return false;
-}
 
 GptCfg parse_gpt_cfg(const int32_t* ci, int ni) {
     MI_REQUIRE(ci && (ni == 9 || ni == 10), "gpt cfg: expected 9 or 10 ints");
@@ -910,8 +902,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     rep_dev.ensure(4);
     MI_HIP(hipStreamSynchronize(s));
     set_rep_value(0.7f);
-    const char* ng = std::getenv("MI355TTS_NO_GRAPH");
-    use_graph = !(ng && ng[0] == '1');
+    use_graph = !env_first_is("MI355TTS_NO_GRAPH", '1');
     // the attention kernel's score buffer is dynamic LDS: max_seq + 64 + 512 floats
     const int lds = (c.max_seq + 64 + 512) * 4;
     MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1135,12 +1126,10 @@ void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int a
     ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * dtype_size(dtype), 2.0 * l.n * l.k * nb);
     const size_t sstride = slot_cache_elems();
     {   // matrix-core path: 16-bit engines, nine or more sentences, K splits into 64-wide blocks per wave
-        static int no_mfma = -1;
-        if (no_mfma < 0) { const char* e = std::getenv("MI355TTS_GPT_NO_MFMA"); no_mfma = (e && e[0] == '1') ? 1 : 0; }
         const int KS = l.k > 2048 ? 8 : 4;
         // measured (1280-wide model): the MFMA kernel costs ~9.5 us per launch whatever the batch, the v_dot2 GEMV
         // 10 / 12.7 / 20 us at 4 / 8 / 16 sentences
-        if (!no_mfma && dtype != MI_F32 && nb >= g_gpt_mfma_min && nb <= 16 && l.k % (KS * 64) == 0) {
+        if (opt(OPT_GPT_MFMA) && dtype != MI_F32 && nb >= opt(OPT_GPT_MFMA_MIN) && nb <= 16 && l.k % (KS * 64) == 0) {
             const int TR = 8 / KS;
             const dim3 gs((unsigned)((l.n + 16 * TR - 1) / (16 * TR)));
             const bool u5 = (l.k / KS) % 320 == 0;

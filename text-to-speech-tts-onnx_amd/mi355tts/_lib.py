@@ -141,6 +141,7 @@ def load() -> C.CDLL:
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]
     L.mi_bench_conv_gemm.restype = C.c_int
     L.mi_set_option.argtypes = [C.c_char_p, C.c_int64]; L.mi_set_option.restype = C.c_int
+    L.mi_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]; L.mi_get_option.restype = C.c_int
     L.mi_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_int]; L.mi_device_pci_bus_id.restype = C.c_int
     L.mi_prof_enable.argtypes = [C.c_int]; L.mi_prof_enable.restype = C.c_int
     L.mi_prof_reset.argtypes = []; L.mi_prof_reset.restype = C.c_int
@@ -231,3 +232,11 @@ def device_pci_bus_id(device: int) -> str:
 
 def set_option(key: str, value: int) -> None:
     check(load().mi_set_option(key.encode(), int(value)), "mi_set_option")
+
+
+def get_option(key: str) -> int:
+    """What the process runs with: the default, overridden by the environment (read once, at the first call into the library),
+    overridden by set_option."""
+    v = C.c_int64(0)
+    check(load().mi_get_option(key.encode(), C.byref(v)), "mi_get_option")
+    return int(v.value)

@@ -139,6 +139,8 @@ int         mi_f5_tables(mi_f5* h, float* time_expand, float* delta_t);
  *   "saturation_events"  calls on this handle during which a pair operand met the fp16 range limit and that were therefore
  *                        re-run on three bf16 planes (0 or 1: the switch is permanent)
  *   "adaln_fold"         1 when the load-time vectors of the AdaLN fold exist (LayerNorm statistics carried by the GEMM epilogues)
+ *   "attn_v_rows"        1 when an fp32 engine's QKV epilogue hands pre-split V to attention as rows like K (the default), 0 when
+ *                        transposed (environment MI355TTS_ATTN_V_ROWS=0, or K / V not pre-split)
  * Returns the value, or a negative MI_E* code for a null handle / unknown key.                                              */
 int64_t     mi_f5_info(mi_f5* h, const char* key);
 /* graph A.  audio (L) int16, text_ids (T) int32 (pad value -1 allowed), max_duration N.

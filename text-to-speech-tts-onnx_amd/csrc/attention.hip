@@ -502,6 +502,53 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 // operands of attention are of order one, their residuals stay above fp16's subnormal floor where it matters) and Q / P are
 // split the same way: three partial products per block, small terms first, into the one accumulator — half the MFMAs of the
 // three-plane form, 4 instead of 6 bytes per K / V element, no second accumulator set.
+// VROWS (only with KVP): V arrives as rows like K, v = [bh][NP][kld][64] — the QKV epilogue then has no transposing branch for
+// V (its 2-byte stores, 32 different rows per instruction, were ~4 us of that launch).  A stage of V is copied to LDS exactly like
+// K, one 16-byte store per unit, into plain 128-byte rows [key][64 d] whose 16-byte chunk index is XORed with 4 * ((key >> 1) & 1);
+// the P V operand (d along the lanes, eight keys per lane) comes out of the transposing LDS read of gfx950, two reads per
+// fragment as before.  Bank arithmetic (bank = (byte / 4) mod 64 over a 32-lane half, 4 keys x 32 d per half): key parity selects
+// the 128-byte half of the bank row, the XOR moves keys 2, 3 of a block onto the other 64 bytes, the 32 d are 64 contiguous bytes:
+// every bank once.  The 16-byte stage stores cover one whole row per eight lanes whatever the XOR: conflict-free too.  The
+// fragment holds the same keys in the same element order as the V^T form (keys 16 s2 + 4 hi + {0..3} and + 8), so the MFMA sequence
+// and every operand are unchanged: results are bit-identical to the V^T layout.  Rows of the global planes past N may hold any
+// bytes (another mode's, another length's): the last stage clears whole units by their key row, not by what the buffer holds.
+typedef unsigned attn_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned attn_lds_addr(const void* p) {
+    return (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)p;
+}
+// one transposing read: per 16-lane group a block of 4 rows x 16 columns of 16-bit elements; lane 4q + p of the group supplies the
+// (8-byte aligned) address of row q, columns 4p .. 4p + 3, lane i receives column i, row q in element q.  EXEC must be all ones.
+// Inline asm: the compiler does NOT wait for it (attn_tr_wait).
+template <int OFF> __device__ __forceinline__ void attn_lds_rd64_tr16(attn_u2& d, unsigned a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF) : "memory");
+#endif
+}
+__device__ __forceinline__ void attn_tr_wait() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+}
+// after attn_tr_wait(): volatile asm statements keep their order, so a use of d cannot move above the wait.  This rests on the
+// compiler placing no copy or spill of d between the read and the wait (it cannot know that d is still in flight there): the VROWS
+// instantiations build without spills (tools/kernel_resources.py) — check that again after any change that adds register pressure.
+__device__ __forceinline__ void attn_tr_use(attn_u2& d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(d));
+#endif
+}
+template <int N, int I = 0, typename F> __device__ __forceinline__ void attn_unroll(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); attn_unroll<N, I + 1>(f); }
+}
+// the 2 x NP fragments of the keys 16 S2 .. 16 S2 + 15 of a 32-key tile: a0 / a1 = the lane's address for head-dim half 0 / 1 in
+// plane 0 at the tile's first key; PLB = bytes per plane.  Low planes first: the order in which the products use them.
+template <int NP, int PLB, int S2> __device__ __forceinline__ void attn_v_tr_read(attn_u2 (&t)[2][NP][2], unsigned a0, unsigned a1) {
+    attn_unroll<NP>([&](auto PL) {
+        constexpr int pl = NP - 1 - decltype(PL)::value, o = pl * PLB + S2 * 16 * 128;
+        attn_lds_rd64_tr16<o>(t[0][pl][0], a0); attn_lds_rd64_tr16<o + 8 * 128>(t[0][pl][1], a0);
+        attn_lds_rd64_tr16<o>(t[1][pl][0], a1); attn_lds_rd64_tr16<o + 8 * 128>(t[1][pl][1], a1);
+    });
+}
 #if defined(MI355TTS_ATTN_TRACE)      // tuning only: s_memtime stamps at the phase boundaries of one wave (tools/dbg/attn_trace.sh)
 #define TSTAMP(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define TACC(k, t1, t0) tr_[k] += (t1) - (t0)
@@ -509,7 +556,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 #define TSTAMP(v) do { } while (0)
 #define TACC(k, t1, t0) do { } while (0)
 #endif
-template <bool SPLIT2, bool KVP = false, int NP = 3, bool VARLEN = false>
+template <bool SPLIT2, bool KVP = false, int NP = 3, bool VARLEN = false, bool VROWS = false>
 __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, float* __restrict__ o, int H, int N,
                                                        float* __restrict__ ws, int* __restrict__ cnt,
@@ -519,11 +566,13 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     // o_planes != null: the output leaves as gemm_x3p.hip panel planes of the [B * N][H * 64] matrix (the A operand of the O
     // projection), split here (o_np = 3 bf16 planes | 2 fp16 planes), instead of fp32 rows in o
     static_assert(NP == 3 || (NP == 2 && KVP), "attn_x3f: the two-plane form reads pre-split K / V");
+    static_assert(!VROWS || KVP, "attn_x3f: V as rows is a layout of the pre-split planes");
     using MF = std::conditional_t<NP == 3, Mfma<bf16>, Mfma<f16>>;
     using Frag = typename MF::Frag;
     constexpr int D = 64, KT = 64;
-    constexpr int LDK = D + 8, LDV = KT + 4;                // bf16 elements per plane row
-    constexpr int KPL = KT * LDK, VPL = D * LDV;            // elements per plane
+    constexpr int LDK = D + 8, LDV = VROWS ? D : KT + 4;    // bf16 elements per plane row (VROWS: V rows are keys, unpadded, chunks XORed)
+    constexpr int KPL = KT * LDK, VPL = VROWS ? KT * LDV : D * LDV;            // elements per plane
+    static_assert((NP * KPL * 2) % 16 == 0 && (VPL * 2) % 16 == 0, "attn_x3f: 16-byte aligned V planes");
     __shared__ __attribute__((aligned(16))) bf16 smem[NP * KPL + NP * VPL];            // 16-bit storage (bf16 or fp16 bit patterns)
     static_assert(sizeof(smem) >= (2 * 32 * 64 + 2 * 64 * 2 + 4) * sizeof(float), "merge buffer fits the stage");
     bf16* Ks = smem;
@@ -586,21 +635,29 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
         }
     }
 
-    // ---- stage loads: 64 keys x 64 d of K (rows = keys) and of V^T (rows = d), four float4 per thread each ----------------
+    // ---- stage loads: 64 keys x 64 d of K (rows = keys) and of V (VROWS: rows = keys like K; else V^T, rows = d) ----------------
     float4 kreg[KVP ? 1 : 4], vreg[KVP ? 1 : 4];
     constexpr int NU = 2 * NP;                              // KVP: 16-byte units per thread and operand per stage
     x3_u4 kpl[KVP ? NU : 1], vpl[KVP ? NU : 1];
     auto load_regs = [&](int key0) {
         if constexpr (KVP) {
-            // unit u = tid + 256 i: plane u / 512 ; K: key (u % 512) / 8, 8 d's ; V^T: d (u % 512) / 8, 8 keys.  Rows past N are
-            // inside the padded planes (K: any finite-or-not value, masked below; V: zero since allocation)
+            // unit u = tid + 256 i: plane u / 512 ; K (and V with VROWS): key (u % 512) / 8, 8 d's ; V^T: d (u % 512) / 8, 8 keys.
+            // Keys past N are inside the padded planes and may hold any bytes, finite or not (another length's, another layout's):
+            // K's scores are masked in the tile, V's values are cleared below
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 const int u = tid + i * 256, pl = u >> 9, r = (u & 511) >> 3, c = u & 7;
                 kpl[i] = *reinterpret_cast<const x3_u4*>(kpb + ((long)pl * vld + key0 + r) * D + c * 8);
-                vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * D + r) * vld + key0 + c * 8);
+                if constexpr (VROWS) vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * vld + key0 + r) * D + c * 8);
+                else vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * D + r) * vld + key0 + c * 8);
             }
-            if (key0 + KT > NL) {
+            if (VROWS && key0 + KT > NL) {
+                // last stage, V as rows: a unit is eight d's of ONE key — cleared whole when that key is >= NL (0 x NaN is NaN, and
+                // the rows past N hold whatever the buffer held before)
+#pragma unroll
+                for (int i = 0; i < NU; ++i)
+                    if (key0 + (((tid + i * 256) & 511) >> 3) >= NL) vpl[i] = x3_u4{0u, 0u, 0u, 0u};
+            } else if (key0 + KT > NL) {
                 // last stage: the V^T values of keys >= N meet probabilities that are exactly zero, but 0 x NaN is NaN and
                 // the pad columns hold whatever the buffer held before (another layout, another mode): clear them here
 #pragma unroll
@@ -639,8 +696,12 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
             for (int i = 0; i < NU; ++i) {
                 const int u = tid + i * 256, pl = u >> 9, r = (u & 511) >> 3, c = u & 7;
                 *reinterpret_cast<x3_u4*>(Ks + pl * KPL + r * LDK + c * 8) = kpl[i];                 // 144-byte rows: 16-byte aligned
+                if constexpr (VROWS) {
+                    *reinterpret_cast<x3_u4*>(Vs + pl * VPL + r * LDV + ((c ^ ((r & 2) << 1)) * 8)) = vpl[i];   // 128-byte rows, chunk ^ 4 * ((key >> 1) & 1)
+                } else {
                 uint2* vd = reinterpret_cast<uint2*>(Vs + pl * VPL + r * LDV + c * 8);                // 136-byte rows: 8-byte aligned
                 vd[0] = uint2{vpl[i].x, vpl[i].y}; vd[1] = uint2{vpl[i].z, vpl[i].w};
+                }
             }
         } else {
 #pragma unroll
@@ -660,6 +721,15 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
         }
     };
 
+    // VROWS: this lane's address in the transposed reads of V, plane 0, key 0 of the stage, head-dim half 0 / 1: block row q =
+    // (lane >> 2) & 3 of keys 4 hi + q, columns 16 * ((lane >> 4) & 1) + 4 * (lane & 3) .. + 3 of the half (dt ^ (q >> 1): the XOR)
+    unsigned vtr[2] = {0u, 0u};
+    if constexpr (VROWS) {
+        const int q4 = (lane >> 2) & 3;
+        const unsigned a = attn_lds_addr(Vs) + (4 * hi + q4) * (LDV * 2) + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
+        vtr[0] = a + (q4 >> 1) * 64;
+        vtr[1] = a + ((q4 >> 1) ^ 1) * 64;
+    }
     f32x16 oacc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { oacc[0][r] = 0.f; oacc[1][r] = 0.f; }
@@ -733,18 +803,21 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { oacc[0][r] *= alpha; oacc[1][r] *= alpha; }
             }
-            typedef float f2 __attribute__((ext_vector_type(2)));
+            // s - m and the row sum as SCALAR fp32 VALU: packed fp32 instructions beside MFMAs cost more than the two scalar ones they
+            // replace (the float2 form of this loop, and the compiler's own pairing of adjacent scalar operations, measured
+            // +0.66 ms per step: LOG.md round 7).  The empty asm statements keep the vectoriser from pairing them again.  Two
+            // partial sums, even and odd registers, added at the end: the values and the order of the float2 form, bit-identical.
             float p[16];
-            f2 ls2 = f2{0.f, 0.f};
-            const f2 m2 = f2{m_run, m_run};
+            float ls0 = 0.f, ls1 = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                const f2 dd = f2{sacc[r], sacc[r + 1]} - m2;
-                const f2 e = f2{__builtin_amdgcn_exp2f(dd.x), __builtin_amdgcn_exp2f(dd.y)};
-                p[r] = e.x; p[r + 1] = e.y;
-                ls2 += e;
+                float d0 = sacc[r] - m_run, d1 = sacc[r + 1] - m_run;
+                asm("" : "+v"(d0)); asm("" : "+v"(d1));
+                p[r] = __builtin_amdgcn_exp2f(d0); p[r + 1] = __builtin_amdgcn_exp2f(d1);
+                ls0 += p[r]; ls1 += p[r + 1];
+                asm("" : "+v"(ls0)); asm("" : "+v"(ls1));
             }
-            float lsum = ls2.x + ls2.y;
+            float lsum = ls0 + ls1;
             lsum = xor32_sum(lsum);
             l_run = l_run * alpha + lsum;
 #if defined(MI355TTS_ATTN_TRACE)
@@ -766,6 +839,20 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                 // (The same for the two score tiles of a stage in the 128-query form was measured too: 27 spilled registers and
                 // the stage loads issued one tile later cost more than the chains gain, 56.9 -> 70.8 us.)
                 Frag vf[2][NP];
+                if constexpr (VROWS) {
+                    // the same eight keys per lane, in the same order, as the two 8-byte row reads of the V^T image below
+                    attn_u2 t[2][NP][2];
+                    const unsigned a0 = vtr[0] + kt * (32 * LDV * 2), a1 = vtr[1] + kt * (32 * LDV * 2);
+                    if (s2 == 0) attn_v_tr_read<NP, VPL * 2, 0>(t, a0, a1); else attn_v_tr_read<NP, VPL * 2, 1>(t, a0, a1);
+                    attn_tr_wait();
+#pragma unroll
+                    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                        for (int pl = 0; pl < NP; ++pl) {
+                            attn_tr_use(t[dt][pl][0]); attn_tr_use(t[dt][pl][1]);
+                            vf[dt][pl] = __builtin_bit_cast(Frag, x3_u4{t[dt][pl][0].x, t[dt][pl][0].y, t[dt][pl][1].x, t[dt][pl][1].y});
+                        }
+                } else {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -776,6 +863,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                         a2[1] = *reinterpret_cast<const uint2*>(row + 8);
                         vf[dt][pl] = __builtin_bit_cast(Frag, x3_u4{a2[0].x, a2[0].y, a2[1].x, a2[1].y});
                     }
+                }
                 if constexpr (NP == 3) {
 #pragma unroll
                     for (int t = 0; t < 6; ++t)
@@ -981,6 +1069,7 @@ bool attention_takes_kv_planes(int N, int BH, int dtype) {
 }
 
 int attention_kv_planes_format() { return opt_attn_np(); }
+bool attention_kv_v_rows() { return opt(OPT_ATTN_V_ROWS) != 0; }
 
 bool attention_can_write_planes(int N, int BH, int dtype) {
     (void)N; (void)BH;
@@ -1042,11 +1131,20 @@ static AttnSlices attn_pick_slices(long units, int S, int slots, int zmax) {
 
 // One launch of either kernel.  lens != nullptr: the VARLEN instantiation (ragged batch, ATTN_VARLEN_PROLOGUE); the grid, the
 // slices and every other argument are those of the uniform launch at the same N.
+// v_rows: the layout the QKV epilogue wrote for V (ConvGemm::v_rows), passed by the caller — only with KVP.
 template <bool SPLIT2, bool KVP, int NP>
 static void go_x3f(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int H, int N, float* ws, int* cnt,
-                   void* o_planes, int o_np, int xm, int c1, int c2, int c3, const int* lens) {
+                   void* o_planes, int o_np, int xm, int c1, int c2, int c3, const int* lens, bool v_rows) {
     const float *qf = (const float*)q, *kf = (const float*)k, *vf = (const float*)v;
     if (lens) prof_kernel_suffix(" + lengths");
+    if constexpr (KVP) {
+        if (v_rows) {
+            if (lens) hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, true, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3, lens);
+            else hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, false, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3);
+            return;
+        }
+    }
+    MI_REQUIRE(!v_rows, "attention: V as rows is a layout of the pre-split planes");
     if (lens) hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3, lens);
     else hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3);
 }
@@ -1061,7 +1159,8 @@ static void go_attn(dim3 grid, hipStream_t s, const void* q, const void* k, cons
 
 void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
                       float* ws, long ws_floats, int* cnt, long cnt_n, void* o_planes, int kv_planes, int o_np, float ref_fp16_scale,
-                      const int* lens) {
+                      const int* lens, int v_rows) {
+    MI_REQUIRE(!v_rows || kv_planes, "attention: V as rows comes with pre-split K / V");
     MI_REQUIRE(ref_fp16_scale == 0.f || (dtype == MI_F16 && ref_fp16_scale > 0.f), "attention: the reference-fp16 score form needs f16 operands");
     MI_REQUIRE(o_np == 2 || o_np == 3, "attention: 2 or 3 output planes");
     MI_REQUIRE(!o_planes || attention_can_write_planes(N, BH, dtype), "attention: panel-plane output needs the fp32 split kernel");
@@ -1146,17 +1245,17 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
                 }
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs> + key slices", "", "");
                 go_x3f<false, true, 2>(dim3((N + 127) / 128, BH, sl.Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm,
-                                       sl.Z > 1 ? sl.cut[0] : 0, sl.cut[1], sl.cut[2], lens);
+                                       sl.Z > 1 ? sl.cut[0] : 0, sl.cut[1], sl.cut[2], lens, v_rows != 0);
             } else if (opt_attn_x3() == 2) {
                 if (kv_planes == 2) {
                     prof_set_kernel("attn_x3f_kernel<true, pre-split K V, fp16 pairs>", "", "");
-                    go_x3f<true, true, 2>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens);
+                    go_x3f<true, true, 2>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens, v_rows != 0);
                 } else if (kv_planes) {
                     prof_set_kernel("attn_x3f_kernel<true, pre-split K V>", "", "");
-                    go_x3f<true, true, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
+                    go_x3f<true, true, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
                 } else {
                 prof_set_kernel("attn_x3f_kernel<true>", "", "");
-                go_x3f<true, false, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
+                go_x3f<true, false, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
                 }
             } else if (opt_attn_x3() == 1) {
                 prof_set_kernel("attn_kernel<float, true, x3>", "", "");
@@ -1166,13 +1265,13 @@ void launch_attention(const void* q, const void* k, const void* v, void* o, int 
         } else if (opt_attn_x3() == 2) {
             if (kv_planes == 2) {
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs>", "", "");
-                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens);
+                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens, v_rows != 0);
             } else if (kv_planes) {
                 prof_set_kernel("attn_x3f_kernel<false, pre-split K V>", "", "");
-                go_x3f<false, true, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
+                go_x3f<false, true, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
             } else {
             prof_set_kernel("attn_x3f_kernel<false>", "", "");
-            go_x3f<false, false, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens);
+            go_x3f<false, false, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
             }
         } else if (opt_attn_x3() == 1) {
             prof_set_kernel("attn_kernel<float, false, x3>", "", "");

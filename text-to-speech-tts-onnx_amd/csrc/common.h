@@ -163,6 +163,7 @@ struct ConvGemm {
     // fp32 + LDS-staged QKV epilogue only: K and V^T leave as the three bf16 planes of x3_split.h (the attention kernel then
     // stages them without splitting): out2 = [b*H + h][3][k_ld][64], out3 = [b*H + h][3][64][v_ld]; q stays fp32
     int kv_planes = 0; long k_ld = 0;
+    int v_rows = 0;               // with kv_planes: V leaves as rows like K, out3 = [b*H + h][np][k_ld][64] (the attention kernel's VROWS form)
     // stream-K workspace of the caller (gemm_sk.hip): sk_slots x 64 KB of partial tiles + sk_slots zero-initialised flags;
     // null: plain linear layers run one tile per workgroup
     float* sk_ws = nullptr; int* sk_flags = nullptr; int sk_slots = 0;

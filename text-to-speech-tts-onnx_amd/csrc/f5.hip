@@ -795,7 +795,8 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
         g.v_ld = attention_v_ld(N, dtype);
         return g;
     };
-    const int kvp_fmt = attention_kv_planes_format();       // K / V^T pre-split for the attention kernel: 2 fp16 planes or 3 bf16 planes
+    const int kvp_fmt = attention_kv_planes_format();       // K / V pre-split for the attention kernel: 2 fp16 planes or 3 bf16 planes
+    const int v_rows = attention_kv_v_rows() ? 1 : 0;        // ... V as rows like K (default) or transposed: one answer for the epilogue and the kernel
     // which form: decided on block 0's layers (every block has the same shapes and the same weight formats)
     bool planes = false, fold = false;
     {
@@ -836,11 +837,11 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
                 g.x = Ub.p; g.bias = nullptr;
                 if (f32) with_planes(g, bk.qkv, ApN.p);
                 consume(g); g.ln_p = lt; g.ln_c = lt + 3 * d;
-                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); }
+                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); g.v_rows = v_rows; }
                 launch_conv_gemm(g, s);
             }
             launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             f32 ? Ap.p : nullptr, kvp ? kvp_fmt : 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens);
+                             f32 ? Ap.p : nullptr, kvp ? kvp_fmt : 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens, kvp ? v_rows : 0);
             {
                 ConvGemm g = lin(bk.o, d, MI_F32, X.p);
                 g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d;
@@ -874,12 +875,12 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
             {
                 ConvGemm g = qkv_gemm(bk);
                 g.x = Ub.p; with_planes(g, bk.qkv, Ap.p);
-                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); }
+                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); g.v_rows = v_rows; }
                 MI_REQUIRE(gemm_x3p_would_run(g), "f5: the QKV layer left the panel-plane kernel between the decision and the launch");
                 launch_conv_gemm(g, s);
             }
             launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             Ap.p, kvp ? kvp_fmt : 0, np, 0.f, lens);
+                             Ap.p, kvp ? kvp_fmt : 0, np, 0.f, lens, kvp ? v_rows : 0);
             {
                 ConvGemm g = lin(bk.o, d, MI_F32, X.p);
                 g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d; with_planes(g, bk.o, Ap.p);

@@ -53,12 +53,16 @@ void launch_sum_parts(const float* in, float* out, long rows, int M, int parts, 
 // counter per tile); without them every query tile is one workgroup
 void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
                       float* ws = nullptr, long ws_floats = 0, int* cnt = nullptr, long cnt_n = 0, void* o_planes = nullptr,
-                      int kv_planes = 0, int o_np = 3, float ref_fp16_scale = 0.f, const int* lens = nullptr);
+                      int kv_planes = 0, int o_np = 3, float ref_fp16_scale = 0.f, const int* lens = nullptr, int v_rows = 0);
 // ref_fp16_scale (f16 engines; 0 = off): the score rounding points of the reference's fp16-transformer export — q k scores
 // rounded to fp16, then x ref_fp16_scale (= 100, undoing the extra x0.1 folded into q and k) in fp32 (F5/fp16/modules.py:467)
 // kv_planes (fp32 engines, both products split): k and v are the pre-split bf16 planes the QKV epilogue wrote (ConvGemm::kv_planes:
-// k [BH][3][ld][64], v [BH][3][64][ld], ld = N rounded up to 64, pad keys of v zero) — ask attention_takes_kv_planes() first
+// k [BH][np][ld][64], v [BH][np][64][ld] — or [BH][np][ld][64] with v_rows —, ld = N rounded up to 64; the pad keys may hold any bytes, the
+// kernel clears them) — ask attention_takes_kv_planes() first
 bool attention_takes_kv_planes(int N, int BH, int dtype);
+// v_rows (with kv_planes): v is [BH][np][ld][64] like k (ConvGemm::v_rows) and any bytes may lie in its rows past N — the caller passes
+// the layout the QKV epilogue wrote, attention_kv_v_rows() at the time of that launch
+bool attention_kv_v_rows();
 int attention_kv_planes_format();        // 2: fp16 {hi, lo} pairs (option "attn_f32_planes", default) | 3: three bf16 planes — pass it as kv_planes
 // o_planes (fp32 engines, both products split): the output as gemm_x3p.hip panel planes of the [B * N][H * 64] matrix instead
 // of rows in o — ask attention_can_write_planes() first

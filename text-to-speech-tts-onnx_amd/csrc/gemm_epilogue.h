@@ -44,7 +44,8 @@ struct ConvGemmDev {
     const void* w3;                              // gemm_x3.hip: weight planes [3][N][K] bf16 (null: not available)
     const void* xp; const void* w3p; int np;     // gemm_x3p.hip: A and B as panel planes (null: not available), np planes each (3 bf16 | 2 fp16)
     void* out_planes;                            // gemm_x3p.hip: output as panel planes of an [M][N] matrix (null: rows in `out`)
-    int kv_planes; long k_ld;                    // EPI_QKV_ROPE, fp32: K and V^T leave pre-split (attention.hip KVP), np = kv_planes planes (3 bf16 | 2 fp16 pairs with the low part unscaled, x2u_split_pair; 1 = 3): out2 = [bh][np][k_ld][64], out3 = [bh][np][64][v_ld]
+    int kv_planes; long k_ld;                    // EPI_QKV_ROPE, fp32: K and V^T leave pre-split (attention.hip KVP), np = kv_planes planes (3 bf16 | 2 fp16 pairs with the low part unscaled, x2u_split_pair; 1 = 3): out2 = [bh][np][k_ld][64], out3 = [bh][np][64][v_ld] (v_rows below: like out2)
+    int v_rows;                                  // ... with kv_planes: V leaves as rows like K, out3 = [bh][np][k_ld][64] (attention.hip VROWS transposes it on the LDS read)
     int tail_tiles, tail_split;                  // gemm_ph8.hip: the last tail_tiles tiles are cut into tail_split K slices (0 / 1: none)
     // AdaLN fold (ConvGemm, common.h): producer side (ln_stats_out) / consumer side (ln_stats_in)
     const float* ln_scale = nullptr; void* ln_out = nullptr; float* ln_stats_out = nullptr; int ln_out_np = 0;
@@ -382,7 +383,8 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
     const int mrow = m0 + wm * (32 * TMQ);                                   // row of this launch
     const int mbase = mrow + p.m_off;                                        // ... of the flattened [batch item][token] axis
     const int bi0 = mbase / Mb, mloc0 = mbase - bi0 * Mb;
-    const bool vt = which == 2 && p.v_ld > 0;
+    const bool vrow = sizeof(TO) == 4 && p.kv_planes && p.v_rows && which == 2;      // V takes K's row branch (no RoPE)
+    const bool vt = which == 2 && p.v_ld > 0 && !vrow;
     TO* base = (TO*)(which == 0 ? p.out : which == 1 ? p.out2 : p.out3);
     struct alignas(16) Pk { TO v[8]; };
     unsigned qkv_sat = 0;            // fp32 engines with fp16-pair attention operands: range watch (x3_split.h)
@@ -476,9 +478,10 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                         x[q + 1] = o * c[q + 1] + e * sn[q + 1];
                     }
                 }
-                if constexpr (sizeof(TO) == 4) if (p.kv_planes && which == 1) {
-                    // K for the fp32 attention kernel with pre-split operands: the three bf16 pieces of the row's eight values,
-                    // one 16-byte store per plane ([bh][plane][key][64])
+                if constexpr (sizeof(TO) == 4) if (p.kv_planes && (which == 1 || vrow)) {
+                    // K (and V with v_rows) for the fp32 attention kernel with pre-split operands: the three bf16 pieces of the
+                    // row's eight values, one 16-byte store per plane ([bh][plane][key][64])
+                    bf16* kvo = (bf16*)(which == 1 ? p.out2 : p.out3);
                     if (p.kv_planes == 2) {          // fp16 {hi, lo} pairs: [bh][2][key][64]
                         x3_u4 pl[2];                  // unscaled low part: the attention kernel sums both parts into one accumulator
                         {
@@ -488,7 +491,7 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                             pl[0] = x3_u4{wh[0], wh[1], wh[2], wh[3]}; pl[1] = x3_u4{wl[0], wl[1], wl[2], wl[3]};
                             qkv_sat |= x2_sat_word(wh[0]) | x2_sat_word(wh[1]) | x2_sat_word(wh[2]) | x2_sat_word(wh[3]);
                         }
-                        bf16* kp = (bf16*)p.out2 + ((((long)b + biv[gi]) * p.heads + hh) * 2 * p.k_ld + mv[gi]) * 64 + c8;
+                        bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 2 * p.k_ld + mv[gi]) * 64 + c8;
                         if (okv[gi]) {
                             *reinterpret_cast<x3_u4*>(kp) = pl[0];
                             *reinterpret_cast<x3_u4*>(kp + p.k_ld * 64) = pl[1];
@@ -498,7 +501,7 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                     unsigned p1[4], p2[4], p3[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) x3_split_pair(x[2 * q], x[2 * q + 1], p1[q], p2[q], p3[q]);
-                    bf16* kp = (bf16*)p.out2 + ((((long)b + biv[gi]) * p.heads + hh) * 3 * p.k_ld + mv[gi]) * 64 + c8;
+                    bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 3 * p.k_ld + mv[gi]) * 64 + c8;
                     if (okv[gi]) {
                         *reinterpret_cast<x3_u4*>(kp) = x3_u4{p1[0], p1[1], p1[2], p1[3]};
                         *reinterpret_cast<x3_u4*>(kp + p.k_ld * 64) = x3_u4{p2[0], p2[1], p2[2], p2[3]};

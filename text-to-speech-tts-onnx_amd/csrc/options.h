@@ -77,6 +77,7 @@ namespace mi {
     X(ATTN_SPLIT, "attn_split", "MI355TTS_ATTN_NO_SPLIT", ENV_ONE_OFF, 2, CLAMP, 0, 2) /* small grids: 1 = 64-query workgroups, keys split between wave pairs (+ key slices); 2 = fp32 pairs kernel: 128-query workgroups + key slices */ \
     X(ATTN_XCD_MAP, "attn_xcd_map", nullptr, ENV_INT, 1, BOOL, 0, 1) /* XCD-aware (query tile, head) map of the workgroup ids (-1 % per launch, bit-neutral) */ \
     X(ATTN_KV_PLANES, "attn_kv_planes", "MI355TTS_ATTN_KVP", ENV_INT, 1, BOOL, 0, 1) /* fp32, both products split: K / V^T pre-split by the QKV epilogue */ \
+    X(ATTN_V_ROWS, nullptr, "MI355TTS_ATTN_V_ROWS", ENV_ZERO_OFF, 1, BOOL, 0, 1) /* pre-split V leaves the QKV epilogue as rows like K, transposed on the LDS read; '0': V^T planes (the A/B switch) */ \
     X(ATTN_LPT, "attn_lpt", "MI355TTS_ATTN_LPT", ENV_INT, 1, BOOL, 0, 1) /* fp32 128-query kernel: uneven key slices, longest first */ \
     X(ATTN_Z_FORCE, "attn_z_force", nullptr, ENV_INT, 0, CLAMP, 0, 4) /* tests: exactly that many slices, even empty ones */ \
     /* key slices of the SPLIT2 form: at most Z for fp32, Z16 for 16-bit operands (1 = off: no gain measured) */        \

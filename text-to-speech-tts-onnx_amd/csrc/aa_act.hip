@@ -342,13 +342,7 @@ static void launch_t(const AAAct& p, hipStream_t s) {
             const int nvec = (TT + 10) * CT / VEC;
             const int xsp = (nvec + 63) / 64 * 64 * VEC;
             const size_t lds2 = ((size_t)2 * xsp + (size_t)TT * CT) * sizeof(T);
-            int dev = 0, cus = 256;
-            MI_HIP(hipGetDevice(&dev));
-            {
-                static int cu_count[16] = {0};
-                if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-                cus = cu_count[dev & 15];
-            }
+            const int cus = device_cus();
             const int per_cu = (int)std::min<size_t>(3, (size_t)(160 * 1024) / lds2);
             if (per_cu >= 1 && lds2 <= 64 * 1024 && ntiles < 0x7fffffffL) {
                 const int grid_p = (int)std::min<long>(ntiles, (long)cus * per_cu);

@@ -17,10 +17,13 @@
 //   fp32 : v_mfma_f32_32x32x2_f32 (exact fp32 products, K = 2 keys per instruction)
 //   f16/bf16 : v_mfma_f32_32x32x16 — V is staged transposed ([d][key]) so that the 8 keys a lane feeds
 //                 per instruction are two contiguous 8-byte LDS reads.
+// Host side (end of this file): attention_plan() decides the K / V layout the QKV epilogue writes together with the kernel form, the
+// grid and the key slices, once per evaluation; launch_attention() looks the plan's form up in one dispatch table and launches.
 #include "common.h"
 #include <functional>
 #include <map>
 #include <mutex>
+#include <tuple>
 #include "mfma.h"
 #include "f5_kernels.h"
 #include "x3_split.h"
@@ -1053,27 +1056,26 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     }
 }
 
-// fp32 attention: 0 = native fp32 MFMA ; 1 = q.k as exact bf16 splits (attn_kernel X3S) ; 2 = both products (attn_x3f_kernel;
-// V then arrives transposed like in the 16-bit engines: attention_v_ld() tells the QKV epilogue)
-// (The MI355TTS_ATTN_* variables are part of the one read of the option table, options.h: F5::dit_eval asks attention_v_ld() for the V
-// layout of the QKV epilogue before the first launch_attention() of the process, and a lazy read inside launch_attention() once made
-// that first block write V transposed for a kernel that then read it untransposed.)
-static inline int opt_attn_x3() { const int o = arith_tls().attn_x3; return o >= 0 ? o : (int)opt(OPT_ATTN_F32_X3); }      // the engine's arithmetic first (ArithScope, common.h)
+// ---- host side: the plan, then the launch ------------------------------------------------------------------------------------
+// attention_plan() reads the options and the engine's arithmetic (ArithScope, common.h) ONCE per evaluation, before the QKV
+// projection, and its answer serves both sides: F5::dit_eval copies plan.kv into the QKV ConvGemm and hands the same plan to
+// launch_attention(), which only launches.  (Five separate query functions used to be asked at different moments; a lazy option
+// read inside the launcher once made the first block write V transposed for a kernel that then read it untransposed.)
+// attn_f32_x3: 0 = native fp32 MFMA ; 1 = q.k as exact bf16 splits (attn_kernel X3S) ; 2 = both products (attn_x3f_kernel; V then
+// arrives transposed like in the 16-bit engines)
+static inline int opt_attn_x3() { const int o = arith_tls().attn_x3; return o >= 0 ? o : (int)opt(OPT_ATTN_F32_X3); }      // the engine's arithmetic first
 static inline int opt_attn_np() { const int o = arith_tls().attn_np; return (o == 2 || o == 3) ? o : (int)opt(OPT_ATTN_F32_PLANES); }
-long attention_v_ld(int N, int dtype) {
-    return (dtype == MI_F32 && opt_attn_x3() != 2) ? 0 : (long)((N + 7) / 8 * 8);
-}
-bool attention_takes_kv_planes(int N, int BH, int dtype) {
-    (void)N; (void)BH;
-    return dtype == MI_F32 && opt_attn_x3() == 2 && opt(OPT_ATTN_KV_PLANES) != 0;
-}
 
-int attention_kv_planes_format() { return opt_attn_np(); }
-bool attention_kv_v_rows() { return opt(OPT_ATTN_V_ROWS) != 0; }
-
-bool attention_can_write_planes(int N, int BH, int dtype) {
-    (void)N; (void)BH;
-    return dtype == MI_F32 && opt_attn_x3() == 2;
+AttnKvLayout attention_kv_layout(int N, int dtype, bool caller_can_presplit_kv) {
+    AttnKvLayout l;
+    const bool x3f = dtype == MI_F32 && opt_attn_x3() == 2;
+    if (x3f && caller_can_presplit_kv && opt(OPT_ATTN_KV_PLANES) != 0) {
+        l.kv_planes = opt_attn_np();
+        l.k_ld = l.v_ld = (long)((N + ATTN_STAGE - 1) / ATTN_STAGE * ATTN_STAGE);
+        l.v_rows = opt(OPT_ATTN_V_ROWS) != 0;
+    } else if (x3f || dtype != MI_F32)
+        l.v_ld = (long)((N + 7) / 8 * 8);
+    return l;
 }
 
 // Key slices of the 128-query fp32 kernel, sized for the dispatch order (round 6).  The launch is (query tiles x heads) units x Z
@@ -1083,7 +1085,7 @@ bool attention_can_write_planes(int N, int BH, int dtype) {
 // they free: list scheduling, makespan 8 stage times instead of 12.  The search simulates that for every non-increasing split of the
 // stages into 1 .. zmax slices (identical pieces handled in bulk: a few map operations per split) and keeps the best.
 struct AttnSlices { int Z = 1, cut[3] = {0, 0, 0}; };
-static AttnSlices attn_pick_slices(long units, int S, int slots, int zmax) {
+static AttnSlices attn_search_slices(long units, int S, int slots, int zmax) {
     AttnSlices best;
     double best_t = 1e30;
     auto makespan = [&](const int* len, int Z) -> double {
@@ -1129,173 +1131,146 @@ static AttnSlices attn_pick_slices(long units, int S, int slots, int zmax) {
     return best;
 }
 
-// One launch of either kernel.  lens != nullptr: the VARLEN instantiation (ragged batch, ATTN_VARLEN_PROLOGUE); the grid, the
-// slices and every other argument are those of the uniform launch at the same N.
-// v_rows: the layout the QKV epilogue wrote for V (ConvGemm::v_rows), passed by the caller — only with KVP.
-template <bool SPLIT2, bool KVP, int NP>
-static void go_x3f(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int H, int N, float* ws, int* cnt,
-                   void* o_planes, int o_np, int xm, int c1, int c2, int c3, const int* lens, bool v_rows) {
-    const float *qf = (const float*)q, *kf = (const float*)k, *vf = (const float*)v;
-    if (lens) prof_kernel_suffix(" + lengths");
-    if constexpr (KVP) {
-        if (v_rows) {
-            if (lens) hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, true, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3, lens);
-            else hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, false, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3);
-            return;
-        }
-    }
-    MI_REQUIRE(!v_rows, "attention: V as rows is a layout of the pre-split planes");
-    if (lens) hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, true>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3, lens);
-    else hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP>), grid, dim3(256), 0, s, qf, kf, vf, (float*)o, H, N, ws, cnt, (unsigned char*)o_planes, o_np, xm, c1, c2, c3);
-}
-template <typename T, bool SPLIT2, bool X3S = false, bool REFH = false>
-static void go_attn(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int H, int N, float* ws, int* cnt,
-                    float sscale, int xm, const int* lens) {
-    const T *qt = (const T*)q, *kt = (const T*)k, *vt = (const T*)v;
-    if (lens) prof_kernel_suffix(" + lengths");
-    if (lens) hipLaunchKernelGGL((attn_kernel<T, SPLIT2, X3S, REFH, true>), grid, dim3(256), 0, s, qt, kt, vt, (T*)o, H, N, ws, cnt, sscale, xm, lens);
-    else hipLaunchKernelGGL((attn_kernel<T, SPLIT2, X3S, REFH>), grid, dim3(256), 0, s, qt, kt, vt, (T*)o, H, N, ws, cnt, sscale, xm);
+// ... remembered per argument tuple: everything the result depends on is in the key
+static AttnSlices attn_pick_slices(long units, int S, int slots, int zmax) {
+    static std::mutex mu;
+    static std::map<std::tuple<long, int, int, int>, AttnSlices> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_tuple(units, S, slots, zmax);
+    auto it = cache.find(key);
+    if (it == cache.end()) it = cache.emplace(key, attn_search_slices(units, S, slots, zmax)).first;
+    return it->second;
 }
 
-void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
-                      float* ws, long ws_floats, int* cnt, long cnt_n, void* o_planes, int kv_planes, int o_np, float ref_fp16_scale,
-                      const int* lens, int v_rows) {
-    MI_REQUIRE(!v_rows || kv_planes, "attention: V as rows comes with pre-split K / V");
-    MI_REQUIRE(ref_fp16_scale == 0.f || (dtype == MI_F16 && ref_fp16_scale > 0.f), "attention: the reference-fp16 score form needs f16 operands");
-    MI_REQUIRE(o_np == 2 || o_np == 3, "attention: 2 or 3 output planes");
-    MI_REQUIRE(!o_planes || attention_can_write_planes(N, BH, dtype), "attention: panel-plane output needs the fp32 split kernel");
-    MI_REQUIRE(!kv_planes || attention_can_write_planes(N, BH, dtype), "attention: pre-split K / V need the fp32 split kernel");
-    MI_REQUIRE(kv_planes == 0 || kv_planes == 1 || kv_planes == 2 || kv_planes == 3, "attention: kv_planes is 0, 2 or 3 (1 = 3)");
-    MI_REQUIRE(BH % H == 0 && N > 0, "attention: bad shape");
-    const double esz = (double)dtype_size(dtype);
-    ProfScope ps(FAM_ATTN, s, 4.0 * BH * N * 64.0 * esz, 4.0 * BH * (double)N * N * 64.0);
-#define ATTN_LAUNCH(TT, SP, GRID, SSCALE, XM)                                    \
-    do {                                                                        \
-        prof_set_kernel("attn_kernel<T, " #SP ">", type_label<TT>());           \
-        go_attn<TT, SP>(GRID, s, q, k, v, o, H, N, ws, cnt, SSCALE, XM, lens);  \
-    } while (0)
-    const int xm = (opt(OPT_ATTN_XCD_MAP) != 0 && BH % 8 == 0) ? 1 : 0;
-    const int zmax = opt(OPT_ATTN_Z);
-    // key slices for the SPLIT2 form (see attn_kernel): makespan(Z) = ceil(units * Z / CUs) / Z in units of one unsliced
-    // workgroup, + 6 % per extra slice for the prologue and the merge (measured, fp32, one utterance = 576 units:
-    // Z = 1 / 2 / 3 / 4 -> 135 / 122 / 121 / 126 us in round 2; 62.1 / 58.8 / 60.8 / 60.7 us with the fp16-pair kernel of
-    // round 3, whose slices are shorter against the same merge: + 9 % for fp32)
-    auto pick_z = [&](int zlimit16, bool wide = false) -> int {
-        const long units = (long)(wide ? (N + 127) / 128 : (N + 63) / 64) * BH;
-        const long slot = wide ? 4 * (32 * 64 + 64 * 2) : 2 * 32 * 64 + 2 * 64 * 2;
-        const int nstage = (N + 63) / 64;
-        int dev = 0, cus = 256;
-        MI_HIP(hipGetDevice(&dev));
-        {
-            static int cu_count[16] = {0};
-            if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-            cus = cu_count[dev & 15];
-        }
-        if (opt(OPT_ATTN_Z_FORCE) > 0)
-            return (ws && cnt && units * opt(OPT_ATTN_Z_FORCE) * slot <= ws_floats && units <= cnt_n) ? (int)opt(OPT_ATTN_Z_FORCE) : 1;
-        int Z = 1;
-        double best = 1e30;
-        const int zm = dtype == MI_F32 ? zmax : std::min(zmax, zlimit16);
-        for (int z = 1; z <= zm; ++z) {
-            if (z > 1 && (!ws || !cnt || units * z * slot > ws_floats || units > cnt_n || nstage < 2 * z)) break;
-            const double cost = (double)((units * z + cus - 1) / cus) / z * (1.0 + (dtype == MI_F32 ? 0.09 : 0.06) * (z - 1));
-            if (cost < best - 1e-9) { best = cost; Z = z; }
-        }
-        return Z;
-    };
-    const int z16 = opt(OPT_ATTN_Z16);
-    if (dtype == MI_F32) {
-        // few 128-query workgroups (one or two utterances): halve them along the keys, see attn_kernel — or (attn_split = 2, the
-        // default for the pre-split fp16-pair kernel, round 4) keep the 128-query workgroups, whose four waves share every K / V
-        // stage and multiply two tiles per barrier pair, and cut only the key range into slices: 288 x 3 workgroups for one
-        // utterance, 56.3 against 60.0 us per launch on the same box (step 177.8 -> 174.3 ms)
-        if (opt(OPT_ATTN_SPLIT) && (long)((N + 127) / 128) * BH < 1024 && N >= 64) {
-            // ... and cut the key range into Z slices when that evens out the workgroups per CU
-            const bool wide = opt(OPT_ATTN_SPLIT) == 2 && opt_attn_x3() == 2 && kv_planes == 2;
-            const int Z = pick_z(1, wide);
-            if (wide) {
-                // uneven slices, longest first (attn_pick_slices): cached per (N, BH)
-                AttnSlices sl;
-                sl.Z = Z;
-                if (opt(OPT_ATTN_LPT) && opt(OPT_ATTN_Z_FORCE) == 0 && Z >= 1 && ws && cnt) {
-                    static std::mutex mu;
-                    static std::map<std::pair<int, int>, AttnSlices> cache;
-                    std::lock_guard<std::mutex> lk(mu);
-                    auto key = std::make_pair(N, BH);
-                    auto it = cache.find(key);
-                    if (it == cache.end()) {
-                        int dev = 0, cus = 256;
-                        MI_HIP(hipGetDevice(&dev));
-                        hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cus = pr.multiProcessorCount;
-                        const long units = (long)((N + 127) / 128) * BH;
-                        const long slot = 4 * (32 * 64 + 64 * 2);
-                        int zm = std::min((int)opt(OPT_ATTN_Z), 4);
-                        while (zm > 1 && (units * zm * slot > ws_floats || units > cnt_n)) --zm;
-                        it = cache.emplace(key, attn_pick_slices(units, (N + 63) / 64, 3 * cus, zm)).first;
-                    }
-                    sl = it->second;
-                    if (const AttnCuts& e = opt_attn_cuts(); e.n) {          // experiments: MI355TTS_ATTN_CUTS
-                        const int S = (N + 63) / 64, n = e.n;
-                        const int* c = e.c;
-                        const long units = (long)((N + 127) / 128) * BH;
-                        if (n >= 1 && c[0] > 0 && c[0] < S && units * (n + 1) * 4 * (32 * 64 + 64 * 2) <= ws_floats && units <= cnt_n) {
-                            sl.Z = n + 1; sl.cut[0] = c[0]; sl.cut[1] = n >= 2 ? c[1] : S; sl.cut[2] = n >= 3 ? c[2] : S;
-                        }
-                    }
-                }
-                prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs> + key slices", "", "");
-                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH, sl.Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm,
-                                       sl.Z > 1 ? sl.cut[0] : 0, sl.cut[1], sl.cut[2], lens, v_rows != 0);
-            } else if (opt_attn_x3() == 2) {
-                if (kv_planes == 2) {
-                    prof_set_kernel("attn_x3f_kernel<true, pre-split K V, fp16 pairs>", "", "");
-                    go_x3f<true, true, 2>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens, v_rows != 0);
-                } else if (kv_planes) {
-                    prof_set_kernel("attn_x3f_kernel<true, pre-split K V>", "", "");
-                    go_x3f<true, true, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
-                } else {
-                prof_set_kernel("attn_x3f_kernel<true>", "", "");
-                go_x3f<true, false, 3>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
-                }
-            } else if (opt_attn_x3() == 1) {
-                prof_set_kernel("attn_kernel<float, true, x3>", "", "");
-                go_attn<float, true, true>(dim3((N + 63) / 64, BH, Z), s, q, k, v, o, H, N, ws, cnt, 1.f, 0, lens);
-            } else
-                ATTN_LAUNCH(float, true, dim3((N + 63) / 64, BH, Z), 1.f, 0);
-        } else if (opt_attn_x3() == 2) {
-            if (kv_planes == 2) {
-                prof_set_kernel("attn_x3f_kernel<false, pre-split K V, fp16 pairs>", "", "");
-                go_x3f<false, true, 2>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, xm, 0, 0, 0, lens, v_rows != 0);
-            } else if (kv_planes) {
-                prof_set_kernel("attn_x3f_kernel<false, pre-split K V>", "", "");
-                go_x3f<false, true, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
-            } else {
-            prof_set_kernel("attn_x3f_kernel<false>", "", "");
-            go_x3f<false, false, 3>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, o_planes, o_np, 0, 0, 0, 0, lens, v_rows != 0);
-            }
-        } else if (opt_attn_x3() == 1) {
-            prof_set_kernel("attn_kernel<float, false, x3>", "", "");
-            go_attn<float, false, true>(dim3((N + 127) / 128, BH), s, q, k, v, o, H, N, ws, cnt, 1.f, 0, lens);
-        } else
-            ATTN_LAUNCH(float, false, dim3((N + 127) / 128, BH), 1.f, 0);
-    } else {
-        // 16-bit: the same split below 512 workgroups (one utterance: attention 24.3 -> 21.1 ms per step; at two utterances,
-        // 576 workgroups, the 128-query form is already balanced and shares each K / V stage among more waves)
-        const bool sp = opt(OPT_ATTN_SPLIT) && (long)((N + 127) / 128) * BH < 512 && N >= 64;
-        const dim3 grid(sp ? (N + 63) / 64 : (N + 127) / 128, BH, sp ? pick_z(z16) : 1);
-        if (dtype == MI_F16 && ref_fp16_scale != 0.f) {
-            prof_set_kernel(sp ? "attn_kernel<T, true, reference-fp16 scores>" : "attn_kernel<T, false, reference-fp16 scores>", type_label<f16>());
-            if (sp) go_attn<f16, true, false, true>(grid, s, q, k, v, o, H, N, ws, cnt, ref_fp16_scale, 0, lens);
-            else go_attn<f16, false, false, true>(grid, s, q, k, v, o, H, N, ws, cnt, ref_fp16_scale, 0, lens);
-        } else if (dtype == MI_F16) {
-            if (sp) ATTN_LAUNCH(f16, true, grid, 1.f, xm);
-            else ATTN_LAUNCH(f16, false, grid, 1.f, xm);
-        } else {
-            if (sp) ATTN_LAUNCH(bf16, true, grid, 1.f, xm);
-            else ATTN_LAUNCH(bf16, false, grid, 1.f, xm);
-        }
+// Even key slices: makespan(Z) = ceil(units * Z / CUs) / Z in units of one unsliced workgroup, + 6 % per extra slice for the
+// prologue and the merge (measured, fp32, one utterance = 576 units: Z = 1 / 2 / 3 / 4 -> 135 / 122 / 121 / 126 us in round 2;
+// 62.1 / 58.8 / 60.8 / 60.7 us with the fp16-pair kernel of round 3, whose slices are shorter against the same merge: + 9 % for fp32).
+// A slice count must fit the workspace: units x Z slots of `slot` floats and one counter per unit.
+static int attn_pick_z(long units, long slot, int nstage, bool f32, int zmax, long ws_floats, long cnt_n) {
+    auto fits = [&](int z) { return units * z * slot <= ws_floats && units <= cnt_n; };
+    if (const int zf = opt(OPT_ATTN_Z_FORCE); zf > 0) return fits(zf) ? zf : 1;
+    const int cus = device_cus();
+    int Z = 1;
+    double best = 1e30;
+    for (int z = 1; z <= zmax; ++z) {
+        if (z > 1 && (!fits(z) || nstage < 2 * z)) break;
+        const double cost = (double)((units * z + cus - 1) / cus) / z * (1.0 + (f32 ? 0.09 : 0.06) * (z - 1));
+        if (cost < best - 1e-9) { best = cost; Z = z; }
     }
-#undef ATTN_LAUNCH
+    return Z;
+}
+
+// ---- the dispatch table: one entry per AttnForm (+ SPLIT2), {profiler label, launch thunk [lengths][V as rows]} ---------------------
+// lengths: the VARLEN instantiation (ragged batch, ATTN_VARLEN_PROLOGUE).  V as rows (AttnKvLayout::v_rows) exists for the pre-split
+// forms only: the other entries have no thunk there.
+struct AttnArgs { const AttnPlan& p; const void *q, *k, *v; void *o, *o_planes; int o_np; float* ws; int* cnt; const int* lens; hipStream_t s; };
+using AttnThunk = void (*)(const AttnArgs&);
+static dim3 attn_grid(const AttnPlan& p) { return dim3(p.grid[0], p.grid[1], p.grid[2]); }
+template <typename T, bool SPLIT2, bool X3S, bool REFH, bool VARLEN> static void attn_go(const AttnArgs& a) {
+    hipLaunchKernelGGL((attn_kernel<T, SPLIT2, X3S, REFH, VARLEN>), attn_grid(a.p), dim3(256), 0, a.s, (const T*)a.q, (const T*)a.k, (const T*)a.v,
+                       (T*)a.o, a.p.H, a.p.N, a.ws, a.cnt, a.p.sscale, a.p.xmap, a.lens);
+}
+template <bool SPLIT2, bool KVP, int NP, bool VARLEN, bool VROWS> static void x3f_go(const AttnArgs& a) {
+    hipLaunchKernelGGL((attn_x3f_kernel<SPLIT2, KVP, NP, VARLEN, VROWS>), attn_grid(a.p), dim3(256), 0, a.s, (const float*)a.q, (const float*)a.k,
+                       (const float*)a.v, (float*)a.o, a.p.H, a.p.N, a.ws, a.cnt, (unsigned char*)a.o_planes, a.o_np, a.p.xmap, a.p.cut[0], a.p.cut[1],
+                       a.p.cut[2], a.lens);
+}
+struct AttnEntry { const char* label; AttnThunk go[2][2]; };
+#define ATTN_ROWS(T, SP, X3S, REFH) {{attn_go<T, SP, X3S, REFH, false>, nullptr}, {attn_go<T, SP, X3S, REFH, true>, nullptr}}
+#define X3F_SPLITS(SP) {{x3f_go<SP, false, 3, false, false>, nullptr}, {x3f_go<SP, false, 3, true, false>, nullptr}}
+#define X3F_PLANES(SP, NP) {{x3f_go<SP, true, NP, false, false>, x3f_go<SP, true, NP, false, true>}, {x3f_go<SP, true, NP, true, false>, x3f_go<SP, true, NP, true, true>}}
+static const AttnEntry attn_table[ATTN_FORMS] = {
+    /* ATTN_F32              */ {"attn_kernel<float, false>", ATTN_ROWS(float, false, false, false)},
+    /*                       */ {"attn_kernel<float, true>", ATTN_ROWS(float, true, false, false)},
+    /* ATTN_F32_QK_X3        */ {"attn_kernel<float, false, x3>", ATTN_ROWS(float, false, true, false)},
+    /*                       */ {"attn_kernel<float, true, x3>", ATTN_ROWS(float, true, true, false)},
+    /* ATTN_X3F              */ {"attn_x3f_kernel<false>", X3F_SPLITS(false)},
+    /*                       */ {"attn_x3f_kernel<true>", X3F_SPLITS(true)},
+    /* ATTN_X3F_BF16X3       */ {"attn_x3f_kernel<false, pre-split K V>", X3F_PLANES(false, 3)},
+    /*                       */ {"attn_x3f_kernel<true, pre-split K V>", X3F_PLANES(true, 3)},
+    /* ATTN_X3F_PAIRS        */ {"attn_x3f_kernel<false, pre-split K V, fp16 pairs>", X3F_PLANES(false, 2)},
+    /*                       */ {"attn_x3f_kernel<true, pre-split K V, fp16 pairs>", X3F_PLANES(true, 2)},
+    /* ATTN_X3F_PAIRS_SLICED */ {"attn_x3f_kernel<false, pre-split K V, fp16 pairs> + key slices", X3F_PLANES(false, 2)},
+    /* ATTN_F16              */ {"attn_kernel<_Float16, false>", ATTN_ROWS(f16, false, false, false)},
+    /*                       */ {"attn_kernel<_Float16, true>", ATTN_ROWS(f16, true, false, false)},
+    /* ATTN_F16_REF          */ {"attn_kernel<_Float16, false, reference-fp16 scores>", ATTN_ROWS(f16, false, false, true)},
+    /*                       */ {"attn_kernel<_Float16, true, reference-fp16 scores>", ATTN_ROWS(f16, true, false, true)},
+    /* ATTN_BF16             */ {"attn_kernel<__bf16, false>", ATTN_ROWS(bf16, false, false, false)},
+    /*                       */ {"attn_kernel<__bf16, true>", ATTN_ROWS(bf16, true, false, false)},
+};
+#undef ATTN_ROWS
+#undef X3F_SPLITS
+#undef X3F_PLANES
+
+AttnPlan attention_plan(int BH, int H, int N, int dtype, bool caller_can_presplit_kv, bool has_lens, float ref_fp16_scale, long ws_floats,
+                        long cnt_n) {
+    MI_REQUIRE(ref_fp16_scale == 0.f || (dtype == MI_F16 && ref_fp16_scale > 0.f), "attention: the reference-fp16 score form needs f16 operands");
+    MI_REQUIRE(H > 0 && BH % H == 0 && N > 0, "attention: bad shape");
+    const bool f32 = dtype == MI_F32;
+    AttnPlan p;
+    p.kv = attention_kv_layout(N, dtype, caller_can_presplit_kv);
+    p.varlen = has_lens; p.BH = BH; p.H = H; p.N = N; p.dtype = dtype;
+    const int x3 = f32 ? opt_attn_x3() : 0, split = opt(OPT_ATTN_SPLIT);
+    p.o_planes = f32 && x3 == 2;
+    const int xm = (opt(OPT_ATTN_XCD_MAP) != 0 && BH % 8 == 0) ? 1 : 0;
+    const int tiles = (N + ATTN_TILE - 1) / ATTN_TILE, tiles_split = (N + ATTN_TILE_SPLIT - 1) / ATTN_TILE_SPLIT, nstage = (N + ATTN_STAGE - 1) / ATTN_STAGE;
+    if (ws_floats <= 0 || cnt_n <= 0) ws_floats = cnt_n = 0;
+    // Few 128-query workgroups (fp32: one or two utterances; 16-bit: one — attention 24.3 -> 21.1 ms per step; at two utterances,
+    // 576 workgroups, the 128-query form is already balanced and shares each K / V stage among more waves): halve them along the
+    // keys, see attn_kernel, and cut the key range into Z slices when that evens out the workgroups per CU.
+    const bool small = split && (long)tiles * BH < (f32 ? 1024 : 512) && N >= 64;
+    int base, Z = 1;
+    if (!f32) {
+        base = dtype == MI_BF16 ? ATTN_BF16 : ref_fp16_scale != 0.f ? ATTN_F16_REF : ATTN_F16;
+        if (base == ATTN_F16_REF) p.sscale = ref_fp16_scale; else p.xmap = xm;
+        if (small) Z = attn_pick_z((long)tiles_split * BH, ATTN_SLOT_SPLIT, nstage, false, std::min((int)opt(OPT_ATTN_Z), (int)opt(OPT_ATTN_Z16)), ws_floats, cnt_n);
+    } else {
+        base = x3 == 1 ? ATTN_F32_QK_X3 : x3 != 2 ? ATTN_F32 : p.kv.kv_planes == 2 ? ATTN_X3F_PAIRS : p.kv.kv_planes ? ATTN_X3F_BF16X3 : ATTN_X3F;
+        if (base == ATTN_X3F_PAIRS) p.xmap = xm;
+        // attn_split = 2 (the default for the pre-split fp16-pair kernel, round 4): keep the 128-query workgroups, whose four waves
+        // share every K / V stage and multiply two tiles per barrier pair, and cut only the key range into slices: 288 x 3 workgroups
+        // for one utterance, 56.3 against 60.0 us per launch on the same box (step 177.8 -> 174.3 ms)
+        if (small && base == ATTN_X3F_PAIRS && split == 2) {
+            const long units = (long)tiles * BH;
+            AttnSlices sl;
+            sl.Z = attn_pick_z(units, ATTN_SLOT, nstage, true, opt(OPT_ATTN_Z), ws_floats, cnt_n);
+            auto fits = [&](int z) { return units * z * ATTN_SLOT <= ws_floats && units <= cnt_n; };
+            if (opt(OPT_ATTN_LPT) && opt(OPT_ATTN_Z_FORCE) == 0 && ws_floats > 0) {      // uneven slices, longest first (attn_pick_slices)
+                int zm = std::min((int)opt(OPT_ATTN_Z), ATTN_MAX_SLICES);
+                while (zm > 1 && !fits(zm)) --zm;
+                sl = attn_pick_slices(units, nstage, 3 * device_cus(), zm);
+                if (const AttnCuts& e = opt_attn_cuts(); e.n >= 1 && e.c[0] > 0 && e.c[0] < nstage && fits(e.n + 1)) {      // experiments: MI355TTS_ATTN_CUTS
+                    sl.Z = e.n + 1; sl.cut[0] = e.c[0]; sl.cut[1] = e.n >= 2 ? e.c[1] : nstage; sl.cut[2] = e.n >= 3 ? e.c[2] : nstage;
+                }
+            }
+            p.form = ATTN_X3F_PAIRS_SLICED;
+            p.grid[0] = tiles; p.grid[1] = BH; p.grid[2] = sl.Z;
+            p.cut[0] = sl.Z > 1 ? sl.cut[0] : 0; p.cut[1] = sl.cut[1]; p.cut[2] = sl.cut[2];
+            p.label = attn_table[p.form].label;
+            return p;
+        }
+        if (small) Z = attn_pick_z((long)tiles_split * BH, ATTN_SLOT_SPLIT, nstage, true, opt(OPT_ATTN_Z), ws_floats, cnt_n);
+    }
+    p.form = base + (small ? 1 : 0);
+    p.grid[0] = small ? tiles_split : tiles; p.grid[1] = BH; p.grid[2] = Z;
+    p.label = attn_table[p.form].label;
+    return p;
+}
+
+void launch_attention(const AttnPlan& p, const void* q, const void* k, const void* v, void* o, void* o_planes, int o_np, float* ws, int* cnt,
+                      const int* lens, hipStream_t s) {
+    MI_REQUIRE(p.form >= 0 && p.form < ATTN_FORMS && p.BH > 0, "attention: no plan");
+    MI_REQUIRE(o_np == 2 || o_np == 3, "attention: 2 or 3 output planes");
+    MI_REQUIRE(!o_planes || p.o_planes, "attention: panel-plane output needs the fp32 split kernel");
+    MI_REQUIRE(p.varlen == (lens != nullptr), "attention: the plan was made for a batch of the other kind (uniform / ragged)");
+    MI_REQUIRE(p.grid[2] == 1 || (ws && cnt), "attention: the plan's key slices need the workspace it was told of");
+    const AttnThunk go = attn_table[p.form].go[p.varlen ? 1 : 0][p.kv.v_rows ? 1 : 0];
+    MI_REQUIRE(go, "attention: V as rows is a layout of the pre-split planes");
+    const double esz = (double)dtype_size(p.dtype);
+    ProfScope ps(FAM_ATTN, s, 4.0 * p.BH * p.N * 64.0 * esz, 4.0 * p.BH * (double)p.N * p.N * 64.0);
+    prof_set_kernel(p.label);
+    if (lens) prof_kernel_suffix(" + lengths");
+    go({p, q, k, v, o, o_planes, o_np, ws, cnt, lens, s});
     MI_HIP(hipGetLastError());
 }
 

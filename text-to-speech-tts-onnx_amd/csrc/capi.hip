@@ -314,7 +314,7 @@ int64_t mi_f5_info(mi_f5* h, const char* key) {
         if (k == "f32_arithmetic") v = e.dtype != MI_F32 ? -1 : !gemm_x3_enabled() ? ARITH_NATIVE : (gemm_x3p_enabled() ? e.np : ARITH_BF16X3);
         else if (k == "saturation_events") v = e.sat_events;
         else if (k == "adaln_fold") v = (e.fold_built && e.cfg.ln_fold != 0) ? 1 : 0;
-        else if (k == "attn_v_rows") v = (e.dtype == MI_F32 && attention_takes_kv_planes(0, 0, MI_F32) && attention_kv_v_rows()) ? 1 : 0;
+        else if (k == "attn_v_rows") v = attention_kv_layout(0, e.dtype, true).v_rows;       // of an evaluation whose QKV epilogue pre-splits K / V
         else MI_REQUIRE(false, "mi_f5_info: unknown key");
     });
     return rc == MI_OK ? v : (int64_t)rc;

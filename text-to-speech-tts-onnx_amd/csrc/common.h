@@ -83,6 +83,9 @@ struct DevBuf {
 // host fp32 -> device tensor of dtype dt
 void upload_as(DevBuf& dst, const float* src, size_t n, int dt, hipStream_t s);
 void upload_f32(DevBuf& dst, const float* src, size_t n, hipStream_t s);
+// compute units of the current device (the launchers size their grids and slices by it): asked once per device, thread-safe;
+// 256 (an MI355X) should the runtime report none
+int device_cus();
 
 // Reader of a packed fp32 weight blob that lives in host OR device memory (the `mem` flag of mi_*_create_mem; a blob that
 // arrived over RCCL stays on the device).  put(): blob range -> device tensor of dtype dt (device blobs: a conversion

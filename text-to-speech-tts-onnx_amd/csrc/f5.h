@@ -11,7 +11,7 @@ struct F5Cfg {
     int dim, depth, heads, dim_head, ff_mult, mel, text_dim, vocab, conv_layers, conv_mult, pos_k, pos_g, freq_dim,
         nfe, max_len, n_fft, hop, sr, vd, vi, vlayers;
     float cfg_strength, sway;
-    float score_scale = 1.f;   // != 1 (f16 engines only): the reference's fp16-transformer score form, see launch_attention(ref_fp16_scale)
+    float score_scale = 1.f;   // != 1 (f16 engines only): the reference's fp16-transformer score form, see attention_plan(ref_fp16_scale)
     // optional trailing ints of the config array (mi355tts/config.py F5Config.to_int_array):
     int f32_arith = ARITH_DEFAULT;   // fp32 engines: ARITH_PAIRS | ARITH_BF16X3 | ARITH_NATIVE; ARITH_DEFAULT = the process-wide options (fp16 pairs)
     int mel_type = 0;                // prompt mel front end: 0 vocos (HTK fbank of the magnitude, Export_F5.py:113,125) | 1 bigvgan (slaney, modules.py:30-72)

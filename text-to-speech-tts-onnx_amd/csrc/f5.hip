@@ -508,16 +508,15 @@ void F5::ensure_workspace(int U, int N) {
     sk.ensure(1024, stream);     // 64 MB: stream-K slots (64 KB) and the split-tail slabs of gemm_ph8.hip (256 KB)
     {
         // key-sliced attention (attention.hip): used while a launch has fewer than 1024 (fp32) / 512 (16-bit) 128-query
-        // workgroups, i.e. fewer than 2048 64-query tiles — whatever the LARGEST batch this handle has seen (the running
+        // workgroups, i.e. fewer than ATTN_WS_TILES 64-query tiles — whatever the LARGEST batch this handle has seen (the running
         // maxima Um, Nm only size the activations: a handle that first ran 8 utterances must still slice a later single
-        // one).  Reserved once: 2048 tiles x 4 slices x (8192 + 256) floats = 277 MB of the 288 GB.
-        const long tiles = 2048;
-        if (tiles > attn_cnt_n) {
-            attn_ws_floats = tiles * 4 * (2 * 32 * 64 + 2 * 64 * 2);
+        // one).  Reserved once: 2048 tiles x 4 slices x 4352 floats = 143 MB of the 288 GB.
+        if (ATTN_WS_TILES > attn_cnt_n) {
+            attn_ws_floats = ATTN_WS_TILES * ATTN_MAX_SLICES * ATTN_SLOT_SPLIT;
             attn_ws.ensure((size_t)attn_ws_floats * 4);
-            attn_cnt.ensure((size_t)tiles * 4);
-            MI_HIP(hipMemsetAsync(attn_cnt.p, 0, (size_t)tiles * 4, stream));
-            attn_cnt_n = tiles;
+            attn_cnt.ensure((size_t)ATTN_WS_TILES * 4);
+            MI_HIP(hipMemsetAsync(attn_cnt.p, 0, (size_t)ATTN_WS_TILES * 4, stream));
+            attn_cnt_n = ATTN_WS_TILES;
         }
     }
     d_noise.ensure((size_t)Um * Nm * c.mel * 4);
@@ -788,117 +787,96 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
         return g;
     };
     auto with_planes = [&](ConvGemm& g, const Lin& L, const void* xp) { g.xp = xp; g.w3p = L.w3p.p; g.np = np; };
+    // The attention plan (attention.hip): the K / V layout the QKV epilogue writes and the kernel that reads it, decided once per
+    // evaluation.  First for a caller that cannot pre-split K / V (the ROWS form; also what the form decision below is taken on),
+    // then again once the form is known to be one whose QKV epilogue can.
+    auto attn_plan = [&](bool presplit) {
+        return attention_plan(B * H, H, N, dtype, presplit, lens != nullptr, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, attn_ws_floats, attn_cnt_n);
+    };
+    AttnPlan ap = attn_plan(false);
     auto qkv_gemm = [&](const Block& bk) {
         ConvGemm g = lin(bk.qkv, d, -1, qb.p);
-        g.out2 = kb.p; g.out3 = vb.p; g.rows_per_item = N;           // batch flattened into M
+        g.x = Ub.p; g.out2 = kb.p; g.out3 = vb.p; g.rows_per_item = N;           // batch flattened into M
         g.epi = EPI_QKV_ROPE; g.rope_cos = rope_cos.as<float>(); g.rope_sin = rope_sin.as<float>(); g.rope_pack = rope_pack.p; g.heads = H; g.head_dim = D;
-        g.v_ld = attention_v_ld(N, dtype);
+        g.kv_planes = ap.kv.kv_planes; g.k_ld = ap.kv.k_ld; g.v_ld = ap.kv.v_ld; g.v_rows = ap.kv.v_rows;
         return g;
     };
-    const int kvp_fmt = attention_kv_planes_format();       // K / V pre-split for the attention kernel: 2 fp16 planes or 3 bf16 planes
-    const int v_rows = attention_kv_v_rows() ? 1 : 0;        // ... V as rows like K (default) or transposed: one answer for the epilogue and the kernel
     // which form: decided on block 0's layers (every block has the same shapes and the same weight formats)
     bool planes = false, fold = false;
     {
         const Block& b0 = blocks[0];
-        if (f32 && Ap.p && gemm_x3p_enabled() && b0.qkv.w3p.p && b0.o.w3p.p && b0.ff1.w3p.p && b0.ff2.w3p.p && attention_can_write_planes(N, B * H, dtype)) {
-            ConvGemm gq = qkv_gemm(b0); gq.x = Ub.p; with_planes(gq, b0.qkv, Ap.p);
-            ConvGemm go = lin(b0.o, d, MI_F32, X.p); go.x = Ob.p; go.res = X.p; go.gate = modk; with_planes(go, b0.o, Ap.p);
-            ConvGemm g1 = lin(b0.ff1, d, dtype, Hff.p); g1.x = Ub.p; g1.act = ACT_GELU_TANH; with_planes(g1, b0.ff1, Ap.p);
-            ConvGemm g2 = lin(b0.ff2, ff, MI_F32, X.p); g2.x = Hff.p; g2.res = X.p; g2.gate = modk; with_planes(g2, b0.ff2, Ap2.p);
+        ConvGemm gq = qkv_gemm(b0);
+        ConvGemm go = lin(b0.o, d, MI_F32, X.p); go.x = Ob.p; go.res = X.p; go.gate = modk;
+        ConvGemm g1 = lin(b0.ff1, d, dtype, Hff.p); g1.x = Ub.p; g1.act = ACT_GELU_TANH;
+        ConvGemm g2 = lin(b0.ff2, ff, MI_F32, X.p); g2.x = Hff.p; g2.res = X.p; g2.gate = modk;
+        if (f32 && Ap.p && gemm_x3p_enabled() && b0.qkv.w3p.p && b0.o.w3p.p && b0.ff1.w3p.p && b0.ff2.w3p.p && ap.o_planes) {
+            with_planes(gq, b0.qkv, Ap.p); with_planes(go, b0.o, Ap.p); with_planes(g1, b0.ff1, Ap.p); with_planes(g2, b0.ff2, Ap2.p);
             planes = gemm_x3p_would_run(gq) && gemm_x3p_would_run(go) && gemm_x3p_can_write_planes(g1) && gemm_x3p_would_run(g2);
         }
         if (fold_built && cfg.ln_fold != 0 && (planes || !f32) && (!f32 || ApN.p) && ln_stats.p && (f32 || ln_fin.p)) {
-            ConvGemm gq = qkv_gemm(b0); gq.x = Ub.p;
-            ConvGemm go = lin(b0.o, d, MI_F32, X.p); go.x = Ob.p; go.res = X.p; go.gate = modk;
-            ConvGemm g1 = lin(b0.ff1, d, dtype, Hff.p); g1.x = Ub.p; g1.act = ACT_GELU_TANH;
-            ConvGemm g2 = lin(b0.ff2, ff, MI_F32, X.p); g2.x = Hff.p; g2.res = X.p; g2.gate = modk;
-            if (f32) { with_planes(gq, b0.qkv, ApN.p); with_planes(go, b0.o, Ap.p); with_planes(g1, b0.ff1, ApN.p); with_planes(g2, b0.ff2, Ap2.p); }
+            if (f32) { with_planes(gq, b0.qkv, ApN.p); with_planes(g1, b0.ff1, ApN.p); }
             fold = gemm_ln_fold_ok(gq) && gemm_ln_fold_ok(go) && gemm_ln_fold_ok(g1) && gemm_ln_fold_ok(g2);
         }
     }
+    if (f32 && (fold || planes)) ap = attn_plan(true);
+    void* const attn_planes = f32 && (fold || planes) ? Ap.p : nullptr;          // attention -> O: the output as panel planes
+    auto attention = [&] {
+        launch_attention(ap, qb.p, kb.p, vb.p, Ob.p, attn_planes, np, attn_ws.as<float>(), attn_cnt.as<int>(), lens, s);
+    };
     float* stats = ln_stats.as<float>();
     const float* lnk = fold ? ln_tab.as<float>() + (size_t)k * ln_ld : nullptr;
     const bool fin = fold && !f32;               // 16-bit engines: the statistics are finished by one tiny launch, not per column tile
     auto finalize = [&] { if (fin) launch_ln_finalize(stats, ln_fin.as<float>(), rows, d, 1e-6f, s); };
-    auto consume = [&](ConvGemm& g) { g.ln_stats_in = fin ? ln_fin.as<float>() : stats; g.ln_final = fin ? 1 : 0; g.ln_dim = d; g.ln_eps = 1e-6f; };
+    auto consume = [&](ConvGemm& g, const float* p, const float* c_) {
+        g.bias = nullptr; g.ln_p = p; g.ln_c = c_;
+        g.ln_stats_in = fin ? ln_fin.as<float>() : stats; g.ln_final = fin ? 1 : 0; g.ln_dim = d; g.ln_eps = 1e-6f;
+    };
+    auto produce = [&](ConvGemm& g, const float* scale) { g.ln_scale = scale; g.ln_out = f32 ? ApN.p : Ub.p; g.ln_out_np = np; g.ln_stats_out = stats; };
     if (fold) {     // block 0's attention norm: the residual row comes from the position convolution, whose epilogue has no fold
         launch_ln_prologue(X.as<float>(), f32 ? ApN.p : Ub.p, dtype, np, stats, modk + d, rows, d, d_sat.as<int>(), s);
         finalize();
     }
+    // FOLD and PLANES launch the same four layers.  fp32: operands as panel planes — QKV / FF1 read `normed` (FOLD: what the producer's
+    // epilogue left in ApN; PLANES: what the row norm left in Ap), O reads the attention's planes, FF2 reads FF1's (Ap2)
+    const void* normed = fold ? ApN.p : Ap.p;
+    auto layer = [&](ConvGemm& g, const Lin& L, const void* xp, const char* left) {
+        if (f32) { with_planes(g, L, xp); MI_REQUIRE(gemm_x3p_would_run(g), left); }
+        launch_conv_gemm(g, s);
+    };
     for (int i = 0; i < c.depth; ++i) {
         const Block& bk = blocks[i];
         const float* m = modk + (size_t)i * 6 * d;       // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        if (fold) {
-            const float* lt = lnk + (size_t)i * ln_blk;   // W_qkv (1 + sc_a) | W_qkv sh_a + b | W_ff1 (1 + sc_m) | W_ff1 sh_m + b
-            const bool kvp = f32 && attention_takes_kv_planes(N, B * H, dtype);
+        if (fold || planes) {
+            const float* lt = fold ? lnk + (size_t)i * ln_blk : nullptr;   // W_qkv (1 + sc_a) | W_qkv sh_a + b | W_ff1 (1 + sc_m) | W_ff1 sh_m + b
+            const bool last = i + 1 == c.depth;          // the last block's row goes to AdaLN-final below, not to a next attention norm
+            if (!fold) launch_rownorm_x3p(X.as<float>(), Ap.p, m + d, m, rows, d, 1e-6f, s, np, d_sat.as<int>());
             {
                 ConvGemm g = qkv_gemm(bk);
-                g.x = Ub.p; g.bias = nullptr;
-                if (f32) with_planes(g, bk.qkv, ApN.p);
-                consume(g); g.ln_p = lt; g.ln_c = lt + 3 * d;
-                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); g.v_rows = v_rows; }
-                launch_conv_gemm(g, s);
+                if (fold) consume(g, lt, lt + 3 * d);
+                layer(g, bk.qkv, normed, "f5: the QKV layer left the panel-plane kernel between the decision and the launch");
             }
-            launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             f32 ? Ap.p : nullptr, kvp ? kvp_fmt : 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens, kvp ? v_rows : 0);
+            attention();
             {
                 ConvGemm g = lin(bk.o, d, MI_F32, X.p);
                 g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d;
-                if (f32) with_planes(g, bk.o, Ap.p);
-                g.ln_scale = m + 4 * d; g.ln_out = f32 ? ApN.p : Ub.p; g.ln_out_np = np; g.ln_stats_out = stats;       // -> the FF1 norm
-                launch_conv_gemm(g, s);
+                if (fold) produce(g, m + 4 * d);                                  // -> the FF1 norm
+                layer(g, bk.o, Ap.p, "f5: the O projection left the panel-plane kernel between the decision and the launch");
                 finalize();
             }
+            if (!fold) launch_rownorm_x3p(X.as<float>(), Ap.p, m + 4 * d, m + 3 * d, rows, d, 1e-6f, s, np, d_sat.as<int>());
             {
                 ConvGemm g = lin(bk.ff1, d, dtype, Hff.p);
-                g.x = Ub.p; g.bias = nullptr; g.act = ACT_GELU_TANH;
-                if (f32) { with_planes(g, bk.ff1, ApN.p); g.out_planes = Ap2.p; }
-                consume(g); g.ln_p = lt + 6 * d; g.ln_c = lt + 6 * d + ff;
-                launch_conv_gemm(g, s);
+                g.x = Ub.p; g.act = ACT_GELU_TANH;
+                if (f32) g.out_planes = Ap2.p;
+                if (fold) consume(g, lt + 6 * d, lt + 6 * d + ff);
+                layer(g, bk.ff1, normed, "f5: the FF1 layer left the panel-plane kernel between the decision and the launch");
             }
             {
                 ConvGemm g = lin(bk.ff2, ff, MI_F32, X.p);
                 g.x = Hff.p; g.res = X.p; g.gate = m + 5 * d;
-                if (f32) with_planes(g, bk.ff2, Ap2.p);
-                if (i + 1 < c.depth) {                   // -> the next block's attention norm (the last block's row goes to AdaLN-final below)
-                    g.ln_scale = m + 6 * d + d; g.ln_out = f32 ? ApN.p : Ub.p; g.ln_out_np = np; g.ln_stats_out = stats;
-                }
-                launch_conv_gemm(g, s);
-                if (i + 1 < c.depth) finalize();
-            }
-            continue;
-        }
-        if (planes) {
-            const bool kvp = attention_takes_kv_planes(N, B * H, dtype);
-            launch_rownorm_x3p(X.as<float>(), Ap.p, m + d, m, rows, d, 1e-6f, s, np, d_sat.as<int>());
-            {
-                ConvGemm g = qkv_gemm(bk);
-                g.x = Ub.p; with_planes(g, bk.qkv, Ap.p);
-                if (kvp) { g.kv_planes = kvp_fmt; g.k_ld = g.v_ld = (long)((N + 63) / 64 * 64); g.v_rows = v_rows; }
-                MI_REQUIRE(gemm_x3p_would_run(g), "f5: the QKV layer left the panel-plane kernel between the decision and the launch");
-                launch_conv_gemm(g, s);
-            }
-            launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                             Ap.p, kvp ? kvp_fmt : 0, np, 0.f, lens, kvp ? v_rows : 0);
-            {
-                ConvGemm g = lin(bk.o, d, MI_F32, X.p);
-                g.x = Ob.p; g.res = X.p; g.gate = m + 2 * d; with_planes(g, bk.o, Ap.p);
-                MI_REQUIRE(gemm_x3p_would_run(g), "f5: the O projection left the panel-plane kernel between the decision and the launch");
-                launch_conv_gemm(g, s);
-            }
-            launch_rownorm_x3p(X.as<float>(), Ap.p, m + 4 * d, m + 3 * d, rows, d, 1e-6f, s, np, d_sat.as<int>());
-            {
-                ConvGemm g = lin(bk.ff1, d, dtype, Hff.p);
-                g.x = Ub.p; g.act = ACT_GELU_TANH; with_planes(g, bk.ff1, Ap.p); g.out_planes = Ap2.p;
-                MI_REQUIRE(gemm_x3p_would_run(g), "f5: the FF1 layer left the panel-plane kernel between the decision and the launch");
-                launch_conv_gemm(g, s);
-            }
-            {
-                ConvGemm g = lin(bk.ff2, ff, MI_F32, X.p);
-                g.x = Hff.p; g.res = X.p; g.gate = m + 5 * d; with_planes(g, bk.ff2, Ap2.p);
-                MI_REQUIRE(gemm_x3p_would_run(g), "f5: the FF2 layer left the panel-plane kernel between the decision and the launch");
-                launch_conv_gemm(g, s);
+                if (fold && !last) produce(g, m + 6 * d + d);                     // -> the next block's attention norm
+                layer(g, bk.ff2, Ap2.p, "f5: the FF2 layer left the panel-plane kernel between the decision and the launch");
+                if (!last) finalize();
             }
             continue;
         }
@@ -906,11 +884,10 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
         launch_rownorm(NORM_LN_MOD, X.as<float>(), Ub.p, dtype, m + d, m, rows, d, 1e-6f, s);
         {
             ConvGemm g = qkv_gemm(bk);
-            g.x = Ub.p; g.x_bstride = (long)B * N * d;
+            g.x_bstride = (long)B * N * d;
             launch_conv_gemm(g, s);
         }
-        launch_attention(qb.p, kb.p, vb.p, Ob.p, B * H, H, N, dtype, s, attn_ws.as<float>(), attn_ws_floats, attn_cnt.as<int>(), attn_cnt_n,
-                         nullptr, 0, np, cfg.score_scale != 1.f ? cfg.score_scale : 0.f, lens);
+        attention();
         gemm(dtype, Ob.p, (long)N * d, d, d, bk.o, X.p, MI_F32, (long)N * d, d, B, N, ACT_NONE, X.p, m + 2 * d);
         launch_rownorm(NORM_LN_MOD, X.as<float>(), Ub.p, dtype, m + 4 * d, m + 3 * d, rows, d, 1e-6f, s);
         gemm(dtype, Ub.p, (long)N * d, d, d, bk.ff1, Hff.p, dtype, (long)N * ff, ff, B, N, ACT_GELU_TANH);

@@ -46,29 +46,50 @@ void launch_zero_pad_rows(void* x, long row_bytes, int items, int N, const int* 
 void launch_sum_parts(const float* in, float* out, long rows, int M, int parts, hipStream_t s);
 
 // attention.hip: softmax_fp32(q k^T) v, no mask, no scale (q/k are pre-scaled): modules.py:467
-//   q,k [BH][N][64], v [BH][N][64] (fp32, native / q.k-split kernels) or transposed [BH][64][v_ld] (16-bit, and the fp32
-//   kernel with both products split; v_ld = attention_v_ld(N, dtype))
-//   -> o [B][N][H*64] (dtype), B = BH / H
-// ws / cnt: optional workspace of the key-sliced fp32 kernel ((2*32*64 + 256) floats per 64-query tile and slice; one zeroed
-// counter per tile); without them every query tile is one workgroup
-void launch_attention(const void* q, const void* k, const void* v, void* o, int BH, int H, int N, int dtype, hipStream_t s,
-                      float* ws = nullptr, long ws_floats = 0, int* cnt = nullptr, long cnt_n = 0, void* o_planes = nullptr,
-                      int kv_planes = 0, int o_np = 3, float ref_fp16_scale = 0.f, const int* lens = nullptr, int v_rows = 0);
-// ref_fp16_scale (f16 engines; 0 = off): the score rounding points of the reference's fp16-transformer export — q k scores
-// rounded to fp16, then x ref_fp16_scale (= 100, undoing the extra x0.1 folded into q and k) in fp32 (F5/fp16/modules.py:467)
-// kv_planes (fp32 engines, both products split): k and v are the pre-split bf16 planes the QKV epilogue wrote (ConvGemm::kv_planes:
-// k [BH][np][ld][64], v [BH][np][64][ld] — or [BH][np][ld][64] with v_rows —, ld = N rounded up to 64; the pad keys may hold any bytes, the
-// kernel clears them) — ask attention_takes_kv_planes() first
-bool attention_takes_kv_planes(int N, int BH, int dtype);
-// v_rows (with kv_planes): v is [BH][np][ld][64] like k (ConvGemm::v_rows) and any bytes may lie in its rows past N — the caller passes
-// the layout the QKV epilogue wrote, attention_kv_v_rows() at the time of that launch
-bool attention_kv_v_rows();
-int attention_kv_planes_format();        // 2: fp16 {hi, lo} pairs (option "attn_f32_planes", default) | 3: three bf16 planes — pass it as kv_planes
-// o_planes (fp32 engines, both products split): the output as gemm_x3p.hip panel planes of the [B * N][H * 64] matrix instead
-// of rows in o — ask attention_can_write_planes() first
-bool attention_can_write_planes(int N, int BH, int dtype);
-// row length of the transposed V the attention kernel in use expects (0: V untransposed, [BH][N][64]) — ask per launch: the
-// fp32 answer follows the attn_f32_x3 option
-long attention_v_ld(int N, int dtype);
+//   q [BH][N][64], k, v in the layout of AttnKvLayout -> o [B][N][H*64] (dtype), B = BH / H
+// One AttnPlan, made by attention_plan() BEFORE the QKV projection of an evaluation, decides both sides of the K / V contract: the
+// layout the QKV epilogue writes (ConvGemm::kv_planes / k_ld / v_ld / v_rows are copied from plan.kv) and the kernel that reads it.
+// The options and the engine's arithmetic (ArithScope) are read there and nowhere else.
+struct AttnKvLayout {
+    int kv_planes = 0;     // 0: k as rows [BH][N][64] of the engine's type.  2 | 3 (fp32 engines, both products split, a caller that can
+                           // pre-split): k [BH][np][k_ld][64] as np = 2 fp16 {hi, lo} or 3 bf16 planes (x3_split.h), v alike: [BH][np][64][v_ld],
+                           // or [BH][np][k_ld][64] with v_rows; the pad keys may hold any bytes, the kernel clears them
+    long k_ld = 0;         // with kv_planes: N rounded up to the 64-key stage
+    long v_ld = 0;         // 0: v as rows [BH][N][64] (fp32, native and q.k-split kernels); else v transposed [BH][64][v_ld]: N rounded up to 8
+                           // (16-bit engines, and fp32 with both products split), to 64 with kv_planes
+    int v_rows = 0;        // with kv_planes: v as rows like k (the kernel's VROWS form transposes on its LDS reads)
+};
+AttnKvLayout attention_kv_layout(int N, int dtype, bool caller_can_presplit_kv);
+// the kernels: even = 128-query workgroups, + 1 = 64-query workgroups whose wave pairs share the keys (SPLIT2)
+enum AttnForm {
+    ATTN_F32 = 0, ATTN_F32_QK_X3 = 2, ATTN_X3F = 4, ATTN_X3F_BF16X3 = 6, ATTN_X3F_PAIRS = 8,      // fp32: native | q.k split | both split: K / V split in the kernel | pre-split, 3 bf16 planes | 2 fp16 planes
+    ATTN_X3F_PAIRS_SLICED = 10,                                                                   // ... 128-query workgroups over (uneven) key slices
+    ATTN_F16 = 11, ATTN_F16_REF = 13, ATTN_BF16 = 15, ATTN_FORMS = 17
+};
+// queries per workgroup, keys per LDS stage, and the key-slice workspace: one slot of partial (m, l, O) per (query tile, slice) — two
+// 32-query groups per 64-query tile, four per 128-query tile — and one zeroed ticket counter per tile.  F5::ensure_workspace reserves
+// ATTN_WS_TILES 64-query tiles x ATTN_MAX_SLICES; attention_plan() slices only what fits the workspace it is told of.
+constexpr int ATTN_TILE = 128, ATTN_TILE_SPLIT = 64, ATTN_STAGE = 64, ATTN_MAX_SLICES = 4;
+constexpr long ATTN_SLOT_GROUP = 32 * 64 + 64 * 2, ATTN_SLOT_SPLIT = 2 * ATTN_SLOT_GROUP, ATTN_SLOT = 4 * ATTN_SLOT_GROUP;      // floats
+constexpr long ATTN_WS_TILES = 2048;
+struct AttnPlan {
+    AttnKvLayout kv;            // what the QKV epilogue must write
+    bool o_planes = false;      // the kernel can also leave its output as gemm_x3p.hip panel planes of the [B * N][H * 64] matrix
+    int form = ATTN_F32;        // AttnForm (+ 1: SPLIT2)
+    bool varlen = false;        // ragged batch: launch_attention() is given the device table of lengths
+    int BH = 0, H = 0, N = 0, dtype = MI_F32;
+    unsigned grid[3] = {1, 1, 1};      // query tiles x BH x key slices
+    int cut[3] = {0, 0, 0};     // ATTN_X3F_PAIRS_SLICED: cut[0] > 0 = uneven slices [0, cut[0]), [cut[0], cut[1]), ... in stages, longest first
+    int xmap = 0;               // XCD-aware workgroup map (ATTN_XCD_MAP)
+    float sscale = 1.f;         // ATTN_F16_REF: the reference's fp16 score form, scores rounded to fp16 and x sscale in fp32 (F5/fp16/modules.py:467)
+    const char* label = "";     // the profiler's name of the launch (rocprofv3 shows the instantiation itself)
+};
+// ref_fp16_scale (f16 engines; 0 = off) selects ATTN_F16_REF.  ws_floats / cnt_n: the caller's key-slice workspace (0: none, every
+// query tile is one workgroup).  has_lens: a ragged batch — the grid, the slices and the cuts are those of the uniform launch at N.
+AttnPlan attention_plan(int BH, int H, int N, int dtype, bool caller_can_presplit_kv, bool has_lens, float ref_fp16_scale, long ws_floats,
+                        long cnt_n);
+// o_planes (null: rows in o) needs plan.o_planes; o_np = its planes per value (2 | 3).  ws / cnt: the workspace the plan was told of.
+void launch_attention(const AttnPlan& plan, const void* q, const void* k, const void* v, void* o, void* o_planes, int o_np, float* ws,
+                      int* cnt, const int* lens, hipStream_t s);
 
 }  // namespace mi

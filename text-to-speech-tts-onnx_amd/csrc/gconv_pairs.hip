@@ -363,14 +363,7 @@ bool launch_gconv_pairs(const ConvGemm& p, hipStream_t s) {
     d.K = p.taps * GCP_C; d.sat = p.sat;
     // rows per workgroup: 128 (two workgroups per CU) or 192 (one), whichever puts fewer rows on the busiest CU — one
     // utterance (B = 2, M = 1126, 16 groups) is 288 workgroups of 128 rows (32 CUs get two: 256 rows) or 192 of 192 rows
-    int cus = 256;
-    {
-        int dev = 0;
-        MI_HIP(hipGetDevice(&dev));
-        static int cu_count[16] = {0};
-        if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-        cus = cu_count[dev & 15];
-    }
+    const int cus = device_cus();
     auto load = [&](int bm) { const long n = (long)((p.M + bm - 1) / bm) * p.G * p.B; return ((n + cus - 1) / cus) * bm; };
     const int BM = load(192) < load(128) ? 192 : 128;
     const int rows_a = BM + p.taps - 1;

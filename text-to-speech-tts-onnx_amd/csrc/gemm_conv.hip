@@ -847,13 +847,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
                                                       // tokens from the flattened row: the second launch carries its row offset (m_off)
     if (!p.lens && opt(OPT_GEMM_ROW_SPLIT) != 0 && opt(OPT_GEMM_PH8) != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
         (split_plain || split_qkv) && p.M == p.T_in && p.N % 256 == 0 && !p.xp) {
-        int dev = 0, cus = 256;
-        MI_HIP(hipGetDevice(&dev));
-        {
-            static int cu_count[16] = {0};
-            if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-            cus = cu_count[dev & 15];
-        }
+        const int cus = device_cus();
         const long ntn = p.N / 256;
         long gc = cus, t = ntn;
         while (t) { const long u = gc % t; gc = t; t = u; }       // gcd(cus, ntn)

@@ -330,13 +330,7 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
 template <typename T, typename TO>
 void launch_linear_ph8(const ConvGemmDev& e_in, hipStream_t s) {
     ConvGemmDev e = e_in;
-    int dev = 0, cus = 256;
-    MI_HIP(hipGetDevice(&dev));
-    {
-        static int cu_count[16] = {0};
-        if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-        cus = cu_count[dev & 15];
-    }
+    const int cus = device_cus();
     const int T_all = e.Tm * e.Tn, nk = e.K / 64;
     // split tail: the largest S (<= gemm_ph8_split_max) with S * rem workgroups on the chip at once, >= 4 K tiles per slice and
     // (S - 1) * rem slabs of 256 KB in the workspace; worth it only when the tail round is mostly empty

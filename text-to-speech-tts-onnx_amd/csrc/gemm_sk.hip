@@ -400,13 +400,7 @@ void launch_linear_sk(const ConvGemmDev& e, int stages, hipStream_t s) {
     constexpr int KC = 128 / (int)sizeof(T);
     const int nst = stages ? stages : (sizeof(T) == 4 ? 3 : 2);
     (void)KC;
-    int dev = 0, cus = 256;
-    MI_HIP(hipGetDevice(&dev));
-    {
-        static int cu_count[16] = {0};
-        if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-        cus = cu_count[dev & 15];
-    }
+    const int cus = device_cus();
     const int P = std::min(cus * (nst <= 2 ? 2 : 1), e.sk_slots) & ~7;         // a multiple of the 8 XCD groups
     const dim3 grid(P);
 #define SK_LAUNCH(LE, NS)                                                                                              \

@@ -369,13 +369,7 @@ __global__ __launch_bounds__(SHAPE >= 2 ? 512 : 256, 1) void linear_x3_kernel(co
 void launch_linear_x3(const ConvGemmDev& e_in, hipStream_t s) {
     ConvGemmDev e = e_in;
     e.tail_tiles = 0;
-    int dev = 0, cus = 256;
-    MI_HIP(hipGetDevice(&dev));
-    {
-        static int cu_count[16] = {0};
-        if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-        cus = cu_count[dev & 15];
-    }
+    const int cus = device_cus();
     const int P = std::min(cus, e.sk_slots) & ~7;
     const dim3 grid(P);
     if (e.lds_epi) {

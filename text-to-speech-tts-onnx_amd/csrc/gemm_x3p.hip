@@ -478,13 +478,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
 void launch_linear_x3p(const ConvGemmDev& e_in, hipStream_t s) {
     ConvGemmDev e = e_in;
     MI_REQUIRE(!e.out_planes || e.lds_epi, "linear_x3p: out_planes needs the LDS-staged epilogue");
-    int dev = 0, cus = 256;
-    MI_HIP(hipGetDevice(&dev));
-    {
-        static int cu_count[16] = {0};
-        if (!cu_count[dev & 15]) { hipDeviceProp_t pr; MI_HIP(hipGetDeviceProperties(&pr, dev)); cu_count[dev & 15] = pr.multiProcessorCount; }
-        cus = cu_count[dev & 15];
-    }
+    const int cus = device_cus();
     // exact-fit data-parallel tiling (gemm_x3d.hip) when the output divides into whole rounds of the CUs; else stream-K below
     if (!(e.dbg & ~4)) {
         int tw, rgn, cgn, band;

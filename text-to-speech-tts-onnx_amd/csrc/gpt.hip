@@ -968,8 +968,7 @@ static void gemv_d_dispatch(const Gpt::GLin& l, const void* x, const float* ln_w
         // rows per wave: the fewest (most waves in flight) for which the launch is one round of 512-thread blocks, one per CU
         // (5120 rows at R = 2 are 320 blocks on 256 CUs: the 64 CUs that get two set the time — 6.1 us against 4.7 for the
         // 3840-row layer; R = 3: 214 blocks, 5.4 us)
-        static int cus = 0;
-        if (!cus) { int dev = 0; hipDeviceProp_t pr; MI_HIP(hipGetDevice(&dev)); MI_HIP(hipGetDeviceProperties(&pr, dev)); cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+        const int cus = device_cus();
         int r = 1;
         while (r < (kcl ? 2 : 5) && (l.n + 8 * r - 1) / (8 * r) > cus) ++r;
 #define GD_K(RR, QK)                                                                              \

@@ -2,6 +2,7 @@
 #include "common.h"
 #include <mutex>
 #include <algorithm>
+#include <atomic>
 
 namespace mi {
 
@@ -13,6 +14,21 @@ void upload_f32(DevBuf& dst, const float* src, size_t n, hipStream_t s) {
     dst.ensure(n * 4);
     MI_HIP(hipMemcpyAsync(dst.p, src, n * 4, hipMemcpyHostToDevice, s));
     MI_HIP(hipStreamSynchronize(s));
+}
+
+int device_cus() {
+    static std::atomic<int> cache[64];                 // 0: not asked yet.  Two threads may both ask; they store the same count
+    int dev = 0;
+    MI_HIP(hipGetDevice(&dev));
+    std::atomic<int>* slot = dev >= 0 && dev < 64 ? &cache[dev] : nullptr;
+    int cus = slot ? slot->load(std::memory_order_relaxed) : 0;
+    if (!cus) {
+        hipDeviceProp_t pr;
+        MI_HIP(hipGetDeviceProperties(&pr, dev));
+        cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+        if (slot) slot->store(cus, std::memory_order_relaxed);
+    }
+    return cus;
 }
 
 static inline uint16_t f32_to_bf16_bits(float f) {

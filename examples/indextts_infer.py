@@ -13,6 +13,11 @@ is noise-like audio, but every shape, dtype and call is the real one.  For the r
 `import mi355tts.ort_compat as onnxruntime`, see INTEGRATION.md section 4 and tests/test_gpu_compat.py.
 
     python examples/indextts_infer.py --prompt prompt.wav --text "..." --out generated.wav [--small] [--device-type cuda]
+
+Decoding is greedy like the reference's unless one of --temperature / --top-k / --top-p / --sample-seed is given: then every mel
+code is drawn on the device (`Sampling`, upstream IndexTTS's temperature 1.0 / top_k 30 / top_p 0.8 where not given).
+`--takes N` decodes every sentence in N batch slots at once, seeds sample-seed .. sample-seed + N - 1, and writes
+<out>_<i>.wav: N takes for the weight traffic of one.
 """
 import argparse
 import dataclasses
@@ -28,7 +33,7 @@ sys.path.insert(0, os.path.join(ROOT, "text-to-speech-tts-onnx_amd"))
 from mi355tts import audio_io, weights                                       # noqa: E402
 from mi355tts.bigvgan import BigVGANVocoder                                   # noqa: E402
 from mi355tts.config import BigVGANConfig, IndexCondConfig, IndexGPTConfig    # noqa: E402
-from mi355tts.indextts import IndexCond, IndexGPT                             # noqa: E402
+from mi355tts.indextts import IndexCond, IndexGPT, Sampling                   # noqa: E402
 from mi355tts.indextts_text import TextNormalizer, TextTokenizer              # noqa: E402
 
 
@@ -58,6 +63,7 @@ def build_engines(args, vocab):
         gcfg, ccfg, vcfg = IndexGPTConfig(), IndexCondConfig(), BigVGANConfig.indextts()
         if args.max_generate_length:
             gcfg = dataclasses.replace(gcfg, max_generate_length=args.max_generate_length)
+    gcfg = dataclasses.replace(gcfg, max_batch=max(gcfg.max_batch, args.takes))
     fast = not args.small
     state = lambda spec: weights.synth_state(spec, args.seed, fast=fast)
     cond = IndexCond(ccfg, state(weights.cond_spec(ccfg)))
@@ -78,8 +84,21 @@ def main():
     ap.add_argument("--small", action="store_true", help="reduced synthetic models (smoke runs)")
     ap.add_argument("--max-generate-length", type=int, default=None)
     ap.add_argument("--ignore-stop", action="store_true", help="decode to the length limit (synthetic weights emit the stop code at random)")
-    ap.add_argument("--seed", type=int, default=9527)
+    ap.add_argument("--seed", type=int, default=9527, help="seed of the synthetic weights")
+    ap.add_argument("--temperature", type=float, default=None, help="sample the mel codes (default: greedy, like the reference)")
+    ap.add_argument("--top-k", type=int, default=None, help="0 = every code")
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--sample-seed", type=int, default=None, help="seed of the draws (--seed is the synthetic weights')")
+    ap.add_argument("--takes", type=int, default=1, help="decode every sentence N times in one batch, seeds sample-seed .. + N - 1; writes <out>_<i>.wav")
     args = ap.parse_args()
+    if not 1 <= args.takes <= 16:
+        ap.error("--takes must be in 1..16 (the engine's batch slots)")
+    sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
+    take_sampling = [Sampling(1.0 if args.temperature is None else args.temperature, 30 if args.top_k is None else args.top_k,
+                              0.8 if args.top_p is None else args.top_p, (args.sample_seed or 0) + i)
+                     for i in range(args.takes)] if sampled else None
+    if args.takes > 1 and args.device_type == "cuda":
+        ap.error("--takes uses the host-array batch call (generate_batch); run it with --device-type cpu")
 
     sp, tokenizer = build_tokenizer(args.tokenizer)
     (gcfg, ccfg, vcfg), (cond, gpt, voc) = build_engines(args, sp.get_piece_size())
@@ -102,20 +121,35 @@ def main():
         voc_cond_dev = torch.from_numpy(np.concatenate([np.ravel(c) for c in stage_conds] + [np.ravel(embed_cond)]).astype(np.float32)).to(dev)
         penalty_dev = torch.ones(gcfg.mel_codes, dtype=torch.float32, device=dev)     # carried from sentence to sentence, like the host form
     pieces, n_codes = [], 0
+    take_pieces = [[] for _ in range(args.takes)]
+    take_penalty = None
     sentences = tokenizer.split_sentences(tokenizer.tokenize(args.text))
     for sentence in sentences:
         print("Generate the Voice for '" + "".join(sentence).replace("▁", " ") + "'")
         ids = np.asarray(tokenizer.convert_tokens_to_ids(sentence), dtype=np.int32)
         t_dec = time.time()
+        if args.takes > 1:                         # the same sentence in every slot: one pass over the weights per step for all takes
+            prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
+            budget = gcfg.max_generate_length - int(prompt_len[0])
+            results, take_penalty = gpt.generate_batch([prompt_rows] * args.takes, [budget] * args.takes, stop_tokens=stops,
+                                                       repeat_penality=take_penalty, sampling=take_sampling)
+            n = sum(h.shape[0] for _, h in results)
+            print(f"Decode Speed: {n / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n} tokens in {args.takes} takes)")
+            n_codes += n
+            for i, (_, hidden) in enumerate(results):
+                if hidden.shape[0] >= 3:
+                    take_pieces[i].append(np.concatenate([voc.run_latent(hidden, list(stage_conds) + [embed_cond]), gap], axis=-1))
+            continue
         if on_device:
             prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
             budget = gcfg.max_generate_length - int(prompt_len[0])
             codes = torch.zeros(max(budget, 1), dtype=torch.int32, device=dev)
             hidden = torch.zeros((max(budget, 1), gcfg.hidden), dtype=torch.float32, device=dev)
-            n = gpt.generate_torch(torch.from_numpy(prompt_rows[0]).to(dev), budget, codes, hidden, stop_tokens=stops, repeat_penality=penalty_dev)
+            n = gpt.generate_torch(torch.from_numpy(prompt_rows[0]).to(dev), budget, codes, hidden, stop_tokens=stops, repeat_penality=penalty_dev,
+                                   sampling=take_sampling[0] if sampled else None)
             hidden = hidden[:n].contiguous()
         else:
-            _, hidden, _ = gpt.generate(conds_latent[None], ids, stop_tokens=stops)
+            _, hidden, _ = gpt.generate(conds_latent[None], ids, stop_tokens=stops, sampling=take_sampling[0] if sampled else None)
             n = hidden.shape[0]
         print(f"Decode Speed: {n / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n} tokens)")
         n_codes += n
@@ -126,10 +160,20 @@ def main():
                 wav = voc.run_latent(hidden, list(stage_conds) + [embed_cond])
             pieces.append(np.concatenate([wav, gap], axis=-1))
     elapsed = time.time() - t_start
-    out = np.concatenate(pieces, axis=-1) if pieces else gap
-    audio_io.write_wavex(args.out, out.reshape(-1), rate)
-    secs = out.size / rate
-    print(f"{args.out}: {len(sentences)} sentence(s), {n_codes} mel codes, {secs:.2f} s of audio in {elapsed:.3f} s (RTF {elapsed / max(secs, 1e-9):.4f})")
+    if args.takes > 1:
+        base, ext = os.path.splitext(args.out)
+        secs = 0.0
+        for i, tp in enumerate(take_pieces):
+            out = np.concatenate(tp, axis=-1) if tp else gap
+            audio_io.write_wavex(f"{base}_{i}{ext}", out.reshape(-1), rate)
+            secs += out.size / rate
+        print(f"{base}_0{ext} .. {base}_{args.takes - 1}{ext}: {len(sentences)} sentence(s) x {args.takes} takes, {n_codes} mel codes, "
+              f"{secs:.2f} s of audio in {elapsed:.3f} s (RTF {elapsed / max(secs, 1e-9):.4f})")
+    else:
+        out = np.concatenate(pieces, axis=-1) if pieces else gap
+        audio_io.write_wavex(args.out, out.reshape(-1), rate)
+        secs = out.size / rate
+        print(f"{args.out}: {len(sentences)} sentence(s), {n_codes} mel codes, {secs:.2f} s of audio in {elapsed:.3f} s (RTF {elapsed / max(secs, 1e-9):.4f})")
     for e in (cond, gpt, voc):
         e.close()
 

@@ -255,6 +255,56 @@ int         mi_gpt_generate_batch(mi_gpt* h, int nb, const float* prompts, const
                                   int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden, int cap,
                                   int32_t* n_out, int mem);
 
+/* ---- sampling: seeded temperature / top-k / top-p choice of the mel code, on the device ------------------------------------
+ * The reference decodes greedily and so do the entries above; these are the engine's own.  Each sentence has
+ * temperature > 0, top_k >= 0, top_p in (0, 1] and a 64-bit seed.  For decode index n (the number of tokens the sentence has
+ * produced before this one; n = 0 is the token of the prompt pass) the token is chosen from the step's logits as follows.
+ *   1. z[c] = (logits[c] * pen[c]) * inv_T in fp32, inv_T = 1.0f / temperature computed once on the host in fp32.  The
+ *      penalty multiply is the reference's (its quirk on negative logits included).  Two multiplies, no add: nothing
+ *      contracts to an FMA and z is bit-reproducible in numpy float32.
+ *   2. top-k: t_k = the k-th largest value of z counted with multiplicity, K = {c : z[c] >= t_k} (ties at the threshold
+ *      are all kept).  top_k == 0 or top_k >= codes: K = every code.
+ *   3. e[c] = exp(z[c] - max z) for c in K, S = sum of e over K.
+ *   4. top-p: t_p = the largest value v taken by z on K for which sum{e[c] : c in K, z[c] >= v} >= top_p * S;
+ *      P = {c in K : z[c] >= t_p}: the smallest set of most probable codes that reaches the mass, closed under ties; it
+ *      always holds the argmax.  top_p >= 1: P = K.
+ *   5. u = (w0 >> 8) * 2^-24 in [0, 1), w0 = the first output word of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ *      and counter (n, 0, 0, 0) (mi_gpt_sample_logits: (n & 0xffffffff, n >> 32, 0, 0)).  The token is the first c of P in
+ *      ascending index order with sum{e[c'] : c' in P, c' <= c} > u * S_P, S_P = sum of e over P; the last index of P should
+ *      rounding leave none.  (The CDF runs in index order, not probability order: the same distribution, and no sort.)
+ *   6. top_k == 1 is greedy exactly: argmax of logits * pen, lowest index on ties, no draw: the tokens of mi_gpt_generate.
+ * The device evaluates e as 2^-40 fixed point and sums integers, so the choice does not depend on the order of any sum: with the
+ * counter the sentence's own decode index and the key its own seed, the tokens do not depend on the slot, the batch size,
+ * the host's 16-step chunking, or eager launch versus graph replay.  Everything after the choice (token store, stop test,
+ * penalty update and reset, limit, last_hidden_state row) is the greedy entries', unchanged.  Handles with more than 16384
+ * mel codes cannot sample (MI_EINVAL).
+ *
+ * mi_gpt_generate_sampled = mi_gpt_generate + the sentence's parameters; mi_gpt_generate_batch_sampled =
+ * mi_gpt_generate_batch + host arrays of nb parameters (an item with top_k == 1 decodes greedily).  MI_EINVAL, with the
+ * handle still usable, for temperature <= 0 or not finite, top_k < 0, top_p outside (0, 1] or not finite.               */
+int         mi_gpt_generate_sampled(mi_gpt* h, const float* prompt, int P, int max_new, const int32_t* stop_ids, int n_stop,
+                                    float repeat_value, int penalty_range, float* repeat_penality, int32_t* tokens,
+                                    float* hidden, int32_t* n_out, int mem, float temperature, int top_k, float top_p,
+                                    uint64_t seed);
+int         mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows,
+                                          const int32_t* max_new, const int32_t* stop_ids, int n_stop, float repeat_value,
+                                          int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden, int cap,
+                                          int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
+                                          const float* top_p, const uint64_t* seeds);
+/* unit-level entry (tests, no handle): the same device code on rows of logits.  logits (rows, codes), pen (rows, codes) or
+ * NULL (= ones), 1 <= codes <= 16384; temperature / top_k / top_p / seeds / positions (= n) are HOST arrays of `rows`
+ * entries; tokens (rows), u_out (rows) = the u of step 5, prob_out (rows, codes) or NULL = e[c] / S_P on P and 0 elsewhere
+ * (top_k == 1: 1 at the token) follow `mem` like logits and pen.                                                        */
+int         mi_gpt_sample_logits(const float* logits, const float* pen, int rows, int codes, const float* temperature,
+                                 const int32_t* top_k, const float* top_p, const uint64_t* seeds, const int64_t* positions,
+                                 int32_t* tokens, float* u_out, float* prob_out, int mem);
+
+/* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
+ * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these
+ * host arrays of nb parameters.  The slots are marked done for the measurement: no token is stored and no state moves.    */
+int         mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* temperature, const int32_t* top_k, const float* top_p,
+                              double* us);
+
 /* tuning hook: time `iters` launches of the implicit-GEMM conv kernel on random device data (no host copies);
  * returns average milliseconds per launch in *ms.  x (B,T,Cin), w (N, taps*Cin), out (B,T,N), "same" padding. */
 int         mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int iters,

@@ -3,6 +3,7 @@
 #include "bigvgan.h"
 #include "f5.h"
 #include "gpt.h"
+#include "gpt_pick.h"
 #include "cond.h"
 #include <algorithm>
 #include <mutex>
@@ -772,125 +773,252 @@ int mi_gpt_kv_write(mi_gpt* h, int layer, const float* keys, const float* values
     });
 }
 
+// the calls that follow on the handle choose tokens by `recs` (null: greedy); greedy again when the scope ends
+struct GptModeScope {
+    Gpt& e;
+    GptModeScope(Gpt& g, const GptSampleRec* recs, int nb) : e(g) {
+        if (recs) {
+            MI_REQUIRE(e.cfg.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
+            e.set_sampling(recs, nb);
+        }
+        e.sampled = recs ? 1 : 0;
+    }
+    ~GptModeScope() { e.sampled = 0; }
+};
+
+// one sentence's parameters, validated -> the device record
+static GptSampleRec gpt_sample_rec(float temperature, int top_k, float top_p, uint64_t seed) {
+    MI_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "gpt sampling: temperature must be finite and > 0");
+    MI_REQUIRE(top_k >= 0, "gpt sampling: top_k must be >= 0 (0 = every code)");
+    MI_REQUIRE(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "gpt sampling: top_p must be in (0, 1]");
+    GptSampleRec r{};
+    r.inv_T = 1.0f / temperature; r.top_p = top_p; r.top_k = top_k;
+    r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
+    return r;
+}
+
+static void gpt_generate_impl(mi_gpt* h, const float* prompt, int P, int max_new, const int32_t* stop_ids, int n_stop,
+                              float repeat_value, int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden,
+                              int32_t* n_out, int mem, const GptSampleRec* rec, const std::string& who) {
+    MI_REQUIRE(h && h->impl, who + ": null handle");
+    std::lock_guard<std::mutex> lk_(h->mu);
+    MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+    MI_HIP(hipSetDevice(h->impl->device));
+    Gpt& e = *h->impl;
+    const GptCfg& c = e.cfg;
+    GptModeScope mode(e, rec, 1);
+    MI_REQUIRE(prompt && P >= 1 && n_out, who + ": null argument");
+    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+    *n_out = 0;
+    if (max_new <= 0) return;                                        // `while num_decode < generate_limit` never runs
+    MI_REQUIRE(P + max_new - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
+    MI_REQUIRE(max_new <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+    hipStream_t s = e.stream;
+    const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    MI_HIP(hipMemcpyAsync(e.X.p, prompt, (size_t)P * c.hidden * 4, in, s));
+    if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)c.mel_codes * 4, in, s));
+    else {
+        std::vector<float> ones(c.mel_codes, 1.f);
+        MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));
+    }
+    e.set_rep_value(repeat_value);
+    std::vector<int32_t> w(GS_WORDS, 0);
+    w[GS_GEN_LEN] = 0; w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1;
+    if (mem == MI_HOST) for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stop_ids[i];
+    else MI_HIP(hipMemcpy(&w[GS_STOP0], stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+    e.set_state(w);
+    e.forward_rows(P, 1);                                            // prompt pass: first token
+    int left = max_new - 1;
+    // the stop test needs the host: look at the state every `chunk` tokens (steps after a stop are no-ops)
+    const int chunk = 16;
+    for (;;) {
+        w = e.get_state();
+        if (w[GS_DONE] || left <= 0) break;
+        const int n = left < chunk ? left : chunk;
+        e.decode_steps(n);
+        left -= n;
+    }
+    const int n = w[GS_NDEC];
+    *n_out = n;
+    copy_out(tokens, e.toks.p, (size_t)n * 4, mem, s);
+    copy_out(hidden, e.hid.p, (size_t)n * c.hidden * 4, mem, s);
+    copy_out(repeat_penality, e.pen.p, (size_t)c.mel_codes * 4, mem, s);
+    MI_HIP(hipStreamSynchronize(s));
+}
+
 int mi_gpt_generate(mi_gpt* h, const float* prompt, int P, int max_new, const int32_t* stop_ids, int n_stop,
                     float repeat_value, int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden,
                     int32_t* n_out, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_generate");
-        Gpt& e = *h->impl;
-        const GptCfg& c = e.cfg;
-        MI_REQUIRE(prompt && P >= 1 && n_out, "mi_gpt_generate: null argument");
-        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), "mi_gpt_generate: at most 6 stop ids");
-        *n_out = 0;
-        if (max_new <= 0) return;                                        // `while num_decode < generate_limit` never runs
-        MI_REQUIRE(P + max_new - 1 <= c.max_seq, "mi_gpt_generate: prompt + max_new exceeds the KV cache (max_seq)");
-        MI_REQUIRE(max_new <= c.max_mel_pos, "mi_gpt_generate: max_new exceeds the mel position table");
-        hipStream_t s = e.stream;
-        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        MI_HIP(hipMemcpyAsync(e.X.p, prompt, (size_t)P * c.hidden * 4, in, s));
-        if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)c.mel_codes * 4, in, s));
-        else {
-            std::vector<float> ones(c.mel_codes, 1.f);
-            MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
-            MI_HIP(hipStreamSynchronize(s));
-        }
-        e.set_rep_value(repeat_value);
-        std::vector<int32_t> w(GS_WORDS, 0);
-        w[GS_GEN_LEN] = 0; w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1;
-        if (mem == MI_HOST) for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stop_ids[i];
-        else MI_HIP(hipMemcpy(&w[GS_STOP0], stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
-        e.set_state(w);
-        e.forward_rows(P, 1);                                            // prompt pass: first token
-        int left = max_new - 1;
-        // the stop test needs the host: look at the state every `chunk` tokens (steps after a stop are no-ops)
-        const int chunk = 16;
-        for (;;) {
-            w = e.get_state();
-            if (w[GS_DONE] || left <= 0) break;
-            const int n = left < chunk ? left : chunk;
-            e.decode_steps(n);
-            left -= n;
-        }
-        const int n = w[GS_NDEC];
-        *n_out = n;
-        copy_out(tokens, e.toks.p, (size_t)n * 4, mem, s);
-        copy_out(hidden, e.hid.p, (size_t)n * c.hidden * 4, mem, s);
-        copy_out(repeat_penality, e.pen.p, (size_t)c.mel_codes * 4, mem, s);
-        MI_HIP(hipStreamSynchronize(s));
+        gpt_generate_impl(h, prompt, P, max_new, stop_ids, n_stop, repeat_value, penalty_range, repeat_penality, tokens, hidden,
+                          n_out, mem, nullptr, "mi_gpt_generate");
     });
+}
+
+int mi_gpt_generate_sampled(mi_gpt* h, const float* prompt, int P, int max_new, const int32_t* stop_ids, int n_stop,
+                            float repeat_value, int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden,
+                            int32_t* n_out, int mem, float temperature, int top_k, float top_p, uint64_t seed) {
+    return guard([&] {
+        const GptSampleRec rec = gpt_sample_rec(temperature, top_k, top_p, seed);
+        gpt_generate_impl(h, prompt, P, max_new, stop_ids, n_stop, repeat_value, penalty_range, repeat_penality, tokens, hidden,
+                          n_out, mem, &rec, "mi_gpt_generate_sampled");
+    });
+}
+
+static void gpt_generate_batch_impl(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                    const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                                    float* repeat_penality, int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
+                                    const GptSampleRec* recs, const std::string& who) {
+    MI_REQUIRE(h && h->impl, who + ": null handle");
+    std::lock_guard<std::mutex> lk_(h->mu);
+    MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+    MI_HIP(hipSetDevice(h->impl->device));
+    Gpt& e = *h->impl;
+    const GptCfg& c = e.cfg;
+    MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
+    MI_REQUIRE(nb >= 1 && nb <= c.max_batch, who + ": batch exceeds the handle's max_batch");
+    GptModeScope mode(e, recs, nb);
+    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+    hipStream_t s = e.stream;
+    const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    std::vector<int32_t> stops(n_stop);
+    if (n_stop) {
+        if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
+        else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+    }
+    size_t row0 = 0;
+    for (int b = 0; b < nb; ++b) {
+        MI_REQUIRE(prompt_rows[b] >= 1 && max_new[b] >= 0 && max_new[b] <= cap, who + ": prompt_rows / max_new");
+        MI_REQUIRE(max_new[b] == 0 || prompt_rows[b] + max_new[b] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
+        MI_REQUIRE(max_new[b] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+    }
+    if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)nb * c.mel_codes * 4, in, s));
+    else {
+        std::vector<float> ones((size_t)nb * c.mel_codes, 1.f);
+        MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));
+    }
+    e.set_rep_value(repeat_value);
+    bool any = false;
+    for (int b = 0; b < nb; ++b) {                               // prompt passes, one sentence at a time
+        std::vector<int32_t> w(GS_WORDS, 0);
+        w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[b];
+        for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stops[i];
+        if (max_new[b] == 0) w[GS_DONE] = 1;
+        e.set_state(w, b);
+        if (max_new[b] > 0) {
+            MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[b] * c.hidden * 4, in, s));
+            e.forward_rows(prompt_rows[b], 1, b);
+            any = true;
+        }
+        row0 += prompt_rows[b];
+    }
+    std::vector<int32_t> all((size_t)nb * GS_WORDS);
+    auto read_states = [&] {
+        MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+        bool done = true;
+        for (int b = 0; b < nb; ++b) done &= all[(size_t)b * GS_WORDS + GS_DONE] != 0;
+        return done;
+    };
+    int guard_steps = 0;
+    while (any && !read_states()) {
+        e.decode_batch_steps(nb, 16);
+        guard_steps += 16;
+        MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
+    }
+    if (!any) read_states();
+    e.history = all[GS_HIST];
+    for (int b = 0; b < nb; ++b) {
+        const int n = all[(size_t)b * GS_WORDS + GS_NDEC];
+        n_out[b] = n;
+        copy_out(tokens ? tokens + (size_t)b * cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)n * 4, mem, s);
+        copy_out(hidden ? hidden + (size_t)b * cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
+                 (size_t)n * c.hidden * 4, mem, s);
+    }
+    copy_out(repeat_penality, e.pen.p, (size_t)nb * c.mel_codes * 4, mem, s);
+    MI_HIP(hipStreamSynchronize(s));
 }
 
 int mi_gpt_generate_batch(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                           const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
                           float* repeat_penality, int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_generate_batch");
+        gpt_generate_batch_impl(h, nb, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                                repeat_penality, tokens, hidden, cap, n_out, mem, nullptr, "mi_gpt_generate_batch");
+    });
+}
+
+int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                  const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                                  float* repeat_penality, int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
+                                  const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds) {
+    return guard([&] {
+        MI_REQUIRE(nb >= 1 && nb <= 4096 && temperature && top_k && top_p && seeds, "mi_gpt_generate_batch_sampled: null argument");
+        std::vector<GptSampleRec> recs(nb);
+        for (int b = 0; b < nb; ++b) recs[b] = gpt_sample_rec(temperature[b], top_k[b], top_p[b], seeds[b]);
+        gpt_generate_batch_impl(h, nb, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                                repeat_penality, tokens, hidden, cap, n_out, mem, recs.data(),
+                                "mi_gpt_generate_batch_sampled");
+    });
+}
+
+int mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* temperature, const int32_t* top_k, const float* top_p,
+                      double* us) {
+    return guard([&] {
+        GPT_CHECK(h, MI_HOST, "mi_gpt_bench_pick");
         Gpt& e = *h->impl;
-        const GptCfg& c = e.cfg;
-        MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, "mi_gpt_generate_batch: null argument");
-        MI_REQUIRE(nb >= 1 && nb <= c.max_batch, "mi_gpt_generate_batch: batch exceeds the handle's max_batch");
-        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), "mi_gpt_generate_batch: at most 6 stop ids");
-        hipStream_t s = e.stream;
-        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        std::vector<int32_t> stops(n_stop);
-        if (n_stop) {
-            if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
-            else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+        MI_REQUIRE(us && nb >= 1 && nb <= e.cfg.max_batch && iters >= 1, "mi_gpt_bench_pick: bad arguments");
+        std::vector<GptSampleRec> recs;
+        if (temperature) {
+            MI_REQUIRE(top_k && top_p, "mi_gpt_bench_pick: null argument");
+            for (int b = 0; b < nb; ++b) recs.push_back(gpt_sample_rec(temperature[b], top_k[b], top_p[b], 1 + b));
         }
-        size_t row0 = 0;
-        for (int b = 0; b < nb; ++b) {
-            MI_REQUIRE(prompt_rows[b] >= 1 && max_new[b] >= 0 && max_new[b] <= cap, "mi_gpt_generate_batch: prompt_rows / max_new");
-            MI_REQUIRE(max_new[b] == 0 || prompt_rows[b] + max_new[b] - 1 <= c.max_seq, "mi_gpt_generate_batch: prompt + max_new exceeds the KV cache (max_seq)");
-            MI_REQUIRE(max_new[b] <= c.max_mel_pos, "mi_gpt_generate_batch: max_new exceeds the mel position table");
+        GptModeScope mode(e, temperature ? recs.data() : nullptr, nb);
+        *us = e.bench_pick(nb, iters);
+    });
+}
+
+int mi_gpt_sample_logits(const float* logits, const float* pen, int rows, int codes, const float* temperature,
+                         const int32_t* top_k, const float* top_p, const uint64_t* seeds, const int64_t* positions,
+                         int32_t* tokens, float* u_out, float* prob_out, int mem) {
+    return guard([&] {
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_gpt_sample_logits: bad mem kind");
+        MI_REQUIRE(logits && temperature && top_k && top_p && seeds && positions && tokens && u_out, "mi_gpt_sample_logits: null argument");
+        MI_REQUIRE(rows >= 1 && rows <= (1 << 20), "mi_gpt_sample_logits: rows");
+        MI_REQUIRE(codes >= 1 && codes <= GPT_SAMPLE_MAX_CODES, "mi_gpt_sample_logits: sampling supports 1..16384 codes");
+        std::vector<GptSampleRec> recs(rows);
+        for (int r = 0; r < rows; ++r) {
+            recs[r] = gpt_sample_rec(temperature[r], top_k[r], top_p[r], seeds[r]);
+            MI_REQUIRE(positions[r] >= 0, "mi_gpt_sample_logits: positions must be >= 0");
         }
-        if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)nb * c.mel_codes * 4, in, s));
-        else {
-            std::vector<float> ones((size_t)nb * c.mel_codes, 1.f);
-            MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
-            MI_HIP(hipStreamSynchronize(s));
+        hipStream_t s;
+        MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        struct Fin { hipStream_t s; ~Fin() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } fin{s};
+        DevBuf drec, dpos, dl, dp, dt, du, dpr;
+        const size_t n = (size_t)rows * codes;
+        drec.ensure(recs.size() * sizeof(GptSampleRec)); dpos.ensure((size_t)rows * 8);
+        MI_HIP(hipMemcpyAsync(drec.p, recs.data(), recs.size() * sizeof(GptSampleRec), hipMemcpyHostToDevice, s));
+        MI_HIP(hipMemcpyAsync(dpos.p, positions, (size_t)rows * 8, hipMemcpyHostToDevice, s));
+        const float* l = (const float*)stage_in(dl, logits, n * 4, mem, s);
+        const float* p = pen ? (const float*)stage_in(dp, pen, n * 4, mem, s) : nullptr;
+        int32_t* t = tokens; float* u = u_out; float* pr = prob_out;
+        if (mem == MI_HOST) {
+            dt.ensure((size_t)rows * 4); du.ensure((size_t)rows * 4);
+            t = dt.as<int32_t>(); u = du.as<float>();
+            if (prob_out) { dpr.ensure(n * 4); pr = dpr.as<float>(); }
         }
-        e.set_rep_value(repeat_value);
-        bool any = false;
-        for (int b = 0; b < nb; ++b) {                               // prompt passes, one sentence at a time
-            std::vector<int32_t> w(GS_WORDS, 0);
-            w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[b];
-            for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stops[i];
-            if (max_new[b] == 0) w[GS_DONE] = 1;
-            e.set_state(w, b);
-            if (max_new[b] > 0) {
-                MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[b] * c.hidden * 4, in, s));
-                e.forward_rows(prompt_rows[b], 1, b);
-                any = true;
-            }
-            row0 += prompt_rows[b];
+        launch_gpt_sample_rows(l, p, rows, codes, drec.as<GptSampleRec>(), dpos.as<int64_t>(), t, u, pr, s);
+        if (mem == MI_HOST) {
+            copy_out(tokens, t, (size_t)rows * 4, mem, s);
+            copy_out(u_out, u, (size_t)rows * 4, mem, s);
+            if (prob_out) copy_out(prob_out, pr, n * 4, mem, s);
         }
-        std::vector<int32_t> all((size_t)nb * GS_WORDS);
-        auto read_states = [&] {
-            MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
-            MI_HIP(hipStreamSynchronize(s));
-            bool done = true;
-            for (int b = 0; b < nb; ++b) done &= all[(size_t)b * GS_WORDS + GS_DONE] != 0;
-            return done;
-        };
-        int guard_steps = 0;
-        while (any && !read_states()) {
-            e.decode_batch_steps(nb, 16);
-            guard_steps += 16;
-            MI_REQUIRE(guard_steps <= c.max_seq + 32, "mi_gpt_generate_batch: decode loop did not terminate");
-        }
-        if (!any) read_states();
-        e.history = all[GS_HIST];
-        for (int b = 0; b < nb; ++b) {
-            const int n = all[(size_t)b * GS_WORDS + GS_NDEC];
-            n_out[b] = n;
-            copy_out(tokens ? tokens + (size_t)b * cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)n * 4, mem, s);
-            copy_out(hidden ? hidden + (size_t)b * cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
-                     (size_t)n * c.hidden * 4, mem, s);
-        }
-        copy_out(repeat_penality, e.pen.p, (size_t)nb * c.mel_codes * 4, mem, s);
         MI_HIP(hipStreamSynchronize(s));
     });
 }
+
 
 int mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int iters, double* ms) {
     return guard([&] {

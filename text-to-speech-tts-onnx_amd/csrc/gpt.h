@@ -36,13 +36,18 @@ struct Gpt {
     DevBuf logits, last, pen, toks, hid, state;       // per slot: [slot][codes] / [slot][h] / [slot][max_seq](x h) / words
     DevBuf Xd, xnd, qkvd, attd, ffd, zd;              // batched decode step: one row per slot
     int MBp = 1;              // max_batch rounded up to a batched-GEMV template width
-    std::map<int, hipGraphExec_t> batch_graphs;       // decode step over nb slots, keyed by nb
+    std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;   // decode step over nb slots, keyed by (nb, sampled)
     DevBuf io_a, io_b;        // host<->device staging
     DevBuf rep_dev;           // REPEAT_PENALITY as a device scalar (read by gpt_pick_kernel, also inside replayed graphs)
     void set_rep_value(float v);
     int history = 0;          // host mirror of state[GS_HIST] (valid outside generate())
 
-    hipGraphExec_t step_graph = nullptr;
+    // token choice of the calls that follow: 0 = greedy (gpt_pick_kernel), 1 = sampled (gpt_sample_kernel reading `samp`).
+    // The C-ABI entry sets it; every launch site and every captured graph is per mode.
+    int sampled = 0;
+    DevBuf samp;              // per slot: GptSampleRec (gpt_pick.h), beside the GS_* state and not part of it
+    void set_sampling(const void* recs, int nb);      // host GptSampleRec[nb] -> samp (synchronous)
+    hipGraphExec_t step_graph[2] = {nullptr, nullptr};      // by mode
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under
     void check_graph_epoch();
@@ -59,6 +64,9 @@ struct Gpt {
     std::vector<int32_t> get_state(int slot = 0);
     void decode_batch_eager(int nb);                                                 // one token for slots 0..nb-1
     void decode_batch_steps(int nb, int n);
+    // tuning: microseconds per launch of the token-choosing kernel of the current mode over nb slots, on the logits the last step
+    // left (every slot is marked done for the measurement, so nothing but the choice runs and no state moves)
+    double bench_pick(int nb, int iters);
     void gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int act, const float* res, void* kcl, void* vcl);
     size_t slot_cache_elems() const { return (size_t)cfg.layers * cfg.hidden * cfg.max_seq; }
     void decode_step_eager();                                                        // C (from state) + E + bookkeeping

@@ -14,6 +14,7 @@
 // every weight byte is read once per token), so the GEMV kernel is a plain coalesced 16-byte-per-lane dot product,
 // not an MFMA tile; the prompt pass (ids_len rows at once) goes through the MFMA implicit-GEMM kernel instead.
 #include "gpt.h"
+#include "gpt_pick.h"
 #include "mfma.h"
 #include "wave_reduce.h"
 
@@ -741,32 +742,16 @@ __global__ __launch_bounds__(1024) void gpt_pick_kernel(const float* __restrict_
                                                         int max_pos, float* xa, float* xb) {
     __shared__ float bv[16];
     __shared__ int bi[16];
-    __shared__ int slot;
     {   // one block per sentence slot
         const size_t sl = blockIdx.x;
         logits += sl * codes; pen += sl * codes; last += sl * hidden; st += sl * GS_WORDS; toks += sl * max_tok;
         hid += sl * (size_t)max_tok * hidden;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ int next_id, next_gen;
     // everything that does not depend on the argmax is requested first (the kernel is a chain of dependent round trips: 8.4 us
     // for 33 KB of logits): the state words, the penalty scalar, the oldest penalised token, the last_hidden_state row
-    int w[GS_WORDS];
-    float repv = 0.f;
-    int tok_r = 0;
-    if (tid == 0) {
-#pragma unroll
-        for (int q = 0; q < GS_WORDS; q += 4) {
-            const int4 v = *reinterpret_cast<const int4*>(st + q);
-            w[q] = v.x; w[q + 1] = v.y; w[q + 2] = v.z; w[q + 3] = v.w;
-        }
-        repv = rep_dev[0];
-        const int r = w[GS_RESET];
-        tok_r = (r >= 0 && r < max_tok) ? toks[r] : 0;
-    }
-    float lastv[2];                                        // hidden <= 2048
-#pragma unroll
-    for (int q = 0; q < 2; ++q) lastv[q] = tid + q * 1024 < hidden ? last[tid + q * 1024] : 0.f;
+    GptPickLoads L;
+    gpt_pick_load(L, st, rep_dev, toks, last, max_tok, hidden);
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int c = tid; c < codes; c += 1024) {
@@ -785,46 +770,8 @@ __global__ __launch_bounds__(1024) void gpt_pick_kernel(const float* __restrict_
         for (int q = 1; q < 16; ++q)
             if (bv[q] > best || (bv[q] == best && bi[q] < idx)) { best = bv[q]; idx = bi[q]; }
         if (idx == 0x7fffffff) idx = 0;
-        slot = -1;
-        if (!w[GS_DONE]) {
-            const int t = idx, n = w[GS_NDEC];
-            w[GS_TOKEN] = t;
-            if (n < max_tok) { toks[n] = t; slot = n; }
-            w[GS_NDEC] = n + 1;
-            bool stop = false;
-#pragma unroll
-            for (int q = 0; q < GS_WORDS - GS_STOP0; ++q) stop |= (q < w[GS_NSTOP] && w[GS_STOP0 + q] == t);
-            if (stop) w[GS_DONE] = 1;
-            else if (w[GS_UPDATE_PEN]) {                      // Inference_IndexTTS_ONNX.py:768-772
-                pen[t] = repv;            // device scalar: the captured decode graphs must see a changed REPEAT_PENALITY
-                const int r = w[GS_RESET];
-                // toks[r] was fetched before toks[n] = t above: the same element only if r == n
-                const int tr = (r == n && n < max_tok) ? t : tok_r;
-                if (n + 1 > w[GS_RANGE] && r < max_tok && tr != t) { pen[tr] = 1.f; w[GS_RESET] = r + 1; }
-            }
-            w[GS_HIST] += rows;
-            w[GS_GEN_LEN] += 1;
-            if (w[GS_LIMIT] > 0 && n + 1 >= w[GS_LIMIT]) w[GS_DONE] = 1;      // `while num_decode < generate_limit`
-#pragma unroll
-            for (int q = 0; q < GS_STOP0; q += 4) *reinterpret_cast<int4*>(st + q) = make_int4(w[q], w[q + 1], w[q + 2], w[q + 3]);
-            if (GS_STOP0 % 4) { for (int q = GS_STOP0 / 4 * 4; q < GS_STOP0; ++q) st[q] = w[q]; }
-        }
-        next_id = w[GS_TOKEN]; next_gen = w[GS_GEN_LEN];
     }
-    __syncthreads();
-    if (slot >= 0) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (tid + q * 1024 < hidden) hid[(size_t)slot * hidden + tid + q * 1024] = lastv[q];
-    }
-    // graph C for the next decode step (IndexTTS_C.forward, Export_IndexTTS.py:222-225) from the state just written:
-    // the step's input row, so that a decode step does not start with a launch of its own for it
-    const int id = min(max(next_id, 0), codes - 1), g = min(max(next_gen, 0), max_pos - 1);
-    for (int c = tid; c < hidden; c += 1024) {
-        const float v = emb[(size_t)id * hidden + c] + pos[(size_t)g * hidden + c];
-        if (xa) xa[c] = v;
-        if (xb) xb[(size_t)blockIdx.x * hidden + c] = v;
-    }
+    gpt_pick_finish(idx, L, pen, st, toks, hid, codes, hidden, rows, max_tok, emb, pos, max_pos, xa, xb);
 }
 
 // cache <-> the reference's tensor layouts: keys (H, D, hist), values (H, hist, D), fp32
@@ -900,6 +847,8 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     std::vector<float> ones(P * c.mel_codes, 1.f);
     MI_HIP(hipMemcpyAsync(pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
     rep_dev.ensure(4);
+    samp.ensure(P * sizeof(GptSampleRec));
+    MI_HIP(hipMemsetAsync(samp.p, 0, samp.bytes, s));
     MI_HIP(hipStreamSynchronize(s));
     set_rep_value(0.7f);
     use_graph = !env_first_is("MI355TTS_NO_GRAPH", '1');
@@ -911,7 +860,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
 }
 
 Gpt::~Gpt() {
-    if (step_graph) (void)hipGraphExecDestroy(step_graph);
+    for (auto& g : step_graph) if (g) (void)hipGraphExecDestroy(g);
     for (auto& kv : batch_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
 }
@@ -1066,12 +1015,26 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     // ln_f (-> last_hidden_state) and final_norm in front of the lm_head, one launch
     gemv(head, xl, fn_w.as<float>(), fn_b.as<float>(), logits_s, MI_F32, ACT_NONE, nullptr, nullptr, nullptr, 0,
          lnf_w.as<float>(), lnf_b.as<float>(), last_s);
-    hipLaunchKernelGGL(gpt_pick_kernel, dim3(1), dim3(1024), 0, s, logits_s, pen.as<float>() + (size_t)slot * c.mel_codes,
-                       last_s, state.as<int>() + (size_t)slot * GS_WORDS, toks.as<int>() + (size_t)slot * S,
-                       hid.as<float>() + (size_t)slot * S * h, c.mel_codes, h, rows, rep_dev.as<float>(), S,
-                       mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, slot == 0 ? X.as<float>() : nullptr,
-                       Xd.as<float>() + (size_t)slot * h);
+    float* pen_s = pen.as<float>() + (size_t)slot * c.mel_codes;
+    int* st_s = state.as<int>() + (size_t)slot * GS_WORDS;
+    int* toks_s = toks.as<int>() + (size_t)slot * S;
+    float* hid_s = hid.as<float>() + (size_t)slot * S * h;
+    float* xa = slot == 0 ? X.as<float>() : nullptr;
+    float* xb = Xd.as<float>() + (size_t)slot * h;
+    if (sampled)
+        launch_gpt_sample(1, logits_s, pen_s, last_s, st_s, toks_s, hid_s, c.mel_codes, h, rows, rep_dev.as<float>(), S,
+                          mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, xa, xb, samp.as<GptSampleRec>() + slot, s);
+    else
+        hipLaunchKernelGGL(gpt_pick_kernel, dim3(1), dim3(1024), 0, s, logits_s, pen_s, last_s, st_s, toks_s, hid_s,
+                           c.mel_codes, h, rows, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
+                           c.max_mel_pos, xa, xb);
     MI_HIP(hipGetLastError());
+}
+
+void Gpt::set_sampling(const void* recs, int nb) {
+    MI_REQUIRE(recs && nb >= 1 && nb <= cfg.max_batch, "gpt: sampling records");
+    MI_HIP(hipMemcpyAsync(samp.p, recs, (size_t)nb * sizeof(GptSampleRec), hipMemcpyHostToDevice, stream));
+    MI_HIP(hipStreamSynchronize(stream));      // `recs` may be a temporary
 }
 
 void Gpt::set_rep_value(float v) {
@@ -1085,7 +1048,7 @@ void Gpt::decode_step_eager() { forward_rows(1, 0); }
 
 void Gpt::check_graph_epoch() {
     if (graph_epoch == option_epoch()) return;
-    if (step_graph) { (void)hipGraphExecDestroy(step_graph); step_graph = nullptr; }
+    for (auto& g : step_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto& kv : batch_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     batch_graphs.clear();
     graph_epoch = option_epoch();
@@ -1095,7 +1058,8 @@ void Gpt::decode_steps(int n) {
     if (n <= 0) return;
     if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) decode_step_eager(); return; }
     check_graph_epoch();
-    if (!step_graph) {
+    hipGraphExec_t& exec = step_graph[sampled ? 1 : 0];
+    if (!exec) {
         decode_step_eager();                   // first step eager (one-time lazy initialisation stays out of the capture)
         --n;
         hipGraph_t graph = nullptr;
@@ -1108,11 +1072,11 @@ void Gpt::decode_steps(int n) {
             throw;
         }
         MI_HIP(hipStreamEndCapture(stream, &graph));
-        hipError_t err = hipGraphInstantiate(&step_graph, graph, nullptr, nullptr, 0);
+        hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
-        if (err != hipSuccess) { step_graph = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_step_eager(); return; }
+        if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_step_eager(); return; }
     }
-    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(step_graph, stream));
+    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
 }
 
 // batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N)
@@ -1186,9 +1150,14 @@ void Gpt::decode_batch_eager(int nb) {
     launch_rownorm(NORM_LN_AFFINE, x, last.p, MI_F32, lnf_w.as<float>(), lnf_b.as<float>(), nb, h, 1e-5f, s);
     launch_rownorm(NORM_LN_AFFINE, last.as<float>(), zd.p, dtype, fn_w.as<float>(), fn_b.as<float>(), nb, h, 1e-5f, s);
     gemv_b(head, zd.p, nb, logits.p, MI_F32, ACT_NONE, nullptr, nullptr, nullptr);
-    hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, s, logits.as<float>(), pen.as<float>(), last.as<float>(),
-                       state.as<int>(), toks.as<int>(), hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S,
-                       mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, (float*)nullptr, Xd.as<float>());
+    if (sampled)
+        launch_gpt_sample(nb, logits.as<float>(), pen.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(),
+                          hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
+                          c.max_mel_pos, (float*)nullptr, Xd.as<float>(), samp.as<GptSampleRec>(), s);
+    else
+        hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, s, logits.as<float>(), pen.as<float>(), last.as<float>(),
+                           state.as<int>(), toks.as<int>(), hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S,
+                           mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, (float*)nullptr, Xd.as<float>());
     MI_HIP(hipGetLastError());
 }
 
@@ -1196,7 +1165,7 @@ void Gpt::decode_batch_steps(int nb, int n) {
     if (n <= 0) return;
     if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) decode_batch_eager(nb); return; }
     check_graph_epoch();
-    hipGraphExec_t& exec = batch_graphs[nb];
+    hipGraphExec_t& exec = batch_graphs[{nb, sampled ? 1 : 0}];
     if (!exec) {
         decode_batch_eager(nb);
         --n;
@@ -1215,6 +1184,43 @@ void Gpt::decode_batch_steps(int nb, int n) {
         if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_batch_eager(nb); return; }
     }
     for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
+}
+
+double Gpt::bench_pick(int nb, int iters) {
+    const GptCfg& c = cfg;
+    MI_REQUIRE(nb >= 1 && nb <= c.max_batch && iters >= 1, "gpt: bench_pick arguments");
+    const int h = c.hidden, S = c.max_seq;
+    std::vector<int32_t> saved((size_t)nb * GS_WORDS), done;
+    MI_HIP(hipMemcpyAsync(saved.data(), state.p, saved.size() * 4, hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipStreamSynchronize(stream));
+    done = saved;
+    for (int b = 0; b < nb; ++b) done[(size_t)b * GS_WORDS + GS_DONE] = 1;
+    MI_HIP(hipMemcpyAsync(state.p, done.data(), done.size() * 4, hipMemcpyHostToDevice, stream));
+    auto launch = [&] {
+        if (sampled)
+            launch_gpt_sample(nb, logits.as<float>(), pen.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(),
+                              hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
+                              c.max_mel_pos, (float*)nullptr, Xd.as<float>(), samp.as<GptSampleRec>(), stream);
+        else
+            hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, stream, logits.as<float>(), pen.as<float>(),
+                               last.as<float>(), state.as<int>(), toks.as<int>(), hid.as<float>(), c.mel_codes, h, 1,
+                               rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, (float*)nullptr,
+                               Xd.as<float>());
+    };
+    for (int i = 0; i < 3; ++i) launch();
+    hipEvent_t e0, e1;
+    MI_HIP(hipEventCreate(&e0)); MI_HIP(hipEventCreate(&e1));
+    MI_HIP(hipEventRecord(e0, stream));
+    for (int i = 0; i < iters; ++i) launch();
+    MI_HIP(hipEventRecord(e1, stream));
+    hipError_t err = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    MI_HIP(hipMemcpyAsync(state.p, saved.data(), saved.size() * 4, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipStreamSynchronize(stream));
+    MI_HIP(err);
+    return (double)ms * 1e3 / iters;
 }
 
 void Gpt::text_embed(const int32_t* ids_dev, int n, float* out_dev) {

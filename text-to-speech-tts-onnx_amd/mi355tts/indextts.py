@@ -14,6 +14,8 @@ There is no CPU fallback: without libmi355tts.so and an MI355X every call raises
 from __future__ import annotations
 
 import ctypes as C
+import math
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -21,6 +23,76 @@ import numpy as np
 from . import _lib
 from .config import IndexGPTConfig
 from .weights import pack_gpt
+
+
+@dataclass(frozen=True)
+class Sampling:
+    """How ``IndexGPT.generate*`` chooses each mel code (include/mi355tts.h, "sampling"): temperature, top-k (0 = every
+    code, 1 = greedy), top-p and a 64-bit seed.  The defaults are upstream IndexTTS's.  The draw for a sentence's n-th token
+    depends on (seed, n) alone: one seed gives one take, whatever batch the sentence is decoded in."""
+    temperature: float = 1.0
+    top_k: int = 30
+    top_p: float = 0.8
+    seed: int = 0
+
+    def __post_init__(self):
+        t, p = float(self.temperature), float(self.top_p)
+        if not (math.isfinite(t) and t > 0.0):
+            raise ValueError(f"temperature must be finite and > 0, got {self.temperature}")
+        if int(self.top_k) != self.top_k or self.top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0 (0 = every code), got {self.top_k}")
+        if not (math.isfinite(p) and 0.0 < p <= 1.0):
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p}")
+        if int(self.seed) != self.seed or not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {self.seed}")
+
+
+_GREEDY = Sampling(1.0, 1, 1.0, 0)
+
+
+def _sampling_arrays(items):
+    """list of Sampling (None = greedy) -> the four host arrays of the batched C-ABI entries"""
+    it = [_GREEDY if x is None else x for x in items]
+    return (np.ascontiguousarray([x.temperature for x in it], dtype=np.float32),
+            np.ascontiguousarray([x.top_k for x in it], dtype=np.int32),
+            np.ascontiguousarray([x.top_p for x in it], dtype=np.float32),
+            np.ascontiguousarray([x.seed for x in it], dtype=np.uint64))
+
+
+def _batch_sampling(sampling, nb):
+    """generate_batch*'s ``sampling`` argument -> None (all greedy) or a list of nb Sampling / None"""
+    if sampling is None:
+        return None
+    items = [sampling] * nb if isinstance(sampling, Sampling) else list(sampling)
+    if len(items) != nb or not all(x is None or isinstance(x, Sampling) for x in items):
+        raise ValueError(f"sampling must be one Sampling or a list of {nb} Sampling / None")
+    return None if all(x is None for x in items) else items
+
+
+def sample_logits(logits, *, temperature, top_k, top_p, seeds, positions, pen=None, return_probs: bool = False):
+    """The decode step's sampler on rows of logits (unit entry mi_gpt_sample_logits).  logits (rows, codes); the parameters
+    are scalars or sequences of ``rows`` entries; positions = each row's decode index n.  Returns (tokens int32 (rows,),
+    u float32 (rows,)[, probabilities float32 (rows, codes): e / S_P on the kept set, 0 elsewhere])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim != 2:
+        raise ValueError("logits must be (rows, codes)")
+    rows, codes = lg.shape
+    pn = None
+    if pen is not None:
+        pn = np.ascontiguousarray(np.broadcast_to(np.asarray(pen, np.float32), lg.shape))
+    T = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (rows,)))
+    K = np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.int32), (rows,)))
+    Pp = np.ascontiguousarray(np.broadcast_to(np.asarray(top_p, np.float32), (rows,)))
+    Sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64), (rows,)))
+    Ps = np.ascontiguousarray(np.broadcast_to(np.asarray(positions, np.int64), (rows,)))
+    toks = np.zeros((rows,), np.int32)
+    u = np.zeros((rows,), np.float32)
+    probs = np.zeros((rows, codes), np.float32) if return_probs else None
+    _lib.check(_lib.load().mi_gpt_sample_logits(
+        lg.ctypes.data, None if pn is None else pn.ctypes.data, rows, codes, T.ctypes.data, K.ctypes.data, Pp.ctypes.data,
+        Sd.ctypes.data, Ps.ctypes.data, toks.ctypes.data, u.ctypes.data, None if probs is None else probs.ctypes.data,
+        _lib.MI_HOST), "mi_gpt_sample_logits")
+    return (toks, u, probs) if return_probs else (toks, u)
 
 
 class IndexGPT:
@@ -148,8 +220,9 @@ class IndexGPT:
 
     # ---- the per-sentence loop ------------------------------------------------------------------------------------
     def generate_from_prompt(self, prompt, max_new: int, *, stop_tokens=None, repeat_value=None, penalty_range=None,
-                             repeat_penality=None):
-        """prompt (1, P, hidden) = graph D's output.  Returns (tokens (n,), hidden (n, hidden), repeat_penality)."""
+                             repeat_penality=None, sampling: Optional[Sampling] = None):
+        """prompt (1, P, hidden) = graph D's output.  Returns (tokens (n,), hidden (n, hidden), repeat_penality).
+        sampling: a ``Sampling`` draws each token on the device; None decodes greedily like the reference."""
         c = self.cfg
         p = np.ascontiguousarray(prompt, dtype=np.float32)
         if p.ndim != 3 or p.shape[0] != 1 or p.shape[2] != c.hidden or p.shape[1] < 1:
@@ -162,17 +235,22 @@ class IndexGPT:
         hid = np.zeros((max(max_new, 1), c.hidden), np.float32)
         import ctypes as C
         n = C.c_int32(0)
-        _lib.check(_lib.load().mi_gpt_generate(
-            self._h, p.ctypes.data, p.shape[1], max_new, stops.ctypes.data if stops.size else None, stops.size,
-            float(c.repeat_penalty if repeat_value is None else repeat_value),
-            int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, toks.ctypes.data,
-            hid.ctypes.data, C.byref(n), _lib.MI_HOST), "mi_gpt_generate")
+        args = (self._h, p.ctypes.data, p.shape[1], max_new, stops.ctypes.data if stops.size else None, stops.size,
+                float(c.repeat_penalty if repeat_value is None else repeat_value),
+                int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, toks.ctypes.data,
+                hid.ctypes.data, C.byref(n), _lib.MI_HOST)
+        if sampling is None:
+            _lib.check(_lib.load().mi_gpt_generate(*args), "mi_gpt_generate")
+        else:
+            _lib.check(_lib.load().mi_gpt_generate_sampled(*args, float(sampling.temperature), int(sampling.top_k),
+                                                           float(sampling.top_p), int(sampling.seed)),
+                       "mi_gpt_generate_sampled")
         if repeat_penality is None:
             self.repeat_penality = pen
         return toks[: n.value].copy(), hid[: n.value].copy(), pen
 
     def generate_torch(self, prompt, max_new: int, tokens, hidden, *, stop_tokens=None, repeat_value=None,
-                       penalty_range=None, repeat_penality=None) -> int:
+                       penalty_range=None, repeat_penality=None, sampling: Optional[Sampling] = None) -> int:
         """Device-resident variant: prompt (P, hidden) float32 CUDA tensor; tokens (>= max_new) int32 and hidden
         (>= max_new, hidden) float32 CUDA tensors are filled; repeat_penality (mel_codes) float32 CUDA tensor or None
         (= ones, not written back).  Returns the number of tokens produced."""
@@ -186,21 +264,28 @@ class IndexGPT:
         st = torch.tensor(stops, dtype=torch.int32, device=prompt.device) if stops else None
         torch.cuda.current_stream(prompt.device).synchronize()
         n = C.c_int32(0)
-        _lib.check(_lib.load().mi_gpt_generate(
-            self._h, prompt.data_ptr(), prompt.shape[-2], int(max_new), st.data_ptr() if st is not None else None,
-            len(stops), float(c.repeat_penalty if repeat_value is None else repeat_value),
-            int(c.penalty_range if penalty_range is None else penalty_range),
-            repeat_penality.data_ptr() if repeat_penality is not None else None, tokens.data_ptr(), hidden.data_ptr(),
-            C.byref(n), _lib.MI_DEVICE), "mi_gpt_generate")
+        args = (self._h, prompt.data_ptr(), prompt.shape[-2], int(max_new), st.data_ptr() if st is not None else None,
+                len(stops), float(c.repeat_penalty if repeat_value is None else repeat_value),
+                int(c.penalty_range if penalty_range is None else penalty_range),
+                repeat_penality.data_ptr() if repeat_penality is not None else None, tokens.data_ptr(), hidden.data_ptr(),
+                C.byref(n), _lib.MI_DEVICE)
+        if sampling is None:
+            _lib.check(_lib.load().mi_gpt_generate(*args), "mi_gpt_generate")
+        else:
+            _lib.check(_lib.load().mi_gpt_generate_sampled(*args, float(sampling.temperature), int(sampling.top_k),
+                                                           float(sampling.top_p), int(sampling.seed)),
+                       "mi_gpt_generate_sampled")
         return int(n.value)
 
     def generate_batch(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None,
-                       repeat_penality=None):
+                       repeat_penality=None, sampling=None):
         """Several sentences at once (engine extension: the reference decodes one sentence at a time).  prompts = list
         of (1, P_b, hidden) graph-D outputs, max_new = list of per-sentence limits.  Every decode step streams the
-        weights once for all sentences.  Returns a list of (tokens, hidden) and the (nb, mel_codes) penalty matrix."""
+        weights once for all sentences.  Returns a list of (tokens, hidden) and the (nb, mel_codes) penalty matrix.
+        sampling: None (greedy), one ``Sampling`` for every sentence, or a list of nb ``Sampling`` / None (greedy item)."""
         c = self.cfg
         nb = len(prompts)
+        samp = _batch_sampling(sampling, nb)
         if nb < 1 or nb > c.max_batch or len(max_new) != nb:
             raise ValueError(f"batch of {nb} sentences; this engine was created with max_batch = {c.max_batch}")
         ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
@@ -214,15 +299,20 @@ class IndexGPT:
         toks = np.zeros((nb, cap), np.int32)
         hid = np.zeros((nb, cap, c.hidden), np.float32)
         n = np.zeros((nb,), np.int32)
-        _lib.check(_lib.load().mi_gpt_generate_batch(
-            self._h, nb, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None,
-            stops.size, float(c.repeat_penalty if repeat_value is None else repeat_value),
-            int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, toks.ctypes.data,
-            hid.ctypes.data, cap, _lib.i32p(n), _lib.MI_HOST), "mi_gpt_generate_batch")
+        args = (self._h, nb, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None,
+                stops.size, float(c.repeat_penalty if repeat_value is None else repeat_value),
+                int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, toks.ctypes.data,
+                hid.ctypes.data, cap, _lib.i32p(n), _lib.MI_HOST)
+        if samp is None:
+            _lib.check(_lib.load().mi_gpt_generate_batch(*args), "mi_gpt_generate_batch")
+        else:
+            sa = _sampling_arrays(samp)
+            _lib.check(_lib.load().mi_gpt_generate_batch_sampled(*args, *(a.ctypes.data for a in sa)),
+                       "mi_gpt_generate_batch_sampled")
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy()) for b in range(nb)], pen
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
-                             repeat_value=None, penalty_range=None):
+                             repeat_value=None, penalty_range=None, sampling=None):
         """Device-resident variant: prompts_cat (sum P_b, hidden) float32 CUDA tensor; tokens (nb, cap) int32 and hidden
         (nb, cap, hidden) float32 CUDA tensors are filled.  Returns the per-sentence token counts."""
         import torch
@@ -237,16 +327,23 @@ class IndexGPT:
         st = torch.tensor(stops, dtype=torch.int32, device=prompts_cat.device) if stops else None
         torch.cuda.current_stream(prompts_cat.device).synchronize()
         n = np.zeros((nb,), np.int32)
-        _lib.check(_lib.load().mi_gpt_generate_batch(
-            self._h, nb, prompts_cat.data_ptr(), _lib.i32p(rows), _lib.i32p(mx), st.data_ptr() if st is not None else None,
-            len(stops), float(c.repeat_penalty if repeat_value is None else repeat_value),
-            int(c.penalty_range if penalty_range is None else penalty_range), None, tokens.data_ptr(), hidden.data_ptr(),
-            int(tokens.shape[1]), _lib.i32p(n), _lib.MI_DEVICE), "mi_gpt_generate_batch")
+        samp = _batch_sampling(sampling, nb)
+        args = (self._h, nb, prompts_cat.data_ptr(), _lib.i32p(rows), _lib.i32p(mx), st.data_ptr() if st is not None else None,
+                len(stops), float(c.repeat_penalty if repeat_value is None else repeat_value),
+                int(c.penalty_range if penalty_range is None else penalty_range), None, tokens.data_ptr(), hidden.data_ptr(),
+                int(tokens.shape[1]), _lib.i32p(n), _lib.MI_DEVICE)
+        if samp is None:
+            _lib.check(_lib.load().mi_gpt_generate_batch(*args), "mi_gpt_generate_batch")
+        else:
+            sa = _sampling_arrays(samp)
+            _lib.check(_lib.load().mi_gpt_generate_batch_sampled(*args, *(a.ctypes.data for a in sa)),
+                       "mi_gpt_generate_batch_sampled")
         return n
 
     def generate(self, conds_latent, text_ids, *, max_generate_length=None, **kw):
         """Inference_IndexTTS_ONNX.py:723-783 for one sentence: B, C, D then E until a stop token or
-        MAX_GENERATE_LENGTH - concat_len tokens.  Returns (tokens, save_last_hidden_state (n, hidden), penalty)."""
+        MAX_GENERATE_LENGTH - concat_len tokens.  Returns (tokens, save_last_hidden_state (n, hidden), penalty).
+        ``sampling=Sampling(...)`` (passed on to generate_from_prompt) draws the tokens; the default is greedy."""
         c = self.cfg
         text_h = self.text_embed(text_ids)
         mel_h, _ = self.mel_embed(c.start_mel_token, 0)

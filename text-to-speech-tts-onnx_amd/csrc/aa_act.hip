@@ -19,6 +19,7 @@
 // result goes back through LDS so the HBM store is again 16-byte coalesced.
 #include "common.h"
 #include "aa_math.h"
+#include "lds_dma.h"         // wait_vm, buf_rsrc
 #include <algorithm>
 
 namespace mi {
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
 #if defined(__HIP_DEVICE_COMPILE__)
         int o0, c0, b;
         decode(t, o0, c0, b);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (long)b * Tlen * C), 0, (int)((long)Tlen * C * (long)sizeof(T)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(x + (long)b * Tlen * C, (int)((long)Tlen * C * (long)sizeof(T)));
         T* dst = xs0 + buf * xsp;
         for (int v = tid; v < xsp / VEC; v += 256) {
             const int row = v / cvn, cv = v - row * cvn;
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256) void aa_act_pipe_kernel(const T* __restrict__ 
     if (!dead(t)) dma(t, 0);
     int buf = 0, tprev = -1;
     for (; t < ntiles; t += gridDim.x) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this tile's rows have landed (this wave's share); the stores before them too
+        wait_vm<0>();     // this tile's rows have landed (this wave's share); the stores before them too
         __syncthreads();
         if (tprev >= 0) store(tprev);                         // the previous tile leaves while this one is computed
         __syncthreads();                                      // ys is free again

@@ -27,6 +27,7 @@
 #include "mfma.h"
 #include "f5_kernels.h"
 #include "x3_split.h"
+#include "lds_dma.h"         // lds_addr, wait_vm, wait_lgkm, buf_rsrc
 #include <type_traits>
 #include <string>
 #include <algorithm>
@@ -147,9 +148,9 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
             x3_split_pair(a.z * L2E, a.w * L2E, u1[1], u2[1], u3[1]);
             x3_split_pair(b.x * L2E, b.y * L2E, u1[2], u2[2], u3[2]);
             x3_split_pair(b.z * L2E, b.w * L2E, u1[3], u2[3], u3[3]);
-            qf3[ks][0] = __builtin_bit_cast(bf16x8, x3_u4{u1[0], u1[1], u1[2], u1[3]});
-            qf3[ks][1] = __builtin_bit_cast(bf16x8, x3_u4{u2[0], u2[1], u2[2], u2[3]});
-            qf3[ks][2] = __builtin_bit_cast(bf16x8, x3_u4{u3[0], u3[1], u3[2], u3[3]});
+            qf3[ks][0] = __builtin_bit_cast(bf16x8, u32x4{u1[0], u1[1], u1[2], u1[3]});
+            qf3[ks][1] = __builtin_bit_cast(bf16x8, u32x4{u2[0], u2[1], u2[2], u2[3]});
+            qf3[ks][2] = __builtin_bit_cast(bf16x8, u32x4{u3[0], u3[1], u3[2], u3[3]});
         }
     } else {
         const int qr = q0 + lr;
@@ -249,9 +250,9 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
                     x3_split_pair(a.z, a.w, u1[1], u2[1], u3[1]);
                     x3_split_pair(b.x, b.y, u1[2], u2[2], u3[2]);
                     x3_split_pair(b.z, b.w, u1[3], u2[3], u3[3]);
-                    const bf16x8 k1 = __builtin_bit_cast(bf16x8, x3_u4{u1[0], u1[1], u1[2], u1[3]});
-                    const bf16x8 k2 = __builtin_bit_cast(bf16x8, x3_u4{u2[0], u2[1], u2[2], u2[3]});
-                    const bf16x8 k3 = __builtin_bit_cast(bf16x8, x3_u4{u3[0], u3[1], u3[2], u3[3]});
+                    const bf16x8 k1 = __builtin_bit_cast(bf16x8, u32x4{u1[0], u1[1], u1[2], u1[3]});
+                    const bf16x8 k2 = __builtin_bit_cast(bf16x8, u32x4{u2[0], u2[1], u2[2], u2[3]});
+                    const bf16x8 k3 = __builtin_bit_cast(bf16x8, u32x4{u3[0], u3[1], u3[2], u3[3]});
                     // six partial products, small terms first
                     sacc = Mfma<bf16>::mma(k1, qf3[ks][2], sacc);
                     sacc = Mfma<bf16>::mma(k2, qf3[ks][1], sacc);
@@ -398,15 +399,14 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
             const int unit = (int)(by_ * gridDim.x + bx_);
             constexpr int SLOT = 2 * 32 * 64 + 2 * 64 * 2;           // floats per (unit, slice)
             // write-through (sc1) stores / sc1 loads through a buffer descriptor, as in gemm_sk.hip: no L2-wide write-back fence
-            typedef unsigned int u4 __attribute__((ext_vector_type(4)));
             typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-            __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(ws + (long)unit * Z * SLOT), 0, Z * SLOT * 4, 0x00020000);
+            __amdgpu_buffer_rsrc_t rsw = buf_rsrc(ws + (long)unit * Z * SLOT, Z * SLOT * 4);
             if (owner) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        u4 val;
+                        u32x4 val;
                         val.x = __float_as_uint(oacc[dt][4 * g4]); val.y = __float_as_uint(oacc[dt][4 * g4 + 1]);
                         val.z = __float_as_uint(oacc[dt][4 * g4 + 2]); val.w = __float_as_uint(oacc[dt][4 * g4 + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(val, rsw, (z * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
                 u2 st2; st2.x = __float_as_uint(m_run); st2.y = __float_as_uint(l_run);
                 __builtin_amdgcn_raw_buffer_store_b64(st2, rsw, (z * SLOT + 2 * 32 * 64 + (grp * 64 + lane) * 2) * 4, 0, 16);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             int* ticket = reinterpret_cast<int*>(stats + 2 * 64 * 2);
             if (tid == 0) *ticket = __hip_atomic_fetch_add(cnt + unit, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
                     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4) {
-                            const u4 val = __builtin_amdgcn_raw_buffer_load_b128(rsw, (zz * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
+                            const u32x4 val = __builtin_amdgcn_raw_buffer_load_b128(rsw, (zz * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
                             osum[dt][4 * g4] += __uint_as_float(val.x) * sc; osum[dt][4 * g4 + 1] += __uint_as_float(val.y) * sc;
                             osum[dt][4 * g4 + 2] += __uint_as_float(val.z) * sc; osum[dt][4 * g4 + 3] += __uint_as_float(val.w) * sc;
                         }
@@ -516,9 +516,6 @@ __global__ __launch_bounds__(256, 3) void attn_kernel(const T* __restrict__ q, c
 // and every operand are unchanged: results are bit-identical to the V^T layout.  Rows of the global planes past N may hold any
 // bytes (another mode's, another length's): the last stage clears whole units by their key row, not by what the buffer holds.
 typedef unsigned attn_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned attn_lds_addr(const void* p) {
-    return (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)p;
-}
 // one transposing read: per 16-lane group a block of 4 rows x 16 columns of 16-bit elements; lane 4q + p of the group supplies the
 // (8-byte aligned) address of row q, columns 4p .. 4p + 3, lane i receives column i, row q in element q.  EXEC must be all ones.
 // Inline asm: the compiler does NOT wait for it (attn_tr_wait).
@@ -529,7 +526,7 @@ template <int OFF> __device__ __forceinline__ void attn_lds_rd64_tr16(attn_u2& d
 }
 __device__ __forceinline__ void attn_tr_wait() {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
 #endif
 }
 // after attn_tr_wait(): volatile asm statements keep their order, so a use of d cannot move above the wait.  This rests on the
@@ -599,25 +596,25 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     auto split8 = [&](const float4 a, const float4 b, Frag& f1, Frag& f2, Frag& f3) __attribute__((always_inline)) {
         uint2 a1, a2, a3, b1, b2, b3;
         split4(a, a1, a2, a3); split4(b, b1, b2, b3);
-        f1 = __builtin_bit_cast(Frag, x3_u4{a1.x, a1.y, b1.x, b1.y});
-        f2 = __builtin_bit_cast(Frag, x3_u4{a2.x, a2.y, b2.x, b2.y});
-        f3 = __builtin_bit_cast(Frag, x3_u4{a3.x, a3.y, b3.x, b3.y});
+        f1 = __builtin_bit_cast(Frag, u32x4{a1.x, a1.y, b1.x, b1.y});
+        f2 = __builtin_bit_cast(Frag, u32x4{a2.x, a2.y, b2.x, b2.y});
+        f3 = __builtin_bit_cast(Frag, u32x4{a3.x, a3.y, b3.x, b3.y});
     };
 
     auto split8h = [&](const float4 a, const float4 b, Frag& f1, Frag& f2) __attribute__((always_inline)) {
         unsigned h[4], l[4];
         x2u_split_pair(a.x, a.y, h[0], l[0]); x2u_split_pair(a.z, a.w, h[1], l[1]);
         x2u_split_pair(b.x, b.y, h[2], l[2]); x2u_split_pair(b.z, b.w, h[3], l[3]);
-        f1 = __builtin_bit_cast(Frag, x3_u4{h[0], h[1], h[2], h[3]});
-        f2 = __builtin_bit_cast(Frag, x3_u4{l[0], l[1], l[2], l[3]});
+        f1 = __builtin_bit_cast(Frag, u32x4{h[0], h[1], h[2], h[3]});
+        f2 = __builtin_bit_cast(Frag, u32x4{l[0], l[1], l[2], l[3]});
     };
     // the probabilities: in [0, 1] by construction, no range clamp
     auto split8p = [&](const float4 a, const float4 b, Frag& f1, Frag& f2) __attribute__((always_inline)) {
         unsigned h[4], l[4];
         x2u_split_pair_raw_mix(a.x, a.y, h[0], l[0]); x2u_split_pair_raw_mix(a.z, a.w, h[1], l[1]);
         x2u_split_pair_raw_mix(b.x, b.y, h[2], l[2]); x2u_split_pair_raw_mix(b.z, b.w, h[3], l[3]);
-        f1 = __builtin_bit_cast(Frag, x3_u4{h[0], h[1], h[2], h[3]});
-        f2 = __builtin_bit_cast(Frag, x3_u4{l[0], l[1], l[2], l[3]});
+        f1 = __builtin_bit_cast(Frag, u32x4{h[0], h[1], h[2], h[3]});
+        f2 = __builtin_bit_cast(Frag, u32x4{l[0], l[1], l[2], l[3]});
     };
 
     // ---- Q: the NP pieces of log2(e) * Q[q0 + lr][16 ks + 8 hi .. +8] ------------------------------------------------
@@ -641,7 +638,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     // ---- stage loads: 64 keys x 64 d of K (rows = keys) and of V (VROWS: rows = keys like K; else V^T, rows = d) ----------------
     float4 kreg[KVP ? 1 : 4], vreg[KVP ? 1 : 4];
     constexpr int NU = 2 * NP;                              // KVP: 16-byte units per thread and operand per stage
-    x3_u4 kpl[KVP ? NU : 1], vpl[KVP ? NU : 1];
+    u32x4 kpl[KVP ? NU : 1], vpl[KVP ? NU : 1];
     auto load_regs = [&](int key0) {
         if constexpr (KVP) {
             // unit u = tid + 256 i: plane u / 512 ; K (and V with VROWS): key (u % 512) / 8, 8 d's ; V^T: d (u % 512) / 8, 8 keys.
@@ -650,16 +647,16 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 const int u = tid + i * 256, pl = u >> 9, r = (u & 511) >> 3, c = u & 7;
-                kpl[i] = *reinterpret_cast<const x3_u4*>(kpb + ((long)pl * vld + key0 + r) * D + c * 8);
-                if constexpr (VROWS) vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * vld + key0 + r) * D + c * 8);
-                else vpl[i] = *reinterpret_cast<const x3_u4*>(vpb + ((long)pl * D + r) * vld + key0 + c * 8);
+                kpl[i] = *reinterpret_cast<const u32x4*>(kpb + ((long)pl * vld + key0 + r) * D + c * 8);
+                if constexpr (VROWS) vpl[i] = *reinterpret_cast<const u32x4*>(vpb + ((long)pl * vld + key0 + r) * D + c * 8);
+                else vpl[i] = *reinterpret_cast<const u32x4*>(vpb + ((long)pl * D + r) * vld + key0 + c * 8);
             }
             if (VROWS && key0 + KT > NL) {
                 // last stage, V as rows: a unit is eight d's of ONE key — cleared whole when that key is >= NL (0 x NaN is NaN, and
                 // the rows past N hold whatever the buffer held before)
 #pragma unroll
                 for (int i = 0; i < NU; ++i)
-                    if (key0 + (((tid + i * 256) & 511) >> 3) >= NL) vpl[i] = x3_u4{0u, 0u, 0u, 0u};
+                    if (key0 + (((tid + i * 256) & 511) >> 3) >= NL) vpl[i] = u32x4{0u, 0u, 0u, 0u};
             } else if (key0 + KT > NL) {
                 // last stage: the V^T values of keys >= N meet probabilities that are exactly zero, but 0 x NaN is NaN and
                 // the pad columns hold whatever the buffer held before (another layout, another mode): clear them here
@@ -670,7 +667,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                         unsigned w[4] = {vpl[i].x, vpl[i].y, vpl[i].z, vpl[i].w};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) w[e] &= (2 * e < keep ? 0x0000ffffu : 0u) | (2 * e + 1 < keep ? 0xffff0000u : 0u);
-                        vpl[i] = x3_u4{w[0], w[1], w[2], w[3]};
+                        vpl[i] = u32x4{w[0], w[1], w[2], w[3]};
                     }
                 }
             }
@@ -698,9 +695,9 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 const int u = tid + i * 256, pl = u >> 9, r = (u & 511) >> 3, c = u & 7;
-                *reinterpret_cast<x3_u4*>(Ks + pl * KPL + r * LDK + c * 8) = kpl[i];                 // 144-byte rows: 16-byte aligned
+                *reinterpret_cast<u32x4*>(Ks + pl * KPL + r * LDK + c * 8) = kpl[i];                 // 144-byte rows: 16-byte aligned
                 if constexpr (VROWS) {
-                    *reinterpret_cast<x3_u4*>(Vs + pl * VPL + r * LDV + ((c ^ ((r & 2) << 1)) * 8)) = vpl[i];   // 128-byte rows, chunk ^ 4 * ((key >> 1) & 1)
+                    *reinterpret_cast<u32x4*>(Vs + pl * VPL + r * LDV + ((c ^ ((r & 2) << 1)) * 8)) = vpl[i];   // 128-byte rows, chunk ^ 4 * ((key >> 1) & 1)
                 } else {
                 uint2* vd = reinterpret_cast<uint2*>(Vs + pl * VPL + r * LDV + c * 8);                // 136-byte rows: 8-byte aligned
                 vd[0] = uint2{vpl[i].x, vpl[i].y}; vd[1] = uint2{vpl[i].z, vpl[i].w};
@@ -729,7 +726,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
     unsigned vtr[2] = {0u, 0u};
     if constexpr (VROWS) {
         const int q4 = (lane >> 2) & 3;
-        const unsigned a = attn_lds_addr(Vs) + (4 * hi + q4) * (LDV * 2) + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
+        const unsigned a = lds_addr(Vs) + (4 * hi + q4) * (LDV * 2) + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
         vtr[0] = a + (q4 >> 1) * 64;
         vtr[1] = a + ((q4 >> 1) ^ 1) * 64;
     }
@@ -853,7 +850,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
 #pragma unroll
                         for (int pl = 0; pl < NP; ++pl) {
                             attn_tr_use(t[dt][pl][0]); attn_tr_use(t[dt][pl][1]);
-                            vf[dt][pl] = __builtin_bit_cast(Frag, x3_u4{t[dt][pl][0].x, t[dt][pl][0].y, t[dt][pl][1].x, t[dt][pl][1].y});
+                            vf[dt][pl] = __builtin_bit_cast(Frag, u32x4{t[dt][pl][0].x, t[dt][pl][0].y, t[dt][pl][1].x, t[dt][pl][1].y});
                         }
                 } else {
 #pragma unroll
@@ -864,7 +861,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                         uint2 a2[2];
                         a2[0] = *reinterpret_cast<const uint2*>(row);
                         a2[1] = *reinterpret_cast<const uint2*>(row + 8);
-                        vf[dt][pl] = __builtin_bit_cast(Frag, x3_u4{a2[0].x, a2[0].y, a2[1].x, a2[1].y});
+                        vf[dt][pl] = __builtin_bit_cast(Frag, u32x4{a2[0].x, a2[0].y, a2[1].x, a2[1].y});
                     }
                 }
                 if constexpr (NP == 3) {
@@ -953,15 +950,14 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
             const int unit = (int)(by_ * gridDim.x + bx_);
             constexpr int SLOT = NG * (32 * 64 + 64 * 2);            // floats per (unit, slice)
             // write-through (sc1) stores / sc1 loads through a buffer descriptor, as in gemm_sk.hip: no L2-wide write-back fence
-            typedef unsigned int u4 __attribute__((ext_vector_type(4)));
             typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-            __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(ws + (long)unit * Z * SLOT), 0, Z * SLOT * 4, 0x00020000);
+            __amdgpu_buffer_rsrc_t rsw = buf_rsrc(ws + (long)unit * Z * SLOT, Z * SLOT * 4);
             if (owner) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        u4 val;
+                        u32x4 val;
                         val.x = __float_as_uint(oacc[dt][4 * g4]); val.y = __float_as_uint(oacc[dt][4 * g4 + 1]);
                         val.z = __float_as_uint(oacc[dt][4 * g4 + 2]); val.w = __float_as_uint(oacc[dt][4 * g4 + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(val, rsw, (z * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
@@ -969,7 +965,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                 u2 st2; st2.x = __float_as_uint(m_run); st2.y = __float_as_uint(l_run);
                 __builtin_amdgcn_raw_buffer_store_b64(st2, rsw, (z * SLOT + NG * 32 * 64 + (grp * 64 + lane) * 2) * 4, 0, 16);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();                                         // (also: every wave is done with the K / V stage the ticket word lies in)
             int* ticket = reinterpret_cast<int*>(stats + 2 * 64 * 2);
             if (tid == 0) *ticket = __hip_atomic_fetch_add(cnt + unit, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1009,7 +1005,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void attn_x3f_kernel(const fl
                     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4) {
-                            const u4 val = __builtin_amdgcn_raw_buffer_load_b128(rsw, (zz * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
+                            const u32x4 val = __builtin_amdgcn_raw_buffer_load_b128(rsw, (zz * SLOT + (((grp * 2 + dt) * 4 + g4) * 64 + lane) * 4) * 4, 0, 16);
                             osum[dt][4 * g4] += __uint_as_float(val.x) * sc; osum[dt][4 * g4 + 1] += __uint_as_float(val.y) * sc;
                             osum[dt][4 * g4 + 2] += __uint_as_float(val.z) * sc; osum[dt][4 * g4 + 3] += __uint_as_float(val.w) * sc;
                         }

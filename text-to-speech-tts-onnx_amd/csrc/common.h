@@ -44,6 +44,7 @@ void set_last_error(const std::string& m);
 // ---------------------------------------------------------------------------------------------
 using f16 = _Float16;
 using bf16 = __bf16;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));     // 16 bytes: one lane's share of a b128 load / store / LDS-DMA
 
 template <typename T> struct DT;
 template <> struct DT<float> { static constexpr int id = MI_F32; };

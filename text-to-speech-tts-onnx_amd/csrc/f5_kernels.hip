@@ -160,11 +160,11 @@ __global__ __launch_bounds__(256) void rownorm_x3p_kernel(const float* __restric
             const float aa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = (o[k] - mean) * inv * (1.f + aa[k]) + bb[k];
-            x3_u4 pl[NP];
+            u32x4 pl[NP];
             xnp_split8_sat<NP>(o, pl, sat);
             unsigned char* dst = planes + x3p_slot_offset(row, s8, nch, NP);
 #pragma unroll
-            for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+            for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
         }
     }
     if constexpr (NP == 2) sat_publish(satp, sat);
@@ -212,11 +212,11 @@ __global__ __launch_bounds__(256) void ln_prologue_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] *= g[k];
             if constexpr (sizeof(TA) == 4) {
-                x3_u4 pl[NP];
+                u32x4 pl[NP];
                 xnp_split8_sat<NP>(o, pl, sat);
                 unsigned char* dst = (unsigned char*)aout + x3p_slot_offset(row, s8, D >> 5, NP);
 #pragma unroll
-                for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+                for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
             } else {
                 struct alignas(16) Pk { TA v[8]; } pk;
 #pragma unroll

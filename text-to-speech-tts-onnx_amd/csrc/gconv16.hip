@@ -15,6 +15,7 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "mfma.h"
+#include "lds_dma.h"         // wait_vm
 #include <algorithm>
 
 namespace mi {
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(512, 2) void gconv16_kernel(const GConv16Dev p) {
             *reinterpret_cast<uint4*>(AP + row * S + c8 * 8) = u;
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
 
     f32x16 acc[TM];
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(512, 2) void gconv16_kernel(const GConv16Dev p) {
                 for (int i = 0; i < TM; ++i) acc[i] = MF::mma(af[i], bf, acc[i]);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of pair j + 1 (a whole pair period to land)
+        wait_vm<0>();            // this wave's pieces of pair j + 1 (a whole pair period to land)
         __syncthreads();                                            // ... and every wave is done with pair j's slots (and, at the end, with the plane)
     }
     // ---- odd taps -> LDS, even taps added in place, coalesced epilogue --------------------------------------------------------

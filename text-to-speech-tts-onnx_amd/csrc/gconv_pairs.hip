@@ -21,6 +21,7 @@
 #include "gemm_epilogue.h"
 #include "mfma.h"
 #include "x3_split.h"
+#include "lds_dma.h"         // wait_vm
 
 namespace mi {
 
@@ -36,7 +37,7 @@ constexpr int GCP_C = 64;                 // channels per group (in and out)
 constexpr int GCP_S = GCP_C + 8;          // fp16 row stride of the LDS planes: S / 8 odd -> conflict-free ds_read_b128 rows
 
 // eight fp32 -> the 16-byte slot of the hi plane and of the lo plane
-__device__ __forceinline__ void gcp_split8(const float4 u, const float4 v, x3_u4& hi, x3_u4& lo, bool clamp) {
+__device__ __forceinline__ void gcp_split8(const float4 u, const float4 v, u32x4& hi, u32x4& lo, bool clamp) {
     const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
     unsigned h[4], l[4];
 #pragma unroll
@@ -44,8 +45,8 @@ __device__ __forceinline__ void gcp_split8(const float4 u, const float4 v, x3_u4
         if (clamp) x2_split_pair(f[2 * q], f[2 * q + 1], h[q], l[q]);
         else x2_split_pair_raw(f[2 * q], f[2 * q + 1], h[q], l[q]);        // weights: finite and in range
     }
-    hi = x3_u4{h[0], h[1], h[2], h[3]};
-    lo = x3_u4{l[0], l[1], l[2], l[3]};
+    hi = u32x4{h[0], h[1], h[2], h[3]};
+    lo = u32x4{l[0], l[1], l[2], l[3]};
 }
 
 // Mish(v) = v tanh(log(1 + e^v)) = v n / (n + 2), n = e^v (e^v + 2) — the same function without the log1pf / tanhf expansions
@@ -94,10 +95,10 @@ __global__ __launch_bounds__(256, BM <= 128 ? 2 : 1) void gconv_pairs_kernel(con
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int v = tid + q * 256, co = v >> 3, c8 = v & 7;
-            x3_u4 h, l;
+            u32x4 h, l;
             gcp_split8(wreg[q][0], wreg[q][1], h, l, false);
-            *reinterpret_cast<x3_u4*>(WH + co * S + c8 * 8) = h;
-            *reinterpret_cast<x3_u4*>(WL + co * S + c8 * 8) = l;
+            *reinterpret_cast<u32x4*>(WH + co * S + c8 * 8) = h;
+            *reinterpret_cast<u32x4*>(WL + co * S + c8 * 8) = l;
         }
     };
     wload(0);
@@ -115,11 +116,11 @@ __global__ __launch_bounds__(256, BM <= 128 ? 2 : 1) void gconv_pairs_kernel(con
                 u = *reinterpret_cast<const float4*>(src);
                 w2 = *reinterpret_cast<const float4*>(src + 4);
             }
-            x3_u4 h, l;
+            u32x4 h, l;
             gcp_split8(u, w2, h, l, true);
             sat |= x2_sat_word(h.x) | x2_sat_word(h.y) | x2_sat_word(h.z) | x2_sat_word(h.w);
-            *reinterpret_cast<x3_u4*>(AH + row * S + c8 * 8) = h;
-            *reinterpret_cast<x3_u4*>(AL + row * S + c8 * 8) = l;
+            *reinterpret_cast<u32x4*>(AH + row * S + c8 * 8) = h;
+            *reinterpret_cast<u32x4*>(AL + row * S + c8 * 8) = l;
         }
         sat_publish(p.sat, sat);
     }
@@ -209,11 +210,11 @@ __global__ __launch_bounds__(256) void gconv_split_weights_kernel(const float* _
     const long gt = i >> 9;
     const int t = (int)(gt % taps), g = (int)(gt / taps);
     const float* src = w + (((long)g * GCP_C + co) * taps + t) * GCP_C + c8 * 8;
-    x3_u4 h, l;
+    u32x4 h, l;
     gcp_split8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), h, l, false);
     f16* dst = wp + ((long)g * tp + t) * GCP_WTAP + co * GCP_S + c8 * 8;
-    *reinterpret_cast<x3_u4*>(dst) = h;
-    *reinterpret_cast<x3_u4*>(dst + GCP_C * GCP_S) = l;
+    *reinterpret_cast<u32x4*>(dst) = h;
+    *reinterpret_cast<u32x4*>(dst + GCP_C * GCP_S) = l;
 }
 
 // wp: gconv_pairs_planes_bytes(G, taps) bytes; w: fp32 [G][64 co][taps][64 ci] (the layout launch_conv_gemm takes)
@@ -271,15 +272,15 @@ __global__ __launch_bounds__(512, 1) void gconv_pairs2_kernel(const GConvPairsDe
                 u = *reinterpret_cast<const float4*>(src);
                 w2 = *reinterpret_cast<const float4*>(src + 4);
             }
-            x3_u4 h, l;
+            u32x4 h, l;
             gcp_split8(u, w2, h, l, true);
             sat |= x2_sat_word(h.x) | x2_sat_word(h.y) | x2_sat_word(h.z) | x2_sat_word(h.w);
-            *reinterpret_cast<x3_u4*>(AH + row * S + c8 * 8) = h;
-            *reinterpret_cast<x3_u4*>(AL + row * S + c8 * 8) = l;
+            *reinterpret_cast<u32x4*>(AH + row * S + c8 * 8) = h;
+            *reinterpret_cast<u32x4*>(AL + row * S + c8 * 8) = l;
         }
         sat_publish(p.sat, sat);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
 
     f32x16 acc[TM], accb[TM];
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(512, 1) void gconv_pairs2_kernel(const GConvPairsDe
                 }
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of pair j + 1 (a whole pair period to land)
+        wait_vm<0>();            // this wave's pieces of pair j + 1 (a whole pair period to land)
         __syncthreads();                                            // ... and every wave is done with pair j's slots (and, at the end, with the planes)
     }
     // ---- accumulators -> LDS (one image per tap-parity group) -> summed in the coalesced epilogue ---------------------------------

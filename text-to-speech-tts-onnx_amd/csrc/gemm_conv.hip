@@ -23,6 +23,7 @@
 #include <mutex>
 #include "mfma.h"
 #include "gemm_epilogue.h"
+#include "lds_dma.h"         // wait_vm, wait_lgkm, buf_rsrc
 
 namespace mi {
 
@@ -231,8 +232,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
     __amdgpu_buffer_rsrc_t rsa, rsb;
     int avo[DJ], bvo[DJ];
     if (p.use_buf) {
-        rsa = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)), 0x00020000);
-        rsb = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, (int)((long)p.N * p.K * (long)sizeof(T)), 0x00020000);
+        rsa = buf_rsrc(xb, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)));
+        rsb = buf_rsrc(wg, (int)((long)p.N * p.K * (long)sizeof(T)));
 #pragma unroll
         for (int j = 0; j < DJ; ++j) {
             const int R0 = (wave * DJ + j) * 8;
@@ -323,8 +324,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
                     if (clamp) { a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f); b2 = __builtin_amdgcn_fmed3f(b2, -65504.f, 65504.f); }
                     x2_split_pair_raw(a, b2, h[q], l[q]);
                 }
-                fh = __builtin_bit_cast(FH, x3_u4{h[0], h[1], h[2], h[3]});
-                fl = __builtin_bit_cast(FH, x3_u4{l[0], l[1], l[2], l[3]});
+                fh = __builtin_bit_cast(FH, u32x4{h[0], h[1], h[2], h[3]});
+                fl = __builtin_bit_cast(FH, u32x4{l[0], l[1], l[2], l[3]});
             };
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
         };
         auto advance = [&]() { if (++tap >= ntaps) { tap = 0; c0 += KC; } };
         issue(0, tap, c0); advance();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         if (nchunks > 1) { issue(1, tap, c0); advance(); }
         ldfrag(0, 0, 0);
@@ -438,8 +439,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (c + 1 < nchunks) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // chunk c+1 has landed (this wave's share)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // every read of chunk c's stage has retired
+                wait_vm<0>();   // chunk c+1 has landed (this wave's share)
+                wait_lgkm<0>(); // every read of chunk c's stage has retired
                 __builtin_amdgcn_s_barrier();
                 if (c + 2 < nchunks) { issue(c & 1, tap, c0); advance(); }
                 ldfrag((c + 1) & 1, 0, 0);
@@ -449,12 +450,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (LEPI) {                                      // the staging epilogue reuses the stages: all reads must be done
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();
         }
     } else if constexpr (NST == 2) {
         issue(0, 0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         for (int c = 0; c < nchunks; ++c) {
             const int buf = c & 1;
@@ -462,7 +463,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
             if (ntap >= ntaps) { ntap = 0; nc0 += KC; }
             if (c + 1 < nchunks) issue(buf ^ 1, ntap, nc0);
             compute(buf);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             tap = ntap; c0 = nc0;
         }
@@ -478,16 +479,16 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_dma_kernel(const ConvGemmDev
         issue(1, tap, c0); advance();
         issue(2, tap, c0); advance();
         static_assert(BT == 128, "the ring's vmcnt(16) assumes eight DMA instructions per wave per chunk");
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        wait_vm<16>();
         __builtin_amdgcn_s_barrier();
         for (int c = 0; c < nchunks; ++c) {
             issue((c + 3) & 3, tap, c0); advance();         // overwrites the stage read in iteration c-1 (all waves passed its barrier)
             compute(c & 3);
-            asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // chunk c+1 has landed (this wave's share)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_vm<16>();   // chunk c+1 has landed (this wave's share)
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the trailing zero-page chunks must not land on the epilogue's staging
+        wait_vm<0>();       // the trailing zero-page chunks must not land on the epilogue's staging
         __builtin_amdgcn_s_barrier();
     }
     if constexpr (PAIRS) {

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
+#include "lds_dma.h"         // wait_vm, wait_lgkm, buf_rsrc
 #include <type_traits>
 
 namespace mi {
@@ -31,7 +32,6 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
     static_assert(NW == 8 || NW == 4, "eight or four waves");
     constexpr int TILE = (BM + BN) * KC;
     constexpr int AJ = BM / 8 / NW, BJ = BN / 8 / NW, PERW = AJ + BJ;     // 8-row DMA groups per wave per chunk
-    static_assert(NST == 2 || PERW == 6 || PERW == 8, "counted vmcnt immediates of the 3-stage ring");
     __shared__ __attribute__((aligned(1024))) T smem[NST * TILE];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
     __amdgpu_buffer_rsrc_t rsa, rsb;
     int avo[AJ], bvo[BJ];                                         // per-lane byte offsets, loop-invariant
     if constexpr (BUF) {
-        rsa = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)), 0x00020000);
-        rsb = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, (int)((long)p.N * p.K * (long)sizeof(T)), 0x00020000);
+        rsa = buf_rsrc(xb, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)));
+        rsb = buf_rsrc(wg, (int)((long)p.N * p.K * (long)sizeof(T)));
 #pragma unroll
         for (int j = 0; j < AJ; ++j) {
             const int R0 = (wave * AJ + j) * 8;
@@ -148,9 +148,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
     auto wait_next = [&](bool more_in_flight) {
         // everything except (optionally) this wave's newest PERW DMA instructions has landed
         if (more_in_flight) {
-            if constexpr (PERW == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<PERW>();
+        } else wait_vm<0>();
     };
     constexpr int AHEAD = NST - 1;                                // chunks in flight beyond the one being computed
     issue(0, itap, ic0); advance();
@@ -195,8 +194,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (c + 1 < nchunks) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk c+1 (issued a chunk period ago) has landed
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");// every read of chunk c's stage has retired
+                wait_vm<0>();                                     // chunk c+1 (issued a chunk period ago) has landed
+                wait_lgkm<0>();                                   // every read of chunk c's stage has retired
                 __builtin_amdgcn_s_barrier();
                 if (c + 2 < nchunks) { issue(c & 1, itap, ic0); advance(); }
                 ldfrag(smem + ((c + 1) & 1) * TILE, 0, 0);        // register set 0 is free: k-step 3 runs from set 1
@@ -251,9 +250,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void conv_gemm_dma3_ker
             }
         }
         // the next chunk to be computed must have landed for every wave; the newest one may stay in flight (3-stage)
-        if (p.dbg == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (p.dbg == 1) wait_vm<0>();
         else wait_next(AHEAD == 2 && pre);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         if (++st == NST) st = 0;
     }

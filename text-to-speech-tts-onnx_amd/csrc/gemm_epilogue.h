@@ -46,7 +46,9 @@ struct ConvGemmDev {
     void* out_planes;                            // gemm_x3p.hip: output as panel planes of an [M][N] matrix (null: rows in `out`)
     int kv_planes; long k_ld;                    // EPI_QKV_ROPE, fp32: K and V^T leave pre-split (attention.hip KVP), np = kv_planes planes (3 bf16 | 2 fp16 pairs with the low part unscaled, x2u_split_pair; 1 = 3): out2 = [bh][np][k_ld][64], out3 = [bh][np][64][v_ld] (v_rows below: like out2)
     int v_rows;                                  // ... with kv_planes: V leaves as rows like K, out3 = [bh][np][k_ld][64] (attention.hip VROWS transposes it on the LDS read)
-    int tail_tiles, tail_split;                  // gemm_ph8.hip: the last tail_tiles tiles are cut into tail_split K slices (0 / 1: none)
+    // tail_tiles is read by two kernels only — gemm_ph8.hip: the last tail_tiles tiles are cut into tail_split K slices (0 / 1: none);
+    // gemm_x3p.hip: bit 0 = no cyclic K alignment (option gemm_x3p_noalign).  Every other launcher leaves it alone.
+    int tail_tiles, tail_split;
     // AdaLN fold (ConvGemm, common.h): producer side (ln_stats_out) / consumer side (ln_stats_in)
     const float* ln_scale = nullptr; void* ln_out = nullptr; float* ln_stats_out = nullptr; int ln_out_np = 0;
     const float* ln_stats_in = nullptr; const float* ln_p = nullptr; const float* ln_c = nullptr; int ln_dim = 0; float ln_eps = 0.f;
@@ -483,18 +485,18 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                     // row's eight values, one 16-byte store per plane ([bh][plane][key][64])
                     bf16* kvo = (bf16*)(which == 1 ? p.out2 : p.out3);
                     if (p.kv_planes == 2) {          // fp16 {hi, lo} pairs: [bh][2][key][64]
-                        x3_u4 pl[2];                  // unscaled low part: the attention kernel sums both parts into one accumulator
+                        u32x4 pl[2];                  // unscaled low part: the attention kernel sums both parts into one accumulator
                         {
                             unsigned wh[4], wl[4];
 #pragma unroll
                             for (int q = 0; q < 4; ++q) x2u_split_pair(x[2 * q], x[2 * q + 1], wh[q], wl[q]);
-                            pl[0] = x3_u4{wh[0], wh[1], wh[2], wh[3]}; pl[1] = x3_u4{wl[0], wl[1], wl[2], wl[3]};
+                            pl[0] = u32x4{wh[0], wh[1], wh[2], wh[3]}; pl[1] = u32x4{wl[0], wl[1], wl[2], wl[3]};
                             qkv_sat |= x2_sat_word(wh[0]) | x2_sat_word(wh[1]) | x2_sat_word(wh[2]) | x2_sat_word(wh[3]);
                         }
                         bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 2 * p.k_ld + mv[gi]) * 64 + c8;
                         if (okv[gi]) {
-                            *reinterpret_cast<x3_u4*>(kp) = pl[0];
-                            *reinterpret_cast<x3_u4*>(kp + p.k_ld * 64) = pl[1];
+                            *reinterpret_cast<u32x4*>(kp) = pl[0];
+                            *reinterpret_cast<u32x4*>(kp + p.k_ld * 64) = pl[1];
                         }
                         continue;
                     }
@@ -503,9 +505,9 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                     for (int q = 0; q < 4; ++q) x3_split_pair(x[2 * q], x[2 * q + 1], p1[q], p2[q], p3[q]);
                     bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 3 * p.k_ld + mv[gi]) * 64 + c8;
                     if (okv[gi]) {
-                        *reinterpret_cast<x3_u4*>(kp) = x3_u4{p1[0], p1[1], p1[2], p1[3]};
-                        *reinterpret_cast<x3_u4*>(kp + p.k_ld * 64) = x3_u4{p2[0], p2[1], p2[2], p2[3]};
-                        *reinterpret_cast<x3_u4*>(kp + 2 * p.k_ld * 64) = x3_u4{p3[0], p3[1], p3[2], p3[3]};
+                        *reinterpret_cast<u32x4*>(kp) = u32x4{p1[0], p1[1], p1[2], p1[3]};
+                        *reinterpret_cast<u32x4*>(kp + p.k_ld * 64) = u32x4{p2[0], p2[1], p2[2], p2[3]};
+                        *reinterpret_cast<u32x4*>(kp + 2 * p.k_ld * 64) = u32x4{p3[0], p3[1], p3[2], p3[3]};
                     }
                     continue;
                 }
@@ -671,12 +673,12 @@ __device__ __forceinline__ void gemm_epilogue_ln_in(f32x16 (&acc)[TM][TN], const
             for (int q = 0; q < 8; ++q) x[q] = __builtin_fmaf(rs, x[q], __builtin_fmaf(-mr, pv[q], cv[q]));
             ln_act8<TO>(x, p.act);
             if constexpr (sizeof(TO) == 4) {
-                x3_u4 pl[NP];
+                u32x4 pl[NP];
                 xnp_split8_sat<NP>(x, pl, sat);
                 if (m < Mlim) {
                     unsigned char* dst = (unsigned char*)p.out_planes + x3p_slot_offset(m, col >> 3, p.N >> 5, NP);
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+                    for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
                 }
             } else {
                 Pk o;
@@ -756,12 +758,12 @@ __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], co
 #pragma unroll
             for (int q = 0; q < 8; ++q) x[q] *= gsc[q];
             if constexpr (sizeof(TA) == 4) {
-                x3_u4 pl[NP];
+                u32x4 pl[NP];
                 xnp_split8_sat<NP>(x, pl, sat);
                 if (ok[it]) {
                     unsigned char* dst = (unsigned char*)p.ln_out + x3p_slot_offset(m, col >> 3, p.N >> 5, NP);
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+                    for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
                 }
             } else {
                 Pk o;
@@ -821,12 +823,12 @@ __device__ __forceinline__ void x3p_epilogue_planes(f32x16 (&acc)[TM][TN], const
         const float4 t0 = *reinterpret_cast<const float4*>(&stage[rr * 64 + c8]);
         const float4 t1 = *reinterpret_cast<const float4*>(&stage[rr * 64 + c8 + 4]);
         const float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-        x3_u4 pl[NP];
+        u32x4 pl[NP];
         xnp_split8_sat<NP>(v, pl, sat);
         if (m < Mlim) {
             unsigned char* dst = planes + x3p_slot_offset(m, s8, nch_out, NP);
 #pragma unroll
-            for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+            for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

@@ -37,17 +37,9 @@
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
+#include "lds_dma.h"         // lds_addr, dma16_buf, wait_vm, wait_lgkm, buf_rsrc
 
 namespace mi {
-
-template <typename RSRC>
-__device__ __forceinline__ void ph8_bufds16(RSRC rsrc, int voff, unsigned lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-#endif
-}
 
 template <typename T, typename TO, bool SPLIT>
 __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p) {
@@ -68,10 +60,10 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
     // descriptors first: values defined after the (uniform, but not provably so) early exit below would be placed in VGPRs
     const T* xb = (const T*)p.x;
     const T* wg = (const T*)p.w;
-    __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * 2L), 0x00020000);
-    __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, (int)((long)p.N * p.K * 2L), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsa = buf_rsrc(xb, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * 2L));
+    __amdgpu_buffer_rsrc_t rsb = buf_rsrc(wg, (int)((long)p.N * p.K * 2L));
     // partial-tile workspace of the split tail (see below): 256 KB slabs
-    __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.sk_ws, 0, (int)((long)p.sk_slots * 65536L), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsw = buf_rsrc(p.sk_ws, (int)((long)p.sk_slots * 65536L));
     // Tile list.  The first T_full tiles run one per workgroup over the whole K; XCD-aware order: workgroup b lands on XCD
     // b % 8 and each XCD walks a contiguous range of the list (panels fastest), so the 32 tiles an XCD runs together share
     // a few row panels and the weight panels in its own L2.
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
     const int nk = kend;                                        // K tiles >= kend are out-of-range dummies
 
     constexpr int OOB = 0x7fffff00;
-    const unsigned smem_lds = (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)smem;
+    const unsigned smem_lds = lds_addr(smem);
 
     // DMA: one instruction moves 8 rows x 128 bytes (lane -> row lane/8, 16-byte slot lane%8 holding k-vector
     // slot ^ ((row >> 1) & 7)); a half-tile is 16 row groups = 2 instructions for each of the 8 waves (row group j*8 + wave)
@@ -133,8 +125,8 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
         for (int j = 0; j < 2; ++j) {
             const int vo = h < 2 ? avo[h][j] : bvo[h - 2][j];
             const unsigned dst = __builtin_amdgcn_readfirstlane(base + (unsigned)(j * 8192));
-            if (h < 2) ph8_bufds16(rsa, (int)((unsigned)vo + (unsigned)kb), dst);
-            else ph8_bufds16(rsb, (int)((unsigned)vo + (unsigned)kb), dst);
+            if (h < 2) dma16_buf(rsa, (int)((unsigned)vo + (unsigned)kb), dst);
+            else dma16_buf(rsb, (int)((unsigned)vo + (unsigned)kb), dst);
         }
     };
 
@@ -178,7 +170,6 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
     };
 #define PH8_SB() __builtin_amdgcn_sched_barrier(0)
 #define PH8_BAR() do { PH8_SB(); __builtin_amdgcn_s_barrier(); PH8_SB(); } while (0)
-#define PH8_WAIT5() asm volatile("s_waitcnt vmcnt(10)" ::: "memory")
 
     if (p.dbg & 2) {
 #pragma unroll
@@ -187,7 +178,7 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
     // prologue: the seven half-tiles the phases before the first K tile would have issued, in pipeline order
     dma_half(0, 2, kbeg); dma_half(0, 0, kbeg); dma_half(0, 3, kbeg); dma_half(0, 1, kbeg);
     dma_half(1, 2, kbeg + 1); dma_half(1, 0, kbeg + 1); dma_half(1, 3, kbeg + 1);
-    PH8_WAIT5();                                                 // B_0, A_0 of the first K tile
+    wait_vm<10>();                                               // B_0, A_0 of the first K tile
     PH8_BAR();
     if (wr == 1) PH8_BAR();                                     // group 1 runs one barrier behind
 
@@ -197,48 +188,48 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
         rdB(st, 0, fb0); PH8_SB();
         rdA(st, 0); PH8_SB();
         dma_half(st ^ 1, 1, k + 1); PH8_SB();
-        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");       // the four B_0 reads have retired: B_0 may be re-staged in phase 1
-        PH8_WAIT5();                                             // B_1(k)
+        wait_lgkm<8>();       // the four B_0 reads have retired: B_0 may be re-staged in phase 1
+        wait_vm<10>();                                           // B_1(k)
         PH8_BAR();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         PH8_SB(); mm(0, 0, fb0);
         PH8_BAR();
         // phase 1
         rdB(st, 1, fb1); PH8_SB();
         dma_half(st, 2, k + 2); PH8_SB();
-        PH8_WAIT5();                                             // A_1(k)
+        wait_vm<10>();                                           // A_1(k)
         PH8_BAR();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         PH8_SB(); mm(0, 1, fb1);
         PH8_BAR();
         // phase 2
         rdA(st, 1); PH8_SB();
         dma_half(st, 0, k + 2);
         PH8_BAR();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         PH8_SB(); mm(1, 1, fb1);
         PH8_BAR();
         // phase 3
         dma_half(st, 3, k + 2); PH8_SB();
-        PH8_WAIT5();                                             // B_0, A_0 of K tile k+1
+        wait_vm<10>();                                           // B_0, A_0 of K tile k+1
         PH8_BAR();
         mm(1, 0, fb0);
         PH8_BAR();
     }
     if (wr == 0) PH8_BAR();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing out-of-range pieces must not land on the epilogue's staging
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_vm<0>();             // the trailing out-of-range pieces must not land on the epilogue's staging
+    wait_lgkm<0>();
     PH8_BAR();
-#undef PH8_WAIT5
 #undef PH8_SB
 #undef PH8_BAR
     if (p.dbg & 4) return;
 
+    // the gemm_sk.hip hand-off with this kernel's slot geometry; the other three copies are in gemm_sk.hip, gemm_x3.hip and gemm_x3p.hip:
+    // a fix to the protocol goes into all four
     if constexpr (SPLIT) if (tile >= T_full && S > 1) {
         const int ti = tile - T_full;
         int tidx = tid;
         asm volatile("" : "+v"(tidx));                          // keeps the 32 slab offsets from being hoisted above the K loop (they spilled an accumulator block there)
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
         int* flags = p.sk_flags;
         if (slice > 0) {
             const int q = ti * (S - 1) + slice - 1;
@@ -248,13 +239,13 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        u4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(acc[i][j][4 * e]); v.y = __float_as_uint(acc[i][j][4 * e + 1]);
                         v.z = __float_as_uint(acc[i][j][4 * e + 2]); v.w = __float_as_uint(acc[i][j][4 * e + 3]);
                         const int unit = ((i * 2 + j) * 4 + e) * 512 + tidx;
                         __builtin_amdgcn_raw_buffer_store_b128(v, rsw, (q * 16384 + unit) * 16, 0, 16 /* sc1: write-through */);
                     }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             if (tid == 0) __hip_atomic_store(flags + q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                u4 v[8];
+                u32x4 v[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
                     v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (q * 16384 + (i * 8 + u) * 512 + tidx) * 16, 0, 16 /* sc1 */);
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(512, 1) void linear_ph8_kernel(const ConvGemmDev p)
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const u4 w = v[j * 4 + e];
+                        const u32x4 w = v[j * 4 + e];
                         acc[i][j][4 * e] += __uint_as_float(w.x); acc[i][j][4 * e + 1] += __uint_as_float(w.y);
                         acc[i][j][4 * e + 2] += __uint_as_float(w.z); acc[i][j][4 * e + 3] += __uint_as_float(w.w);
                     }

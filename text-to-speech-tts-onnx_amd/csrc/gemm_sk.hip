@@ -13,59 +13,27 @@
 // the epilogue.  A range that starts mid-tile computes that piece FIRST and publishes it at once, so by the time the
 // head owner gets to its last piece the partials it needs were written long ago.  Ranges are numbered against the
 // workgroup ids (see the XCD note in the kernel): the ranges a finisher waits for belong to LOWER workgroup ids, which the
-// dispatcher started earlier — the wait cannot deadlock even if the grid is not fully resident.  Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility):
-// write-through (sc1) 16-byte slab stores -> s_waitcnt vmcnt(0) in every wave -> barrier -> relaxed agent-scope flag
-// store; the finisher polls the flag with relaxed agent loads, then reads the slab with sc1 loads (they bypass L1 and
-// are served by L2, which the write-through stores did not leave a stale line in).  The finisher resets the flag, so a
-// hipGraph replay of the same launch finds the workspace clean.
+// dispatcher started earlier — the wait cannot deadlock even if the grid is not fully resident.
+// Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): write-through (sc1) 16-byte slab stores -> s_waitcnt vmcnt(0)
+// in every wave -> barrier -> relaxed agent-scope flag store; the finisher polls the flag with relaxed agent loads, then
+// reads the slab with sc1 loads (they bypass L1 and are served by L2, which the write-through stores did not leave a stale
+// line in).  The finisher resets the flag, so a hipGraph replay of the same launch finds the workspace clean.
 #include "common.h"
 #include "mfma.h"
 #include "gemm_epilogue.h"
+#include "lds_dma.h"         // lds_addr, dma16_buf, wait_vm, wait_lgkm, buf_rsrc
 #include <type_traits>
 
 namespace mi {
 
-typedef unsigned int sk_u4 __attribute__((ext_vector_type(4)));
-
-// LDS-DMA of 16 bytes per lane, issued from inline asm so that hipcc does not see an LDS write: for the builtin forms
-// (global_load_lds and buffer_load ... lds alike) it puts s_waitcnt vmcnt(0) in front of the next ds_read, which drains the
-// ring every chunk (seen in the ISA of this kernel; it knows nothing of the counted inline-asm waits).  M0 carries the
-// wave-uniform LDS byte address and is saved / restored around the instruction (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ void sk_glds16(const void* gsrc, unsigned lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#endif
-}
-// the same through a buffer descriptor (buffer_load_dwordx4 ... offen lds): one 32-bit per-lane offset, and the hardware
-// range check writes ZEROS for offsets outside [0, num_records) — row tails and dummy chunks need no select
-template <typename RSRC>
-__device__ __forceinline__ void sk_bufds16(RSRC rsrc, int voff, unsigned lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-#endif
-}
-__device__ __forceinline__ unsigned sk_lds_addr(const void* p) {
-    return (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)p;
-}
-
-// PROD: two extra waves do nothing but issue the LDS-DMA (wave 4: the 16 x-row pieces of a chunk, wave 5: the 16 weight-row
-// pieces) and wait for it; the four MFMA waves
-// carry no VMEM instruction and no vmcnt wait.  Why: a DMA instruction costs its wave ~100 cycles of issue (M0 write, address
-// add, the instruction itself) during which that wave — alone on its SIMD — issues no MFMA: eight per 4096-cycle fp32 chunk
-// were the 18 % the "no DMA" ablation recovered.  The producer shares SIMD 0 with wave 0 and is paced by the same barriers.
-template <typename T, typename TO, bool LEPI, int NST, bool PROD = false>
-__global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_kernel(const ConvGemmDev p) {
+template <typename T, typename TO, bool LEPI, int NST>
+__global__ __launch_bounds__(256, NST <= 2 ? 2 : 1) void linear_sk_kernel(const ConvGemmDev p) {
     using MF = Mfma<T>;
     constexpr int VEC = 16 / (int)sizeof(T), KC = 8 * VEC;      // a tile row is 128 bytes: 64 halfs or 32 floats per K chunk
     constexpr int BM = 128, BN = 128, WM = 64, WN = 64, TM = 2, TN = 2, DJ = 4, PER = 2 * DJ;
     constexpr int TILE = (BM + BN) * KC;
     constexpr int AHEAD = NST - 1;                              // chunks in flight beyond the one being computed
     static_assert(NST >= 2 && NST <= 4, "ring depth");
-    static_assert(!PROD || NST == 3, "the producer wave runs two chunks ahead in a three-stage ring");
     // ONE static array (a dynamic `extern __shared__` block makes hipcc put s_waitcnt vmcnt(0) in front of every ds_read
     // that follows an LDS-DMA: the ring then drains every chunk — seen in the ISA, 56 % MFMA duty instead of ~90 %)
     __shared__ __attribute__((aligned(1024))) T smem[NST * TILE];
@@ -105,11 +73,11 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
     const int lrow = lane >> 3;
     const T* xb = (const T*)p.x;
     const T* wg = (const T*)p.w;
-    __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)), 0x00020000);
-    __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)wg, 0, (int)((long)p.N * p.K * (long)sizeof(T)), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsa = buf_rsrc(xb, (int)((((long)p.T_in - 1) * p.x_rstride + p.Cin) * (long)sizeof(T)));
+    __amdgpu_buffer_rsrc_t rsb = buf_rsrc(wg, (int)((long)p.N * p.K * (long)sizeof(T)));
     constexpr int OOB = 0x7fffff00;                             // beyond every num_records (and OOB + OOB wraps to a value >= 2^31 - 512: still out of range as unsigned)
-    const unsigned smem_lds = sk_lds_addr(smem);
-    __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.sk_ws, 0, (int)((long)P * BM * BN * 4), 0x00020000);
+    const unsigned smem_lds = lds_addr(smem);
+    __amdgpu_buffer_rsrc_t rsw = buf_rsrc(p.sk_ws, (int)((long)P * BM * BN * 4));
     int* flags = p.sk_flags;
 
     while (dp_done < full || it < it1) {
@@ -142,8 +110,8 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
             const int cbytes = chunk < ce ? chunk * KC * (int)sizeof(T) : OOB;      // wave-uniform
             const int jj = j & 3;
             const int R0 = (wave * DJ + jj) * 8;
-            if (j < 4) sk_bufds16(rsa, (int)((unsigned)avo[jj] + (unsigned)cbytes), base + (unsigned)(R0 * KC * (int)sizeof(T)));
-            else sk_bufds16(rsb, (int)((unsigned)bvo[jj] + (unsigned)cbytes), base + (unsigned)((BM + R0) * KC * (int)sizeof(T)));
+            if (j < 4) dma16_buf(rsa, (int)((unsigned)avo[jj] + (unsigned)cbytes), base + (unsigned)(R0 * KC * (int)sizeof(T)));
+            else dma16_buf(rsb, (int)((unsigned)bvo[jj] + (unsigned)cbytes), base + (unsigned)((BM + R0) * KC * (int)sizeof(T)));
         };
         auto issue = [&](int st, int chunk) {
 #pragma unroll
@@ -152,16 +120,8 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
         // at a chunk boundary: chunk c+1 has landed; younger DMAs may stay in flight = the later prefetched chunks plus the
         // 6 instructions of the newest one that were already interleaved into this chunk (the prologue passes 8 instead)
         auto wait_landed = [&](bool prologue) {
-            if (prologue) {
-                if constexpr (AHEAD == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if constexpr (AHEAD == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            } else {
-                if constexpr (AHEAD == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // see the AHEAD == 1 note in the loop
-                else if constexpr (AHEAD == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-            }
-            static_assert(PER == 8, "counted vmcnt immediates");
+            if (prologue) wait_vm<(AHEAD - 1) * PER>();
+            else wait_vm<AHEAD == 1 ? 0 : (AHEAD - 1) * PER - 2>();       // AHEAD == 1: see the note in the loop
         };
 
         f32x16 acc[TM][TN];
@@ -212,69 +172,6 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
         //      instructions with MFMA execution only if they sit BETWEEN MFMAs in program order, so every k-vector step is
         //      Q0 | fragment reads of the next step | Q1 | DMA | Q2 | DMA | Q3  (PMC before: 26 % of the busy cycles had no
         //      MFMA in flight, the eight address-computation + DMA blocks ran in front of the MFMA group) ---------------------
-        if constexpr (PROD) {
-            if (wave >= 4) {
-                const bool pa = wave == 4;                       // wave 4 stages the x rows, wave 5 the weight rows
-                // ---- producer: chunk c+2 goes out right after the barrier that ended the reads of chunk c-1 (same stage);
-                //      s_waitcnt vmcnt(16) = everything but this wave's newest chunk has landed; then the barrier that publishes
-                //      chunk c+1.  Rows past M / N are beyond num_records: the range check writes zeros.
-                const int a_ev = (int)(((long)(m0 + lrow) * p.x_rstride + kvl0 * VEC) * (long)sizeof(T));
-                const int a_od = (int)(((long)(m0 + 8 + lrow) * p.x_rstride + kvl1 * VEC) * (long)sizeof(T));
-                const int b_ev = (int)(((long)(n0 + lrow) * p.K + kvl0 * VEC) * (long)sizeof(T));
-                const int b_od = (int)(((long)(n0 + 8 + lrow) * p.K + kvl1 * VEC) * (long)sizeof(T));
-                const int a_step = (int)((long)16 * p.x_rstride * (long)sizeof(T)), b_step = (int)((long)16 * p.K * (long)sizeof(T));
-                auto issue_all = [&](int stg, int chunk) __attribute__((always_inline)) {
-                    if (p.dbg & 1) return;
-                    const unsigned base = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(stg * TILE * (int)sizeof(T)));
-                    const int cbytes = chunk < ce ? chunk * KC * (int)sizeof(T) : OOB;
-                    if (pa) {
-#pragma unroll
-                        for (int g = 0; g < 8; ++g) {
-                            sk_bufds16(rsa, (int)((unsigned)a_ev + (unsigned)(g * a_step) + (unsigned)cbytes), base + (unsigned)((2 * g) * 8 * KC * (int)sizeof(T)));
-                            sk_bufds16(rsa, (int)((unsigned)a_od + (unsigned)(g * a_step) + (unsigned)cbytes), base + (unsigned)((2 * g + 1) * 8 * KC * (int)sizeof(T)));
-                        }
-                    } else {
-#pragma unroll
-                        for (int g = 0; g < 8; ++g) {
-                            sk_bufds16(rsb, (int)((unsigned)b_ev + (unsigned)(g * b_step) + (unsigned)cbytes), base + (unsigned)((BM + (2 * g) * 8) * KC * (int)sizeof(T)));
-                            sk_bufds16(rsb, (int)((unsigned)b_od + (unsigned)(g * b_step) + (unsigned)cbytes), base + (unsigned)((BM + (2 * g + 1) * 8) * KC * (int)sizeof(T)));
-                        }
-                    }
-                };
-                issue_all(0, cb); issue_all(1, cb + 1);
-                asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                int stp = 2;
-                for (int c = 0; c + 1 < n; ++c) {
-                    issue_all(stp, cb + c + 2);
-                    if (++stp == NST) stp = 0;
-                    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                }
-            } else {
-                __builtin_amdgcn_s_barrier();                   // chunk cb has landed
-                ldfrag(0, 0, 0);
-                int st = 0;
-                for (int c = 0; c < n; ++c) {
-                    int stn = st + 1; if (stn == NST) stn = 0;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        const int set = ks & 1;
-                        if (ks == 3 && c + 1 < n) {
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            __builtin_amdgcn_s_barrier();       // chunk c+1 published, stage of chunk c released
-                        }
-                        SK_SB(); mma_q(set, 0); SK_SB();
-                        if (ks < 3) ldfrag(st, ks + 1, set ^ 1);
-                        else if (c + 1 < n) ldfrag(stn, 0, 0);
-                        SK_SB(); mma_q(set, 1); SK_SB();
-                        SK_SB(); mma_q(set, 2); SK_SB();
-                        SK_SB(); mma_q(set, 3); SK_SB();
-                    }
-                    st = stn;
-                }
-            }
-        } else {
 #pragma unroll
         for (int a = 0; a < AHEAD; ++a) issue(a, cb + a);
         wait_landed(true);
@@ -290,7 +187,7 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
                     // publish chunk c+1 before the LAST step of chunk c (its fragments are in registers): the barrier
                     // latency and the first fragment reads of chunk c+1 run under those MFMAs
                     wait_landed(false);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    wait_lgkm<0>();
                     __builtin_amdgcn_s_barrier();
                 }
                 // DMA slots of this step: ring (AHEAD >= 2): two per step, the last two of a chunk after the boundary wait
@@ -314,31 +211,30 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
             if (++st_issue == NST) st_issue = 0;
             st = stn;
         }
-        }
 #undef SK_SB
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // trailing dummies have landed: the ring may be reused
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_vm<0>();        // trailing dummies have landed: the ring may be reused
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
 
         // ---- partial tile: publish (tail / middle piece) or collect (head piece) -------------------------------------------
-        const int slot_lane = (wave * 16) * 64 + lane;          // + (i*2+j)*4*64 + q*64 : 16-byte units inside a 64 KB slot
+        // (this hand-off is written out four times — gemm_sk.hip, gemm_x3.hip, gemm_x3p.hip and, with its own slot geometry, gemm_ph8.hip:
+        //  a fix to the protocol goes into all four; shared inline helpers changed the compiled code, profiles/r9/gemm_prims_identity.txt)
+        const int slot_lane = (wave * (TM * TN * 4)) * 64 + lane;   // + ((i*TN+j)*4 + q)*64 : 16-byte units inside a 64 KB slot
         if (p.dbg & 4) { if (dp) ++dp_done; else it += n; continue; }                    // tuning: no fix-up, no epilogue
-        const bool worker = !PROD || wave < 4;                   // the producer wave only takes part in the barriers below
         if (cb > 0) {
-            if (worker)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        sk_u4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(acc[i][j][4 * q]); v.y = __float_as_uint(acc[i][j][4 * q + 1]);
                         v.z = __float_as_uint(acc[i][j][4 * q + 2]); v.w = __float_as_uint(acc[i][j][4 * q + 3]);
                         const int unit = slot_lane + ((i * 2 + j) * 4 + q) * 64;
                         __builtin_amdgcn_raw_buffer_store_b128(v, rsw, ((slot0 + l) * (BM * BN / 4) + unit) * 16, 0, 16 /* sc1: write-through */);
                     }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             if (tid == 0) __hip_atomic_store(flags + slot0 + l, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
@@ -351,8 +247,7 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
                         while (__hip_atomic_load(flags + slot0 + q_l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(2);
                     }
                     __syncthreads();
-                    sk_u4 v[TM * TN * 4];
-                    if (worker) {
+                    u32x4 v[TM * TN * 4];
 #pragma unroll
                     for (int u = 0; u < TM * TN * 4; ++u)
                         v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsw, ((slot0 + q_l) * (BM * BN / 4) + slot_lane + u * 64) * 16, 0, 16 /* sc1 */);
@@ -362,17 +257,15 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
                         for (int j = 0; j < TN; ++j)
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                const sk_u4 w = v[(i * 2 + j) * 4 + q];
+                                const u32x4 w = v[(i * 2 + j) * 4 + q];
                                 acc[i][j][4 * q] += __uint_as_float(w.x); acc[i][j][4 * q + 1] += __uint_as_float(w.y);
                                 acc[i][j][4 * q + 2] += __uint_as_float(w.z); acc[i][j][4 * q + 3] += __uint_as_float(w.w);
                             }
-                    }
                     __syncthreads();                            // every lane holds its share: the slot may be recycled
                     if (tid == 0) __hip_atomic_store(flags + slot0 + q_l, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     cov += (int)((q1 - q0) < (long)(nch - cov) ? (q1 - q0) : (long)(nch - cov));
                 }
             }
-            if (worker) {
             if constexpr (LEPI) {
                 constexpr int ERT = 2;
                 float* stage = reinterpret_cast<float*>(smem) + wave * (ERT * 32 * WN);
@@ -384,7 +277,6 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
             } else {
                 gemm_epilogue<TO, TM, TN, WM, WN>(acc, p, m0, n0, 0, 0, wm, wn, lr, lk);
             }
-            }
             __syncthreads();                                    // the staging epilogue read the ring's LDS
         }
         if (dp) ++dp_done; else it += n;
@@ -393,8 +285,9 @@ __global__ __launch_bounds__(PROD ? 384 : 256, NST <= 2 ? 2 : 1) void linear_sk_
 }
 
 // stages: 0 = automatic (fp32: three-stage ring, one workgroup per CU; 16-bit: two stages, two workgroups per CU).
-// Round 3 pruned the A/B losers: the producer-wave form (PROD = true: 93.0 / 88.3 vs 83.9 us) is no longer
-// instantiated, the whole-tiles-first hybrid (87.0 / 87.2 vs 83.7 us) is no longer reachable (tail_tiles stays 0).
+// Measured and removed (LOG.md): a producer-wave form (two extra waves that only issue the DMA: 93.0 / 88.3 vs
+// 83.9 us).  The whole-tiles-first hybrid (87.0 / 87.2 vs 83.7 us) is not reachable — launch_conv_gemm leaves tail_tiles at 0 —
+// but stays in the kernel: without it two of the thirty instantiations spill more registers (profiles/r9/gemm_prims_identity.txt).
 template <typename T, typename TO>
 void launch_linear_sk(const ConvGemmDev& e, int stages, hipStream_t s) {
     constexpr int KC = 128 / (int)sizeof(T);

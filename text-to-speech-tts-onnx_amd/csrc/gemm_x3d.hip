@@ -31,6 +31,7 @@
 #include "mfma.h"
 #include "gemm_epilogue.h"
 #include "x3_split.h"
+#include "lds_dma.h"         // lds_addr, dma16_buf, wait_vm, wait_lgkm, buf_rsrc
 #include <type_traits>
 #include <algorithm>
 
@@ -62,21 +63,8 @@ template <int TW> struct X3dGeom {
     static_assert(SMEM <= 163840, "x3d: LDS");
 };
 
-// one 1 KB piece: 64 lanes x 16 bytes from byte offset voff (per lane; beyond the buffer: zeros, nothing fetched) to LDS byte
-// address lds_dst + 16 * lane.  The whole offset travels in the VGPR: the range check of a raw buffer does not see soffset.
-template <typename RSRC>
-__device__ __forceinline__ void x3d_dma(RSRC rsrc, int voff, unsigned lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void x3d_wait_lgkm() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory");
-#endif
-}
+// A DMA piece here (dma16_buf, lds_dma.h) is 1 KB: 64 lanes x 16 bytes from byte offset voff (per lane) to LDS byte address
+// lds_dst + 16 * lane.  The whole offset travels in the VGPR: the range check of a raw buffer does not see soffset.
 // N fragment reads (16 bytes per lane, 1 KB apart) from LDS byte address a + OFF: inline asm, NOT waited for by the compiler
 template <int OFF> __device__ __forceinline__ void x3d_lds_rd128(f16x8& d, unsigned a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -95,12 +83,6 @@ template <int OFF> struct X3dRd<OFF, 1> {
 template <int N, int I = 0, typename F> __device__ __forceinline__ void x3d_unroll(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); x3d_unroll<N, I + 1>(f); }
 }
-template <int N> __device__ __forceinline__ void x3d_wait_vm() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-#endif
-}
-
 // p.x = A panel planes, p.w3 = B panel planes (np = 2), p.Tm x p.Tn = row groups x column groups, p.RT = band height of the
 // tile order (row groups an XCD's 32 consecutive tiles span), p.dbg bit 2: no epilogue (tuning)
 template <int TW, bool FOLD, int EPK>
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
 
     // ---- LDS-DMA pieces of this wave: piece q = wave + 12 i of the step's P (chunk-in-step, operand, plane, 16-row group) -----
     const int bytesA = (int)((long)((p.M + 127) >> 7) * nch * 16384), bytesB = (int)((long)((p.N + 127) >> 7) * nch * 16384);
-    const unsigned smem_lds = (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)smem;
+    const unsigned smem_lds = lds_addr(smem);
     const int voff = lane * 16;
     constexpr int OOB = 0x7fffff00;
     int pc_gbase[G::NHI], pc_cs[G::NHI];
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
         const int plane = rr / gpp, g16 = rr - plane * gpp;
         const int row = (isA ? m0 : n0) + 16 * g16;
         pc_cs[i] = cs;
-        pc_rs[i] = __builtin_amdgcn_make_buffer_rsrc(isA ? (void*)p.x : (void*)p.w3, 0, isA ? bytesA : bytesB, 0x00020000);
+        pc_rs[i] = buf_rsrc(isA ? p.x : p.w3, isA ? bytesA : bytesB);
         pc_gbase[i] = __builtin_amdgcn_readfirstlane((row >> 7) * nch * 16384 + plane * 8192 + (row & 127) * 64);
         pc_lofs[i] = (unsigned)__builtin_amdgcn_readfirstlane(isA ? plane * G::A_PLANE + g16 * 1024 : G::A_BYTES + plane * G::B_PLANE + g16 * 1024);
     }
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
             const int chunk = t * G::S + pc_cs[i];
             const int soff = __builtin_amdgcn_readfirstlane(chunk < nch ? pc_gbase[i] + chunk * 16384 : OOB);
             const unsigned dst = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((chunk % G::R) * G::CH) + pc_lofs[i]);
-            x3d_dma(pc_rs[i], (int)((unsigned)voff + (unsigned)soff), dst);
+            dma16_buf(pc_rs[i], (int)((unsigned)voff + (unsigned)soff), dst);
         }
     };
     auto issue_batch = [&](int t) __attribute__((always_inline)) {
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
     };
     auto wait_batches = [&](auto NB_) __attribute__((always_inline)) {    // all but the NB_ youngest batches of this wave have landed
         constexpr int n = decltype(NB_)::value;
-        if (hi_wave) x3d_wait_vm<n * G::NHI>(); else x3d_wait_vm<n * (G::NHI - 1)>();
+        if (hi_wave) wait_vm<n * G::NHI>(); else wait_vm<n * (G::NHI - 1)>();
     };
 
     // ---- fragment addresses: MFMA row i = lane & 15 <-> row 4 sigma(i >> 2) + (i & 3) of the 16-row block, k-slot lane >> 4 ------
@@ -232,18 +214,18 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
     // matrix pipe idled for them).  Past the last chunk the barrier block runs once more: zero fill into a dead slot.
     auto chunk = [&](int j, auto BAR_) __attribute__((always_inline)) {
         constexpr bool BAR = decltype(BAR_)::value;
-        x3d_wait_lgkm<MB + NB>();                                   // lo(A), hi(B) of this chunk are in (hi(A), lo(B) may be on their way)
+        wait_lgkm<MB + NB>();                                   // lo(A), hi(B) of this chunk are in (hi(A), lo(B) may be on their way)
         X3D_SB(); mma(a_lo, b_hi, acc1); X3D_SB();                  // phase 0: lo(A) x hi(B)
         const int jn = j + 1;
         const int ts = jn / G::WSTEP;
         if constexpr (BAR) {
             wait_batches(std::integral_constant<int, G::LB - 1>{});
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();
         }
         const unsigned sn = smem_lds + (unsigned)(((jn * G::KG + kg) % G::R) * G::CH);
         rd_a(sn + fa_off, P1{}, a_lo);
-        x3d_wait_lgkm<MB>();                                        // hi(A), lo(B) are in
+        wait_lgkm<MB>();                                        // hi(A), lo(B) are in
         X3D_SB();
         x3d_unroll<MB * NB>([&](auto IDX_) __attribute__((always_inline)) {       // phase 1: hi x hi
             constexpr int idx = decltype(IDX_)::value, i = idx / NB, jj = idx % NB;
@@ -261,8 +243,8 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
         chunk(j + G::WSTEP - 1, std::true_type{});
     }
 #undef X3D_SB
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_vm<0>();
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     if (p.dbg & 4) return;                                         // tuning: main loop only
 

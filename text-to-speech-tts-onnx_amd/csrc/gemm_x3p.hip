@@ -26,7 +26,7 @@
 //    32x64 wave tiles of round 2); the two groups' accumulators meet once per tile in LDS.  Two waves per SIMD.
 //  * LDS-DMA ring.  NP = 3: three stages of 48 KB, one barrier per chunk in front of the last six MFMAs.  NP = 2 (fp16
 //    {hi, lo * 2^11} pairs, the default — three MFMAs per block on two accumulator sets): FIVE stages of 32 KB (all 160 KB)
-//    and ONE barrier per TWO chunks (X3P_BAR2): the DMA of chunk c + 4 is issued first in the body into the stage chunk
+//    and ONE barrier per TWO chunks (BAR2): the DMA of chunk c + 4 is issued first in the body into the stage chunk
 //    c - 1 left, the fragments of chunk c + 1 are read into a second register set under the MFMAs of chunk c, every wait
 //    is a counted vmcnt.
 //  * One epilogue per instantiation (EPK, round 4): the kernel sits at the 256-VGPR limit and each epilogue compiled into
@@ -41,6 +41,7 @@
 #include "mfma.h"
 #include "gemm_epilogue.h"
 #include "x3_split.h"
+#include "lds_dma.h"         // lds_addr, dma16_buf, wait_vm, wait_lgkm, buf_rsrc
 #include <type_traits>
 
 namespace mi {
@@ -62,12 +63,12 @@ __global__ __launch_bounds__(256) void x3p_split_rows_kernel(const float* __rest
         v0 = src[0]; v1 = src[1];
     }
     const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    x3_u4 pl[NP];
+    u32x4 pl[NP];
     unsigned sat = 0;
     xnp_split8_sat<NP>(v, pl, sat);
     unsigned char* dst = out + x3p_slot_offset(row, s8, K >> 5, NP);
 #pragma unroll
-    for (int q = 0; q < NP; ++q) *reinterpret_cast<x3_u4*>(dst + q * X3P_PLANE) = pl[q];
+    for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
     if constexpr (NP == 2) sat_publish(satp, sat);
 }
 
@@ -87,17 +88,9 @@ void x3p_split_rows(const float* x, long ld, void* planes, int rows, int K, hipS
     MI_HIP(hipGetLastError());
 }
 
-template <typename RSRC>
-__device__ __forceinline__ void x3p_dma16(RSRC rsrc, int voff, unsigned lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-#endif
-}
-
-// the same with an instruction offset OFF (0 / 1024 / 2048 / 3072): it advances the global address AND the LDS address, and the
-// operand chunk is laid out in LDS exactly as in memory, so four consecutive 1 KB pieces share one M0 value
+// The prologue uses dma16_buf (lds_dma.h: M0 saved / set / restored per instruction).  In the loop M0 is set once (x3p_set_m0) for
+// four pieces, each a buffer_load ... lds with an instruction offset OFF (0 / 1024 / 2048 / 3072): the offset advances the global
+// address AND the LDS address, and the operand chunk is laid out in LDS exactly as in memory.
 template <int OFF, typename RSRC>
 __device__ __forceinline__ void x3p_dma16_off(RSRC rsrc, int voff) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -105,11 +98,6 @@ __device__ __forceinline__ void x3p_dma16_off(RSRC rsrc, int voff) {
     else if constexpr (OFF == 1024) asm volatile("buffer_load_dwordx4 %0, %1, 0 offen offset:1024 lds" :: "v"(voff), "s"(rsrc) : "memory");
     else if constexpr (OFF == 2048) asm volatile("buffer_load_dwordx4 %0, %1, 0 offen offset:2048 lds" :: "v"(voff), "s"(rsrc) : "memory");
     else asm volatile("buffer_load_dwordx4 %0, %1, 0 offen offset:3072 lds" :: "v"(voff), "s"(rsrc) : "memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void x3p_wait_vm() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
 #endif
 }
 __device__ __forceinline__ void x3p_set_m0(unsigned v) {
@@ -136,23 +124,17 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
     using MF = std::conditional_t<NP == 3, Mfma<bf16>, Mfma<f16>>;
     using Frag = typename MF::Frag;
     constexpr int BM = 128, BN = 128, WM = 64, WN = 64, TM = 2, TN = 2;
-#ifndef X3P_NST2
-#define X3P_NST2 4
-#endif
-    // LDS stages: a chunk is requested NST - 1 chunk times before its barrier.  Three for NP = 3 (a chunk time is ~3000 clk);
-    // with half the MFMAs per chunk (NP = 2) the same distance in TIME needs one stage more (32 KB stages: 128 KB)
-#ifndef X3P_BAR2
-#define X3P_BAR2 1          // -DX3P_BAR2=0: the round-3 loop (four stages, a barrier per chunk) for A/B builds
-#endif
+    // LDS stages (NST): three for NP = 3 — a chunk is requested NST - 1 chunk times (~3000 clk each) before its barrier.
     // BAR2 (NP = 2, round 4): five stages = the whole 160 KB of LDS, ONE barrier per TWO chunks.  With a barrier per 12 MFMAs both
     // waves of every SIMD park together (PMC: 42 % of the wave cycles in s_waitcnt / s_barrier); here the boundary after an odd
     // chunk makes chunks c+2 AND c+3 visible (only the youngest request, chunk c+4, stays in flight), the even chunk runs into the
     // odd one without a wait, and each body requests chunk c+4 FIRST (under its first MFMAs: two chunk times of lead, like the
     // three-stage ring that measured the same as four) into the stage of chunk c-1 — read two bodies ago, i.e. always behind a
     // barrier.  Same MFMAs in the same order on the same fragments: bit-identical results (checked: int16 waveforms array_equal).
-    // Same-box A/B (tools/dbg/ab_bar2.sh, profiles/r4/x3p_bar2_ab.txt): 51.5 -> 50.35 us per launch, step 182.8 -> 178.8 ms.
-    constexpr bool BAR2 = (X3P_BAR2 != 0) && NP == 2;             // (round 5: the tuning instantiations run the product loop too)
-    constexpr int NST = NP == 3 ? 3 : (BAR2 ? 5 : X3P_NST2);
+    // Same-box A/B against the round-3 loop (four stages, a barrier per chunk; profiles/r4/x3p_bar2_ab.txt): 51.5 -> 50.35 us per
+    // launch, step 182.8 -> 178.8 ms.
+    constexpr bool BAR2 = NP == 2;                                // (round 5: the tuning instantiations run the product loop too)
+    constexpr int NST = NP == 3 ? 3 : 5;
     constexpr int CHB = NP * X3P_PLANE;                         // bytes of one operand chunk
     constexpr int STAGE = 2 * CHB;                              // 48 | 32 KB: A chunk then B chunk
     constexpr int PER = 2 * NP;                                 // DMA instructions per wave per chunk (1 KB each, 8 waves)
@@ -182,12 +164,12 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
     const long it1 = (long)(l + 1) * I / R;
     const int slot0 = xg * R;
 
-    __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.sk_ws, 0, (int)((long)P * BM * BN * 4), 0x00020000);
+    __amdgpu_buffer_rsrc_t rsw = buf_rsrc(p.sk_ws, (int)((long)P * BM * BN * 4));
     const bool opA = wave < 4;                                  // waves 0-3 stage the A chunk, waves 4-7 the B chunk
     constexpr int OOB = 0x7fffff00;
-    const unsigned smem_lds = (unsigned)(unsigned long)(const __attribute__((address_space(3))) void*)smem;
+    const unsigned smem_lds = lds_addr(smem);
     int* flags = p.sk_flags;
-    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)(opA ? p.x : p.w3), 0, (int)((long)(opA ? p.Tm : p.Tn) * nch * CHB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsd = buf_rsrc(opA ? p.x : p.w3, (int)((long)(opA ? p.Tm : p.Tn) * nch * CHB));
     const int lane16 = lane * 16;
     const unsigned lds_part = (unsigned)((opA ? 0 : CHB) + w4 * PER * 1024);
     // fragment addresses inside a stage: row (wm*64 + i*32 + lr) of plane pl, k-slot 2*kg + lk, swizzled
@@ -229,7 +211,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
             const unsigned base = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)(st * STAGE) + lds_part);
             if constexpr (DBG & 1) return;
 #pragma unroll
-            for (int j = 0; j < PER; ++j) x3p_dma16(rsd, (int)((unsigned)vb[j] + (unsigned)coff), base + (unsigned)(j * 1024));
+            for (int j = 0; j < PER; ++j) dma16_buf(rsd, (int)((unsigned)vb[j] + (unsigned)coff), base + (unsigned)(j * 1024));
         };
 
         // AdaLN fold, consumer side: the LayerNorm statistics of the 32 rows this wave will own in the epilogue (block wm * 2 + kg of the
@@ -279,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
         constexpr int NPRE = BAR2 ? NST - 1 : NST;             // chunks requested by the prologue
 #pragma unroll
         for (int q = 0; q < NPRE; ++q) issue(q, cb + q);
-        x3p_wait_vm<(NPRE - 1) * PER>();
+        wait_vm<(NPRE - 1) * PER>();
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int q = 0; q < NR; ++q) ldfrag1(smem + fa_off, smem + fb_off, std::integral_constant<int, 0>{}, q);
@@ -287,8 +269,8 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
 #pragma unroll
             for (int q = 0; q < NR; ++q) ldfrag1(smem + fa_off, smem + fb_off, std::integral_constant<int, 1>{}, q);
         }
-        x3p_wait_vm<(BAR2 ? 1 : NST - 2) * PER>();              // BAR2: chunks cb+1 AND cb+2 landed (cb+3 may be in flight)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_vm<(BAR2 ? 1 : NST - 2) * PER>();              // BAR2: chunks cb+1 AND cb+2 landed (cb+3 may be in flight)
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();                           // chunk cb+1 landed, stage 0 free
         int st_next = 1, st_free = BAR2 ? 4 : 0;                // stage of chunk c+1 ; stage the chunk requested in body(c) goes to (chunk c+NST -> stage of chunk c ; BAR2: chunk c+4 -> stage of chunk c-1)
         // One chunk: 24 MFMAs on the fragments of chunk c (register set SET).  Under twelve of them the fragments of chunk c+1
@@ -310,8 +292,8 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
                 if constexpr (DBG & 32) return;                 // tuning: no waits, no barriers in the loop (wrong numbers, right MFMA stream)
                 // chunk c+2 has landed (this wave's PER pieces of chunk c+3 may stay in flight), the fragments of chunk c+1 are
                 // in registers (its stage is free); for NP = 3 the last six MFMAs run behind the barrier
-                x3p_wait_vm<(BAR2 ? 1 : NST - 2) * PER>();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_vm<(BAR2 ? 1 : NST - 2) * PER>();
+                wait_lgkm<0>();
                 __builtin_amdgcn_s_barrier();
             };
 #pragma unroll
@@ -350,8 +332,8 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
             }
         }
 #undef X3P_SB
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_vm<0>();
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         f32x16 (&acc)[TM][TN] = accs[0];
         if constexpr (NP == 2) {
@@ -369,13 +351,13 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
         //      (with waves 4-7 merely handing their sums to waves 0-3 the epilogue phase ran on half the workgroup) ----
         f32x16 h[1][TN];
         {
-            x3_u4* red = reinterpret_cast<x3_u4*>(smem);             // [wave][j][q][lane] 16-byte units: 8 KB per wave
+            u32x4* red = reinterpret_cast<u32x4*>(smem);             // [wave][j][q][lane] 16-byte units: 8 KB per wave
             auto park = [&](const f32x16 (&src)[TN]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        x3_u4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(src[j][4 * q]); v.y = __float_as_uint(src[j][4 * q + 1]);
                         v.z = __float_as_uint(src[j][4 * q + 2]); v.w = __float_as_uint(src[j][4 * q + 3]);
                         red[(wave * 8 + j * 4 + q) * 64 + lane] = v;
@@ -387,7 +369,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const x3_u4 v = red[(other * 8 + j * 4 + q) * 64 + lane];
+                        const u32x4 v = red[(other * 8 + j * 4 + q) * 64 + lane];
                         h[0][j][4 * q] = mine[j][4 * q] + __uint_as_float(v.x); h[0][j][4 * q + 1] = mine[j][4 * q + 1] + __uint_as_float(v.y);
                         h[0][j][4 * q + 2] = mine[j][4 * q + 2] + __uint_as_float(v.z); h[0][j][4 * q + 3] = mine[j][4 * q + 3] + __uint_as_float(v.w);
                     }
@@ -400,6 +382,9 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
         const int wm2 = wm * 2 + kg;                            // 32-row block of the tile this wave now owns
 
         // ---- partial tile: publish or collect (gemm_sk.hip), eight waves x 8 KB ------------------------------------------------
+        // (this hand-off is written out four times — gemm_sk.hip, gemm_x3.hip, gemm_x3p.hip and, with its own slot geometry, gemm_ph8.hip:
+        //  a fix to the protocol goes into all four; shared inline helpers changed the compiled code, profiles/r9/gemm_prims_identity.txt)
+        // (only this copy bounds its spin)
         const int slot_lane = (wave * (TN * 4)) * 64 + lane;
         if (p.dbg & 4) { it += n; continue; }                  // tuning: no fix-up, no epilogue
         if (cb > 0) {
@@ -407,13 +392,13 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    x3_u4 v;
+                    u32x4 v;
                     v.x = __float_as_uint(h[0][j][4 * q]); v.y = __float_as_uint(h[0][j][4 * q + 1]);
                     v.z = __float_as_uint(h[0][j][4 * q + 2]); v.w = __float_as_uint(h[0][j][4 * q + 3]);
                     const int unit = slot_lane + (j * 4 + q) * 64;
                     __builtin_amdgcn_raw_buffer_store_b128(v, rsw, ((slot0 + l) * (BM * BN / 4) + unit) * 16, 0, 16);
                 }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             if (tid == 0) __hip_atomic_store(flags + slot0 + l, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
@@ -435,7 +420,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
                     }
                     __syncthreads();
                     {
-                        x3_u4 v[TN * 4];
+                        u32x4 v[TN * 4];
 #pragma unroll
                         for (int u = 0; u < TN * 4; ++u)
                             v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsw, ((slot0 + q_l) * (BM * BN / 4) + slot_lane + u * 64) * 16, 0, 16);
@@ -443,7 +428,7 @@ __global__ __launch_bounds__(512, 1) void linear_x3p_kernel(const ConvGemmDev p)
                         for (int j = 0; j < TN; ++j)
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                const x3_u4 w = v[j * 4 + q];
+                                const u32x4 w = v[j * 4 + q];
                                 h[0][j][4 * q] += __uint_as_float(w.x); h[0][j][4 * q + 1] += __uint_as_float(w.y);
                                 h[0][j][4 * q + 2] += __uint_as_float(w.z); h[0][j][4 * q + 3] += __uint_as_float(w.w);
                             }

@@ -16,6 +16,7 @@
 #include "gpt.h"
 #include "gpt_pick.h"
 #include "mfma.h"
+#include "lds_dma.h"         // buf_rsrc
 #include "wave_reduce.h"
 
 namespace mi {
@@ -109,10 +110,9 @@ __device__ inline float gelu_new(float x) {
 #else
 #define GPT_WLOAD ld16
 #endif
-typedef unsigned int gd_u4 __attribute__((ext_vector_type(4)));
 template <typename T> __device__ inline Pack16<T> ldnt16(const T* p) {
     Pack16<T> r;
-    *reinterpret_cast<gd_u4*>(&r) = __builtin_nontemporal_load(reinterpret_cast<const gd_u4*>(p));
+    *reinterpret_cast<u32x4*>(&r) = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     return r;
 }
 
@@ -255,8 +255,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_d_kernel(const T* __restrict_
     } else {
         const T* xr = (const T*)xin;
         constexpr int XI = (KI + WAVES - 1) / WAVES;       // the x row first (L2), then the weights (HBM)
-        gd_u4 xv[XI];                                      // bounds-checked buffer loads: 0 beyond K, no branch
-        const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)xr, 0, K * (int)sizeof(T), 0x00020000);
+        u32x4 xv[XI];                                      // bounds-checked buffer loads: 0 beyond K, no branch
+        const __amdgpu_buffer_rsrc_t rsx = buf_rsrc(xr, K * (int)sizeof(T));
 #pragma unroll
         for (int i = 0; i < XI; ++i)
             xv[i] = __builtin_amdgcn_raw_buffer_load_b128(rsx, (int)((threadIdx.x + i * WAVES * 64) * 16), 0, 0);
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_d_kernel(const T* __restrict_
         load_weights();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < XI; ++i) *reinterpret_cast<gd_u4*>(&xt[(threadIdx.x + i * WAVES * 64) * V]) = xv[i];
+        for (int i = 0; i < XI; ++i) *reinterpret_cast<u32x4*>(&xt[(threadIdx.x + i * WAVES * 64) * V]) = xv[i];
         __syncthreads();
     }
     float acc[R];                                         // rows beyond N: computed on clamped rows, never stored

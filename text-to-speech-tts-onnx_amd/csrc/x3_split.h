@@ -5,7 +5,6 @@
 
 namespace mi {
 
-typedef unsigned int x3_u4 __attribute__((ext_vector_type(4)));
 typedef float x3_f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 x3_b2 __attribute__((ext_vector_type(2)));
 
@@ -83,7 +82,7 @@ __device__ __forceinline__ unsigned f16_range_word(const float (&v)[8]) {
     return m > 65504.0f ? 1u : 0u;              // (a NaN operand is not a range event: it propagates and the parity gates see it)
 }
 // eight consecutive values -> the 16-byte slot of each plane
-template <int NP> __device__ __forceinline__ void xnp_split8(const float (&v)[8], x3_u4 (&pl)[NP]) {
+template <int NP> __device__ __forceinline__ void xnp_split8(const float (&v)[8], u32x4 (&pl)[NP]) {
     unsigned w[NP][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -91,10 +90,10 @@ template <int NP> __device__ __forceinline__ void xnp_split8(const float (&v)[8]
         else x2_split_pair(v[2 * i], v[2 * i + 1], w[0][i], w[1][i]);
     }
 #pragma unroll
-    for (int q = 0; q < NP; ++q) pl[q] = x3_u4{w[q][0], w[q][1], w[q][2], w[q][3]};
+    for (int q = 0; q < NP; ++q) pl[q] = u32x4{w[q][0], w[q][1], w[q][2], w[q][3]};
 }
 // ... and the range watch of the pair format folded in (three bf16 planes cover the whole fp32 exponent range: nothing to watch)
-template <int NP> __device__ __forceinline__ void xnp_split8_sat(const float (&v)[8], x3_u4 (&pl)[NP], unsigned& sat) {
+template <int NP> __device__ __forceinline__ void xnp_split8_sat(const float (&v)[8], u32x4 (&pl)[NP], unsigned& sat) {
     xnp_split8<NP>(v, pl);
     if constexpr (NP == 2) sat |= x2_sat_word(pl[0].x) | x2_sat_word(pl[0].y) | x2_sat_word(pl[0].z) | x2_sat_word(pl[0].w);
 }

@@ -2,14 +2,20 @@
 """Did a host-only change leave the device code alone?
 
     hipcc <build.py FLAGS> -S --cuda-device-only csrc/X.hip -o a/X.s      (once per tree)
-    python tools/device_asm_diff.py a/X.s b/X.s
+    python tools/device_asm_diff.py [--map REGEX=REPLACEMENT ...] a/X.s b/X.s
 
  Same kernel symbols, and per kernel the same instruction stream and kernel descriptor, whatever the order
-in which the instantiations were emitted (function-numbered local labels and the per-file __hip_cuid hash are normalised)"""
+in which the instantiations were emitted (function-numbered local labels and the per-file __hip_cuid hash are normalised).
+--map rewrites the first file's text before the comparison, for a kernel whose template parameter list (and so its mangled
+name) changed:  --map '(linear_sk_kernelI\w+?)Lb0E(EEv)=\1\2'  drops a trailing `false` argument."""
 import re, sys
-def load(path):
+args, maps = sys.argv[1:], []
+while "--map" in args:
+    i = args.index("--map"); old, new = args[i + 1].split("=", 1); maps.append((re.compile(old), new)); del args[i:i + 2]
+def load(path, maps=()):
     fn, desc, cur, kind = {}, {}, None, None
     for line in open(path):
+        for rx, new in maps: line = rx.sub(new, line)
         line = re.sub(r"\.L(BB|func_end|func_begin|tmp|JTI)(\d+)", r".L\1#", line.rstrip("\n"))
         if "__hip_cuid_" in line:
             continue
@@ -30,9 +36,9 @@ def load(path):
         if kind == "fn": fn[cur].append(line)
         elif kind == "desc": desc[cur].append(line)
     return fn, desc
-fa, da = load(sys.argv[1]); fb, db = load(sys.argv[2])
+fa, da = load(args[0], maps); fb, db = load(args[1])
 ok = set(fa) == set(fb) and set(da) == set(db)
 bad = [k for k in fa if k in fb and fa[k] != fb[k]] + [k for k in da if k in db and da[k] != db[k]]
-print(f"{sys.argv[2].split('/')[-1]}: {len(da)} kernels, {len(fa)} functions, {sum(len(v) for v in fa.values())} lines; symbols {'identical' if ok else 'DIFFER'}; "
+print(f"{args[1].split('/')[-1]}: {len(da)} kernels, {len(fa)} functions, {sum(len(v) for v in fa.values())} lines; symbols {'identical' if ok else 'DIFFER'}; "
       f"bodies / descriptors {'identical' if not bad else 'DIFFER: ' + ' '.join(bad[:5])}")
 sys.exit(0 if ok and not bad else 1)

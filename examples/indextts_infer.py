@@ -18,6 +18,9 @@ Decoding is greedy like the reference's unless one of --temperature / --top-k / 
 code is drawn on the device (`Sampling`, upstream IndexTTS's temperature 1.0 / top_k 30 / top_p 0.8 where not given).
 `--takes N` decodes every sentence in N batch slots at once, seeds sample-seed .. sample-seed + N - 1, and writes
 <out>_<i>.wav: N takes for the weight traffic of one.
+`--num-beams N` decodes every sentence by beam search instead (upstream IndexTTS runs 3 beams): N hypotheses in N batch slots
+over one shared KV cache, the most probable one goes to the vocoder.  Beam search is deterministic and does not combine with the
+sampling flags.
 """
 import argparse
 import dataclasses
@@ -63,7 +66,8 @@ def build_engines(args, vocab):
         gcfg, ccfg, vcfg = IndexGPTConfig(), IndexCondConfig(), BigVGANConfig.indextts()
         if args.max_generate_length:
             gcfg = dataclasses.replace(gcfg, max_generate_length=args.max_generate_length)
-    gcfg = dataclasses.replace(gcfg, max_batch=max(gcfg.max_batch, args.takes))
+    # batch slots: one sentence at a time here, so its takes or its beams (sentences per batch x beams in general)
+    gcfg = dataclasses.replace(gcfg, max_batch=max(gcfg.max_batch, args.takes, args.num_beams))
     fast = not args.small
     state = lambda spec: weights.synth_state(spec, args.seed, fast=fast)
     cond = IndexCond(ccfg, state(weights.cond_spec(ccfg)))
@@ -90,10 +94,15 @@ def main():
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--sample-seed", type=int, default=None, help="seed of the draws (--seed is the synthetic weights')")
     ap.add_argument("--takes", type=int, default=1, help="decode every sentence N times in one batch, seeds sample-seed .. + N - 1; writes <out>_<i>.wav")
+    ap.add_argument("--num-beams", type=int, default=1, help="beam search with N hypotheses per sentence (1..8; 1 = greedy)")
     args = ap.parse_args()
+    if not 1 <= args.num_beams <= 8:
+        ap.error("--num-beams must be in 1..8")
     if not 1 <= args.takes <= 16:
         ap.error("--takes must be in 1..16 (the engine's batch slots)")
     sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
+    if args.num_beams > 1 and sampled:
+        ap.error("--num-beams does not combine with --temperature / --top-k / --top-p / --sample-seed / --takes: beam search is deterministic")
     take_sampling = [Sampling(1.0 if args.temperature is None else args.temperature, 30 if args.top_k is None else args.top_k,
                               0.8 if args.top_p is None else args.top_p, (args.sample_seed or 0) + i)
                      for i in range(args.takes)] if sampled else None
@@ -146,10 +155,11 @@ def main():
             codes = torch.zeros(max(budget, 1), dtype=torch.int32, device=dev)
             hidden = torch.zeros((max(budget, 1), gcfg.hidden), dtype=torch.float32, device=dev)
             n = gpt.generate_torch(torch.from_numpy(prompt_rows[0]).to(dev), budget, codes, hidden, stop_tokens=stops, repeat_penality=penalty_dev,
-                                   sampling=take_sampling[0] if sampled else None)
+                                   sampling=take_sampling[0] if sampled else None, beams=args.num_beams)
             hidden = hidden[:n].contiguous()
         else:
-            _, hidden, _ = gpt.generate(conds_latent[None], ids, stop_tokens=stops, sampling=take_sampling[0] if sampled else None)
+            _, hidden, _ = gpt.generate(conds_latent[None], ids, stop_tokens=stops, sampling=take_sampling[0] if sampled else None,
+                                        beams=args.num_beams)
             n = hidden.shape[0]
         print(f"Decode Speed: {n / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n} tokens)")
         n_codes += n

@@ -299,6 +299,49 @@ int         mi_gpt_sample_logits(const float* logits, const float* pen, int rows
                                  const int32_t* top_k, const float* top_p, const uint64_t* seeds, const int64_t* positions,
                                  int32_t* tokens, float* u_out, float* prob_out, int mem);
 
+/* ---- beam search: num_beams hypotheses per sentence over one shared KV cache, on the device ------------------------------------
+ * The scheme of upstream IndexTTS's third knob (it runs 3 beams) in its simplest exact form.  One sentence runs with
+ * B = num_beams hypotheses in B consecutive slots; its starting penalty vector is pen0.
+ *   Selection 0.  The one prompt pass gives logits L.  z[c] = L[c] * pen0[c] in fp32 (one multiply: the reference's penalty,
+ *      its quirk on negative logits included), lp[c] = z[c] - lse(z), lse(z) = m + log(sum exp(z - m)), m = max z.  Hypotheses
+ *      0..B-1 are the B codes of largest lp in descending order, a tie going to the lower code; score_b = lp[c_b].
+ *   Selection n >= 1.  Every hypothesis b runs one decode step (graph C of its last token at gen_len = n, keys and values of
+ *      its own history) that gives L_b; z_b = L_b * pen_b, cand(b, c) = score_b + (z_b[c] - lse(z_b)).  The new hypotheses
+ *      0..B-1 are the B largest candidates over all B * codes in descending order, a tie going to the lower flat index
+ *      b * codes + c.  New hypothesis i = (parent b_i, code c_i) takes score = cand and inherits everything from its parent:
+ *      token history, KV history, penalty vector, reset index, last_hidden_state rows.  It then does the greedy loop's
+ *      bookkeeping with its own token: token store, penalty write, reset over penalty_range.
+ *   End.  The sentence is done after selection n when hypothesis 0's token is a stop id or n + 1 == max_new; the stop token is
+ *      stored and counted and, as in the greedy loop, not penalised.  The result is hypothesis 0: its n + 1 tokens, its n + 1
+ *      last_hidden_state rows (row n = the row of the forward pass whose logits produced token n, on that hypothesis' own
+ *      path: what graph F consumes), its score, and its penalty vector written back to repeat_penality.
+ *   Property: a hypothesis other than 0 that emits a stop id stays an ordinary hypothesis — the token is stored and penalised
+ *      like any other and the hypothesis keeps decoding.  There is no pool of finished hypotheses and no length penalty
+ *      (upstream's default is 0).
+ *   num_beams == 1 is greedy exactly: the argmax of z, lowest index on ties, the choice not passing through lse: the tokens
+ *      and rows of mi_gpt_generate_batch.
+ * Scores are fp32 and the order of the sum inside lse is the implementation's (fixed: the same bits from every launch, slot,
+ * batch and graph replay), so scores hold to a tolerance against another evaluation order and the choice holds wherever
+ * rounding cannot decide.  Nothing is copied when hypotheses change slots: cache rows written so far never change, so the
+ * prompt's keys and values are stored once per sentence (in the group's first slot) and every later position is read from the
+ * slot a small per-hypothesis ancestor table names.  Beams and sampling do not combine: beam search is deterministic.
+ *
+ * MI_EINVAL, with the handle still usable: num_beams < 1 or > 8, nb * num_beams above the handle's max_batch, num_beams >
+ * mel_codes, and what mi_gpt_generate_batch rejects.
+ *
+ * nb sentences, each with num_beams hypotheses in num_beams consecutive slots; arguments as mi_gpt_generate_batch;
+ * scores (nb) or NULL = hypothesis 0's cumulative log-probability; repeat_penality (nb, mel_codes) in/out or NULL. */
+int         mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                 const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                                 float* repeat_penality, int num_beams, int32_t* tokens, float* hidden, int cap, int32_t* n_out,
+                                 float* scores, int mem);
+/* unit entry (tests, no handle): one selection on rows of logits.  logits, pen (or NULL = ones): (groups*beams, codes);
+ * prev_scores (groups*beams); first != 0: selection 0 (only row g*beams of each group is read, prev_scores ignored).
+ * Outputs (groups*beams): parents (row inside the group), tokens, scores.  1 <= codes <= 16384, 1 <= beams <= 8,
+ * beams <= codes. */
+int         mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_scores, int groups, int beams, int codes,
+                               int first, int32_t* parents, int32_t* tokens, float* scores, int mem);
+
 /* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
  * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these
  * host arrays of nb parameters.  The slots are marked done for the measurement: no token is stored and no state moves.    */

@@ -964,6 +964,136 @@ int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const
     });
 }
 
+// beam search (gpt_beam.hip): gpt_generate_batch_impl's loop over nb groups of B slots
+int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                         const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, float* repeat_penality,
+                         int num_beams, int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_generate_beam";
+        GPT_CHECK(h, mem, "mi_gpt_generate_beam");
+        Gpt& e = *h->impl;
+        const GptCfg& c = e.cfg;
+        const int B = num_beams;
+        MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
+        MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
+        MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
+        MI_REQUIRE(nb >= 1 && (long)nb * B <= c.max_batch, who + ": nb * num_beams exceeds the handle's max_batch");
+        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+        hipStream_t s = e.stream;
+        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        std::vector<int32_t> stops(n_stop);
+        if (n_stop) {
+            if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
+            else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+        }
+        for (int b = 0; b < nb; ++b) {
+            MI_REQUIRE(prompt_rows[b] >= 1 && max_new[b] >= 0 && max_new[b] <= cap, who + ": prompt_rows / max_new");
+            MI_REQUIRE(max_new[b] == 0 || prompt_rows[b] + max_new[b] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
+            MI_REQUIRE(max_new[b] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+        }
+        struct BeamScope { Gpt& e; ~BeamScope() { e.beams = 0; } } scope{e};
+        e.beams = B;
+        e.sampled = 0;
+        e.beam_ensure();
+        const int nr = nb * B;
+        // pen0 of sentence g -> side 0 of the group's first slot (selection 0 reads it there)
+        std::vector<float> ones;
+        if (!repeat_penality) ones.assign(c.mel_codes, 1.f);
+        for (int g = 0; g < nb; ++g) {
+            float* dst = e.pen.as<float>() + (size_t)g * B * c.mel_codes;
+            if (repeat_penality) MI_HIP(hipMemcpyAsync(dst, repeat_penality + (size_t)g * c.mel_codes, (size_t)c.mel_codes * 4, in, s));
+            else MI_HIP(hipMemcpyAsync(dst, ones.data(), (size_t)c.mel_codes * 4, hipMemcpyHostToDevice, s));
+        }
+        e.set_rep_value(repeat_value);                               // synchronises: `ones` is done with
+        std::vector<int32_t> all((size_t)nr * GS_WORDS, 0);
+        for (int g = 0; g < nb; ++g)
+            for (int i = 0; i < B; ++i) {
+                int32_t* w = &all[((size_t)g * B + i) * GS_WORDS];
+                w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[g];
+                for (int q = 0; q < n_stop; ++q) w[GS_STOP0 + q] = stops[q];
+                if (max_new[g] == 0) w[GS_DONE] = 1;
+            }
+        MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));
+        e.history = 0;
+        bool any = false;
+        size_t row0 = 0;
+        for (int g = 0; g < nb; ++g) {                               // prompt passes, one per sentence, into the group's first slot
+            if (max_new[g] > 0) {
+                MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[g] * c.hidden * 4, in, s));
+                e.forward_rows(prompt_rows[g], 1, g * B);
+                e.beam_select_first(g, B, prompt_rows[g]);
+                any = true;
+            }
+            row0 += prompt_rows[g];
+        }
+        auto read_states = [&] {
+            MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
+            MI_HIP(hipStreamSynchronize(s));
+            bool done = true;
+            for (int g = 0; g < nb; ++g) done &= all[(size_t)g * B * GS_WORDS + GS_DONE] != 0;
+            return done;
+        };
+        int guard_steps = 0;
+        while (any && !read_states()) {
+            e.decode_beam_steps(nb, B, 16);
+            guard_steps += 16;
+            MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
+        }
+        if (!any) read_states();
+        e.history = all[GS_HIST];
+        // hypothesis 0 of every group, gathered along its ancestors into staging, then out like the batched entry's rows
+        e.io_a.ensure((size_t)nb * cap * 4);
+        if (hidden) e.io_b.ensure((size_t)nb * cap * c.hidden * 4);
+        e.beam_gather(nb, B, e.io_a.as<int32_t>(), hidden ? e.io_b.as<float>() : nullptr, cap);
+        for (int g = 0; g < nb; ++g) {
+            const size_t s0 = (size_t)g * B;
+            const int n = all[s0 * GS_WORDS + GS_NDEC];
+            n_out[g] = n;
+            copy_out(tokens ? tokens + (size_t)g * cap : nullptr, e.io_a.as<int32_t>() + (size_t)g * cap, (size_t)n * 4, mem, s);
+            if (hidden)
+                copy_out(hidden + (size_t)g * cap * c.hidden, e.io_b.as<float>() + (size_t)g * cap * c.hidden,
+                         (size_t)n * c.hidden * 4, mem, s);
+            const float* pen_side = ((n & 1) ? e.pen_b.as<float>() : e.pen.as<float>()) + s0 * c.mel_codes;
+            copy_out(repeat_penality ? repeat_penality + (size_t)g * c.mel_codes : nullptr, pen_side, (size_t)c.mel_codes * 4, mem, s);
+            copy_out(scores ? scores + g : nullptr, e.score.as<float>() + s0, 4, mem, s);
+        }
+        MI_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_scores, int groups, int beams, int codes,
+                       int first, int32_t* parents, int32_t* tokens, float* scores, int mem) {
+    return guard([&] {
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_gpt_beam_select: bad mem kind");
+        MI_REQUIRE(logits && (first || prev_scores) && parents && tokens && scores, "mi_gpt_beam_select: null argument");
+        MI_REQUIRE(groups >= 1 && groups <= (1 << 20), "mi_gpt_beam_select: groups");
+        MI_REQUIRE(codes >= 1 && codes <= GPT_BEAM_MAX_CODES, "mi_gpt_beam_select: supports 1..16384 codes");
+        MI_REQUIRE(beams >= 1 && beams <= GPT_BEAM_MAX && beams <= codes, "mi_gpt_beam_select: beams must be in [1, 8] and <= codes");
+        hipStream_t s;
+        MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        struct Fin { hipStream_t s; ~Fin() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } fin{s};
+        DevBuf dl, dp, dv, dpar, dtok, dsc;
+        const size_t rows = (size_t)groups * beams, n = rows * codes;
+        const float* l = (const float*)stage_in(dl, logits, n * 4, mem, s);
+        const float* p = pen ? (const float*)stage_in(dp, pen, n * 4, mem, s) : nullptr;
+        const float* v = first ? nullptr : (const float*)stage_in(dv, prev_scores, rows * 4, mem, s);
+        int32_t *par = parents, *tok = tokens;
+        float* sc = scores;
+        if (mem == MI_HOST) {
+            dpar.ensure(rows * 4); dtok.ensure(rows * 4); dsc.ensure(rows * 4);
+            par = dpar.as<int32_t>(); tok = dtok.as<int32_t>(); sc = dsc.as<float>();
+        }
+        launch_gpt_beam_select_rows(l, p, v, groups, beams, codes, first, par, tok, sc, s);
+        if (mem == MI_HOST) {
+            copy_out(parents, par, rows * 4, mem, s);
+            copy_out(tokens, tok, rows * 4, mem, s);
+            copy_out(scores, sc, rows * 4, mem, s);
+        }
+        MI_HIP(hipStreamSynchronize(s));
+    });
+}
+
 int mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* temperature, const int32_t* top_k, const float* top_p,
                       double* us) {
     return guard([&] {

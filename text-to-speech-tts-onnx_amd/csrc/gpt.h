@@ -36,7 +36,8 @@ struct Gpt {
     DevBuf logits, last, pen, toks, hid, state;       // per slot: [slot][codes] / [slot][h] / [slot][max_seq](x h) / words
     DevBuf Xd, xnd, qkvd, attd, ffd, zd;              // batched decode step: one row per slot
     int MBp = 1;              // max_batch rounded up to a batched-GEMV template width
-    std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;   // decode step over nb slots, keyed by (nb, sampled)
+    // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams)
+    std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;
     DevBuf io_a, io_b;        // host<->device staging
     DevBuf rep_dev;           // REPEAT_PENALITY as a device scalar (read by gpt_pick_kernel, also inside replayed graphs)
     void set_rep_value(float v);
@@ -47,6 +48,18 @@ struct Gpt {
     int sampled = 0;
     DevBuf samp;              // per slot: GptSampleRec (gpt_pick.h), beside the GS_* state and not part of it
     void set_sampling(const void* recs, int nb);      // host GptSampleRec[nb] -> samp (synchronous)
+    // beam search (gpt_beam.hip; the definition is in include/mi355tts.h): a sentence's hypotheses sit in `beams` consecutive
+    // slots.  What follows a hypothesis from slot to slot exists twice, the side in use being GS_NDEC & 1: the penalty vectors
+    // (side 0 = pen, side 1 = pen_b) and the ancestor table anc[side][slot][n] = the slot inside the group that held this
+    // hypothesis' ancestor after selection n — the cache row, token and last_hidden_state row of step n are read from there.
+    int beams = 0;            // 0 outside mi_gpt_generate_beam; forward_rows then leaves the token choice to the caller
+    DevBuf pen_b, anc, score; // allocated by the first beam call
+    void beam_ensure();
+    void beam_select_first(int group, int B, int rows);                               // selection 0 after a prompt pass
+    void decode_beam_eager(int nb, int B);                                            // one step of nb * B hypotheses + selection
+    void decode_beam_steps(int nb, int B, int n);
+    // hypothesis 0 of every group, gathered along its ancestors: tokens (nb, cap), hidden (nb, cap, hidden), device arrays
+    void beam_gather(int nb, int B, int32_t* tokens, float* hidden, int cap);
     hipGraphExec_t step_graph[2] = {nullptr, nullptr};      // by mode
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under
@@ -78,5 +91,11 @@ struct Gpt {
               const float* res, void* kcl, void* vcl, int slot = 0, const float* pre_w = nullptr, const float* pre_b = nullptr,
               float* pre_out = nullptr);
 };
+
+constexpr int GPT_BEAM_MAX = 8;                  // hypotheses per sentence
+constexpr int GPT_BEAM_MAX_CODES = 16384;        // the unit entry's documented range
+// gpt_beam.hip: one selection per group on rows of logits (mi_gpt_beam_select): device arrays of groups * B rows, pen may be null
+void launch_gpt_beam_select_rows(const float* logits, const float* pen, const float* prev, int groups, int B, int codes,
+                                 int first, int32_t* parents, int32_t* tokens, float* scores, hipStream_t s);
 
 }  // namespace mi

@@ -15,6 +15,7 @@
 // not an MFMA tile; the prompt pass (ids_len rows at once) goes through the MFMA implicit-GEMM kernel instead.
 #include "gpt.h"
 #include "gpt_pick.h"
+#include "gpt_vec.h"
 #include "mfma.h"
 #include "lds_dma.h"         // buf_rsrc
 #include "wave_reduce.h"
@@ -47,38 +48,7 @@ int64_t gpt_param_count(const GptCfg& c) {
 // ---------------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T> struct Pack16 {
-    static constexpr int N = 16 / sizeof(T);
-    T v[N];
-};
-template <typename T> __device__ inline Pack16<T> ld16(const T* p) {
-    Pack16<T> r;
-    *reinterpret_cast<uint4*>(&r) = *reinterpret_cast<const uint4*>(p);
-    return r;
-}
-// acc += dot(a[0..V), b[0..V)) with fp32 accumulation; 16-bit types use the packed dot instructions (v_dot2_f32_f16 /
-// v_dot2_f32_bf16: two multiply-adds per lane per issue, no conversions)
-__device__ inline float dot_pack(const Pack16<float>& a, const Pack16<float>& b, float acc) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = fmaf(a.v[e], b.v[e], acc);
-    return acc;
-}
-__device__ inline float dot_pack(const Pack16<f16>& a, const Pack16<f16>& b, float acc) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2* pa = reinterpret_cast<const h2*>(&a);
-    const h2* pb = reinterpret_cast<const h2*>(&b);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_fdot2(pa[e], pb[e], acc, false);
-    return acc;
-}
-__device__ inline float dot_pack(const Pack16<bf16>& a, const Pack16<bf16>& b, float acc) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    const b2* pa = reinterpret_cast<const b2*>(&a);
-    const b2* pb = reinterpret_cast<const b2*>(&b);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_fdot2_f32_bf16(pa[e], pb[e], acc, false);
-    return acc;
-}
+// Pack16 / ld16 / dot_pack: gpt_vec.h
 
 __device__ inline float gelu_new(float x) {
     return 0.5f * x * (1.f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
@@ -1015,6 +985,7 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     // ln_f (-> last_hidden_state) and final_norm in front of the lm_head, one launch
     gemv(head, xl, fn_w.as<float>(), fn_b.as<float>(), logits_s, MI_F32, ACT_NONE, nullptr, nullptr, nullptr, 0,
          lnf_w.as<float>(), lnf_b.as<float>(), last_s);
+    if (beams) return;                         // beam search: the caller's selection 0 follows (gpt_beam.hip)
     float* pen_s = pen.as<float>() + (size_t)slot * c.mel_codes;
     int* st_s = state.as<int>() + (size_t)slot * GS_WORDS;
     int* toks_s = toks.as<int>() + (size_t)slot * S;

@@ -144,6 +144,11 @@ def load() -> C.CDLL:
     L.mi_gpt_generate_batch_sampled.restype = C.c_int
     L.mi_gpt_sample_logits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.mi_gpt_sample_logits.restype = C.c_int
+    L.mi_gpt_generate_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
+                                       C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), vp, C.c_int]
+    L.mi_gpt_generate_beam.restype = C.c_int
+    L.mi_gpt_beam_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int]
+    L.mi_gpt_beam_select.restype = C.c_int
     L.mi_gpt_bench_pick.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_double)]
     L.mi_gpt_bench_pick.restype = C.c_int
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]

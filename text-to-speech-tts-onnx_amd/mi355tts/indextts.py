@@ -95,6 +95,50 @@ def sample_logits(logits, *, temperature, top_k, top_p, seeds, positions, pen=No
     return (toks, u, probs) if return_probs else (toks, u)
 
 
+MAX_BEAMS = 8
+
+
+def _check_beams(beams, nb, cfg, sampling=None):
+    """The ``beams`` keyword of ``IndexGPT.generate*`` (include/mi355tts.h, "beam search"): an integer in [1, 8], not above the
+    code count, nb * beams slots within the engine's max_batch, and never together with ``sampling``."""
+    if isinstance(beams, bool) or int(beams) != beams or not 1 <= beams <= MAX_BEAMS:
+        raise ValueError(f"beams must be an integer in [1, {MAX_BEAMS}], got {beams}")
+    beams = int(beams)
+    if beams > 1:
+        if sampling is not None:
+            raise ValueError("beams and sampling do not combine: beam search is deterministic")
+        if beams > cfg.mel_codes:
+            raise ValueError(f"beams = {beams} exceeds the {cfg.mel_codes} mel codes")
+        if nb * beams > cfg.max_batch:
+            raise ValueError(f"{nb} sentence(s) x {beams} beams need {nb * beams} slots; this engine was created with "
+                             f"max_batch = {cfg.max_batch}")
+    return beams
+
+
+def beam_select(logits, prev_scores=None, *, beams: int, first: bool = False, pen=None):
+    """One beam selection on rows of logits (unit entry mi_gpt_beam_select).  logits (groups * beams, codes), pen likewise or
+    None (= ones), prev_scores (groups * beams,) — ignored when ``first`` (selection 0: only each group's first row is read).
+    Returns (parents, tokens, scores), each (groups, beams): the new hypotheses best first, parents as rows inside the group."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim != 2 or beams < 1 or lg.shape[0] % beams:
+        raise ValueError("logits must be (groups * beams, codes)")
+    rows, codes = lg.shape
+    pn = None if pen is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pen, np.float32), lg.shape))
+    pv = None
+    if not first:
+        pv = np.ascontiguousarray(np.asarray(prev_scores, np.float32).reshape(-1))
+        if pv.size != rows:
+            raise ValueError(f"prev_scores must hold {rows} values")
+    par = np.zeros((rows,), np.int32)
+    tok = np.zeros((rows,), np.int32)
+    sc = np.zeros((rows,), np.float32)
+    _lib.check(_lib.load().mi_gpt_beam_select(
+        lg.ctypes.data, None if pn is None else pn.ctypes.data, None if pv is None else pv.ctypes.data, rows // beams, int(beams),
+        codes, int(bool(first)), par.ctypes.data, tok.ctypes.data, sc.ctypes.data, _lib.MI_HOST), "mi_gpt_beam_select")
+    g = rows // beams
+    return par.reshape(g, beams), tok.reshape(g, beams), sc.reshape(g, beams)
+
+
 class IndexGPT:
     def __init__(self, cfg: IndexGPTConfig, state: Optional[dict] = None, *, blob: Optional[np.ndarray] = None,
                  blob_device=None, dtype: str = "f32", device: int = 0):
@@ -220,10 +264,18 @@ class IndexGPT:
 
     # ---- the per-sentence loop ------------------------------------------------------------------------------------
     def generate_from_prompt(self, prompt, max_new: int, *, stop_tokens=None, repeat_value=None, penalty_range=None,
-                             repeat_penality=None, sampling: Optional[Sampling] = None):
+                             repeat_penality=None, sampling: Optional[Sampling] = None, beams: int = 1):
         """prompt (1, P, hidden) = graph D's output.  Returns (tokens (n,), hidden (n, hidden), repeat_penality).
-        sampling: a ``Sampling`` draws each token on the device; None decodes greedily like the reference."""
+        sampling: a ``Sampling`` draws each token on the device; None decodes greedily like the reference.
+        beams > 1: beam search with that many hypotheses (needs max_batch >= beams); the best hypothesis is returned."""
         c = self.cfg
+        if _check_beams(beams, 1, c, sampling) > 1:
+            res, pen = self.generate_beam([prompt], [max_new], beams, stop_tokens=stop_tokens, repeat_value=repeat_value,
+                                          penalty_range=penalty_range,
+                                          repeat_penality=self.repeat_penality if repeat_penality is None else repeat_penality)
+            if repeat_penality is None:
+                self.repeat_penality = pen
+            return res[0][0], res[0][1], pen
         p = np.ascontiguousarray(prompt, dtype=np.float32)
         if p.ndim != 3 or p.shape[0] != 1 or p.shape[2] != c.hidden or p.shape[1] < 1:
             raise ValueError(f"prompt must be (1, P >= 1, {c.hidden}), got {p.shape}")
@@ -250,13 +302,14 @@ class IndexGPT:
         return toks[: n.value].copy(), hid[: n.value].copy(), pen
 
     def generate_torch(self, prompt, max_new: int, tokens, hidden, *, stop_tokens=None, repeat_value=None,
-                       penalty_range=None, repeat_penality=None, sampling: Optional[Sampling] = None) -> int:
+                       penalty_range=None, repeat_penality=None, sampling: Optional[Sampling] = None, beams: int = 1) -> int:
         """Device-resident variant: prompt (P, hidden) float32 CUDA tensor; tokens (>= max_new) int32 and hidden
         (>= max_new, hidden) float32 CUDA tensors are filled; repeat_penality (mel_codes) float32 CUDA tensor or None
         (= ones, not written back).  Returns the number of tokens produced."""
         import ctypes as C
         import torch
         c = self.cfg
+        beams = _check_beams(beams, 1, c, sampling)
         assert prompt.is_cuda and prompt.dtype == torch.float32 and prompt.is_contiguous() and prompt.shape[-1] == c.hidden
         assert tokens.is_cuda and tokens.dtype == torch.int32 and tokens.numel() >= max_new
         assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.is_contiguous() and hidden.shape[0] >= max_new
@@ -269,7 +322,13 @@ class IndexGPT:
                 int(c.penalty_range if penalty_range is None else penalty_range),
                 repeat_penality.data_ptr() if repeat_penality is not None else None, tokens.data_ptr(), hidden.data_ptr(),
                 C.byref(n), _lib.MI_DEVICE)
-        if sampling is None:
+        if beams > 1:
+            assert tokens.is_contiguous()
+            rows, mx = np.array([prompt.shape[-2]], np.int32), np.array([int(max_new)], np.int32)
+            _lib.check(_lib.load().mi_gpt_generate_beam(self._h, 1, args[1], _lib.i32p(rows), _lib.i32p(mx), *args[4:9], beams,
+                                                        tokens.data_ptr(), hidden.data_ptr(), int(max_new), C.byref(n), None,
+                                                        _lib.MI_DEVICE), "mi_gpt_generate_beam")
+        elif sampling is None:
             _lib.check(_lib.load().mi_gpt_generate(*args), "mi_gpt_generate")
         else:
             _lib.check(_lib.load().mi_gpt_generate_sampled(*args, float(sampling.temperature), int(sampling.top_k),
@@ -278,13 +337,18 @@ class IndexGPT:
         return int(n.value)
 
     def generate_batch(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None,
-                       repeat_penality=None, sampling=None):
+                       repeat_penality=None, sampling=None, beams: int = 1):
         """Several sentences at once (engine extension: the reference decodes one sentence at a time).  prompts = list
         of (1, P_b, hidden) graph-D outputs, max_new = list of per-sentence limits.  Every decode step streams the
         weights once for all sentences.  Returns a list of (tokens, hidden) and the (nb, mel_codes) penalty matrix.
-        sampling: None (greedy), one ``Sampling`` for every sentence, or a list of nb ``Sampling`` / None (greedy item)."""
+        sampling: None (greedy), one ``Sampling`` for every sentence, or a list of nb ``Sampling`` / None (greedy item).
+        beams > 1: beam search, every sentence with that many hypotheses (nb * beams <= max_batch)."""
         c = self.cfg
         nb = len(prompts)
+        if _check_beams(beams, nb, c, sampling) > 1:
+            res, pen = self.generate_beam(prompts, max_new, beams, stop_tokens=stop_tokens, repeat_value=repeat_value,
+                                          penalty_range=penalty_range, repeat_penality=repeat_penality)
+            return [(t, h) for t, h, _ in res], pen
         samp = _batch_sampling(sampling, nb)
         if nb < 1 or nb > c.max_batch or len(max_new) != nb:
             raise ValueError(f"batch of {nb} sentences; this engine was created with max_batch = {c.max_batch}")
@@ -312,12 +376,13 @@ class IndexGPT:
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy()) for b in range(nb)], pen
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
-                             repeat_value=None, penalty_range=None, sampling=None):
+                             repeat_value=None, penalty_range=None, sampling=None, beams: int = 1):
         """Device-resident variant: prompts_cat (sum P_b, hidden) float32 CUDA tensor; tokens (nb, cap) int32 and hidden
         (nb, cap, hidden) float32 CUDA tensors are filled.  Returns the per-sentence token counts."""
         import torch
         c = self.cfg
         nb = len(prompt_rows)
+        beams = _check_beams(beams, nb, c, sampling)
         assert prompts_cat.is_cuda and prompts_cat.dtype == torch.float32 and prompts_cat.is_contiguous()
         assert tokens.is_cuda and tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.shape[0] == nb
         assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.is_contiguous() and hidden.shape[:2] == tokens.shape
@@ -332,7 +397,10 @@ class IndexGPT:
                 len(stops), float(c.repeat_penalty if repeat_value is None else repeat_value),
                 int(c.penalty_range if penalty_range is None else penalty_range), None, tokens.data_ptr(), hidden.data_ptr(),
                 int(tokens.shape[1]), _lib.i32p(n), _lib.MI_DEVICE)
-        if samp is None:
+        if beams > 1:
+            _lib.check(_lib.load().mi_gpt_generate_beam(*args[:10], beams, *args[10:14], None, _lib.MI_DEVICE),
+                       "mi_gpt_generate_beam")
+        elif samp is None:
             _lib.check(_lib.load().mi_gpt_generate_batch(*args), "mi_gpt_generate_batch")
         else:
             sa = _sampling_arrays(samp)
@@ -340,10 +408,41 @@ class IndexGPT:
                        "mi_gpt_generate_batch_sampled")
         return n
 
+    def generate_beam(self, prompts, max_new, beams: int, *, stop_tokens=None, repeat_value=None, penalty_range=None,
+                      repeat_penality=None):
+        """Beam search (include/mi355tts.h, "beam search"; always the beam entry, beams = 1 included): every sentence runs
+        ``beams`` hypotheses over one shared KV cache and its best one is returned.  prompts / max_new as generate_batch.
+        Returns a list of (tokens, hidden, score) — score = the hypothesis' cumulative log-probability — and the
+        (nb, mel_codes) penalty matrix."""
+        c = self.cfg
+        nb = len(prompts)
+        beams = _check_beams(beams, nb, c)
+        if nb < 1 or nb * beams > c.max_batch or len(max_new) != nb:
+            raise ValueError(f"{nb} sentences x {beams} beams; this engine was created with max_batch = {c.max_batch}")
+        ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
+        rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
+        cat = np.ascontiguousarray(np.concatenate(ps, axis=0))
+        mx = np.ascontiguousarray([int(m) for m in max_new], dtype=np.int32)
+        cap = max(int(mx.max()), 1)
+        stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
+        pen = (np.ones((nb, c.mel_codes), np.float32) if repeat_penality is None
+               else np.ascontiguousarray(repeat_penality, dtype=np.float32).reshape(nb, c.mel_codes).copy())
+        toks = np.zeros((nb, cap), np.int32)
+        hid = np.zeros((nb, cap, c.hidden), np.float32)
+        n = np.zeros((nb,), np.int32)
+        sc = np.zeros((nb,), np.float32)
+        _lib.check(_lib.load().mi_gpt_generate_beam(
+            self._h, nb, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None, stops.size,
+            float(c.repeat_penalty if repeat_value is None else repeat_value),
+            int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, beams, toks.ctypes.data,
+            hid.ctypes.data, cap, _lib.i32p(n), sc.ctypes.data, _lib.MI_HOST), "mi_gpt_generate_beam")
+        return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy(), float(sc[b])) for b in range(nb)], pen
+
     def generate(self, conds_latent, text_ids, *, max_generate_length=None, **kw):
         """Inference_IndexTTS_ONNX.py:723-783 for one sentence: B, C, D then E until a stop token or
         MAX_GENERATE_LENGTH - concat_len tokens.  Returns (tokens, save_last_hidden_state (n, hidden), penalty).
-        ``sampling=Sampling(...)`` (passed on to generate_from_prompt) draws the tokens; the default is greedy."""
+        ``sampling=Sampling(...)`` (passed on to generate_from_prompt) draws the tokens, ``beams=N`` runs beam search; the
+        default is greedy."""
         c = self.cfg
         text_h = self.text_embed(text_ids)
         mel_h, _ = self.mel_embed(c.start_mel_token, 0)

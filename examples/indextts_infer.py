@@ -21,6 +21,12 @@ code is drawn on the device (`Sampling`, upstream IndexTTS's temperature 1.0 / t
 `--num-beams N` decodes every sentence by beam search instead (upstream IndexTTS runs 3 beams): N hypotheses in N batch slots
 over one shared KV cache, the most probable one goes to the vocoder.  Beam search is deterministic and does not combine with the
 sampling flags.
+`--queue` decodes the whole text at once instead of sentence by sentence: every sentence is embedded, `generate_queue` runs them
+through `--slots` batch slots (default 8, 1..16) — a slot is refilled as soon as its sentence stops and the prompts admitted
+together share one pass over the weights — and `run_latent_ragged` vocodes them in one forward, in order, with the same gap.
+Every queued sentence starts from a FRESH penalty vector: the sentences run concurrently, so the carry of the vector from one
+sentence to the next that the sentence-by-sentence forms keep (like the reference) does not exist there.  Sampling flags apply
+(one seed per sentence: sample-seed + its index); beams and takes do not go through the queue.
 """
 import argparse
 import dataclasses
@@ -67,7 +73,7 @@ def build_engines(args, vocab):
         if args.max_generate_length:
             gcfg = dataclasses.replace(gcfg, max_generate_length=args.max_generate_length)
     # batch slots: one sentence at a time here, so its takes or its beams (sentences per batch x beams in general)
-    gcfg = dataclasses.replace(gcfg, max_batch=max(gcfg.max_batch, args.takes, args.num_beams))
+    gcfg = dataclasses.replace(gcfg, max_batch=max(gcfg.max_batch, args.takes, args.num_beams, args.slots if args.queue else 1))
     fast = not args.small
     state = lambda spec: weights.synth_state(spec, args.seed, fast=fast)
     cond = IndexCond(ccfg, state(weights.cond_spec(ccfg)))
@@ -95,7 +101,14 @@ def main():
     ap.add_argument("--sample-seed", type=int, default=None, help="seed of the draws (--seed is the synthetic weights')")
     ap.add_argument("--takes", type=int, default=1, help="decode every sentence N times in one batch, seeds sample-seed .. + N - 1; writes <out>_<i>.wav")
     ap.add_argument("--num-beams", type=int, default=1, help="beam search with N hypotheses per sentence (1..8; 1 = greedy)")
+    ap.add_argument("--queue", action="store_true", help="decode all sentences through the batch slots (refilled as sentences end); "
+                    "every sentence starts from a fresh penalty vector")
+    ap.add_argument("--slots", type=int, default=8, help="batch slots of --queue (1..16)")
     args = ap.parse_args()
+    if not 1 <= args.slots <= 16:
+        ap.error("--slots must be in 1..16 (the engine's batch slots)")
+    if args.queue and (args.takes > 1 or args.num_beams > 1 or args.device_type == "cuda"):
+        ap.error("--queue uses the host-array queue call (generate_queue): no --takes, no --num-beams, --device-type cpu")
     if not 1 <= args.num_beams <= 8:
         ap.error("--num-beams must be in 1..8")
     if not 1 <= args.takes <= 16:
@@ -133,7 +146,25 @@ def main():
     take_pieces = [[] for _ in range(args.takes)]
     take_penalty = None
     sentences = tokenizer.split_sentences(tokenizer.tokenize(args.text))
-    for sentence in sentences:
+    if args.queue:
+        prompts, budgets = [], []
+        for sentence in sentences:
+            print("Queue the Voice for '" + "".join(sentence).replace("▁", " ") + "'")
+            ids = np.asarray(tokenizer.convert_tokens_to_ids(sentence), dtype=np.int32)
+            prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
+            prompts.append(prompt_rows)
+            budgets.append(max(gcfg.max_generate_length - int(prompt_len[0]), 0))
+        t_dec = time.time()
+        q_sampling = [dataclasses.replace(take_sampling[0], seed=take_sampling[0].seed + i) for i in range(len(prompts))] if sampled else None
+        results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, return_stats=True)
+        n_codes = sum(h.shape[0] for _, h in results)
+        print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "
+              f"{gcfg.max_batch} slots: {q_stats['steps']} decode steps, {q_stats['passes']} prompt passes)")
+        latents = [h for _, h in results if h.shape[0] >= 3]         # the vocoder needs three codes
+        if latents:
+            for wav in voc.run_latent_ragged(latents, list(stage_conds) + [embed_cond]):
+                pieces.append(np.concatenate([wav, gap], axis=-1))
+    for sentence in ([] if args.queue else sentences):
         print("Generate the Voice for '" + "".join(sentence).replace("▁", " ") + "'")
         ids = np.asarray(tokenizer.convert_tokens_to_ids(sentence), dtype=np.int32)
         t_dec = time.time()

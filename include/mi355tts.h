@@ -342,6 +342,44 @@ int         mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const 
 int         mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_scores, int groups, int beams, int codes,
                                int first, int32_t* parents, int32_t* tokens, float* scores, int mem);
 
+/* ---- sentence queue: any number of sentences through the handle's slots, a slot refilled as soon as its sentence stops ---------
+ * A decode step costs the same for 1 live slot or 16, so throughput is the number of LIVE slots.  mi_gpt_generate_batch takes
+ * at most max_batch sentences and keeps a finished slot running as a no-op until the longest one ends; this entry takes n >= 1
+ * sentences (n is not bound by max_batch), refills a slot when its sentence stops, and runs the prompts of all sentences
+ * admitted together as ONE packed pass over the weights (one LayerNorm / linear launch per layer over all their rows; the KV
+ * scatter and the causal attention keep every sentence in its own slot, with the reference's additive -128 mask).
+ *
+ * prompts / prompt_rows / max_new / stop_ids / repeat_value / penalty_range / tokens (n, cap) / hidden (n, cap, hidden) / n_out
+ * (host, n) / mem: as mi_gpt_generate_batch.  temperature / top_k / top_p / seeds: HOST arrays of n entries, all four NULL
+ * (greedy) or all four given (as mi_gpt_generate_batch_sampled).  There is NO repeat_penality argument: every sentence starts
+ * from a penalty vector of ones — the sentences run concurrently, so the reference's carry of the vector from one sentence to
+ * the next (:685) has no meaning here.  Per sentence the result is what mi_gpt_generate_batch gives for that sentence from a ones
+ * vector: the decode steps are the same launches; the prompt pass differs from the one-by-one pass in GEMM tiling only (fp32:
+ * summation order).  A sampled sentence's draws depend on its seed and decode index alone, as everywhere.
+ *
+ * Validation is mi_gpt_generate_batch's, per sentence (prompt_rows >= 1, 0 <= max_new <= cap, prompt_rows + max_new - 1 <=
+ * max_seq, max_new <= the mel position table, at most 6 stop ids, valid sampling parameters, the four arrays together), all of
+ * it before anything is launched: MI_EINVAL, with the handle still usable.
+ *
+ * Scheduling policy (mi355tts.indextts.queue_schedule is its host model; stats counts what it did).  S = min(max_batch, n)
+ * slots; sentences are admitted in index order; a sentence with max_new == 0 takes no slot and has n_out = 0.
+ *   1. Admit.  While a slot is free and a sentence waits, form a pass: the next waiting sentence takes the lowest free slot,
+ *      again and again until no slot is free, nothing waits, or the next sentence's rows would push the pass past max_seq
+ *      packed rows (the prompt scratch).  The first sentence of a pass always fits; the pass ends at the first sentence that
+ *      does not — nothing behind it is looked at.  The pass runs and gives every admitted sentence its token 0.  Then the
+ *      slots' states are read.
+ *   2. Retire.  Every slot whose sentence is done (stop id, or max_new tokens — possibly right after its prompt pass) is
+ *      retired: its tokens and rows are copied out and the slot is free.  If a slot was freed and a sentence waits: step 1,
+ *      with no decode step in between.
+ *   3. Finish or decode.  No live slot: finished.  Otherwise c = min(16, min over live slots of (max_new - tokens so far))
+ *      batched decode steps over slots 0..S-1 are replayed (finished and empty slots are no-ops), the states are read: step 2.
+ * stats (host, 2 ints, or NULL): {sum of the c values = decode steps launched, number of prompt passes}.               */
+int         mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                  const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                                  int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
+                                  const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
+                                  int32_t* stats /* host, 2 ints or NULL: {decode steps launched, prompt passes} */);
+
 /* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
  * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these
  * host arrays of nb parameters.  The slots are marked done for the measurement: no token is stored and no state moves.    */

@@ -964,6 +964,124 @@ int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const
     });
 }
 
+// Sentence queue (include/mi355tts.h, "sentence queue"): n sentences through S = min(max_batch, n) slots, a slot refilled as
+// soon as its sentence stops, every prompt pass packed (Gpt::forward_packed).  The policy is the header's, step by step.
+int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                          const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
+                          float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const uint64_t* seeds, int32_t* stats) {
+    return guard([&] {
+        const std::string who = "mi_gpt_generate_queue";
+        GPT_CHECK(h, mem, "mi_gpt_generate_queue");
+        Gpt& e = *h->impl;
+        const GptCfg& c = e.cfg;
+        // everything is validated before anything is launched
+        MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
+        MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
+        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+        const bool any_samp = temperature || top_k || top_p || seeds;
+        MI_REQUIRE(!any_samp || (temperature && top_k && top_p && seeds), who + ": the four sampling arrays come together or not at all");
+        std::vector<size_t> row0(n);
+        size_t rows_total = 0;
+        for (int i = 0; i < n; ++i) {
+            MI_REQUIRE(prompt_rows[i] >= 1 && max_new[i] >= 0 && max_new[i] <= cap, who + ": prompt_rows / max_new");
+            MI_REQUIRE(max_new[i] == 0 || prompt_rows[i] + max_new[i] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
+            MI_REQUIRE(max_new[i] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+            row0[i] = rows_total;
+            rows_total += (size_t)prompt_rows[i];
+        }
+        std::vector<GptSampleRec> recs;
+        if (any_samp) {
+            MI_REQUIRE(c.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
+            recs.resize(n);
+            for (int i = 0; i < n; ++i) recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
+        }
+        struct ModeReset { Gpt& e; ~ModeReset() { e.sampled = 0; } } mode_reset{e};
+        e.sampled = any_samp ? 1 : 0;
+        hipStream_t s = e.stream;
+        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        std::vector<int32_t> stops(n_stop);
+        if (n_stop) {
+            if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
+            else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+        }
+        e.set_rep_value(repeat_value);
+        const int S = std::min(c.max_batch, n);
+        // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
+        std::vector<int32_t> all((size_t)S * GS_WORDS, 0);
+        for (int b = 0; b < S; ++b) all[(size_t)b * GS_WORDS + GS_DONE] = 1;
+        MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));
+        auto read_states = [&] {
+            MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
+            MI_HIP(hipStreamSynchronize(s));
+        };
+        std::vector<int> owner(S, -1);                               // the sentence in each slot, -1 = free
+        for (int i = 0; i < n; ++i) n_out[i] = 0;
+        int next = 0, live = 0;
+        long steps = 0, passes = 0;
+        auto skip_empty = [&] { while (next < n && max_new[next] == 0) ++next; };
+        skip_empty();
+        for (;;) {
+            // 1. admit: passes of the waiting sentences into the free slots, in index order, lowest free slot first
+            bool ran = false;
+            while (live < S && next < n) {
+                Gpt::Seg segs[16];
+                int k = 0, total = 0;
+                while (live < S && next < n) {
+                    const int rows = prompt_rows[next];
+                    if (k > 0 && total + rows > c.max_seq) break;        // the first sentence of a pass always fits
+                    int slot = 0;
+                    while (owner[slot] >= 0) ++slot;
+                    owner[slot] = next; ++live;
+                    std::vector<int32_t> w(GS_WORDS, 0);
+                    w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[next];
+                    for (int q = 0; q < n_stop; ++q) w[GS_STOP0 + q] = stops[q];
+                    e.set_state(w, slot);
+                    e.reset_penalty(slot);
+                    if (any_samp) e.set_sampling_slot(&recs[next], slot);
+                    MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, prompts + row0[next] * c.hidden,
+                                          (size_t)rows * c.hidden * 4, in, s));
+                    segs[k].first = total; segs[k].rows = rows; segs[k].slot = slot; segs[k].pad = 0;
+                    ++k; total += rows;
+                    ++next;
+                    skip_empty();
+                }
+                e.forward_packed(segs, k);
+                ++passes;
+                ran = true;
+            }
+            if (ran) read_states();
+            // 2. retire every finished slot: its tokens and rows go out, the slot is free
+            bool freed = false;
+            for (int b = 0; b < S; ++b) {
+                const int i = owner[b];
+                if (i < 0 || !all[(size_t)b * GS_WORDS + GS_DONE]) continue;
+                const int nt = std::min(all[(size_t)b * GS_WORDS + GS_NDEC], max_new[i]);
+                n_out[i] = nt;
+                copy_out(tokens ? tokens + (size_t)i * cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)nt * 4, mem, s);
+                copy_out(hidden ? hidden + (size_t)i * cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
+                         (size_t)nt * c.hidden * 4, mem, s);
+                owner[b] = -1; --live;
+                freed = true;
+            }
+            if (freed && next < n) continue;                         // refill before the next decode step
+            // 3. finish, or decode up to the nearest limit (at most 16 steps) and look again
+            if (live == 0) break;
+            int cs = 16;
+            for (int b = 0; b < S; ++b)
+                if (owner[b] >= 0) cs = std::min(cs, max_new[owner[b]] - all[(size_t)b * GS_WORDS + GS_NDEC]);
+            MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
+            e.decode_batch_steps(S, cs);
+            steps += cs;
+            read_states();
+        }
+        e.history = all[GS_HIST];
+        MI_HIP(hipStreamSynchronize(s));
+        if (stats) { stats[0] = (int32_t)steps; stats[1] = (int32_t)passes; }
+    });
+}
+
 // beam search (gpt_beam.hip): gpt_generate_batch_impl's loop over nb groups of B slots
 int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                          const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, float* repeat_penality,

@@ -48,6 +48,8 @@ struct Gpt {
     int sampled = 0;
     DevBuf samp;              // per slot: GptSampleRec (gpt_pick.h), beside the GS_* state and not part of it
     void set_sampling(const void* recs, int nb);      // host GptSampleRec[nb] -> samp (synchronous)
+    void set_sampling_slot(const void* rec, int slot);   // one slot's record; the other slots' records stay (synchronous)
+    void reset_penalty(int slot);                     // one slot's penalty row := ones, in stream order (gpt_prompt.hip)
     // beam search (gpt_beam.hip; the definition is in include/mi355tts.h): a sentence's hypotheses sit in `beams` consecutive
     // slots.  What follows a hypothesis from slot to slot exists twice, the side in use being GS_NDEC & 1: the penalty vectors
     // (side 0 = pen, side 1 = pen_b) and the ancestor table anc[side][slot][n] = the slot inside the group that held this
@@ -73,6 +75,16 @@ struct Gpt {
     void reset();
     // graph E on rows new positions whose hidden states are already in X[0..rows): fills last / logits / state token
     void forward_rows(int rows, int flag, int slot = 0);
+    // the token of a prompt pass or single step from the slot's logits / last row (greedy or sampled by `sampled`) and the
+    // driver loop's bookkeeping; x0: slot 0 also gets graph C of that token in X row 0 (the single-sentence decode step's input)
+    void choose_token(int rows, int slot, bool x0);
+    // packed prompt pass (gpt_prompt.hip): k prompts lie back to back in X, segment g = rows [first, first + rows) -> slot,
+    // ascending `first`, no gaps, the total within max_seq, every slot's history 0 and at most once.  One pass over the weights
+    // for all of them, then per segment what the tail of forward_rows does on its last row.
+    struct Seg { int32_t first, rows, slot, pad; };
+    DevBuf segtab;            // the pass's segments on the device (max_batch entries)
+    bool packed_ready = false;
+    void forward_packed(const Seg* segs, int k);
     void set_state(const std::vector<int32_t>& words, int slot = 0);
     std::vector<int32_t> get_state(int slot = 0);
     void decode_batch_eager(int nb);                                                 // one token for slots 0..nb-1

@@ -986,11 +986,20 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     gemv(head, xl, fn_w.as<float>(), fn_b.as<float>(), logits_s, MI_F32, ACT_NONE, nullptr, nullptr, nullptr, 0,
          lnf_w.as<float>(), lnf_b.as<float>(), last_s);
     if (beams) return;                         // beam search: the caller's selection 0 follows (gpt_beam.hip)
+    choose_token(rows, slot, true);
+}
+
+void Gpt::choose_token(int rows, int slot, bool x0) {
+    const GptCfg& c = cfg;
+    const int h = c.hidden, S = c.max_seq;
+    hipStream_t s = stream;
+    float* last_s = last.as<float>() + (size_t)slot * h;
+    float* logits_s = logits.as<float>() + (size_t)slot * c.mel_codes;
     float* pen_s = pen.as<float>() + (size_t)slot * c.mel_codes;
     int* st_s = state.as<int>() + (size_t)slot * GS_WORDS;
     int* toks_s = toks.as<int>() + (size_t)slot * S;
     float* hid_s = hid.as<float>() + (size_t)slot * S * h;
-    float* xa = slot == 0 ? X.as<float>() : nullptr;
+    float* xa = slot == 0 && x0 ? X.as<float>() : nullptr;
     float* xb = Xd.as<float>() + (size_t)slot * h;
     if (sampled)
         launch_gpt_sample(1, logits_s, pen_s, last_s, st_s, toks_s, hid_s, c.mel_codes, h, rows, rep_dev.as<float>(), S,
@@ -1006,6 +1015,12 @@ void Gpt::set_sampling(const void* recs, int nb) {
     MI_REQUIRE(recs && nb >= 1 && nb <= cfg.max_batch, "gpt: sampling records");
     MI_HIP(hipMemcpyAsync(samp.p, recs, (size_t)nb * sizeof(GptSampleRec), hipMemcpyHostToDevice, stream));
     MI_HIP(hipStreamSynchronize(stream));      // `recs` may be a temporary
+}
+
+void Gpt::set_sampling_slot(const void* rec, int slot) {
+    MI_REQUIRE(rec && slot >= 0 && slot < cfg.max_batch, "gpt: sampling record slot");
+    MI_HIP(hipMemcpyAsync(samp.as<GptSampleRec>() + slot, rec, sizeof(GptSampleRec), hipMemcpyHostToDevice, stream));
+    MI_HIP(hipStreamSynchronize(stream));      // `rec` may be a temporary
 }
 
 void Gpt::set_rep_value(float v) {

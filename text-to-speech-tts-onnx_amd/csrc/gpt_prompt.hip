@@ -1,0 +1,230 @@
+// gpt_prompt.hip — packed prompt pass of the IndexTTS GPT: the prompts of all sentences admitted together run graph E in ONE
+// pass over the weights (Gpt::forward_packed), and the per-slot resets a refilled slot needs.
+//
+// forward_rows (gpt.hip) runs one prompt at a time: k prompts are k passes over every weight matrix, each a GEMM with M ~ 100
+// rows.  Here the k prompts lie back to back in X and every LayerNorm / linear layer runs once over all packed rows (the same
+// launch_rownorm / launch_conv_gemm path, M = the packed row count).  Only two things know about sentences:
+//   * the KV scatter: packed row r of segment g -> cache row r - first_g of slot slot_g (the slot's history is 0);
+//   * the attention: work item (head, packed row) finds its segment in a small device table and attends to the keys
+//     0 .. rows_g - 1 of its own slot with the reference's additive mask (-128 on keys j > i, every key visited), exactly as
+//     gpt_attn_kernel does for a lone prompt.  It never reads a cache row beyond rows_g: a refilled slot still holds the rows
+//     of the sentence before.
+// The tail (ln_f + final_norm + lm_head on each segment's last row, then the token choice) is forward_rows' own, per segment.
+#include "gpt.h"
+#include "gpt_pick.h"
+#include "gpt_vec.h"
+#include "wave_reduce.h"
+
+namespace mi {
+
+// the segment that holds packed row r: segments are ascending and gap-free, so it is the last one that starts at or before r
+// (wave-uniform: r comes from blockIdx or is searched per thread over at most 16 entries)
+__device__ __forceinline__ int4 gpt_find_seg(const int4* __restrict__ segs, int nseg, int r) {
+    int4 g = segs[0];
+    for (int q = 1; q < nseg; ++q) {
+        const int4 n = segs[q];
+        if (n.x <= r) g = n;
+    }
+    return g;
+}
+
+// rows of (q | k | v) -> K / V cache rows of each row's own slot, one layer (kc / vc = slot 0's layer; slots are slot_stride
+// apart).  One 16-byte group per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
+                                                         const int4* __restrict__ segs, int nseg, int total, int hidden,
+                                                         int max_seq, int max_batch, size_t slot_stride) {
+    constexpr int V = Pack16<T>::N;
+    const int per = 2 * hidden / V;                        // 16-byte groups of a row's k | v part
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)total * per) return;
+    const int r = (int)(i / per), c = (int)(i % per) * V;
+    const int4 g = gpt_find_seg(segs, nseg, r);
+    const int pos = r - g.x;
+    if (pos < 0 || pos >= g.y || pos >= max_seq || g.z < 0 || g.z >= max_batch) return;
+    const int which = c / hidden, cc = c % hidden, head = cc >> 6, d = cc & 63;
+    const T* src = qkv + (size_t)r * 3 * hidden + hidden + c;
+    T* dst = (which ? vc : kc) + (size_t)g.z * slot_stride + ((size_t)head * max_seq + pos) * 64 + d;
+    *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+}
+
+// one block per (head, packed row): softmax(q K^T + mask) V over the row's own segment.  gpt_attn_kernel (gpt.hip) with the
+// slot, the query index and the key count taken from the segment table: lane-per-key dot products (each lane streams one
+// 64-wide key row with 16-byte loads; keys beyond 512 come round again in the strided loop), then 8 lanes per value row.
+// All LDS scratch is in the dynamic region, carved at multiples of 16 bytes: sc [max_seq rounded up to 4] | qs [64] |
+// red [8 * 64] | bc [4].
+template <typename T>
+__global__ __launch_bounds__(512) void gpt_attn_packed_kernel(const T* __restrict__ qkv, const T* __restrict__ kc,
+                                                              const T* __restrict__ vc, T* __restrict__ out,
+                                                              const int4* __restrict__ segs, int nseg, int hidden,
+                                                              int max_seq, int max_batch, size_t slot_stride) {
+    constexpr int V = Pack16<T>::N;            // elements per 16 bytes
+    constexpr int CH = 64 / V;                 // 16-byte chunks per key row
+    extern __shared__ __attribute__((aligned(16))) float psm[];
+    float* sc = psm;                           // [max_seq rounded up to 4]
+    float* qs = psm + ((max_seq + 3) & ~3);    // [64]
+    float* red = qs + 64;                      // [8 * 64]
+    float* bc = red + 512;                     // [4]
+    const int head = blockIdx.x, row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int4 g = gpt_find_seg(segs, nseg, row);
+    const int i = row - g.x;                   // the query's position inside its sentence
+    const int kv = min(g.y, max_seq);          // keys 0 .. rows_g - 1 of the slot, and no further
+    if (i < 0 || i >= kv || g.z < 0 || g.z >= max_batch) return;      // block-uniform: a table that does not cover the row
+    kc += (size_t)g.z * slot_stride; vc += (size_t)g.z * slot_stride;
+    if (tid < 64) qs[tid] = (float)qkv[(size_t)row * 3 * hidden + head * 64 + tid];
+    __syncthreads();
+    const T* kb = kc + (size_t)head * max_seq * 64;
+    const T* vb = vc + (size_t)head * max_seq * 64;
+    float mx = -3.0e38f;
+    for (int j = tid; j < kv; j += 512) {
+        const T* kr = kb + (size_t)j * 64;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const Pack16<T> p = ld16(kr + c * V);
+#pragma unroll
+            for (int e = 0; e < V; ++e) s = fmaf(qs[c * V + e], (float)p.v[e], s);
+        }
+        if (j > i) s += -128.f;                // the reference's additive mask: not -inf, and no key is skipped
+        sc[j] = s;
+        mx = fmaxf(mx, s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    if (tid == 0) { float m = red[0]; for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w]); bc[0] = m; }
+    __syncthreads();
+    mx = bc[0];
+    float sum = 0.f;
+    for (int j = tid; j < kv; j += 512) { const float e = __expf(sc[j] - mx); sc[j] = e; sum += e; }
+    sum = wave_sum(sum);
+    __syncthreads();
+    if (lane == 0) red[wave] = sum;
+    __syncthreads();
+    if (tid == 0) { float t = 0.f; for (int w = 0; w < 8; ++w) t += red[w]; bc[1] = t; }
+    __syncthreads();
+    const float inv = 1.f / bc[1];
+    // values: lane = (key-in-group gk, chunk c) ; a wave covers 64/CH keys per pass
+    constexpr int KPW = 64 / CH;               // keys per wave pass
+    const int gk = lane / CH, c = lane % CH;
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int j = wave * KPW + gk; j < kv; j += 8 * KPW) {
+        const float p = sc[j];
+        const Pack16<T> v = ld16(vb + (size_t)j * 64 + c * V);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = fmaf(p, (float)v.v[e], acc[e]);
+    }
+    // reduce over gk (lanes that share c): xor over the gk bits
+#pragma unroll
+    for (int o = CH; o < 64; o <<= 1)
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
+    __syncthreads();
+    if (gk == 0)
+#pragma unroll
+        for (int e = 0; e < V; ++e) red[wave * 64 + c * V + e] = acc[e];
+    __syncthreads();
+    if (tid < 64) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) t += red[w * 64 + tid];
+        out[(size_t)row * hidden + head * 64 + tid] = (T)(t * inv);
+    }
+}
+
+__global__ __launch_bounds__(256) void gpt_fill_kernel(float* __restrict__ p, float v, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+void Gpt::reset_penalty(int slot) {
+    MI_REQUIRE(slot >= 0 && slot < cfg.max_batch, "gpt: penalty slot");
+    const int n = cfg.mel_codes;
+    hipLaunchKernelGGL(gpt_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       pen.as<float>() + (size_t)slot * n, 1.f, n);
+    MI_HIP(hipGetLastError());
+}
+
+#define GPT_DISPATCH(KERNEL, ...)                                                     \
+    do {                                                                              \
+        if (dtype == MI_F32) { KERNEL(float, __VA_ARGS__); }                          \
+        else if (dtype == MI_F16) { KERNEL(f16, __VA_ARGS__); }                       \
+        else { KERNEL(bf16, __VA_ARGS__); }                                           \
+        MI_HIP(hipGetLastError());                                                    \
+    } while (0)
+
+void Gpt::forward_packed(const Seg* segs, int k) {
+    const GptCfg& c = cfg;
+    const int h = c.hidden, S = c.max_seq;
+    hipStream_t s = stream;
+    const size_t es = dtype_size(dtype);
+    MI_REQUIRE(segs && k >= 1 && k <= c.max_batch, "gpt: packed pass segments");
+    MI_REQUIRE(!beams, "gpt: the packed prompt pass does not serve beam search");
+    int total = 0;
+    unsigned used = 0;
+    for (int g = 0; g < k; ++g) {
+        MI_REQUIRE(segs[g].first == total && segs[g].rows >= 1, "gpt: packed segments must be ascending and gap-free");
+        MI_REQUIRE(segs[g].slot >= 0 && segs[g].slot < c.max_batch && !(used >> segs[g].slot & 1u), "gpt: packed segment slot");
+        used |= 1u << segs[g].slot;
+        total += segs[g].rows;
+        MI_REQUIRE(total <= S, "gpt: packed rows exceed the prompt scratch (max_seq)");
+    }
+    if (total == 1) {                          // linear() is the multi-row path: a lone one-row prompt is the single-row pass
+        forward_rows(1, 1, segs[0].slot);
+        return;
+    }
+    const int lds = (((S + 3) & ~3) + 64 + 512 + 4) * 4;
+    if (!packed_ready) {
+        segtab.ensure((size_t)c.max_batch * sizeof(Seg));
+        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        packed_ready = true;
+    }
+    static_assert(sizeof(Seg) == sizeof(int4), "Seg is one int4 on the device");
+    MI_HIP(hipMemcpyAsync(segtab.p, segs, (size_t)k * sizeof(Seg), hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));           // `segs` may be a temporary
+    const int4* tab = segtab.as<int4>();
+    float* x = X.as<float>();
+    const size_t sstride = slot_cache_elems();
+    for (int li = 0; li < c.layers; ++li) {
+        Layer& l = L[li];
+        char* kcl = (char*)kc.p + (size_t)li * h * S * es;          // slot 0's layer; slots are slot_cache_elems apart
+        char* vcl = (char*)vc.p + (size_t)li * h * S * es;
+        launch_rownorm(NORM_LN_AFFINE, x, xn.p, dtype, l.ln1_w.as<float>(), l.ln1_b.as<float>(), total, h, 1e-5f, s);
+        linear(l.qkv, xn.p, total, qkv.p, dtype, ACT_NONE, nullptr);
+        {
+            const long items = (long)total * (2 * h / (16 / (int)es));
+            const dim3 grid((unsigned)((items + 255) / 256));
+#define KVS(T, ...) hipLaunchKernelGGL(kv_scatter_kernel<T>, grid, dim3(256), 0, s, (const T*)qkv.p, (T*)kcl, (T*)vcl, tab, k, total, h, S, c.max_batch, sstride)
+            GPT_DISPATCH(KVS, 0);
+#undef KVS
+        }
+        {
+            double keys = 0.0;
+            for (int g = 0; g < k; ++g) keys += (double)segs[g].rows * segs[g].rows;
+            ProfScope ps(FAM_ATTN, s, 2.0 * (double)h * total * es, 4.0 * (double)h * keys);
+#define ATTP(T, ...) hipLaunchKernelGGL(gpt_attn_packed_kernel<T>, dim3(c.heads, total), dim3(512), lds, s, (const T*)qkv.p, (const T*)kcl, (const T*)vcl, (T*)att.p, tab, k, h, S, c.max_batch, sstride)
+            GPT_DISPATCH(ATTP, 0);
+#undef ATTP
+        }
+        linear(l.proj, att.p, total, x, MI_F32, ACT_NONE, x);
+        launch_rownorm(NORM_LN_AFFINE, x, xn.p, dtype, l.ln2_w.as<float>(), l.ln2_b.as<float>(), total, h, 1e-5f, s);
+        linear(l.fc, xn.p, total, ff.p, dtype, ACT_GELU_TANH, nullptr);
+        linear(l.fc2, ff.p, total, x, MI_F32, ACT_NONE, x);
+    }
+    for (int g = 0; g < k; ++g) {
+        const int slot = segs[g].slot;
+        const float* xl = x + (size_t)(segs[g].first + segs[g].rows - 1) * h;
+        // ln_f (-> last_hidden_state) and final_norm in front of the lm_head, one launch, as in forward_rows
+        gemv(head, xl, fn_w.as<float>(), fn_b.as<float>(), logits.as<float>() + (size_t)slot * c.mel_codes, MI_F32, ACT_NONE,
+             nullptr, nullptr, nullptr, 0, lnf_w.as<float>(), lnf_b.as<float>(), last.as<float>() + (size_t)slot * h);
+        // X still holds the other segments' rows: the token's graph C goes to the slot's batched decode row only
+        choose_token(segs[g].rows, slot, false);
+    }
+}
+
+}  // namespace mi

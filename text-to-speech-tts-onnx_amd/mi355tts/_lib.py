@@ -12,6 +12,7 @@ import numpy as np
 
 MI_F32, MI_F16, MI_BF16 = 0, 1, 2
 MI_HOST, MI_DEVICE = 0, 1
+MI_EINVAL = -1
 DTYPES = {"f32": MI_F32, "fp32": MI_F32, "float32": MI_F32, "f16": MI_F16, "fp16": MI_F16, "float16": MI_F16,
           "bf16": MI_BF16, "bfloat16": MI_BF16}
 
@@ -142,6 +143,9 @@ def load() -> C.CDLL:
     L.mi_gpt_generate_sampled.restype = C.c_int
     L.mi_gpt_generate_batch_sampled.argtypes = L.mi_gpt_generate_batch.argtypes + [vp, vp, vp, vp]
     L.mi_gpt_generate_batch_sampled.restype = C.c_int
+    L.mi_gpt_generate_queue.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
+                                        C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp]
+    L.mi_gpt_generate_queue.restype = C.c_int
     L.mi_gpt_sample_logits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.mi_gpt_sample_logits.restype = C.c_int
     L.mi_gpt_generate_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,

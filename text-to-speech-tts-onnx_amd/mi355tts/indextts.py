@@ -95,6 +95,79 @@ def sample_logits(logits, *, temperature, top_k, top_p, seeds, positions, pen=No
     return (toks, u, probs) if return_probs else (toks, u)
 
 
+def queue_schedule(prompt_rows, max_new, lengths, slots, max_seq):
+    """Host model of ``mi_gpt_generate_queue``'s scheduling policy (include/mi355tts.h, "sentence queue") -> (steps, passes).
+
+    prompt_rows / max_new: per sentence, as given to the entry; lengths: what each sentence actually produced (<= max_new; 0
+    where max_new is 0); slots = the handle's max_batch; max_seq = the packed-row capacity of a prompt pass.  ``steps`` is
+    the number of batched decode steps the entry launches (its stats[0]); ``passes`` lists every prompt pass as a list of
+    (sentence, slot) in packing order.  Pure host code: it documents the policy, feeds tools/gpt_queue_bench.py and is what the
+    tests hold the entry's stats against."""
+    rows = [int(r) for r in prompt_rows]
+    limit = [int(m) for m in max_new]
+    length = [int(x) for x in lengths]
+    n = len(rows)
+    if not (len(limit) == n and len(length) == n and n >= 1 and slots >= 1):
+        raise ValueError("queue_schedule: prompt_rows, max_new and lengths must have one entry per sentence, slots >= 1")
+    for i in range(n):
+        if rows[i] < 1 or limit[i] < 0 or not (0 <= length[i] <= limit[i]) or (limit[i] > 0 and length[i] < 1):
+            raise ValueError(f"queue_schedule: sentence {i}: rows {rows[i]}, max_new {limit[i]}, length {length[i]}")
+    S = min(int(slots), n)
+    owner = [-1] * S                      # the sentence in each slot
+    got = [0] * n                         # tokens so far
+    nxt, steps, passes = 0, 0, []
+
+    def skip_empty(i):
+        while i < n and limit[i] == 0:
+            i += 1
+        return i
+
+    nxt = skip_empty(nxt)
+    while True:
+        # 1. admit
+        while -1 in owner and nxt < n:
+            this, total = [], 0
+            while -1 in owner and nxt < n:
+                if this and total + rows[nxt] > max_seq:
+                    break
+                slot = owner.index(-1)
+                owner[slot] = nxt
+                got[nxt] = 1              # the pass gives token 0
+                this.append((nxt, slot))
+                total += rows[nxt]
+                nxt = skip_empty(nxt + 1)
+            passes.append(this)
+        # 2. retire
+        freed = False
+        for b in range(S):
+            i = owner[b]
+            if i >= 0 and got[i] >= length[i]:
+                owner[b] = -1
+                freed = True
+        if freed and nxt < n:
+            continue
+        # 3. finish or decode
+        live = [i for i in owner if i >= 0]
+        if not live:
+            return steps, passes
+        c = min(16, min(limit[i] - got[i] for i in live))
+        steps += c
+        for i in live:
+            got[i] = min(length[i], got[i] + c)
+
+
+def lockstep_steps(lengths, slots):
+    """Batched decode steps of the yardstick ``queue_schedule`` is compared with: ``generate_batch`` over index-order groups of
+    ``slots`` sentences, each group decoding in 16-step chunks until its longest member is done."""
+    ls = [int(x) for x in lengths]
+    steps = 0
+    for g in range(0, len(ls), int(slots)):
+        longest = max(ls[g:g + int(slots)])
+        if longest > 1:
+            steps += 16 * -(-(longest - 1) // 16)
+    return steps
+
+
 MAX_BEAMS = 8
 
 
@@ -137,6 +210,26 @@ def beam_select(logits, prev_scores=None, *, beams: int, first: bool = False, pe
         codes, int(bool(first)), par.ctypes.data, tok.ctypes.data, sc.ctypes.data, _lib.MI_HOST), "mi_gpt_beam_select")
     g = rows // beams
     return par.reshape(g, beams), tok.reshape(g, beams), sc.reshape(g, beams)
+
+
+def _queue_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays):
+    """mi_gpt_generate_queue on host arrays.  sampling_arrays: None or (temperature, top_k, top_p, seeds), an item of which may
+    be None.  What the entry rejects before launching anything (MI_EINVAL) is a ValueError; the handle stays usable."""
+    n = int(rows.size)
+    toks = np.zeros((n, cap), np.int32)
+    hid = np.zeros((n, cap, cfg.hidden), np.float32)
+    cnt = np.zeros((n,), np.int32)
+    stats = np.zeros((2,), np.int32)
+    sa = (None,) * 4 if sampling_arrays is None else tuple(sampling_arrays)
+    L = _lib.load()
+    rc = L.mi_gpt_generate_queue(handle, n, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx),
+                                 stops.ctypes.data if stops.size else None, stops.size, repeat_value, penalty_range,
+                                 toks.ctypes.data, hid.ctypes.data, cap, _lib.i32p(cnt), _lib.MI_HOST,
+                                 *(None if a is None else a.ctypes.data for a in sa), _lib.i32p(stats))
+    if rc == _lib.MI_EINVAL:
+        raise ValueError("mi_gpt_generate_queue: " + L.mi_last_error().decode("utf-8", "replace"))
+    _lib.check(rc, "mi_gpt_generate_queue")
+    return toks, hid, cnt, stats
 
 
 class IndexGPT:
@@ -374,6 +467,32 @@ class IndexGPT:
             _lib.check(_lib.load().mi_gpt_generate_batch_sampled(*args, *(a.ctypes.data for a in sa)),
                        "mi_gpt_generate_batch_sampled")
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy()) for b in range(nb)], pen
+
+    def generate_queue(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
+                       return_stats: bool = False):
+        """Any number of sentences through the engine's max_batch slots (include/mi355tts.h, "sentence queue"): a slot is
+        refilled as soon as its sentence stops, and the prompts admitted together run as one packed pass over the weights.
+        prompts = list of (1, P_i, hidden) graph-D outputs, max_new = list of per-sentence limits.  Every sentence starts from a
+        penalty vector of ones (nothing is carried between sentences: they run concurrently).  sampling: None (greedy), one
+        ``Sampling`` for every sentence, or a list of n ``Sampling`` / None.  Beam search does not go through the queue.
+        Returns a list of (tokens, hidden) per sentence[, {"steps": decode steps launched, "passes": prompt passes}]."""
+        c = self.cfg
+        n = len(prompts)
+        if n < 1 or len(max_new) != n:
+            raise ValueError(f"{n} prompts and {len(max_new)} limits: generate_queue needs one limit per sentence, n >= 1")
+        samp = _batch_sampling(sampling, n)
+        ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
+        rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
+        cat = np.ascontiguousarray(np.concatenate(ps, axis=0))
+        mx = np.ascontiguousarray([int(m) for m in max_new], dtype=np.int32)
+        cap = max(int(mx.max()), 1)
+        stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
+        sa = None if samp is None else _sampling_arrays(samp)
+        toks, hid, cnt, stats = _queue_call(self._h, c, cat, rows, mx, stops,
+                                            float(c.repeat_penalty if repeat_value is None else repeat_value),
+                                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa)
+        res = [(toks[i, : cnt[i]].copy(), hid[i, : cnt[i]].copy()) for i in range(n)]
+        return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
                              repeat_value=None, penalty_range=None, sampling=None, beams: int = 1):

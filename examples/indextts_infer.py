@@ -22,7 +22,7 @@ code is drawn on the device (`Sampling`, upstream IndexTTS's temperature 1.0 / t
 over one shared KV cache, the most probable one goes to the vocoder.  Beam search is deterministic and does not combine with the
 sampling flags.
 `--queue` decodes the whole text at once instead of sentence by sentence: every sentence is embedded, `generate_queue` runs them
-through `--slots` batch slots (default 8, 1..16) — a slot is refilled as soon as its sentence stops and the prompts admitted
+through `--slots` batch slots (default 8, 1..64) — a slot is refilled as soon as its sentence stops and the prompts admitted
 together share one pass over the weights — and `run_latent_ragged` vocodes them in one forward, in order, with the same gap.
 Every queued sentence starts from a FRESH penalty vector: the sentences run concurrently, so the carry of the vector from one
 sentence to the next that the sentence-by-sentence forms keep (like the reference) does not exist there.  Sampling flags apply
@@ -82,7 +82,10 @@ def build_engines(args, vocab):
     return (gcfg, ccfg, vcfg), (cond, gpt, voc)
 
 
-def main():
+MAX_SLOTS = 64                                 # the engine's batch slots (IndexGPTConfig.max_batch)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--prompt", help="reference audio (RIFF/WAVE); default: a synthetic 3 s tone")
     ap.add_argument("--text", default="The quick brown fox jumps over the lazy dog. Pack my box with five dozen liquor jugs!")
@@ -103,24 +106,30 @@ def main():
     ap.add_argument("--num-beams", type=int, default=1, help="beam search with N hypotheses per sentence (1..8; 1 = greedy)")
     ap.add_argument("--queue", action="store_true", help="decode all sentences through the batch slots (refilled as sentences end); "
                     "every sentence starts from a fresh penalty vector")
-    ap.add_argument("--slots", type=int, default=8, help="batch slots of --queue (1..16)")
-    args = ap.parse_args()
-    if not 1 <= args.slots <= 16:
-        ap.error("--slots must be in 1..16 (the engine's batch slots)")
+    ap.add_argument("--slots", type=int, default=8, help=f"batch slots of --queue (1..{MAX_SLOTS})")
+    args = ap.parse_args(argv)
+    if not 1 <= args.slots <= MAX_SLOTS:
+        ap.error(f"--slots must be in 1..{MAX_SLOTS} (the engine's batch slots)")
     if args.queue and (args.takes > 1 or args.num_beams > 1 or args.device_type == "cuda"):
         ap.error("--queue uses the host-array queue call (generate_queue): no --takes, no --num-beams, --device-type cpu")
     if not 1 <= args.num_beams <= 8:
         ap.error("--num-beams must be in 1..8")
-    if not 1 <= args.takes <= 16:
-        ap.error("--takes must be in 1..16 (the engine's batch slots)")
-    sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
-    if args.num_beams > 1 and sampled:
+    if not 1 <= args.takes <= MAX_SLOTS:
+        ap.error(f"--takes must be in 1..{MAX_SLOTS} (the engine's batch slots)")
+    args.sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
+    if args.num_beams > 1 and args.sampled:
         ap.error("--num-beams does not combine with --temperature / --top-k / --top-p / --sample-seed / --takes: beam search is deterministic")
+    if args.takes > 1 and args.device_type == "cuda":
+        ap.error("--takes uses the host-array batch call (generate_batch); run it with --device-type cpu")
+    return args
+
+
+def main():
+    args = parse_args()
+    sampled = args.sampled
     take_sampling = [Sampling(1.0 if args.temperature is None else args.temperature, 30 if args.top_k is None else args.top_k,
                               0.8 if args.top_p is None else args.top_p, (args.sample_seed or 0) + i)
                      for i in range(args.takes)] if sampled else None
-    if args.takes > 1 and args.device_type == "cuda":
-        ap.error("--takes uses the host-array batch call (generate_batch); run it with --device-type cpu")
 
     sp, tokenizer = build_tokenizer(args.tokenizer)
     (gcfg, ccfg, vcfg), (cond, gpt, voc) = build_engines(args, sp.get_piece_size())

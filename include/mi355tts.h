@@ -209,7 +209,9 @@ int         mi_f5_dit_eval_ragged(mi_f5* h, int U, const int64_t* lens, const fl
  * (graph definitions: IndexTTS/Export_IndexTTS.py:203-289).  The KV cache lives in the handle (the reference
  * passes 2*layers growing tensors in and out of every call); mi_gpt_kv_read / _write expose it in the reference's
  * tensor layouts.  cfg = {hidden, layers, heads, inner, mel_codes, text_tokens, max_mel_pos, max_text_pos, max_seq
- * [, max_batch = 1]}.
+ * [, max_batch = 1]}, 1 <= max_batch <= 64 (mi_gpt_create* returns NULL with mi_last_error set otherwise).  Every slot has its own
+ * KV cache, 2 * layers * hidden * max_seq elements of the engine dtype: 126 MB per slot at IndexTTS-1.5 size with max_seq =
+ * 1024 in f16, 8.05 GB at 64 slots; an allocation that fails is reported by mi_gpt_create* like any other error.
  * weights: canonical fp32 blob of mi355tts.weights.pack_gpt (Conv1D weights transposed to (out, in); q and k rows
  * pre-scaled by head_dim^-0.25 like Export_IndexTTS.py:257-258).                                                  */
 typedef struct mi_gpt mi_gpt;
@@ -249,7 +251,17 @@ int         mi_gpt_generate(mi_gpt* h, const float* prompt, int P, int max_new, 
  * GEMV), each sentence with its own cache, history, penalty vector, stop test and limit.  prompts = the nb prompts
  * concatenated row-wise (sum(prompt_rows), hidden); prompt_rows / max_new / n_out are host arrays of nb ints;
  * repeat_penality (nb, mel_codes) in/out or NULL; tokens (nb, cap), hidden (nb, cap, hidden).  Results per sentence
- * are identical to mi_gpt_generate on that sentence alone (fp32: bit-for-bit the same kernels' arithmetic order). */
+ * are identical to mi_gpt_generate on that sentence alone (fp32: bit-for-bit the same kernels' arithmetic order).
+ *
+ * nb may be anything up to max_batch <= 64.  Up to 16 sentences a decode-step linear layer is one launch of the batched GEMV or
+ * of the 16-column matrix-core kernel.  Above 16:
+ *   - 16-bit engines, wherever the matrix-core kernel would serve 16 sentences (option "gpt_mfma" set, nb >= "gpt_mfma_min", K
+ *     splitting into 64-wide blocks per wave): ONE launch whose weight fragments feed ceil(nb / 16) column tiles.  Slot
+ *     independence: the MFMAs that accumulate one (weight row, sentence) output are the 16-column kernel's in its order, so a
+ *     sentence's result does not depend on its slot or on nb — column c is bit for bit column c % 16 of the 16-column kernel.
+ *   - everything else (fp32 engines, "gpt_mfma" = 0, a K that does not split): group rule — slots [16g, 16g + 16) form group g
+ *     and each group runs the launch it would run as a batch of its own size, the weights streamed once per group.  This is
+ *     the correctness path, not a fast one: a wide fp32 batch gives exactly what its index-order groups of 16 give. */
 int         mi_gpt_generate_batch(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows,
                                   const int32_t* max_new, const int32_t* stop_ids, int n_stop, float repeat_value,
                                   int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden, int cap,
@@ -326,7 +338,8 @@ int         mi_gpt_sample_logits(const float* logits, const float* pen, int rows
  * prompt's keys and values are stored once per sentence (in the group's first slot) and every later position is read from the
  * slot a small per-hypothesis ancestor table names.  Beams and sampling do not combine: beam search is deterministic.
  *
- * MI_EINVAL, with the handle still usable: num_beams < 1 or > 8, nb * num_beams above the handle's max_batch, num_beams >
+ * MI_EINVAL, with the handle still usable: num_beams < 1 or > 8, nb * num_beams above the handle's max_batch (<= 64: a
+ * group of hypotheses may lie across a 16-slot boundary, the decode linears do not know about groups), num_beams >
  * mel_codes, and what mi_gpt_generate_batch rejects.
  *
  * nb sentences, each with num_beams hypotheses in num_beams consecutive slots; arguments as mi_gpt_generate_batch;
@@ -343,7 +356,8 @@ int         mi_gpt_beam_select(const float* logits, const float* pen, const floa
                                int first, int32_t* parents, int32_t* tokens, float* scores, int mem);
 
 /* ---- sentence queue: any number of sentences through the handle's slots, a slot refilled as soon as its sentence stops ---------
- * A decode step costs the same for 1 live slot or 16, so throughput is the number of LIVE slots.  mi_gpt_generate_batch takes
+ * A decode step costs little more for 16 live slots than for 1, and 64 cost far less than four times 16,
+ * so throughput is the number of LIVE slots.  mi_gpt_generate_batch takes
  * at most max_batch sentences and keeps a finished slot running as a no-op until the longest one ends; this entry takes n >= 1
  * sentences (n is not bound by max_batch), refills a slot when its sentence stops, and runs the prompts of all sentences
  * admitted together as ONE packed pass over the weights (one LayerNorm / linear launch per layer over all their rows; the KV
@@ -362,7 +376,7 @@ int         mi_gpt_beam_select(const float* logits, const float* pen, const floa
  * it before anything is launched: MI_EINVAL, with the handle still usable.
  *
  * Scheduling policy (mi355tts.indextts.queue_schedule is its host model; stats counts what it did).  S = min(max_batch, n)
- * slots; sentences are admitted in index order; a sentence with max_new == 0 takes no slot and has n_out = 0.
+ * slots (max_batch <= 64, so a pass packs up to 64 prompts); sentences are admitted in index order; a sentence with max_new == 0 takes no slot and has n_out = 0.
  *   1. Admit.  While a slot is free and a sentence waits, form a pass: the next waiting sentence takes the lowest free slot,
  *      again and again until no slot is free, nothing waits, or the next sentence's rows would push the pass past max_seq
  *      packed rows (the prompt scratch).  The first sentence of a pass always fits; the pass ends at the first sentence that

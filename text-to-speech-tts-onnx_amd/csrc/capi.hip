@@ -1026,7 +1026,7 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
             // 1. admit: passes of the waiting sentences into the free slots, in index order, lowest free slot first
             bool ran = false;
             while (live < S && next < n) {
-                Gpt::Seg segs[16];
+                Gpt::Seg segs[GPT_MAX_BATCH];
                 int k = 0, total = 0;
                 while (live < S && next < n) {
                     const int rows = prompt_rows[next];

@@ -8,9 +8,10 @@ namespace mi {
 
 struct GptCfg {
     int hidden, layers, heads, inner, mel_codes, text_tokens, max_mel_pos, max_text_pos, max_seq;
-    int max_batch = 1;          // sentences decoded together (slots); optional 10th cfg int
+    int max_batch = 1;          // sentences decoded together (slots, 1..GPT_MAX_BATCH); optional 10th cfg int
     int head_dim() const { return hidden / heads; }
 };
+constexpr int GPT_MAX_BATCH = 64;                // slots of one handle: four 16-column MFMA tiles in the decode linears
 GptCfg parse_gpt_cfg(const int32_t* ci, int ni);
 int64_t gpt_param_count(const GptCfg& c);
 
@@ -35,7 +36,7 @@ struct Gpt {
     DevBuf X, xn, qkv, att, ff;                       // prompt-pass scratch (max_seq rows), shared by the slots
     DevBuf logits, last, pen, toks, hid, state;       // per slot: [slot][codes] / [slot][h] / [slot][max_seq](x h) / words
     DevBuf Xd, xnd, qkvd, attd, ffd, zd;              // batched decode step: one row per slot
-    int MBp = 1;              // max_batch rounded up to a batched-GEMV template width
+    int MBp = 1;              // max_batch rounded up to a batched-GEMV template width (<= 16) or to a multiple of 16 (above)
     // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams)
     std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;
     DevBuf io_a, io_b;        // host<->device staging
@@ -93,6 +94,9 @@ struct Gpt {
     // left (every slot is marked done for the measurement, so nothing but the choice runs and no state moves)
     double bench_pick(int nb, int iters);
     void gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int act, const float* res, void* kcl, void* vcl);
+    // gemv_b for nb <= 16 rows whose state words start at st (a 16-slot group of a wider batch passes its own bases)
+    void gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                  const int* st);
     size_t slot_cache_elems() const { return (size_t)cfg.layers * cfg.hidden * cfg.max_seq; }
     void decode_step_eager();                                                        // C (from state) + E + bookkeeping
     void decode_steps(int n);                                                        // n graph replays

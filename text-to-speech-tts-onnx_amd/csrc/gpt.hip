@@ -33,7 +33,7 @@ GptCfg parse_gpt_cfg(const int32_t* ci, int ni) {
     MI_REQUIRE(c.layers > 0 && c.mel_codes > 1 && c.text_tokens > 1 && c.max_mel_pos > 1 && c.max_text_pos > 2, "gpt cfg: sizes");
     MI_REQUIRE(c.max_seq >= 8 && c.max_seq <= 8192, "gpt cfg: max_seq must be in [8, 8192]");
     c.max_batch = ni == 10 ? ci[9] : 1;
-    MI_REQUIRE(c.max_batch >= 1 && c.max_batch <= 16, "gpt cfg: max_batch must be in [1, 16]");
+    MI_REQUIRE(c.max_batch >= 1 && c.max_batch <= GPT_MAX_BATCH, "gpt cfg: max_batch must be in [1, 64]");
     return c;
 }
 
@@ -414,6 +414,36 @@ template <> struct Mfma16<bf16> {
     static __device__ __forceinline__ f32x4_t mma(Frag a, Frag b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 };
 
+// epilogue of one lane's four D values of a skinny tile: rows n4 .. n4+3 of sentence b (bias, activation, residual; QKV: the
+// k / v rows go to cache row st[b].hist of slot b)
+template <typename T, bool QKV>
+__device__ __forceinline__ void skinny_store(f32x4_t acc, int b, int n4, const float* __restrict__ bias, const float* res,
+                                             void* out, int out_f32, int act, int N, T* __restrict__ kc, T* __restrict__ vc,
+                                             const int* __restrict__ st, int max_seq, size_t slot_stride) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = n4 + r;
+        if (n >= N) continue;
+        float v = acc[r] + (bias ? bias[n] : 0.f);
+        if (act == ACT_GELU_TANH) v = gelu_new(v);
+        if (res) v += res[(size_t)b * N + n];
+        bool to_cache = false;
+        if (QKV) {
+            const int hidden = N / 3;
+            if (n >= hidden) {
+                const int c = n - hidden, which = c / hidden, cc = c % hidden;
+                const int pos = st[b * GS_WORDS + GS_HIST];
+                if (pos < max_seq)
+                    (which ? vc : kc)[(size_t)b * slot_stride + ((size_t)(cc >> 6) * max_seq + pos) * 64 + (cc & 63)] = (T)v;
+                to_cache = true;
+            }
+        }
+        if (!to_cache) {
+            if (out_f32) ((float*)out)[(size_t)b * N + n] = v; else ((T*)out)[(size_t)b * N + n] = (T)v;
+        }
+    }
+}
+
 template <typename T, bool QKV, int UNR>
 __global__ __launch_bounds__(512) void gemm_skinny_kernel(const T* __restrict__ w, const T* __restrict__ x,
                                                           const float* __restrict__ bias, const float* res, void* out,
@@ -454,27 +484,74 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const T* __restrict__ 
     }
     const int b = i;                                    // D layout: column = lane & 15 (sentence), rows 4*(lane>>4) + r
     if (b >= nb) return;
+    skinny_store<T, QKV>(acc, b, n0 + 4 * g, bias, res, out, out_f32, act, N, kc, vc, st, max_seq, slot_stride);
+}
+
+// The same kernel for 17..64 sentences: the weight rows stay the A operand and the sentences fill CT = ceil(nb / 16) column
+// tiles, so a weight fragment loaded once feeds CT MFMAs.  Each column tile has its own accumulator, and the MFMAs that build
+// it are gemm_skinny_kernel's in gemm_skinny_kernel's order (same KS split, same ascending 64-wide K blocks, same order of the
+// KS partial adds in LDS): column c here is bit for bit column c % 16 of that kernel run on sentences 16 * (c / 16) ..., so a
+// sentence's result depends neither on its slot nor on nb.  A trip holds 2 * UNR * (1 + CT) fragments (200 VGPRs at UNR = 5,
+// CT = 4: the block's two waves per SIMD have 256 each).  Columns at or beyond nb are computed on the clamped row nb - 1 and
+// never written.  A block is blockDim / 64 / KS tiles of KS waves: which tiles share a block changes no sum, and the host
+// launches one tile per block where that spreads the x reads over more CUs (Gpt::gemv_b).
+template <typename T, bool QKV, int UNR, int CT>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_kernel(const T* __restrict__ w, const T* __restrict__ x,
+                                                               const float* __restrict__ bias, const float* res, void* out,
+                                                               int out_f32, int act, int N, int K, int nb, int KS,
+                                                               T* __restrict__ kc, T* __restrict__ vc,
+                                                               const int* __restrict__ st, int max_seq, size_t slot_stride) {
+    using MF = Mfma16<T>;
+    using Frag = typename MF::Frag;
+    __shared__ __attribute__((aligned(16))) float red[CT][8][256];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int TR = (int)(blockDim.x >> 6) / KS, tile = wave / KS, ks = wave - tile * KS;      // KS waves per 16-row tile
+    const int n0 = (blockIdx.x * TR + tile) * 16;
+    const int kw = K / KS;
+    f32x4_t acc[CT];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int n = n0 + 4 * g + r;
-        if (n >= N) continue;
-        float v = acc[r] + (bias ? bias[n] : 0.f);
-        if (act == ACT_GELU_TANH) v = gelu_new(v);
-        if (res) v += res[(size_t)b * N + n];
-        bool to_cache = false;
-        if (QKV) {
-            const int hidden = N / 3;
-            if (n >= hidden) {
-                const int c = n - hidden, which = c / hidden, cc = c % hidden;
-                const int pos = st[b * GS_WORDS + GS_HIST];
-                if (pos < max_seq)
-                    (which ? vc : kc)[(size_t)b * slot_stride + ((size_t)(cc >> 6) * max_seq + pos) * 64 + (cc & 63)] = (T)v;
-                to_cache = true;
+    for (int c = 0; c < CT; ++c) acc[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    if (n0 < N) {
+        const T* wr = w + (size_t)min(n0 + i, N - 1) * K + ks * kw + g * 16;
+        const T* xr[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) xr[c] = x + (size_t)min(16 * c + i, nb - 1) * K + ks * kw + g * 16;
+        for (int kb = 0; kb < kw; kb += 64 * UNR) {
+            // every load of the trip is issued before its first MFMA, in the order the MFMAs consume them (loads return in
+            // order, so block u's MFMAs start while the later blocks are still in flight)
+            Frag a[2 * UNR], bq[CT][2 * UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                a[2 * u] = *reinterpret_cast<const Frag*>(wr + kb + 64 * u);
+                a[2 * u + 1] = *reinterpret_cast<const Frag*>(wr + kb + 64 * u + 8);
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    bq[c][2 * u] = *reinterpret_cast<const Frag*>(xr[c] + kb + 64 * u);
+                    bq[c][2 * u + 1] = *reinterpret_cast<const Frag*>(xr[c] + kb + 64 * u + 8);
+                }
             }
+            __builtin_amdgcn_sched_barrier(0);
+            // per accumulator the chain runs over u ascending, as in gemm_skinny_kernel; the CT chains interleave
+#pragma unroll
+            for (int u = 0; u < 2 * UNR; ++u)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) acc[c] = MF::mma(a[u], bq[c][u], acc[c]);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        if (!to_cache) {
-            if (out_f32) ((float*)out)[(size_t)b * N + n] = v; else ((T*)out)[(size_t)b * N + n] = (T)v;
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) *reinterpret_cast<f32x4_t*>(&red[c][wave][lane * 4]) = acc[c];
+    __syncthreads();
+    if (ks != 0 || n0 >= N) return;
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        for (int q = 1; q < KS; ++q) {
+            const f32x4_t o = *reinterpret_cast<const f32x4_t*>(&red[c][wave + q][lane * 4]);
+            acc[c] += o;
         }
+        const int b = 16 * c + i;                       // D layout: column = lane & 15 of tile c, rows 4*(lane>>4) + r
+        if (b < nb)
+            skinny_store<T, QKV>(acc[c], b, n0 + 4 * g, bias, res, out, out_f32, act, N, kc, vc, st, max_seq, slot_stride);
     }
 }
 
@@ -804,7 +881,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     MI_REQUIRE(p - w == nw, "gpt: blob walk mismatch");
 
     const size_t es = dtype_size(dt), S = c.max_seq, MB = c.max_batch;
-    MBp = c.max_batch <= 1 ? 1 : c.max_batch <= 2 ? 2 : c.max_batch <= 4 ? 4 : c.max_batch <= 8 ? 8 : 16;
+    MBp = c.max_batch <= 1 ? 1 : c.max_batch <= 2 ? 2 : c.max_batch <= 4 ? 4 : c.max_batch <= 8 ? 8 : (c.max_batch + 15) / 16 * 16;
     kc.ensure(MB * slot_cache_elems() * es); vc.ensure(MB * slot_cache_elems() * es);
     X.ensure(S * h * 4); xn.ensure(S * h * es); qkv.ensure(S * 3 * h * es); att.ensure(S * h * es); ff.ensure(S * n * es);
     const size_t P = MBp;                       // padded slot rows of the batched decode scratch
@@ -1065,11 +1142,45 @@ void Gpt::decode_steps(int n) {
     for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
 }
 
-// batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N)
+// batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N).  Up to 16 rows: gemv_b16.  Above: 16-bit engines
+// run the wide matrix-core kernel where the 16-row one would run; everything else (fp32, gpt_mfma = 0, a K that does not
+// split) goes group by group — slots [16g, 16g + 16) through gemv_b16 with their own row count and every per-slot base moved
+// by 16g rows or slots, the weights streamed once per group.
 void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int act, const float* res, void* kcl, void* vcl) {
     MI_REQUIRE(l.k % 8 == 0 && nb >= 1 && nb <= MBp, "gemv_b: shape");
     const int of = odt == MI_F32;
     MI_REQUIRE(of || odt == dtype, "gemv_b: output dtype");
+    if (nb <= 16) { gemv_b16(l, x, nb, out, of, act, res, kcl, vcl, state.as<int>()); return; }
+    const size_t es = dtype_size(dtype), sstride = slot_cache_elems();
+    const int KS = l.k > 2048 ? 8 : 4;
+    if (opt(OPT_GPT_MFMA) && dtype != MI_F32 && nb >= opt(OPT_GPT_MFMA_MIN) && l.k % (KS * 64) == 0) {
+        ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * es, 2.0 * l.n * l.k * nb);
+        // the launch is bound by the bytes a CU has in flight (x is read by every wave): one tile per block while that still
+        // is one round of blocks, so the four-way split's x traffic spreads over twice the CUs
+        const int CT = (nb + 15) / 16;
+        const int TR = KS == 4 && (l.n + 15) / 16 <= device_cus() ? 1 : 8 / KS;
+        const dim3 gs((unsigned)((l.n + 16 * TR - 1) / (16 * TR)));
+        const bool u5 = (l.k / KS) % 320 == 0;
+#define GW1(T, QK, U, C) hipLaunchKernelGGL((gemm_skinny_wide_kernel<T, QK, U, C>), gs, dim3(64 * KS * TR), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, state.as<int>(), cfg.max_seq, sstride)
+#define GW2(T, QK, U) do { if (CT == 2) GW1(T, QK, U, 2); else if (CT == 3) GW1(T, QK, U, 3); else GW1(T, QK, U, 4); } while (0)
+#define GW(T, QK) do { if (u5) GW2(T, QK, 5); else GW2(T, QK, 1); } while (0)
+        if (dtype == MI_F16) { if (kcl) GW(f16, true); else GW(f16, false); }
+        else { if (kcl) GW(bf16, true); else GW(bf16, false); }
+#undef GW
+#undef GW2
+#undef GW1
+        MI_HIP(hipGetLastError());
+        return;
+    }
+    for (int b0 = 0; b0 < nb; b0 += 16)
+        gemv_b16(l, (const char*)x + (size_t)b0 * l.k * es, std::min(16, nb - b0), (char*)out + (size_t)b0 * l.n * (of ? 4 : es), of, act,
+                 res ? res + (size_t)b0 * l.n : nullptr, kcl ? (char*)kcl + (size_t)b0 * sstride * es : nullptr,
+                 vcl ? (char*)vcl + (size_t)b0 * sstride * es : nullptr, state.as<int>() + (size_t)b0 * GS_WORDS);
+}
+
+// up to 16 rows: the batched GEMV at the template width that holds nb, or the matrix-core kernel.  st = the state words of row 0
+void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                   const int* st) {
     const int BB = nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 8 ? 8 : 16;
     const int R = l.n >= 4096 ? 2 : 1;
     ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * dtype_size(dtype), 2.0 * l.n * l.k * nb);
@@ -1082,7 +1193,7 @@ void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int a
             const int TR = 8 / KS;
             const dim3 gs((unsigned)((l.n + 16 * TR - 1) / (16 * TR)));
             const bool u5 = (l.k / KS) % 320 == 0;
-#define GS1(T, QK, U) hipLaunchKernelGGL((gemm_skinny_kernel<T, QK, U>), gs, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, state.as<int>(), cfg.max_seq, sstride)
+#define GS1(T, QK, U) hipLaunchKernelGGL((gemm_skinny_kernel<T, QK, U>), gs, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, st, cfg.max_seq, sstride)
 #define GS(T, QK) do { if (u5) GS1(T, QK, 5); else GS1(T, QK, 1); } while (0)
             if (dtype == MI_F16) { if (kcl) GS(f16, true); else GS(f16, false); }
             else { if (kcl) GS(bf16, true); else GS(bf16, false); }
@@ -1093,7 +1204,7 @@ void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int a
         }
     }
     const dim3 grid((unsigned)((l.n + 8 * R - 1) / (8 * R)));
-#define GB(T, RR, B_, QK) hipLaunchKernelGGL((gemv_b_kernel<T, RR, B_, QK>), grid, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, (T*)kcl, (T*)vcl, state.as<int>(), cfg.max_seq, sstride)
+#define GB(T, RR, B_, QK) hipLaunchKernelGGL((gemv_b_kernel<T, RR, B_, QK>), grid, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, (T*)kcl, (T*)vcl, st, cfg.max_seq, sstride)
 #define GB_B(T, RR, QK) do { if (BB == 2) GB(T, RR, 2, QK); else if (BB == 4) GB(T, RR, 4, QK); else if (BB == 8) GB(T, RR, 8, QK); else GB(T, RR, 16, QK); } while (0)
 #define GB_T(T)                                                                 \
     do {                                                                        \

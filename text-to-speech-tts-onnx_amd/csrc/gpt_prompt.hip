@@ -18,7 +18,7 @@
 namespace mi {
 
 // the segment that holds packed row r: segments are ascending and gap-free, so it is the last one that starts at or before r
-// (wave-uniform: r comes from blockIdx or is searched per thread over at most 16 entries)
+// (wave-uniform: r comes from blockIdx or is searched per thread over at most GPT_MAX_BATCH = 64 entries)
 __device__ __forceinline__ int4 gpt_find_seg(const int4* __restrict__ segs, int nseg, int r) {
     int4 g = segs[0];
     for (int q = 1; q < nseg; ++q) {
@@ -156,6 +156,8 @@ void Gpt::reset_penalty(int slot) {
         MI_HIP(hipGetLastError());                                                    \
     } while (0)
 
+static_assert(GPT_MAX_BATCH <= 64, "forward_packed keeps the slots of a pass in a 64-bit mask");
+
 void Gpt::forward_packed(const Seg* segs, int k) {
     const GptCfg& c = cfg;
     const int h = c.hidden, S = c.max_seq;
@@ -164,11 +166,11 @@ void Gpt::forward_packed(const Seg* segs, int k) {
     MI_REQUIRE(segs && k >= 1 && k <= c.max_batch, "gpt: packed pass segments");
     MI_REQUIRE(!beams, "gpt: the packed prompt pass does not serve beam search");
     int total = 0;
-    unsigned used = 0;
+    uint64_t used = 0;                         // one bit per slot (GPT_MAX_BATCH = 64)
     for (int g = 0; g < k; ++g) {
         MI_REQUIRE(segs[g].first == total && segs[g].rows >= 1, "gpt: packed segments must be ascending and gap-free");
         MI_REQUIRE(segs[g].slot >= 0 && segs[g].slot < c.max_batch && !(used >> segs[g].slot & 1u), "gpt: packed segment slot");
-        used |= 1u << segs[g].slot;
+        used |= (uint64_t)1 << segs[g].slot;
         total += segs[g].rows;
         MI_REQUIRE(total <= S, "gpt: packed rows exceed the prompt scratch (max_seq)");
     }

@@ -203,7 +203,10 @@ class IndexGPTConfig:
     max_mel_pos: int = 803              # mel_pos_embedding rows
     max_text_pos: int = 603             # text_pos_embedding rows
     max_seq: int = 1024                 # KV-cache capacity of this engine (>= MAX_GENERATE_LENGTH = 800)
-    max_batch: int = 1                  # sentences decoded together by generate_batch (engine extension; <= 16)
+    # sentences decoded together (slots) by generate_batch / generate_beam / generate_queue (engine extension; <= 64).  Every slot
+    # has its own KV cache: 2 * layers * hidden * max_seq elements, 126 MB per slot at this size with max_seq = 1024 in f16,
+    # so 8.05 GB at 64 slots
+    max_batch: int = 1
     ln_eps: float = 1e-5
     start_mel_token: int = 8192
     stop_mel_token: int = 8193

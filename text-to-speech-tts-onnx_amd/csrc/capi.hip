@@ -668,6 +668,60 @@ static const void* stage_in(DevBuf& buf, const void* src, size_t bytes, int mem,
     return buf.p;
 }
 
+// what the generate entries share -----------------------------------------------------------------------------------------
+// per-sentence lengths against the caller's row capacity, the KV cache and the mel position table
+static void gpt_check_lengths(const GptCfg& c, int n, const int32_t* prompt_rows, const int32_t* max_new, int cap,
+                              const std::string& who) {
+    for (int i = 0; i < n; ++i) {
+        MI_REQUIRE(prompt_rows[i] >= 1 && max_new[i] >= 0 && max_new[i] <= cap, who + ": prompt_rows / max_new");
+        MI_REQUIRE(max_new[i] == 0 || prompt_rows[i] + max_new[i] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
+        MI_REQUIRE(max_new[i] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+    }
+}
+
+// the stop ids on the host, from the host or the device
+static std::vector<int32_t> gpt_fetch_stops(const int32_t* stop_ids, int n_stop, int mem, const std::string& who) {
+    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+    std::vector<int32_t> stops(n_stop);
+    if (n_stop) {
+        if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
+        else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+    }
+    return stops;
+}
+
+// the state words of a sentence about to start: limit = its max_new (0: none), done = it generates nothing
+static std::vector<int32_t> gpt_state_words(const std::vector<int32_t>& stops, int penalty_range, int limit, bool done) {
+    std::vector<int32_t> w(GS_WORDS, 0);
+    w[GS_NSTOP] = (int32_t)stops.size(); w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = limit;
+    std::copy(stops.begin(), stops.end(), w.begin() + GS_STOP0);
+    if (done) w[GS_DONE] = 1;
+    return w;
+}
+
+// penalty rows := the caller's `rows` vectors, or ones; row r goes to slot r * stride (beam search: a group's first slot)
+static void gpt_fill_penalty(Gpt& e, int rows, const float* src, hipMemcpyKind in_kind, int stride = 1) {
+    const int copies = stride == 1 ? 1 : rows;             // adjacent rows go in one copy
+    const size_t n = e.cfg.mel_codes, len = (size_t)rows / copies * n;
+    std::vector<float> ones;
+    if (!src) ones.assign(len, 1.f);
+    for (size_t r = 0; r < (size_t)copies; ++r) {
+        float* dst = e.pen.as<float>() + r * stride * n;
+        if (src) MI_HIP(hipMemcpyAsync(dst, src + r * len, len * 4, in_kind, e.stream));
+        else MI_HIP(hipMemcpyAsync(dst, ones.data(), len * 4, hipMemcpyHostToDevice, e.stream));
+    }
+    if (!src) MI_HIP(hipStreamSynchronize(e.stream));      // `ones` is done with
+}
+
+// the state words of slots 0 .. all.size() / GS_WORDS - 1 -> all; true when every stride-th slot is done
+static bool gpt_read_states(Gpt& e, std::vector<int32_t>& all, int stride = 1) {
+    MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, e.stream));
+    MI_HIP(hipStreamSynchronize(e.stream));
+    bool done = true;
+    for (size_t b = 0; b < all.size() / GS_WORDS; b += stride) done &= all[b * GS_WORDS + GS_DONE] != 0;
+    return done;
+}
+
 int mi_gpt_text_embed(mi_gpt* h, const int32_t* text_ids, int n, float* out, int mem) {
     return guard([&] {
         GPT_CHECK(h, mem, "mi_gpt_text_embed");
@@ -726,12 +780,7 @@ int mi_gpt_step(mi_gpt* h, const float* hidden_state, int ids_len, const float* 
         hipStream_t s = e.stream;
         const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
         MI_HIP(hipMemcpyAsync(e.X.p, hidden_state, (size_t)ids_len * c.hidden * 4, in, s));
-        if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)c.mel_codes * 4, in, s));
-        else {
-            std::vector<float> ones(c.mel_codes, 1.f);
-            MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
-            MI_HIP(hipStreamSynchronize(s));
-        }
+        gpt_fill_penalty(e, 1, repeat_penality, in);
         std::vector<int32_t> w(GS_WORDS, 0);
         w[GS_HIST] = e.history;
         e.set_state(w);
@@ -773,15 +822,16 @@ int mi_gpt_kv_write(mi_gpt* h, int layer, const float* keys, const float* values
     });
 }
 
-// the calls that follow on the handle choose tokens by `recs` (null: greedy); greedy again when the scope ends
+// the calls that follow on the handle choose tokens by sampling (off: greedy); greedy again when the scope ends.  With `recs`
+// the records of slots 0 .. nb-1 are uploaded as well (null: greedy); the queue uploads a slot's record when it admits a sentence.
 struct GptModeScope {
     Gpt& e;
-    GptModeScope(Gpt& g, const GptSampleRec* recs, int nb) : e(g) {
-        if (recs) {
-            MI_REQUIRE(e.cfg.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
-            e.set_sampling(recs, nb);
-        }
-        e.sampled = recs ? 1 : 0;
+    GptModeScope(Gpt& g, bool on) : e(g) {
+        if (on) MI_REQUIRE(e.cfg.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
+        e.sampled = on ? 1 : 0;
+    }
+    GptModeScope(Gpt& g, const GptSampleRec* recs, int nb) : GptModeScope(g, recs != nullptr) {
+        if (recs) e.set_sampling(recs, nb);
     }
     ~GptModeScope() { e.sampled = 0; }
 };
@@ -808,25 +858,16 @@ static void gpt_generate_impl(mi_gpt* h, const float* prompt, int P, int max_new
     const GptCfg& c = e.cfg;
     GptModeScope mode(e, rec, 1);
     MI_REQUIRE(prompt && P >= 1 && n_out, who + ": null argument");
-    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+    const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
     *n_out = 0;
     if (max_new <= 0) return;                                        // `while num_decode < generate_limit` never runs
-    MI_REQUIRE(P + max_new - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
-    MI_REQUIRE(max_new <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
+    gpt_check_lengths(c, 1, &P, &max_new, max_new, who);             // one sentence; the caller's buffers hold max_new rows
     hipStream_t s = e.stream;
     const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     MI_HIP(hipMemcpyAsync(e.X.p, prompt, (size_t)P * c.hidden * 4, in, s));
-    if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)c.mel_codes * 4, in, s));
-    else {
-        std::vector<float> ones(c.mel_codes, 1.f);
-        MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
-        MI_HIP(hipStreamSynchronize(s));
-    }
+    gpt_fill_penalty(e, 1, repeat_penality, in);
     e.set_rep_value(repeat_value);
-    std::vector<int32_t> w(GS_WORDS, 0);
-    w[GS_GEN_LEN] = 0; w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1;
-    if (mem == MI_HOST) for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stop_ids[i];
-    else MI_HIP(hipMemcpy(&w[GS_STOP0], stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> w = gpt_state_words(stops, penalty_range, 0, false);      // no limit word: the loop below counts
     e.set_state(w);
     e.forward_rows(P, 1);                                            // prompt pass: first token
     int left = max_new - 1;
@@ -879,34 +920,16 @@ static void gpt_generate_batch_impl(mi_gpt* h, int nb, const float* prompts, con
     MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
     MI_REQUIRE(nb >= 1 && nb <= c.max_batch, who + ": batch exceeds the handle's max_batch");
     GptModeScope mode(e, recs, nb);
-    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
     hipStream_t s = e.stream;
     const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    std::vector<int32_t> stops(n_stop);
-    if (n_stop) {
-        if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
-        else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
-    }
-    size_t row0 = 0;
-    for (int b = 0; b < nb; ++b) {
-        MI_REQUIRE(prompt_rows[b] >= 1 && max_new[b] >= 0 && max_new[b] <= cap, who + ": prompt_rows / max_new");
-        MI_REQUIRE(max_new[b] == 0 || prompt_rows[b] + max_new[b] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
-        MI_REQUIRE(max_new[b] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
-    }
-    if (repeat_penality) MI_HIP(hipMemcpyAsync(e.pen.p, repeat_penality, (size_t)nb * c.mel_codes * 4, in, s));
-    else {
-        std::vector<float> ones((size_t)nb * c.mel_codes, 1.f);
-        MI_HIP(hipMemcpyAsync(e.pen.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, s));
-        MI_HIP(hipStreamSynchronize(s));
-    }
+    const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
+    gpt_check_lengths(c, nb, prompt_rows, max_new, cap, who);
+    gpt_fill_penalty(e, nb, repeat_penality, in);
     e.set_rep_value(repeat_value);
     bool any = false;
+    size_t row0 = 0;
     for (int b = 0; b < nb; ++b) {                               // prompt passes, one sentence at a time
-        std::vector<int32_t> w(GS_WORDS, 0);
-        w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[b];
-        for (int i = 0; i < n_stop; ++i) w[GS_STOP0 + i] = stops[i];
-        if (max_new[b] == 0) w[GS_DONE] = 1;
-        e.set_state(w, b);
+        e.set_state(gpt_state_words(stops, penalty_range, max_new[b], max_new[b] == 0), b);
         if (max_new[b] > 0) {
             MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[b] * c.hidden * 4, in, s));
             e.forward_rows(prompt_rows[b], 1, b);
@@ -915,20 +938,13 @@ static void gpt_generate_batch_impl(mi_gpt* h, int nb, const float* prompts, con
         row0 += prompt_rows[b];
     }
     std::vector<int32_t> all((size_t)nb * GS_WORDS);
-    auto read_states = [&] {
-        MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
-        MI_HIP(hipStreamSynchronize(s));
-        bool done = true;
-        for (int b = 0; b < nb; ++b) done &= all[(size_t)b * GS_WORDS + GS_DONE] != 0;
-        return done;
-    };
     int guard_steps = 0;
-    while (any && !read_states()) {
+    while (any && !gpt_read_states(e, all)) {
         e.decode_batch_steps(nb, 16);
         guard_steps += 16;
         MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
     }
-    if (!any) read_states();
+    if (!any) gpt_read_states(e, all);
     e.history = all[GS_HIST];
     for (int b = 0; b < nb; ++b) {
         const int n = all[(size_t)b * GS_WORDS + GS_NDEC];
@@ -978,33 +994,18 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
         // everything is validated before anything is launched
         MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
         MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
-        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+        const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
         const bool any_samp = temperature || top_k || top_p || seeds;
         MI_REQUIRE(!any_samp || (temperature && top_k && top_p && seeds), who + ": the four sampling arrays come together or not at all");
+        gpt_check_lengths(c, n, prompt_rows, max_new, cap, who);
         std::vector<size_t> row0(n);
         size_t rows_total = 0;
-        for (int i = 0; i < n; ++i) {
-            MI_REQUIRE(prompt_rows[i] >= 1 && max_new[i] >= 0 && max_new[i] <= cap, who + ": prompt_rows / max_new");
-            MI_REQUIRE(max_new[i] == 0 || prompt_rows[i] + max_new[i] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
-            MI_REQUIRE(max_new[i] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
-            row0[i] = rows_total;
-            rows_total += (size_t)prompt_rows[i];
-        }
-        std::vector<GptSampleRec> recs;
-        if (any_samp) {
-            MI_REQUIRE(c.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
-            recs.resize(n);
-            for (int i = 0; i < n; ++i) recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
-        }
-        struct ModeReset { Gpt& e; ~ModeReset() { e.sampled = 0; } } mode_reset{e};
-        e.sampled = any_samp ? 1 : 0;
+        for (int i = 0; i < n; ++i) { row0[i] = rows_total; rows_total += (size_t)prompt_rows[i]; }
+        GptModeScope mode(e, any_samp);
+        std::vector<GptSampleRec> recs(any_samp ? n : 0);
+        for (int i = 0; i < (int)recs.size(); ++i) recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
         hipStream_t s = e.stream;
         const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        std::vector<int32_t> stops(n_stop);
-        if (n_stop) {
-            if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
-            else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
-        }
         e.set_rep_value(repeat_value);
         const int S = std::min(c.max_batch, n);
         // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
@@ -1012,10 +1013,6 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
         for (int b = 0; b < S; ++b) all[(size_t)b * GS_WORDS + GS_DONE] = 1;
         MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
         MI_HIP(hipStreamSynchronize(s));
-        auto read_states = [&] {
-            MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
-            MI_HIP(hipStreamSynchronize(s));
-        };
         std::vector<int> owner(S, -1);                               // the sentence in each slot, -1 = free
         for (int i = 0; i < n; ++i) n_out[i] = 0;
         int next = 0, live = 0;
@@ -1034,10 +1031,7 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
                     int slot = 0;
                     while (owner[slot] >= 0) ++slot;
                     owner[slot] = next; ++live;
-                    std::vector<int32_t> w(GS_WORDS, 0);
-                    w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[next];
-                    for (int q = 0; q < n_stop; ++q) w[GS_STOP0 + q] = stops[q];
-                    e.set_state(w, slot);
+                    e.set_state(gpt_state_words(stops, penalty_range, max_new[next], false), slot);
                     e.reset_penalty(slot);
                     if (any_samp) e.set_sampling_slot(&recs[next], slot);
                     MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, prompts + row0[next] * c.hidden,
@@ -1051,7 +1045,7 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
                 ++passes;
                 ran = true;
             }
-            if (ran) read_states();
+            if (ran) gpt_read_states(e, all);
             // 2. retire every finished slot: its tokens and rows go out, the slot is free
             bool freed = false;
             for (int b = 0; b < S; ++b) {
@@ -1074,7 +1068,7 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
             MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
             e.decode_batch_steps(S, cs);
             steps += cs;
-            read_states();
+            gpt_read_states(e, all);
         }
         e.history = all[GS_HIST];
         MI_HIP(hipStreamSynchronize(s));
@@ -1096,41 +1090,23 @@ int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t*
         MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
         MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
         MI_REQUIRE(nb >= 1 && (long)nb * B <= c.max_batch, who + ": nb * num_beams exceeds the handle's max_batch");
-        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
         hipStream_t s = e.stream;
         const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        std::vector<int32_t> stops(n_stop);
-        if (n_stop) {
-            if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
-            else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
-        }
-        for (int b = 0; b < nb; ++b) {
-            MI_REQUIRE(prompt_rows[b] >= 1 && max_new[b] >= 0 && max_new[b] <= cap, who + ": prompt_rows / max_new");
-            MI_REQUIRE(max_new[b] == 0 || prompt_rows[b] + max_new[b] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
-            MI_REQUIRE(max_new[b] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
-        }
+        const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
+        gpt_check_lengths(c, nb, prompt_rows, max_new, cap, who);
         struct BeamScope { Gpt& e; ~BeamScope() { e.beams = 0; } } scope{e};
         e.beams = B;
         e.sampled = 0;
         e.beam_ensure();
         const int nr = nb * B;
         // pen0 of sentence g -> side 0 of the group's first slot (selection 0 reads it there)
-        std::vector<float> ones;
-        if (!repeat_penality) ones.assign(c.mel_codes, 1.f);
-        for (int g = 0; g < nb; ++g) {
-            float* dst = e.pen.as<float>() + (size_t)g * B * c.mel_codes;
-            if (repeat_penality) MI_HIP(hipMemcpyAsync(dst, repeat_penality + (size_t)g * c.mel_codes, (size_t)c.mel_codes * 4, in, s));
-            else MI_HIP(hipMemcpyAsync(dst, ones.data(), (size_t)c.mel_codes * 4, hipMemcpyHostToDevice, s));
-        }
-        e.set_rep_value(repeat_value);                               // synchronises: `ones` is done with
+        gpt_fill_penalty(e, nb, repeat_penality, in, B);
+        e.set_rep_value(repeat_value);
         std::vector<int32_t> all((size_t)nr * GS_WORDS, 0);
-        for (int g = 0; g < nb; ++g)
-            for (int i = 0; i < B; ++i) {
-                int32_t* w = &all[((size_t)g * B + i) * GS_WORDS];
-                w[GS_NSTOP] = n_stop; w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = max_new[g];
-                for (int q = 0; q < n_stop; ++q) w[GS_STOP0 + q] = stops[q];
-                if (max_new[g] == 0) w[GS_DONE] = 1;
-            }
+        for (int g = 0; g < nb; ++g) {
+            const std::vector<int32_t> w = gpt_state_words(stops, penalty_range, max_new[g], max_new[g] == 0);
+            for (int i = 0; i < B; ++i) std::copy(w.begin(), w.end(), all.begin() + ((size_t)g * B + i) * GS_WORDS);
+        }
         MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
         MI_HIP(hipStreamSynchronize(s));
         e.history = 0;
@@ -1145,20 +1121,13 @@ int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t*
             }
             row0 += prompt_rows[g];
         }
-        auto read_states = [&] {
-            MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, s));
-            MI_HIP(hipStreamSynchronize(s));
-            bool done = true;
-            for (int g = 0; g < nb; ++g) done &= all[(size_t)g * B * GS_WORDS + GS_DONE] != 0;
-            return done;
-        };
         int guard_steps = 0;
-        while (any && !read_states()) {
+        while (any && !gpt_read_states(e, all, B)) {
             e.decode_beam_steps(nb, B, 16);
             guard_steps += 16;
             MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
         }
-        if (!any) read_states();
+        if (!any) gpt_read_states(e, all, B);
         e.history = all[GS_HIST];
         // hypothesis 0 of every group, gathered along its ancestors into staging, then out like the batched entry's rows
         e.io_a.ensure((size_t)nb * cap * 4);

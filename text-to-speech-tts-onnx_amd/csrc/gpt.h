@@ -67,6 +67,10 @@ struct Gpt {
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under
     void check_graph_epoch();
+    // n decode steps: `step` launches one.  With graphs on, the first step ever taken under this key runs eagerly (one-time
+    // lazy initialisation stays out of the capture), the second is captured into `exec`, the rest are replays; an
+    // instantiation failure turns graphs off for the handle and the steps run eagerly.
+    template <typename F> void replay(hipGraphExec_t& exec, int n, F&& step);
 
     Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev);
     ~Gpt();
@@ -86,8 +90,22 @@ struct Gpt {
     DevBuf segtab;            // the pass's segments on the device (max_batch entries)
     bool packed_ready = false;
     void forward_packed(const Seg* segs, int k);
+    // one layer's K / V cache of a slot (bytes; slots are slot_cache_elems() elements apart)
+    struct LayerKV { char *k, *v; };
+    LayerKV layer_cache(int layer, int slot = 0) {
+        const size_t off = ((size_t)slot * slot_cache_elems() + (size_t)layer * cfg.hidden * cfg.max_seq) * dtype_size(dtype);
+        return {(char*)kc.p + off, (char*)vc.p + off};
+    }
+    // dynamic LDS of gpt_attn_kernel: the score buffer, the query and the merge scratch (max_seq + 64 + 512 floats)
+    int prompt_attn_lds() const { return (cfg.max_seq + 64 + 512) * 4; }
     void set_state(const std::vector<int32_t>& words, int slot = 0);
     std::vector<int32_t> get_state(int slot = 0);
+    // the greedy or sampled token choice (by `sampled`) of slots slot0 .. slot0 + nb - 1 from their logits / last rows, with
+    // the driver loop's bookkeeping and graph C of the token in the slot's batched decode row; xa: a second copy of slot0's
+    void launch_choice(int nb, int slot0, int rows, float* xa);
+    // one batched decode step over rows 0 .. nr-1 of the decode scratch: the layer loop with `attn(kcl, vcl)` as the
+    // attention launch of a layer (slot 0's cache of that layer), then ln_f / final_norm / lm_head, then `tail()`
+    template <typename A, typename F> void decode_rows_eager(int nr, A&& attn, F&& tail);
     void decode_batch_eager(int nb);                                                 // one token for slots 0..nb-1
     void decode_batch_steps(int nb, int n);
     // tuning: microseconds per launch of the token-choosing kernel of the current mode over nb slots, on the logits the last step
@@ -107,6 +125,62 @@ struct Gpt {
               const float* res, void* kcl, void* vcl, int slot = 0, const float* pre_w = nullptr, const float* pre_b = nullptr,
               float* pre_out = nullptr);
 };
+
+// KERNEL(T, ...) for the engine's dtype (a member `dtype` is in scope), then the launch check
+#define GPT_DISPATCH(KERNEL, ...)                                                     \
+    do {                                                                              \
+        if (dtype == MI_F32) { KERNEL(float, __VA_ARGS__); }                          \
+        else if (dtype == MI_F16) { KERNEL(f16, __VA_ARGS__); }                       \
+        else { KERNEL(bf16, __VA_ARGS__); }                                           \
+        MI_HIP(hipGetLastError());                                                    \
+    } while (0)
+
+template <typename A, typename F> void Gpt::decode_rows_eager(int nr, A&& attn, F&& tail) {
+    const int h = cfg.hidden;
+    hipStream_t s = stream;
+    float* x = Xd.as<float>();                 // row b = graph C of slot b's state, written by the choice or selection before
+    for (int li = 0; li < cfg.layers; ++li) {
+        Layer& l = L[li];
+        const LayerKV kv = layer_cache(li);
+        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln1_w.as<float>(), l.ln1_b.as<float>(), nr, h, 1e-5f, s);
+        gemv_b(l.qkv, xnd.p, nr, qkvd.p, dtype, ACT_NONE, nullptr, kv.k, kv.v);
+        {
+            ProfScope ps(FAM_ATTN, s, 0.0, 0.0);
+            attn(kv.k, kv.v);
+        }
+        gemv_b(l.proj, attd.p, nr, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
+        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln2_w.as<float>(), l.ln2_b.as<float>(), nr, h, 1e-5f, s);
+        gemv_b(l.fc, xnd.p, nr, ffd.p, dtype, ACT_GELU_TANH, nullptr, nullptr, nullptr);
+        gemv_b(l.fc2, ffd.p, nr, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
+    }
+    launch_rownorm(NORM_LN_AFFINE, x, last.p, MI_F32, lnf_w.as<float>(), lnf_b.as<float>(), nr, h, 1e-5f, s);
+    launch_rownorm(NORM_LN_AFFINE, last.as<float>(), zd.p, dtype, fn_w.as<float>(), fn_b.as<float>(), nr, h, 1e-5f, s);
+    gemv_b(head, zd.p, nr, logits.p, MI_F32, ACT_NONE, nullptr, nullptr, nullptr);
+    tail();
+}
+
+template <typename F> void Gpt::replay(hipGraphExec_t& exec, int n, F&& step) {
+    if (n <= 0) return;
+    if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) step(); return; }
+    if (!exec) {
+        step();
+        --n;
+        hipGraph_t graph = nullptr;
+        MI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        try {
+            step();
+        } catch (...) {
+            (void)hipStreamEndCapture(stream, &graph);
+            if (graph) (void)hipGraphDestroy(graph);
+            throw;
+        }
+        MI_HIP(hipStreamEndCapture(stream, &graph));
+        hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) step(); return; }
+    }
+    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
+}
 
 constexpr int GPT_BEAM_MAX = 8;                  // hypotheses per sentence
 constexpr int GPT_BEAM_MAX_CODES = 16384;        // the unit entry's documented range

@@ -13,7 +13,12 @@
 // argument: it is captured once and replayed.  A decode step is a chain of weight-streaming GEMVs (HBM-bound:
 // every weight byte is read once per token), so the GEMV kernel is a plain coalesced 16-byte-per-lane dot product,
 // not an MFMA tile; the prompt pass (ids_len rows at once) goes through the MFMA implicit-GEMM kernel instead.
+//
+// Shared with gpt_beam.hip (beam search) and gpt_prompt.hip (packed prompt pass): the two attention bodies and the cache
+// address (gpt_attn.h); the batched decode step Gpt::decode_rows_eager, the capture-once-then-replay logic Gpt::replay and
+// the dtype dispatch GPT_DISPATCH (gpt.h); the token choice Gpt::launch_choice (here).
 #include "gpt.h"
+#include "gpt_attn.h"
 #include "gpt_pick.h"
 #include "gpt_vec.h"
 #include "mfma.h"
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_d_kernel(const T* __restrict_
             const int hidden = N / 3;
             if (n >= hidden) {
                 const int c = n - hidden, which = c / hidden, cc = c % hidden;
-                if (pos_pre < max_seq) (which ? vc : kc)[((size_t)(cc >> 6) * max_seq + pos_pre) * 64 + (cc & 63)] = (T)v;
+                if (pos_pre < max_seq) (which ? vc : kc)[kv_cache_offset(cc, pos_pre, max_seq)] = (T)v;
                 return;
             }
         }
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(512) void gemv_b_kernel(const T* __restrict__ w, co
                     const int c = n - hidden, which = c / hidden, cc = c % hidden;
                     const int pos = st[b * GS_WORDS + GS_HIST];
                     if (pos < max_seq)
-                        (which ? vc : kc)[(size_t)b * slot_stride + ((size_t)(cc >> 6) * max_seq + pos) * 64 + (cc & 63)] = (T)v;
+                        (which ? vc : kc)[(size_t)b * slot_stride + kv_cache_offset(cc, pos, max_seq)] = (T)v;
                     to_cache = true;
                 }
             }
@@ -434,7 +439,7 @@ __device__ __forceinline__ void skinny_store(f32x4_t acc, int b, int n4, const f
                 const int c = n - hidden, which = c / hidden, cc = c % hidden;
                 const int pos = st[b * GS_WORDS + GS_HIST];
                 if (pos < max_seq)
-                    (which ? vc : kc)[(size_t)b * slot_stride + ((size_t)(cc >> 6) * max_seq + pos) * 64 + (cc & 63)] = (T)v;
+                    (which ? vc : kc)[(size_t)b * slot_stride + kv_cache_offset(cc, pos, max_seq)] = (T)v;
                 to_cache = true;
             }
         }
@@ -495,6 +500,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const T* __restrict__ 
 // CT = 4: the block's two waves per SIMD have 256 each).  Columns at or beyond nb are computed on the clamped row nb - 1 and
 // never written.  A block is blockDim / 64 / KS tiles of KS waves: which tiles share a block changes no sum, and the host
 // launches one tile per block where that spreads the x reads over more CUs (Gpt::gemv_b).
+// Kept beside gemm_skinny_kernel, not folded into it as CT = 1: up to 16 rows run that kernel's measured device code.
 template <typename T, bool QKV, int UNR, int CT>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_kernel(const T* __restrict__ w, const T* __restrict__ x,
                                                                const float* __restrict__ bias, const float* res, void* out,
@@ -579,184 +585,30 @@ __global__ __launch_bounds__(512) void gpt_attn_kernel(const T* __restrict__ qkv
                                                        const T* __restrict__ vc, T* __restrict__ out,
                                                        const int* __restrict__ st, int rows, int flag, int hidden,
                                                        int max_seq, int batched, size_t slot_stride) {
-    constexpr int V = Pack16<T>::N;            // elements per 16 bytes
-    constexpr int CH = 64 / V;                 // 16-byte chunks per key row
     extern __shared__ float sm[];
     float* sc = sm;                            // [max_seq]
     float* qs = sm + max_seq;                  // [64]
     float* red = qs + 64;                      // [8 * 64]
     __shared__ float bc[2];
     // batched decode: blockIdx.y is the slot (one new row each, row index 0 inside its block); otherwise the new row
-    const int head = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row = blockIdx.y, i = batched ? 0 : row;
+    const int head = blockIdx.x, row = blockIdx.y, i = batched ? 0 : row;
     if (batched) { st += row * GS_WORDS; kc += (size_t)row * slot_stride; vc += (size_t)row * slot_stride; }
-    const int hist = st[GS_HIST];
-    const int kv = min(hist + rows, max_seq);
-    if (tid < 64) qs[tid] = (float)qkv[(size_t)row * 3 * hidden + head * 64 + tid];
-    __syncthreads();
-    const T* kb = kc + (size_t)head * max_seq * 64;
-    const T* vb = vc + (size_t)head * max_seq * 64;
-    float mx = -3.0e38f;
-    for (int j = tid; j < kv; j += 512) {
-        const T* kr = kb + (size_t)j * 64;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const Pack16<T> p = ld16(kr + c * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e) s = fmaf(qs[c * V + e], (float)p.v[e], s);
-        }
-        if (flag && j > i) s += -128.f;
-        sc[j] = s;
-        mx = fmaxf(mx, s);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    if (tid == 0) { float m = red[0]; for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w]); bc[0] = m; }
-    __syncthreads();
-    mx = bc[0];
-    float sum = 0.f;
-    for (int j = tid; j < kv; j += 512) { const float e = __expf(sc[j] - mx); sc[j] = e; sum += e; }
-    sum = wave_sum(sum);
-    __syncthreads();
-    if (lane == 0) red[wave] = sum;
-    __syncthreads();
-    if (tid == 0) { float t = 0.f; for (int w = 0; w < 8; ++w) t += red[w]; bc[1] = t; }
-    __syncthreads();
-    const float inv = 1.f / bc[1];
-    // values: lane = (key-in-group g, chunk c) ; a wave covers 64/CH keys per pass
-    constexpr int KPW = 64 / CH;               // keys per wave pass
-    const int g = lane / CH, c = lane % CH;
-    float acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    for (int j = wave * KPW + g; j < kv; j += 8 * KPW) {
-        const float p = sc[j];
-        const Pack16<T> v = ld16(vb + (size_t)j * 64 + c * V);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] = fmaf(p, (float)v.v[e], acc[e]);
-    }
-    // reduce over g (lanes that share c): xor over the g bits
-#pragma unroll
-    for (int o = CH; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    __syncthreads();
-    if (g == 0)
-#pragma unroll
-        for (int e = 0; e < V; ++e) red[wave * 64 + c * V + e] = acc[e];
-    __syncthreads();
-    if (tid < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) t += red[w * 64 + tid];
-        out[(size_t)row * hidden + head * 64 + tid] = (T)(t * inv);
-    }
+    const int kv = min(st[GS_HIST] + rows, max_seq);
+    gpt_prompt_attn_body<T>(i, kv, flag, qkv, kc, vc, out, row, head, hidden, max_seq, sc, qs, red, bc);
 }
 
-// decode-step attention (one new row per sentence, no mask): one block of 4 waves per (head, slot).  Each wave owns
-// every fourth 64-key pass and runs its own online softmax (lane = key for the scores, 16-byte K loads against the
-// packed q; the pass's V rows are fetched before the softmax so their latency overlaps it), so the block needs ONE
-// barrier: the four (max, sum, O) partials meet in LDS at the end.  The general kernel above (scores for all keys in
-// LDS, three block-wide reductions) took 6.5 us per launch at 100-300 keys; this is the latency-critical launch of a
-// decode step (24 per token).
+// decode-step attention (one new row per sentence, no mask): one block of 4 waves per (head, slot) around gpt_attn1_body
+// (gpt_attn.h), every row in the block's own slot.  The general kernel above (scores for all keys in LDS, three block-wide
+// reductions) took 6.5 us per launch at 100-300 keys; this is the latency-critical launch of a decode step (24 per token).
 template <typename T>
 __global__ __launch_bounds__(256) void gpt_attn1_kernel(const T* __restrict__ qkv, const T* __restrict__ kc,
                                                         const T* __restrict__ vc, T* __restrict__ out,
                                                         const int* __restrict__ st, int hidden, int max_seq, int batched,
                                                         size_t slot_stride) {
-    constexpr int V = Pack16<T>::N;            // elements per 16 bytes
-    constexpr int CH = 64 / V;                 // 16-byte chunks per 64-wide row
-    constexpr int KPI = 64 / CH;               // value rows per wave instruction
-    constexpr int NIT = 64 / KPI;              // instructions per 64-key pass
-    __shared__ float part[4][66];
-    const int head = blockIdx.x, slot = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int head = blockIdx.x, slot = blockIdx.y;
     if (batched) { st += slot * GS_WORDS; kc += (size_t)slot * slot_stride; vc += (size_t)slot * slot_stride; }
     const int kv = min(st[GS_HIST] + 1, max_seq);
-    Pack16<T> q[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) q[c] = ld16(qkv + (size_t)slot * 3 * hidden + head * 64 + c * V);
-    const T* kb = kc + (size_t)head * max_seq * 64;
-    const T* vb = vc + (size_t)head * max_seq * 64;
-    const int g = lane / CH, c = lane % CH;
-    float m_run = -INFINITY, l_run = 0.f, acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    struct Pass { Pack16<T> kp[CH], vp[NIT]; };
-    auto load_pass = [&](Pass& ps, int base) {
-        const int j = base + lane;
-        const T* kr = kb + (size_t)(j < kv ? j : base) * 64;
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) ps.kp[cc] = ld16(kr + cc * V);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int jj = base + it * KPI + g;
-            ps.vp[it] = ld16(vb + (size_t)(jj < kv ? jj : base) * 64 + c * V);
-        }
-    };
-    auto fold_pass = [&](const Pass& ps, int base) {
-        const bool kok = base + lane < kv;
-        float s = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) s = dot_pack(ps.kp[cc], q[cc], s);
-        s = kok ? s : -INFINITY;
-        const float mw = wave_max(s);
-        const float m_new = fmaxf(m_run, mw);              // finite: the pass holds at least one key
-        const float pj = kok ? __expf(s - m_new) : 0.f;
-        const float corr = __expf(m_run - m_new);          // exp(-inf) = 0 on the first pass
-        l_run = l_run * corr + wave_sum(pj);
-        m_run = m_new;
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] *= corr;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const float pk = __shfl(pj, it * KPI + g, 64);  // 0 for keys beyond kv
-#pragma unroll
-            for (int e = 0; e < V; ++e) acc[e] = fmaf(pk, (float)ps.vp[it].v[e], acc[e]);
-        }
-    };
-    // the wave's passes (every fourth 64-key block), the next one in flight while the current one is folded in
-    int base = wave * 64;
-    if (base < kv) {
-        Pass pa, pb;
-        load_pass(pa, base);
-        for (;;) {
-            bool more = base + 256 < kv;
-            if (more) load_pass(pb, base + 256);
-            fold_pass(pa, base);
-            if (!more) break;
-            base += 256;
-            more = base + 256 < kv;
-            if (more) load_pass(pa, base + 256);
-            fold_pass(pb, base);
-            if (!more) break;
-            base += 256;
-        }
-    }
-#pragma unroll
-    for (int o = CH; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    if (lane == 0) { part[wave][0] = m_run; part[wave][1] = l_run; }
-    if (g == 0)
-#pragma unroll
-        for (int e = 0; e < V; ++e) part[wave][2 + c * V + e] = acc[e];
-    __syncthreads();
-    if (wave == 0) {
-        float M = part[0][0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) M = fmaxf(M, part[w][0]);
-        float L = 0.f, o = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float f = __expf(part[w][0] - M);        // waves without keys: exp(-inf) = 0
-            L = fmaf(part[w][1], f, L);
-            o = fmaf(part[w][2 + lane], f, o);
-        }
-        out[(size_t)slot * hidden + head * 64 + lane] = (T)(o / L);
-    }
+    gpt_attn1_body<T>(qkv, kc, vc, out, slot, head, hidden, max_seq, kv, AttnRowsOwn{});
 }
 
 __global__ __launch_bounds__(256) void gpt_text_embed_kernel(const int* __restrict__ ids, const float* __restrict__ emb,
@@ -899,8 +751,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     MI_HIP(hipStreamSynchronize(s));
     set_rep_value(0.7f);
     use_graph = !env_first_is("MI355TTS_NO_GRAPH", '1');
-    // the attention kernel's score buffer is dynamic LDS: max_seq + 64 + 512 floats
-    const int lds = (c.max_seq + 64 + 512) * 4;
+    const int lds = prompt_attn_lds();
     MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1005,14 +856,6 @@ void Gpt::gemv(const GLin& l, const void* x, const float* ln_w, const float* ln_
     MI_HIP(hipGetLastError());
 }
 
-#define GPT_DISPATCH(KERNEL, ...)                                                     \
-    do {                                                                              \
-        if (dtype == MI_F32) { KERNEL(float, __VA_ARGS__); }                          \
-        else if (dtype == MI_F16) { KERNEL(f16, __VA_ARGS__); }                       \
-        else { KERNEL(bf16, __VA_ARGS__); }                                           \
-        MI_HIP(hipGetLastError());                                                    \
-    } while (0)
-
 void Gpt::forward_rows(int rows, int flag, int slot) {
     const GptCfg& c = cfg;
     const int h = c.hidden, S = c.max_seq;
@@ -1021,13 +864,13 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     MI_REQUIRE(slot >= 0 && slot < c.max_batch, "gpt: slot");
     const int* st = state.as<int>() + (size_t)slot * GS_WORDS;
     float* x = X.as<float>();
-    const int lds = (S + 64 + 512) * 4;
+    const int lds = prompt_attn_lds();
     float* last_s = last.as<float>() + (size_t)slot * h;
     float* logits_s = logits.as<float>() + (size_t)slot * c.mel_codes;
     for (int li = 0; li < c.layers; ++li) {
         Layer& l = L[li];
-        char* kcl = (char*)kc.p + ((size_t)slot * slot_cache_elems() + (size_t)li * h * S) * es;
-        char* vcl = (char*)vc.p + ((size_t)slot * slot_cache_elems() + (size_t)li * h * S) * es;
+        const LayerKV lc = layer_cache(li, slot);
+        char *kcl = lc.k, *vcl = lc.v;
         if (rows == 1) {
             gemv(l.qkv, x, l.ln1_w.as<float>(), l.ln1_b.as<float>(), qkv.p, dtype, ACT_NONE, nullptr, kcl, vcl, slot);
         } else {
@@ -1066,23 +909,23 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     choose_token(rows, slot, true);
 }
 
-void Gpt::choose_token(int rows, int slot, bool x0) {
+void Gpt::choose_token(int rows, int slot, bool x0) { launch_choice(1, slot, rows, slot == 0 && x0 ? X.as<float>() : nullptr); }
+
+void Gpt::launch_choice(int nb, int slot0, int rows, float* xa) {
     const GptCfg& c = cfg;
     const int h = c.hidden, S = c.max_seq;
-    hipStream_t s = stream;
-    float* last_s = last.as<float>() + (size_t)slot * h;
-    float* logits_s = logits.as<float>() + (size_t)slot * c.mel_codes;
-    float* pen_s = pen.as<float>() + (size_t)slot * c.mel_codes;
-    int* st_s = state.as<int>() + (size_t)slot * GS_WORDS;
-    int* toks_s = toks.as<int>() + (size_t)slot * S;
-    float* hid_s = hid.as<float>() + (size_t)slot * S * h;
-    float* xa = slot == 0 && x0 ? X.as<float>() : nullptr;
-    float* xb = Xd.as<float>() + (size_t)slot * h;
+    float* last_s = last.as<float>() + (size_t)slot0 * h;
+    float* logits_s = logits.as<float>() + (size_t)slot0 * c.mel_codes;
+    float* pen_s = pen.as<float>() + (size_t)slot0 * c.mel_codes;
+    int* st_s = state.as<int>() + (size_t)slot0 * GS_WORDS;
+    int* toks_s = toks.as<int>() + (size_t)slot0 * S;
+    float* hid_s = hid.as<float>() + (size_t)slot0 * S * h;
+    float* xb = Xd.as<float>() + (size_t)slot0 * h;
     if (sampled)
-        launch_gpt_sample(1, logits_s, pen_s, last_s, st_s, toks_s, hid_s, c.mel_codes, h, rows, rep_dev.as<float>(), S,
-                          mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, xa, xb, samp.as<GptSampleRec>() + slot, s);
+        launch_gpt_sample(nb, logits_s, pen_s, last_s, st_s, toks_s, hid_s, c.mel_codes, h, rows, rep_dev.as<float>(), S,
+                          mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, xa, xb, samp.as<GptSampleRec>() + slot0, stream);
     else
-        hipLaunchKernelGGL(gpt_pick_kernel, dim3(1), dim3(1024), 0, s, logits_s, pen_s, last_s, st_s, toks_s, hid_s,
+        hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, stream, logits_s, pen_s, last_s, st_s, toks_s, hid_s,
                            c.mel_codes, h, rows, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
                            c.max_mel_pos, xa, xb);
     MI_HIP(hipGetLastError());
@@ -1118,28 +961,8 @@ void Gpt::check_graph_epoch() {
 }
 
 void Gpt::decode_steps(int n) {
-    if (n <= 0) return;
-    if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) decode_step_eager(); return; }
     check_graph_epoch();
-    hipGraphExec_t& exec = step_graph[sampled ? 1 : 0];
-    if (!exec) {
-        decode_step_eager();                   // first step eager (one-time lazy initialisation stays out of the capture)
-        --n;
-        hipGraph_t graph = nullptr;
-        MI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
-            decode_step_eager();
-        } catch (...) {
-            (void)hipStreamEndCapture(stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        MI_HIP(hipStreamEndCapture(stream, &graph));
-        hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_step_eager(); return; }
-    }
-    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
+    replay(step_graph[sampled ? 1 : 0], n, [&] { decode_step_eager(); });
 }
 
 // batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N).  Up to 16 rows: gemv_b16.  Above: 16-bit engines
@@ -1221,89 +1044,29 @@ void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int 
 // one decode step for slots 0..nb-1 together: graph C from each slot's state, graph E with every weight row streamed
 // once for all slots, per-slot argmax / penalty / stop bookkeeping.  Finished slots keep running as no-ops.
 void Gpt::decode_batch_eager(int nb) {
-    const GptCfg& c = cfg;
-    MI_REQUIRE(nb >= 1 && nb <= c.max_batch, "gpt: batch exceeds max_batch");
-    const int h = c.hidden, S = c.max_seq;
-    hipStream_t s = stream;
-    const size_t es = dtype_size(dtype);
-    float* x = Xd.as<float>();                 // row b = graph C of slot b's state, written by the pick kernel before
-    for (int li = 0; li < c.layers; ++li) {
-        Layer& l = L[li];
-        char* kcl = (char*)kc.p + (size_t)li * h * S * es;          // slot 0's layer; slots are slot_cache_elems apart
-        char* vcl = (char*)vc.p + (size_t)li * h * S * es;
-        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln1_w.as<float>(), l.ln1_b.as<float>(), nb, h, 1e-5f, s);
-        gemv_b(l.qkv, xnd.p, nb, qkvd.p, dtype, ACT_NONE, nullptr, kcl, vcl);
-        {
-            ProfScope ps(FAM_ATTN, s, 0.0, 0.0);
-#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_kernel<T>, dim3(c.heads, nb), dim3(256), 0, s, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), h, S, 1, slot_cache_elems())
-            GPT_DISPATCH(ATT, 0);
+    MI_REQUIRE(nb >= 1 && nb <= cfg.max_batch, "gpt: batch exceeds max_batch");
+    decode_rows_eager(nb, [&](char* kcl, char* vcl) {
+#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_kernel<T>, dim3(cfg.heads, nb), dim3(256), 0, stream, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), cfg.hidden, cfg.max_seq, 1, slot_cache_elems())
+        GPT_DISPATCH(ATT, 0);
 #undef ATT
-        }
-        gemv_b(l.proj, attd.p, nb, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
-        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln2_w.as<float>(), l.ln2_b.as<float>(), nb, h, 1e-5f, s);
-        gemv_b(l.fc, xnd.p, nb, ffd.p, dtype, ACT_GELU_TANH, nullptr, nullptr, nullptr);
-        gemv_b(l.fc2, ffd.p, nb, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
-    }
-    launch_rownorm(NORM_LN_AFFINE, x, last.p, MI_F32, lnf_w.as<float>(), lnf_b.as<float>(), nb, h, 1e-5f, s);
-    launch_rownorm(NORM_LN_AFFINE, last.as<float>(), zd.p, dtype, fn_w.as<float>(), fn_b.as<float>(), nb, h, 1e-5f, s);
-    gemv_b(head, zd.p, nb, logits.p, MI_F32, ACT_NONE, nullptr, nullptr, nullptr);
-    if (sampled)
-        launch_gpt_sample(nb, logits.as<float>(), pen.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(),
-                          hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
-                          c.max_mel_pos, (float*)nullptr, Xd.as<float>(), samp.as<GptSampleRec>(), s);
-    else
-        hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, s, logits.as<float>(), pen.as<float>(), last.as<float>(),
-                           state.as<int>(), toks.as<int>(), hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S,
-                           mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, (float*)nullptr, Xd.as<float>());
-    MI_HIP(hipGetLastError());
+    }, [&] { launch_choice(nb, 0, 1, nullptr); });
 }
 
 void Gpt::decode_batch_steps(int nb, int n) {
-    if (n <= 0) return;
-    if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) decode_batch_eager(nb); return; }
     check_graph_epoch();
-    hipGraphExec_t& exec = batch_graphs[{nb, sampled ? 1 : 0}];
-    if (!exec) {
-        decode_batch_eager(nb);
-        --n;
-        hipGraph_t graph = nullptr;
-        MI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
-            decode_batch_eager(nb);
-        } catch (...) {
-            (void)hipStreamEndCapture(stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        MI_HIP(hipStreamEndCapture(stream, &graph));
-        hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_batch_eager(nb); return; }
-    }
-    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
+    replay(batch_graphs[{nb, sampled ? 1 : 0}], n, [&] { decode_batch_eager(nb); });
 }
 
 double Gpt::bench_pick(int nb, int iters) {
     const GptCfg& c = cfg;
     MI_REQUIRE(nb >= 1 && nb <= c.max_batch && iters >= 1, "gpt: bench_pick arguments");
-    const int h = c.hidden, S = c.max_seq;
     std::vector<int32_t> saved((size_t)nb * GS_WORDS), done;
     MI_HIP(hipMemcpyAsync(saved.data(), state.p, saved.size() * 4, hipMemcpyDeviceToHost, stream));
     MI_HIP(hipStreamSynchronize(stream));
     done = saved;
     for (int b = 0; b < nb; ++b) done[(size_t)b * GS_WORDS + GS_DONE] = 1;
     MI_HIP(hipMemcpyAsync(state.p, done.data(), done.size() * 4, hipMemcpyHostToDevice, stream));
-    auto launch = [&] {
-        if (sampled)
-            launch_gpt_sample(nb, logits.as<float>(), pen.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(),
-                              hid.as<float>(), c.mel_codes, h, 1, rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(),
-                              c.max_mel_pos, (float*)nullptr, Xd.as<float>(), samp.as<GptSampleRec>(), stream);
-        else
-            hipLaunchKernelGGL(gpt_pick_kernel, dim3(nb), dim3(1024), 0, stream, logits.as<float>(), pen.as<float>(),
-                               last.as<float>(), state.as<int>(), toks.as<int>(), hid.as<float>(), c.mel_codes, h, 1,
-                               rep_dev.as<float>(), S, mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, (float*)nullptr,
-                               Xd.as<float>());
-    };
+    auto launch = [&] { launch_choice(nb, 0, 1, nullptr); };
     for (int i = 0; i < 3; ++i) launch();
     hipEvent_t e0, e1;
     MI_HIP(hipEventCreate(&e0)); MI_HIP(hipEventCreate(&e1));
@@ -1339,10 +1102,10 @@ void Gpt::kv_read(int layer, float* keys_dev, float* values_dev) {
     MI_REQUIRE(layer >= 0 && layer < cfg.layers, "gpt: layer index");
     const int hist = history;
     if (hist == 0) return;
-    const size_t es = dtype_size(dtype), off = (size_t)layer * cfg.hidden * cfg.max_seq * es;
+    const LayerKV kv = layer_cache(layer);
     const long items = (long)cfg.heads * hist * 64;
     const dim3 grid((unsigned)((items + 255) / 256));
-#define KVE(T, ...) hipLaunchKernelGGL(kv_export_kernel<T>, grid, dim3(256), 0, stream, (const T*)((char*)kc.p + off), (const T*)((char*)vc.p + off), keys_dev, values_dev, cfg.heads, hist, cfg.max_seq)
+#define KVE(T, ...) hipLaunchKernelGGL(kv_export_kernel<T>, grid, dim3(256), 0, stream, (const T*)kv.k, (const T*)kv.v, keys_dev, values_dev, cfg.heads, hist, cfg.max_seq)
     GPT_DISPATCH(KVE, 0);
 #undef KVE
 }
@@ -1351,10 +1114,10 @@ void Gpt::kv_write(int layer, const float* keys_dev, const float* values_dev, in
     MI_REQUIRE(layer >= 0 && layer < cfg.layers, "gpt: layer index");
     MI_REQUIRE(hist >= 0 && hist < cfg.max_seq, "gpt: history does not fit the KV cache (max_seq)");
     if (hist > 0) {
-        const size_t es = dtype_size(dtype), off = (size_t)layer * cfg.hidden * cfg.max_seq * es;
+        const LayerKV kv = layer_cache(layer);
         const long items = (long)cfg.heads * hist * 64;
         const dim3 grid((unsigned)((items + 255) / 256));
-#define KVI(T, ...) hipLaunchKernelGGL(kv_import_kernel<T>, grid, dim3(256), 0, stream, (T*)((char*)kc.p + off), (T*)((char*)vc.p + off), keys_dev, values_dev, cfg.heads, hist, cfg.max_seq)
+#define KVI(T, ...) hipLaunchKernelGGL(kv_import_kernel<T>, grid, dim3(256), 0, stream, (T*)kv.k, (T*)kv.v, keys_dev, values_dev, cfg.heads, hist, cfg.max_seq)
         GPT_DISPATCH(KVI, 0);
 #undef KVI
     }

@@ -1,20 +1,21 @@
 // gpt_beam.hip — beam search of the IndexTTS decode loop on the device: the definition is in include/mi355tts.h ("beam search"),
 // this is its device form.  A sentence's B hypotheses sit in B consecutive slots (a group) and every decode step is the batched
-// step of gpt.hip over nb * B rows with two kernels of its own:
+// step (Gpt::decode_rows_eager, gpt.h) over nb * B rows with its own attention launch and its own last kernel:
 //
 //   gpt_beam_step_kernel    one 1024-thread workgroup per sentence, like the two pick kernels: row max and lse of the B rows of
 //                           logits * penalty, the B best of the B * codes candidates, then the hypotheses move to their new slots —
 //                           penalty vector, GS_* words, score and ancestor table follow the parent; gpt_pick_finish's bookkeeping
 //                           with the hypothesis' own token; graph C rows for the next step.
-//   gpt_attn1_beam_kernel   gpt_attn1_kernel with the slot of every key / value row taken from the ancestor table: the cache is
-//                           never copied.  Position P + n of hypothesis i lives in slot anc[i][n], positions below P (the prompt)
-//                           in the group's first slot.  Same passes, same order of the online-softmax updates: in fp32 the output
-//                           equals what a privately owned cache would give.
+//   gpt_attn1_beam_kernel   the decode-step attention body (gpt_attn1_body, gpt_attn.h) with the slot of every key / value row
+//                           taken from the ancestor table: the cache is never copied.  Position P + n of hypothesis i lives in
+//                           slot anc[i][n], positions below P (the prompt) in the group's first slot.  The body is the one
+//                           gpt_attn1_kernel runs on a privately owned cache, so in fp32 the two outputs are equal.
 //
 // The move is not in place (two children may share a parent, a child's slot may be another child's parent): penalty vectors and
 // ancestor tables exist twice and the side in use is GS_NDEC & 1, read on the device, so a captured step replays unchanged.
 // State words and scores are small: the workgroup reads all of them before it writes any.
 #include "gpt.h"
+#include "gpt_attn.h"
 #include "gpt_pick.h"
 #include "gpt_vec.h"
 #include "wave_reduce.h"
@@ -269,116 +270,24 @@ __global__ __launch_bounds__(1024) void gpt_beam_step_kernel(const float* __rest
     }
 }
 
-// gpt_attn1_kernel (gpt.hip) with the slot of every key / value row read from the ancestor table.  blockIdx.y = slot; its
-// group's first slot holds the prompt's rows.  A lane's key j >= P sits in slot anc[j - P] of the group; the value rows of a pass
-// take their slots from the lanes that hold the same keys.  One extra dependent load per lane and pass, in front of the K loads.
+// Decode-step attention of a hypothesis: gpt_attn1_body (gpt_attn.h) with the slot of every key / value row read from the
+// ancestor table.  blockIdx.y = slot; its group's first slot holds the prompt's rows.  A lane's key j >= P sits in slot
+// anc[j - P] of the group; the value rows of a pass take their slots from the lanes that hold the same keys.
 template <typename T>
 __global__ __launch_bounds__(256) void gpt_attn1_beam_kernel(const T* __restrict__ qkv, const T* __restrict__ kc,
                                                              const T* __restrict__ vc, T* __restrict__ out,
                                                              const int* __restrict__ st, const int* __restrict__ anc0,
                                                              const int* __restrict__ anc1, int hidden, int max_seq,
                                                              size_t slot_stride, int B) {
-    constexpr int V = Pack16<T>::N;            // elements per 16 bytes
-    constexpr int CH = 64 / V;                 // 16-byte chunks per 64-wide row
-    constexpr int KPI = 64 / CH;               // value rows per wave instruction
-    constexpr int NIT = 64 / KPI;              // instructions per 64-key pass
-    __shared__ float part[4][66];
-    const int head = blockIdx.x, slot = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int head = blockIdx.x, slot = blockIdx.y;
     const int s0 = slot / B * B;               // the group's first slot
     st += slot * GS_WORDS;
     const int hist = st[GS_HIST], ndec = st[GS_NDEC];
     const int kv = min(max(hist, 0) + 1, max_seq);
     const int P = hist - ndec + 1;             // the prompt's rows: history = P + (selections so far - 1)
     const int* anc = ((ndec & 1) ? anc1 : anc0) + (size_t)slot * max_seq;
-    Pack16<T> q[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) q[c] = ld16(qkv + (size_t)slot * 3 * hidden + head * 64 + c * V);
-    const T* kb = kc + (size_t)s0 * slot_stride + (size_t)head * max_seq * 64;
-    const T* vb = vc + (size_t)s0 * slot_stride + (size_t)head * max_seq * 64;
-    const int g = lane / CH, c = lane % CH;
-    float m_run = -INFINITY, l_run = 0.f, acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    struct Pass { Pack16<T> kp[CH], vp[NIT]; };
-    auto load_pass = [&](Pass& ps, int base) {
-        const int j = base + lane;
-        const int jc = j < kv ? j : base;
-        // branch-free: the table is read at a clamped index and the answer dropped for prompt rows; a wrong entry can only
-        // name another slot of the group
-        const int a = anc[min(max(jc - P, 0), max_seq - 1)];
-        const int sl = jc >= P ? min(max(a, 0), B - 1) : 0;
-        const T* kr = kb + (size_t)sl * slot_stride + (size_t)jc * 64;
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) ps.kp[cc] = ld16(kr + cc * V);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int jj = base + it * KPI + g;
-            const bool ok = jj < kv;
-            const int sv = __shfl(sl, ok ? it * KPI + g : 0, 64);
-            ps.vp[it] = ld16(vb + (size_t)sv * slot_stride + (size_t)(ok ? jj : base) * 64 + c * V);
-        }
-    };
-    auto fold_pass = [&](const Pass& ps, int base) {
-        const bool kok = base + lane < kv;
-        float s = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) s = dot_pack(ps.kp[cc], q[cc], s);
-        s = kok ? s : -INFINITY;
-        const float mw = wave_max(s);
-        const float m_new = fmaxf(m_run, mw);              // finite: the pass holds at least one key
-        const float pj = kok ? __expf(s - m_new) : 0.f;
-        const float corr = __expf(m_run - m_new);          // exp(-inf) = 0 on the first pass
-        l_run = l_run * corr + wave_sum(pj);
-        m_run = m_new;
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] *= corr;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const float pk = __shfl(pj, it * KPI + g, 64);  // 0 for keys beyond kv
-#pragma unroll
-            for (int e = 0; e < V; ++e) acc[e] = fmaf(pk, (float)ps.vp[it].v[e], acc[e]);
-        }
-    };
-    // the wave's passes (every fourth 64-key block), the next one in flight while the current one is folded in
-    int base = wave * 64;
-    if (base < kv) {
-        Pass pa, pb;
-        load_pass(pa, base);
-        for (;;) {
-            bool more = base + 256 < kv;
-            if (more) load_pass(pb, base + 256);
-            fold_pass(pa, base);
-            if (!more) break;
-            base += 256;
-            more = base + 256 < kv;
-            if (more) load_pass(pa, base + 256);
-            fold_pass(pb, base);
-            if (!more) break;
-            base += 256;
-        }
-    }
-#pragma unroll
-    for (int o = CH; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    if (lane == 0) { part[wave][0] = m_run; part[wave][1] = l_run; }
-    if (g == 0)
-#pragma unroll
-        for (int e = 0; e < V; ++e) part[wave][2 + c * V + e] = acc[e];
-    __syncthreads();
-    if (wave == 0) {
-        float M = part[0][0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) M = fmaxf(M, part[w][0]);
-        float L = 0.f, o = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float f = __expf(part[w][0] - M);        // waves without keys: exp(-inf) = 0
-            L = fmaf(part[w][1], f, L);
-            o = fmaf(part[w][2 + lane], f, o);
-        }
-        out[(size_t)slot * hidden + head * 64 + lane] = (T)(o / L);
-    }
+    gpt_attn1_body<T>(qkv, kc + (size_t)s0 * slot_stride, vc + (size_t)s0 * slot_stride, out, slot, head, hidden, max_seq, kv,
+                      AttnRowsAncestor{anc, P, B, max_seq, slot_stride});
 }
 
 // hypothesis 0 of every group along its ancestors: token n and last_hidden_state row n were stored by slot anc[n]
@@ -436,64 +345,22 @@ static void beam_step_launch(Gpt& e, int groups, int group0, int B, int rows, in
 
 void Gpt::beam_select_first(int group, int B, int rows) { beam_step_launch(*this, 1, group, B, rows, 1); }
 
-// decode_batch_eager over the nb * B hypotheses, with the attention that follows the ancestor table and the selection
+// the batched decode step over the nb * B hypotheses, with the attention that follows the ancestor table and the selection
 void Gpt::decode_beam_eager(int nb, int B) {
-    const GptCfg& c = cfg;
     const int nr = nb * B;
-    MI_REQUIRE(nb >= 1 && B >= 1 && nr <= c.max_batch && pen_b.p, "gpt beam: batch exceeds max_batch");
-    const int h = c.hidden, S = c.max_seq;
-    hipStream_t s = stream;
-    const size_t es = dtype_size(dtype);
-    float* x = Xd.as<float>();                 // row = graph C of the hypothesis' last token, written by the selection before
+    MI_REQUIRE(nb >= 1 && B >= 1 && nr <= cfg.max_batch && pen_b.p, "gpt beam: batch exceeds max_batch");
     const int* anc0 = anc.as<int>();
-    const int* anc1 = anc0 + (size_t)MBp * S;
-    for (int li = 0; li < c.layers; ++li) {
-        Layer& l = L[li];
-        char* kcl = (char*)kc.p + (size_t)li * h * S * es;
-        char* vcl = (char*)vc.p + (size_t)li * h * S * es;
-        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln1_w.as<float>(), l.ln1_b.as<float>(), nr, h, 1e-5f, s);
-        gemv_b(l.qkv, xnd.p, nr, qkvd.p, dtype, ACT_NONE, nullptr, kcl, vcl);
-        {
-            ProfScope ps(FAM_ATTN, s, 0.0, 0.0);
-#define ATT(T) hipLaunchKernelGGL(gpt_attn1_beam_kernel<T>, dim3(c.heads, nr), dim3(256), 0, s, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), anc0, anc1, h, S, slot_cache_elems(), B)
-            if (dtype == MI_F32) ATT(float); else if (dtype == MI_F16) ATT(f16); else ATT(bf16);
+    const int* anc1 = anc0 + (size_t)MBp * cfg.max_seq;
+    decode_rows_eager(nr, [&](char* kcl, char* vcl) {
+#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_beam_kernel<T>, dim3(cfg.heads, nr), dim3(256), 0, stream, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), anc0, anc1, cfg.hidden, cfg.max_seq, slot_cache_elems(), B)
+        GPT_DISPATCH(ATT, 0);
 #undef ATT
-            MI_HIP(hipGetLastError());
-        }
-        gemv_b(l.proj, attd.p, nr, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
-        launch_rownorm(NORM_LN_AFFINE, x, xnd.p, dtype, l.ln2_w.as<float>(), l.ln2_b.as<float>(), nr, h, 1e-5f, s);
-        gemv_b(l.fc, xnd.p, nr, ffd.p, dtype, ACT_GELU_TANH, nullptr, nullptr, nullptr);
-        gemv_b(l.fc2, ffd.p, nr, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
-    }
-    launch_rownorm(NORM_LN_AFFINE, x, last.p, MI_F32, lnf_w.as<float>(), lnf_b.as<float>(), nr, h, 1e-5f, s);
-    launch_rownorm(NORM_LN_AFFINE, last.as<float>(), zd.p, dtype, fn_w.as<float>(), fn_b.as<float>(), nr, h, 1e-5f, s);
-    gemv_b(head, zd.p, nr, logits.p, MI_F32, ACT_NONE, nullptr, nullptr, nullptr);
-    beam_step_launch(*this, nb, 0, B, 1, 0);
+    }, [&] { beam_step_launch(*this, nb, 0, B, 1, 0); });
 }
 
 void Gpt::decode_beam_steps(int nb, int B, int n) {
-    if (n <= 0) return;
-    if (!use_graph || prof_mask() != 0) { for (int i = 0; i < n; ++i) decode_beam_eager(nb, B); return; }
     check_graph_epoch();
-    hipGraphExec_t& exec = batch_graphs[{nb * B, 1 + B}];
-    if (!exec) {
-        decode_beam_eager(nb, B);              // first step eager (one-time lazy initialisation stays out of the capture)
-        --n;
-        hipGraph_t graph = nullptr;
-        MI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
-            decode_beam_eager(nb, B);
-        } catch (...) {
-            (void)hipStreamEndCapture(stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        MI_HIP(hipStreamEndCapture(stream, &graph));
-        hipError_t err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (err != hipSuccess) { exec = nullptr; use_graph = false; for (int i = 0; i < n; ++i) decode_beam_eager(nb, B); return; }
-    }
-    for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
+    replay(batch_graphs[{nb * B, 1 + B}], n, [&] { decode_beam_eager(nb, B); });
 }
 
 void Gpt::beam_gather(int nb, int B, int32_t* tokens, float* hidden, int cap) {

@@ -6,11 +6,12 @@
 // launch_rownorm / launch_conv_gemm path, M = the packed row count).  Only two things know about sentences:
 //   * the KV scatter: packed row r of segment g -> cache row r - first_g of slot slot_g (the slot's history is 0);
 //   * the attention: work item (head, packed row) finds its segment in a small device table and attends to the keys
-//     0 .. rows_g - 1 of its own slot with the reference's additive mask (-128 on keys j > i, every key visited), exactly as
-//     gpt_attn_kernel does for a lone prompt.  It never reads a cache row beyond rows_g: a refilled slot still holds the rows
-//     of the sentence before.
+//     0 .. rows_g - 1 of its own slot with the reference's additive mask (-128 on keys j > i, every key visited): the prompt
+//     attention body of gpt_attn.h, which gpt_attn_kernel (gpt.hip) runs for a lone prompt.  It never reads a cache row
+//     beyond rows_g: a refilled slot still holds the rows of the sentence before.
 // The tail (ln_f + final_norm + lm_head on each segment's last row, then the token choice) is forward_rows' own, per segment.
 #include "gpt.h"
+#include "gpt_attn.h"
 #include "gpt_pick.h"
 #include "gpt_vec.h"
 #include "wave_reduce.h"
@@ -48,91 +49,26 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ q
     *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
-// one block per (head, packed row): softmax(q K^T + mask) V over the row's own segment.  gpt_attn_kernel (gpt.hip) with the
-// slot, the query index and the key count taken from the segment table: lane-per-key dot products (each lane streams one
-// 64-wide key row with 16-byte loads; keys beyond 512 come round again in the strided loop), then 8 lanes per value row.
-// All LDS scratch is in the dynamic region, carved at multiples of 16 bytes: sc [max_seq rounded up to 4] | qs [64] |
-// red [8 * 64] | bc [4].
+// one block per (head, packed row): gpt_prompt_attn_body (gpt_attn.h) over the row's own segment, with the slot, the query
+// index and the key count taken from the segment table.  All LDS scratch is in the dynamic region, carved at multiples of
+// 16 bytes: sc [max_seq rounded up to 4] | qs [64] | red [8 * 64] | bc [4].
 template <typename T>
 __global__ __launch_bounds__(512) void gpt_attn_packed_kernel(const T* __restrict__ qkv, const T* __restrict__ kc,
                                                               const T* __restrict__ vc, T* __restrict__ out,
                                                               const int4* __restrict__ segs, int nseg, int hidden,
                                                               int max_seq, int max_batch, size_t slot_stride) {
-    constexpr int V = Pack16<T>::N;            // elements per 16 bytes
-    constexpr int CH = 64 / V;                 // 16-byte chunks per key row
     extern __shared__ __attribute__((aligned(16))) float psm[];
     float* sc = psm;                           // [max_seq rounded up to 4]
     float* qs = psm + ((max_seq + 3) & ~3);    // [64]
     float* red = qs + 64;                      // [8 * 64]
     float* bc = red + 512;                     // [4]
-    const int head = blockIdx.x, row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int head = blockIdx.x, row = blockIdx.y;
     const int4 g = gpt_find_seg(segs, nseg, row);
     const int i = row - g.x;                   // the query's position inside its sentence
     const int kv = min(g.y, max_seq);          // keys 0 .. rows_g - 1 of the slot, and no further
     if (i < 0 || i >= kv || g.z < 0 || g.z >= max_batch) return;      // block-uniform: a table that does not cover the row
     kc += (size_t)g.z * slot_stride; vc += (size_t)g.z * slot_stride;
-    if (tid < 64) qs[tid] = (float)qkv[(size_t)row * 3 * hidden + head * 64 + tid];
-    __syncthreads();
-    const T* kb = kc + (size_t)head * max_seq * 64;
-    const T* vb = vc + (size_t)head * max_seq * 64;
-    float mx = -3.0e38f;
-    for (int j = tid; j < kv; j += 512) {
-        const T* kr = kb + (size_t)j * 64;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const Pack16<T> p = ld16(kr + c * V);
-#pragma unroll
-            for (int e = 0; e < V; ++e) s = fmaf(qs[c * V + e], (float)p.v[e], s);
-        }
-        if (j > i) s += -128.f;                // the reference's additive mask: not -inf, and no key is skipped
-        sc[j] = s;
-        mx = fmaxf(mx, s);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    if (tid == 0) { float m = red[0]; for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w]); bc[0] = m; }
-    __syncthreads();
-    mx = bc[0];
-    float sum = 0.f;
-    for (int j = tid; j < kv; j += 512) { const float e = __expf(sc[j] - mx); sc[j] = e; sum += e; }
-    sum = wave_sum(sum);
-    __syncthreads();
-    if (lane == 0) red[wave] = sum;
-    __syncthreads();
-    if (tid == 0) { float t = 0.f; for (int w = 0; w < 8; ++w) t += red[w]; bc[1] = t; }
-    __syncthreads();
-    const float inv = 1.f / bc[1];
-    // values: lane = (key-in-group gk, chunk c) ; a wave covers 64/CH keys per pass
-    constexpr int KPW = 64 / CH;               // keys per wave pass
-    const int gk = lane / CH, c = lane % CH;
-    float acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    for (int j = wave * KPW + gk; j < kv; j += 8 * KPW) {
-        const float p = sc[j];
-        const Pack16<T> v = ld16(vb + (size_t)j * 64 + c * V);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] = fmaf(p, (float)v.v[e], acc[e]);
-    }
-    // reduce over gk (lanes that share c): xor over the gk bits
-#pragma unroll
-    for (int o = CH; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    __syncthreads();
-    if (gk == 0)
-#pragma unroll
-        for (int e = 0; e < V; ++e) red[wave * 64 + c * V + e] = acc[e];
-    __syncthreads();
-    if (tid < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) t += red[w * 64 + tid];
-        out[(size_t)row * hidden + head * 64 + tid] = (T)(t * inv);
-    }
+    gpt_prompt_attn_body<T>(i, kv, 1, qkv, kc, vc, out, row, head, hidden, max_seq, sc, qs, red, bc);
 }
 
 __global__ __launch_bounds__(256) void gpt_fill_kernel(float* __restrict__ p, float v, int n) {
@@ -147,14 +83,6 @@ void Gpt::reset_penalty(int slot) {
                        pen.as<float>() + (size_t)slot * n, 1.f, n);
     MI_HIP(hipGetLastError());
 }
-
-#define GPT_DISPATCH(KERNEL, ...)                                                     \
-    do {                                                                              \
-        if (dtype == MI_F32) { KERNEL(float, __VA_ARGS__); }                          \
-        else if (dtype == MI_F16) { KERNEL(f16, __VA_ARGS__); }                       \
-        else { KERNEL(bf16, __VA_ARGS__); }                                           \
-        MI_HIP(hipGetLastError());                                                    \
-    } while (0)
 
 static_assert(GPT_MAX_BATCH <= 64, "forward_packed keeps the slots of a pass in a 64-bit mask");
 
@@ -194,8 +122,8 @@ void Gpt::forward_packed(const Seg* segs, int k) {
     const size_t sstride = slot_cache_elems();
     for (int li = 0; li < c.layers; ++li) {
         Layer& l = L[li];
-        char* kcl = (char*)kc.p + (size_t)li * h * S * es;          // slot 0's layer; slots are slot_cache_elems apart
-        char* vcl = (char*)vc.p + (size_t)li * h * S * es;
+        const LayerKV lc = layer_cache(li);                          // slot 0's layer; slots are slot_cache_elems apart
+        char *kcl = lc.k, *vcl = lc.v;
         launch_rownorm(NORM_LN_AFFINE, x, xn.p, dtype, l.ln1_w.as<float>(), l.ln1_b.as<float>(), total, h, 1e-5f, s);
         linear(l.qkv, xn.p, total, qkv.p, dtype, ACT_NONE, nullptr);
         {

@@ -27,6 +27,10 @@ together share one pass over the weights — and `run_latent_ragged` vocodes the
 Every queued sentence starts from a FRESH penalty vector: the sentences run concurrently, so the carry of the vector from one
 sentence to the next that the sentence-by-sentence forms keep (like the reference) does not exist there.  Sampling flags apply
 (one seed per sentence: sample-seed + its index); beams and takes do not go through the queue.
+With `--queue`, `--prompt a.wav,b.wav,...` is a dialogue: graph A runs once per file, sentence i is spoken by voice i mod V (or by
+`--voice-of 0,1,1,0,...`, one index per sentence), every sentence's prompt carries its own voice's conditioning rows, and ONE
+`run_latent_voices` call vocodes all of them in order, whatever the mix of voices.  One prompt file is the one-voice case of the
+same calls: the same output file as before.
 """
 import argparse
 import dataclasses
@@ -87,7 +91,9 @@ MAX_SLOTS = 64                                 # the engine's batch slots (Index
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--prompt", help="reference audio (RIFF/WAVE); default: a synthetic 3 s tone")
+    ap.add_argument("--prompt", help="reference audio (RIFF/WAVE); default: a synthetic 3 s tone.  With --queue: a comma-separated list, one file per voice")
+    ap.add_argument("--voice-of", default=None, help="with --queue and several prompts: the voice index of every sentence, comma-separated "
+                    "(default: sentence i speaks with voice i mod V)")
     ap.add_argument("--text", default="The quick brown fox jumps over the lazy dog. Pack my box with five dozen liquor jugs!")
     ap.add_argument("--out", default="generated.wav")
     ap.add_argument("--tokenizer", default=os.path.join(ROOT, "tests", "golden", "indextts_sp.model"),
@@ -108,6 +114,16 @@ def parse_args(argv=None):
                     "every sentence starts from a fresh penalty vector")
     ap.add_argument("--slots", type=int, default=8, help=f"batch slots of --queue (1..{MAX_SLOTS})")
     args = ap.parse_args(argv)
+    args.prompts = args.prompt.split(",") if args.prompt else [None]
+    if (len(args.prompts) > 1 or args.voice_of is not None) and not args.queue:
+        ap.error("several --prompt files / --voice-of need --queue (one run_latent_voices call vocodes the whole dialogue)")
+    if args.voice_of is not None:
+        try:
+            args.voice_of = [int(x) for x in args.voice_of.split(",")]
+        except ValueError:
+            ap.error("--voice-of takes comma-separated integers")
+        if any(not 0 <= x < len(args.prompts) for x in args.voice_of):
+            ap.error(f"--voice-of indices must be in 0..{len(args.prompts) - 1} (one --prompt file per voice)")
     if not 1 <= args.slots <= MAX_SLOTS:
         ap.error(f"--slots must be in 1..{MAX_SLOTS} (the engine's batch slots)")
     if args.queue and (args.takes > 1 or args.num_beams > 1 or args.device_type == "cuda"):
@@ -134,18 +150,20 @@ def main():
     sp, tokenizer = build_tokenizer(args.tokenizer)
     (gcfg, ccfg, vcfg), (cond, gpt, voc) = build_engines(args, sp.get_piece_size())
     rate = vcfg.sampling_rate
-    if args.prompt:
-        prompt_audio = np.asarray(audio_io.load_prompt(args.prompt, rate), dtype=np.int16).reshape(-1)
-    else:
-        prompt_audio = (0.1 * 32767 * np.sin(2 * np.pi * 220 * np.arange(3 * rate) / rate)).astype(np.int16)
+    prompt_audios = [np.asarray(audio_io.load_prompt(f, rate), dtype=np.int16).reshape(-1) if f else
+                     (0.1 * 32767 * np.sin(2 * np.pi * 220 * np.arange(3 * rate) / rate)).astype(np.int16) for f in args.prompts]
     on_device = args.device_type == "cuda"
     if on_device:
         import torch
         dev = torch.device("cuda", 0)
 
     t_start = time.time()
-    voc_cond_flat, conds_latent = cond.run(prompt_audio)                 # once per speaker
-    stage_conds, embed_cond = cond.split_conds(voc_cond_flat)
+    speakers = []                                                       # per voice: (graph F's conditioning list, the GPT prompt's rows)
+    for audio in prompt_audios:                                         # graph A, once per speaker
+        voc_cond_flat, latent_rows = cond.run(audio)
+        stage, embed = cond.split_conds(voc_cond_flat)
+        speakers.append((list(stage) + [embed], latent_rows))
+    (*stage_conds, embed_cond), conds_latent = speakers[0]              # the sentence-by-sentence forms speak with the first voice
     stops = [] if args.ignore_stop else [gcfg.stop_mel_token]
     gap = np.zeros((1, 1, int(rate * 0.2)), dtype=np.int16)              # 0.2 s of silence behind every sentence
     if on_device:
@@ -157,10 +175,13 @@ def main():
     sentences = tokenizer.split_sentences(tokenizer.tokenize(args.text))
     if args.queue:
         prompts, budgets = [], []
-        for sentence in sentences:
-            print("Queue the Voice for '" + "".join(sentence).replace("▁", " ") + "'")
+        voice_of = args.voice_of if args.voice_of is not None else [i % len(speakers) for i in range(len(sentences))]
+        if len(voice_of) != len(sentences):
+            raise SystemExit(f"--voice-of names {len(voice_of)} sentences, the text has {len(sentences)}")
+        for sentence, voice in zip(sentences, voice_of):
+            print(f"Queue voice {voice} for '" + "".join(sentence).replace("▁", " ") + "'")
             ids = np.asarray(tokenizer.convert_tokens_to_ids(sentence), dtype=np.int32)
-            prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
+            prompt_rows, prompt_len = gpt.concat(speakers[voice][1][None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
             prompts.append(prompt_rows)
             budgets.append(max(gcfg.max_generate_length - int(prompt_len[0]), 0))
         t_dec = time.time()
@@ -169,9 +190,9 @@ def main():
         n_codes = sum(h.shape[0] for _, h in results)
         print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "
               f"{gcfg.max_batch} slots: {q_stats['steps']} decode steps, {q_stats['passes']} prompt passes)")
-        latents = [h for _, h in results if h.shape[0] >= 3]         # the vocoder needs three codes
-        if latents:
-            for wav in voc.run_latent_ragged(latents, list(stage_conds) + [embed_cond]):
+        keep = [i for i, (_, h) in enumerate(results) if h.shape[0] >= 3]         # the vocoder needs three codes
+        if keep:                                                     # one forward for every voice in flight
+            for wav in voc.run_latent_voices([results[i][1] for i in keep], [c for c, _ in speakers], [voice_of[i] for i in keep]):
                 pieces.append(np.concatenate([wav, gap], axis=-1))
     for sentence in ([] if args.queue else sentences):
         print("Generate the Voice for '" + "".join(sentence).replace("▁", " ") + "'")

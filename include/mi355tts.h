@@ -87,11 +87,22 @@ int         mi_bigvgan_forward_latent(mi_bigvgan* h, const float* latent, int T_
 int         mi_bigvgan_forward_ragged(mi_bigvgan* h, int B, const float* mel, const int64_t* frames, int16_t* out_i16,
                                       float* out_f32, int64_t out_cap, int64_t* out_lens, int mem);
 /* ... and IndexTTS graph F for B sentences of one speaker: latent = the items' (t_codes[b], gpt_dim) rows concatenated (the last
- * two rows of each are dropped, like mi_bigvgan_forward_latent; t_codes[b] >= 3, host int64); one conditioning vector for all
- * items, in the layout of mi_bigvgan_forward_latent.  out_lens[b] = (t_codes[b] - 2) * hop + 30.                            */
+ * two rows of each are dropped, like mi_bigvgan_forward_latent; t_codes[b] >= 3, host int64); conds = one conditioning vector
+ * in the layout of mi_bigvgan_forward_latent.  This is the one-voice form of mi_bigvgan_forward_latent_voices (n_voices = 1,
+ * voice_of = 0 ... 0): the same forward, the same kernels.  out_lens[b] = (t_codes[b] - 2) * hop + 30.                      */
 int         mi_bigvgan_forward_latent_ragged(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, const float* conds,
                                              int64_t n_conds, int16_t* out_i16, float* out_f32, int64_t out_cap, int64_t* out_lens,
                                              int mem);
+/* ... and for B sentences of several speakers in one forward: conds = (n_voices, n_conds) fp32, row-major, every row in the layout
+ * of mi_bigvgan_forward_latent (follows `mem`); voice_of[b] (host int32, B values in [0, n_voices)) names item b's row.  A kernel
+ * builds the (B, n_conds) table of layer bias + conditioning on the device and conv_pre and the upsamplers read their bias by
+ * item, so with mem = MI_DEVICE the conditioning never visits the host.  Item b gets the waveform a forward of it alone with
+ * voice voice_of[b] gives.  The remaining arguments are those of mi_bigvgan_forward_latent_ragged.  MI_EINVAL, with the handle
+ * still usable, for n_voices < 1, a voice_of[b] outside [0, n_voices), n_conds other than the handle's total, a handle that is
+ * not graph F, and everything mi_bigvgan_forward_latent_ragged rejects.                                                     */
+int         mi_bigvgan_forward_latent_voices(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, int n_voices,
+                                             const float* conds, int64_t n_conds, const int32_t* voice_of, int16_t* out_i16,
+                                             float* out_f32, int64_t out_cap, int64_t* out_lens, int mem);
 /* unit-level entry (tests): one anti-aliased SnakeBeta Activation1d on x (B,C,T) fp32
  * channels-first host memory; post!=0 selects the pad-15 variant (out T+30).                   */
 int         mi_aa_activation1d(const float* x, int B, int C, int T, const float* alpha_log,

@@ -55,18 +55,28 @@ struct BigVGAN {
     // ragged batches (padded slabs of Fmax frames, item b live in its first frames[b]): mel = the items' (num_mels, frames[b])
     // arrays concatenated; the waveforms (frames[b] * hop + 30 samples each) leave concatenated in the same order
     void run_ragged(const float* mel, int B, const int* frames, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
-    // ... and graph F: latent = the items' (T_codes[b], num_mels) rows concatenated, one conditioning vector for all items
+    // ... and graph F: latent = the items' (T_codes[b], num_mels) rows concatenated; item b speaks with voice voice_of[b] (host, B
+    // ints in [0, n_voices)), conds = (n_voices, n_conds) rows in run_latent's layout (follows `mem`).  The seven speaker biases
+    // become one device table of B rows (cond_bias_table_kernel) that conv_pre and the upsamplers index by item.
+    void run_latent_voices(const float* latent, int B, const int* T_codes, int n_voices, const float* conds, long n_conds,
+                           const int* voice_of, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
+    // ... the one-voice form of it: n_voices = 1, voice_of = 0 ... 0
     void run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
                            int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
     // IndexTTS graph F: latent (T_codes, num_mels) channels-last fp32, conds = [cond_0 .. cond_{n_up-1}, cond_pre] concatenated
     void run_latent(const float* latent, int T_codes, const float* conds, long n_conds, float* out_f32, int16_t* out_i16, int mem);
-    void body(const void* x0, int B, int F, const float* const* cond_ptrs, float* out_f32, int16_t* out_i16, int mem);
+    // graph F's speaker conditioning: cond_ptrs = host vectors added per layer on the host (run_latent), or tab = the device table
+    // of layer bias + conditioning, row b for item b, tab_stride floats apart (run_latent_voices); both null: the layers' own biases
+    void body(const void* x0, int B, int F, const float* const* cond_ptrs, const float* tab, long tab_stride, float* out_f32,
+              int16_t* out_i16, int mem);
     // lengths of the current ragged call (null: uniform): d_frames = F_b per item; every launch of body() gets the table with
     // the (mul, add) of its resolution; conv_post writes item b from sample d_out_offs[b] of the output (total samples)
     const int* ln = nullptr; int ln_mul = 1;
     DevBuf d_frames, d_in_offs, d_out_offs;
+    DevBuf d_voice_of, d_conds, d_bias_tab;       // run_latent_voices: voice per item, the host caller's conditioning rows, the (B, total_cond) bias table
     const long* out_offs = nullptr; long out_total = 0;
-    std::vector<long> ragged_tables(int B, const int* frames, long extra_rows);   // checks + uploads; returns the output offsets
+    // uploads (voice_of, when given, goes up with them); returns the output offsets
+    std::vector<long> ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of = nullptr);
     long total_cond() const;
     DevBuf ln_w, ln_b, d_latent;
 };

@@ -252,7 +252,7 @@ void BigVGAN::run(const float* mel, int B, int F, float* out_f32, int16_t* out_i
     }
     // mel (B,100,F) -> channels-last padded (B,F,mel_pad)
     launch_ncl_to_nlc(dmel, bT1.p, B, cfg.num_mels, F, mel_pad, dtype, stream);
-    body(bT1.p, B, F, nullptr, out_f32, out_i16, mem);
+    body(bT1.p, B, F, nullptr, nullptr, 0, out_f32, out_i16, mem);
 }
 
 // IndexTTS graph F (IndexTTS/Export_IndexTTS.py:300-314): gpt.final_norm(latent[:-2]) -> conv_pre + cond_pre -> stages with
@@ -281,14 +281,14 @@ void BigVGAN::run_latent(const float* latent, int T_codes, const float* conds, l
         dl = d_latent.as<float>();
     }
     launch_rownorm(NORM_LN_AFFINE, dl, bT1.p, dtype, ln_w.as<float>(), ln_b.as<float>(), F, cfg.num_mels, 1e-5f, stream);
-    body(bT1.p, 1, F, ptrs.data(), out_f32, out_i16, mem);
+    body(bT1.p, 1, F, ptrs.data(), nullptr, 0, out_f32, out_i16, mem);
 }
 
 // Ragged batches: item b owns slab b of Fmax frames at every layer and every launch gets the frame table with the
 // (mul, add) of its resolution, so that each buffer a layer writes holds exact zeros in the rows past the item's live rows
 // (F_b * prod(rates[0..i]) inside stage i, F_b * hop + 30 after the post activation).  The next layer's zero padding then sees
 // what a solo run sees at the item's end, and stale workspace never reaches a live row.  Host decisions depend on (B, Fmax) only.
-std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_rows) {
+std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of) {
     std::vector<long> in_offs(B), out_offs(B + 1, 0);
     long acc = 0;
     for (int b = 0; b < B; ++b) {
@@ -300,6 +300,10 @@ std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_ro
     MI_HIP(hipMemcpyAsync(d_frames.p, frames, (size_t)B * 4, hipMemcpyHostToDevice, stream));
     MI_HIP(hipMemcpyAsync(d_in_offs.p, in_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
     MI_HIP(hipMemcpyAsync(d_out_offs.p, out_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
+    if (voice_of) {
+        d_voice_of.ensure((size_t)B * 4);
+        MI_HIP(hipMemcpyAsync(d_voice_of.p, voice_of, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+    }
     MI_HIP(hipStreamSynchronize(stream));                // the host tables are temporaries
     return out_offs;
 }
@@ -330,56 +334,96 @@ void BigVGAN::run_ragged(const float* mel, int B, const int* frames, float* out_
     launch_ncl_to_nlc_len(dmel, bT1.p, B, cfg.num_mels, Fmax, mel_pad, dtype, d_frames.as<int>(), d_in_offs.as<long>(), stream);
     ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total;
     try {
-        body(bT1.p, B, Fmax, nullptr, out_f32, out_i16, mem);
+        body(bT1.p, B, Fmax, nullptr, nullptr, 0, out_f32, out_i16, mem);
     } catch (...) { ln = nullptr; out_offs = nullptr; throw; }
     ln = nullptr; out_offs = nullptr;
     for (int b = 0; b < B; ++b) out_lens[b] = offs[b + 1] - offs[b];
 }
 
-void BigVGAN::run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
-                                int16_t* out_i16, long out_cap, int64_t* out_lens, int mem) {
-    MI_REQUIRE(cfg.pre_ln && cfg.cond, "bigvgan_forward_latent_ragged: handle was not created with the IndexTTS graph-F flags");
-    MI_REQUIRE(latent && T_codes && conds && out_lens && B > 0 && (out_f32 || out_i16), "bigvgan_forward_latent_ragged: bad arguments");
-    MI_REQUIRE(n_conds == total_cond(), "bigvgan_forward_latent_ragged: conditioning vector length");
-    MI_REQUIRE(mel_pad == cfg.num_mels, "bigvgan_forward_latent_ragged: the latent width must be a multiple of the 16-byte vector");
+// The speaker biases of a ragged graph-F forward as ONE device table: row b = the seven layers' biases + the conditioning row of
+// item b's voice, columns in the flat layout of `conds` ([cond_0 .. cond_{n_up-1}, cond_pre]).  The same fp32 add eff_bias() does
+// on the host (one add per value, no contraction), so the rows are bit-identical to the b_eff vectors of a one-item run.
+struct CondBiasLayers { const float* bias[9]; int end[9]; int n; };      // end[l]: first column past layer l (n_up <= 8, + conv_pre)
+__global__ __launch_bounds__(256) void cond_bias_table_kernel(CondBiasLayers L, const float* __restrict__ conds,
+                                                              const int* __restrict__ voice_of, float* __restrict__ tab, int total) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (j >= total) return;
+    int l = 0, lo = 0;
+    while (l < L.n - 1 && j >= L.end[l]) { lo = L.end[l]; ++l; }
+    tab[(long)b * total + j] = L.bias[l][j - lo] + conds[(long)voice_of[b] * total + j];
+}
+
+void BigVGAN::run_latent_voices(const float* latent, int B, const int* T_codes, int n_voices, const float* conds, long n_conds,
+                                const int* voice_of, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem) {
+    MI_REQUIRE(cfg.pre_ln && cfg.cond, "bigvgan_forward_latent_voices: handle was not created with the IndexTTS graph-F flags");
+    MI_REQUIRE(latent && T_codes && conds && voice_of && out_lens && B > 0 && (out_f32 || out_i16), "bigvgan_forward_latent_voices: bad arguments");
+    MI_REQUIRE(n_voices >= 1, "bigvgan_forward_latent_voices: at least one voice");
+    MI_REQUIRE(n_conds == total_cond(), "bigvgan_forward_latent_voices: conditioning vector length");
+    MI_REQUIRE(mel_pad == cfg.num_mels, "bigvgan_forward_latent_voices: the latent width must be a multiple of the 16-byte vector");
     std::vector<int> F(B);
     int Fmax = 0;
     long total = 0, rows = 0;
     for (int b = 0; b < B; ++b) {
-        MI_REQUIRE(T_codes[b] >= 3, "bigvgan_forward_latent_ragged: every item needs >= 3 latent rows");
+        MI_REQUIRE(T_codes[b] >= 3, "bigvgan_forward_latent_voices: every item needs >= 3 latent rows");
+        MI_REQUIRE(voice_of[b] >= 0 && voice_of[b] < n_voices, "bigvgan_forward_latent_voices: voice_of holds an index outside [0, n_voices)");
         F[b] = T_codes[b] - 2;                           // the reference drops the last two latent rows
         Fmax = std::max(Fmax, F[b]);
         rows += T_codes[b];
         total += (long)F[b] * cfg.hop + 30;
     }
-    MI_REQUIRE((long)Fmax * cfg.hop < (1L << 30), "bigvgan_forward_latent_ragged: too many frames");
-    MI_REQUIRE(total <= out_cap, "bigvgan_forward_latent_ragged: out_cap is smaller than the sum of the waveform lengths");
+    MI_REQUIRE((long)Fmax * cfg.hop < (1L << 30), "bigvgan_forward_latent_voices: too many frames");
+    MI_REQUIRE(total <= out_cap, "bigvgan_forward_latent_voices: out_cap is smaller than the sum of the waveform lengths");
     MI_HIP(hipSetDevice(device));
+    const int tc = (int)n_conds;
     ensure_workspace(B, Fmax);
-    std::vector<float> hc((size_t)n_conds);
-    if (mem == MI_HOST) std::memcpy(hc.data(), conds, (size_t)n_conds * 4);
-    else MI_HIP(hipMemcpy(hc.data(), conds, (size_t)n_conds * 4, hipMemcpyDeviceToHost));
-    std::vector<const float*> ptrs(cfg.n_up + 1);
-    long off = 0;
-    for (int i = 0; i < cfg.n_up; ++i) { ptrs[i] = hc.data() + off; off += cfg.c0 >> (i + 1); }
-    ptrs[cfg.n_up] = hc.data() + off;
-    const std::vector<long> offs = ragged_tables(B, F.data(), 2);      // latent rows of item b start at sum of T_codes before it
+    d_bias_tab.ensure((size_t)B * tc * 4);               // every buffer of the forward exists before its first launch
+    if (mem == MI_HOST) { d_conds.ensure((size_t)n_voices * tc * 4); d_latent.ensure((size_t)rows * cfg.num_mels * 4); }
+    const std::vector<long> offs = ragged_tables(B, F.data(), 2, voice_of);      // latent rows of item b start at sum of T_codes before it
+    const float* dc = conds;
     const float* dl = latent;
-    if (mem == MI_HOST) {
-        d_latent.ensure((size_t)rows * cfg.num_mels * 4);
+    if (mem == MI_HOST) {                                // the caller's arrays outlive the call: body() ends with a synchronisation
+        MI_HIP(hipMemcpyAsync(d_conds.p, conds, (size_t)n_voices * tc * 4, hipMemcpyHostToDevice, stream));
         MI_HIP(hipMemcpyAsync(d_latent.p, latent, (size_t)rows * cfg.num_mels * 4, hipMemcpyHostToDevice, stream));
+        dc = d_conds.as<float>();
         dl = d_latent.as<float>();
+    }
+    // the table, in stream order in front of the first GEMM: no host hop, no synchronisation
+    CondBiasLayers L;
+    int off = 0;
+    for (int i = 0; i < cfg.n_up; ++i) {
+        L.bias[i] = stages[i].up.b.as<float>();
+        off += cfg.c0 >> (i + 1);
+        L.end[i] = off;
+    }
+    L.bias[cfg.n_up] = pre.b.as<float>();                // cond_pre (c0 values) is last, like the graph's input order
+    L.end[cfg.n_up] = tc;
+    L.n = cfg.n_up + 1;
+    {
+        ProfScope ps(FAM_OTHER, stream, (double)B * tc * 8.0 + (double)tc * 4.0, (double)B * tc);
+        prof_set_kernel("cond_bias_table_kernel");
+        hipLaunchKernelGGL(cond_bias_table_kernel, dim3((tc + 255) / 256, B), dim3(256), 0, stream, L, dc, d_voice_of.as<int>(),
+                           d_bias_tab.as<float>(), tc);
+        MI_HIP(hipGetLastError());
     }
     launch_rownorm_len(NORM_LN_AFFINE, dl, bT1.p, dtype, ln_w.as<float>(), ln_b.as<float>(), B, Fmax, cfg.num_mels, 1e-5f,
                        d_frames.as<int>(), d_in_offs.as<long>(), stream);
     ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total;
     try {
-        body(bT1.p, B, Fmax, ptrs.data(), out_f32, out_i16, mem);
+        body(bT1.p, B, Fmax, nullptr, d_bias_tab.as<float>(), tc, out_f32, out_i16, mem);
     } catch (...) { ln = nullptr; out_offs = nullptr; throw; }
     ln = nullptr; out_offs = nullptr;
     for (int b = 0; b < B; ++b) out_lens[b] = offs[b + 1] - offs[b];
 }
 
+// one voice for all items: the same forward with a one-row conditioning table
+void BigVGAN::run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
+                                int16_t* out_i16, long out_cap, int64_t* out_lens, int mem) {
+    MI_REQUIRE(B > 0, "bigvgan_forward_latent_ragged: bad arguments");
+    const std::vector<int> voice_of((size_t)B, 0);
+    run_latent_voices(latent, B, T_codes, 1, conds, n_conds, voice_of.data(), out_f32, out_i16, out_cap, out_lens, mem);
+}
+
+// x0: channels-last (B, F, mel_pad) in the engine dtype, held in bT1
 static void eff_bias(ConvW& cw, const float* cond, hipStream_t s) {
     std::vector<float> e(cw.hb);
     for (size_t i = 0; i < e.size(); ++i) e[i] += cond[i];
@@ -388,8 +432,11 @@ static void eff_bias(ConvW& cw, const float* cond, hipStream_t s) {
     MI_HIP(hipStreamSynchronize(s));                    // `e` is a stack temporary
 }
 
-// x0: channels-last (B, F, mel_pad) in the engine dtype, held in bT1
-void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float* out_f32, int16_t* out_i16, int mem) {
+// The speaker conditioning of graph F reaches conv_pre and the upsamplers one of two ways: cond = host pointers [cond_0 ..
+// cond_{n_up-1}, cond_pre], added to each layer's bias on the host right before its launch (run_latent); or tab = the device
+// table of cond_bias_table_kernel, row b for item b, tab_stride floats apart (ragged calls only: the launches carry lengths)
+void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, const float* tab, long tab_stride, float* out_f32,
+                   int16_t* out_i16, int mem) {
     const long Tout = (long)F * cfg.hop + 30;
     ls = nullptr;
     const int* lens = ln;                 // ragged call: every launch below carries the frame table (ln_mul = its resolution)
@@ -401,12 +448,14 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
         if (cond) { eff_bias(pre, cond[cfg.n_up], stream); bias = pre.b_eff.as<float>(); }
         ConvGemm p;
         p.dtype = dtype; p.x = x0; p.w = pre.w.p; p.bias = bias; p.out = IN->p;
+        if (tab) { p.bias = tab + (total_cond() - cfg.c0); p.bias_bstride = tab_stride; }      // cond_pre's columns are the last c0
         p.B = B; p.T_in = F; p.M = F; p.N = cfg.c0; p.Cin = mel_pad; p.taps = 7; p.dil = 1; p.pad = 3;
         p.x_bstride = (long)F * mel_pad; p.x_rstride = mel_pad; p.out_bstride = (long)F * cfg.c0; p.out_rstride = cfg.c0;
         p.lens = lens;
         launch_conv_gemm(p, stream);
     }
     int T = F;
+    long tab_off = 0;                     // stage i's columns of the table: after those of stages 0 .. i - 1
     const float inv_nk = 1.0f / (float)cfg.n_kernels;
     for (int i = 0; i < cfg.n_up; ++i) {
         Stage& st = stages[i];
@@ -417,6 +466,8 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, float
             if (cond) { eff_bias(st.up, cond[i], stream); bias = st.up.b_eff.as<float>(); }
             ConvGemm p;
             p.dtype = dtype; p.x = IN->p; p.w = st.up.w.p; p.bias = bias; p.out = X->p;
+            if (tab) { p.bias = tab + tab_off; p.bias_bstride = tab_stride; }
+            tab_off += C;
             p.B = B; p.T_in = T; p.M = T + taps - 1; p.N = st.u * C; p.Cin = st.cin; p.taps = taps; p.dil = 1; p.pad = taps - 1;
             p.x_bstride = (long)T * st.cin; p.x_rstride = st.cin; p.out_bstride = (long)Tn * C; p.out_rstride = C;
             p.epi = EPI_CONVT; p.u = st.u; p.Cout = C; p.padT = (st.k - st.u) / 2; p.T_out = Tn;

@@ -203,6 +203,22 @@ int mi_bigvgan_forward_latent_ragged(mi_bigvgan* h, int B, const float* latent, 
     });
 }
 
+int mi_bigvgan_forward_latent_voices(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, int n_voices, const float* conds,
+                                     int64_t n_conds, const int32_t* voice_of, int16_t* out_i16, float* out_f32, int64_t out_cap,
+                                     int64_t* out_lens, int mem) {
+    return guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_bigvgan_forward_latent_voices: null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_bigvgan_forward_latent_voices: bad mem kind");
+        MI_REQUIRE(out_i16, "mi_bigvgan_forward_latent_voices: null out_i16");
+        MI_REQUIRE(voice_of, "mi_bigvgan_forward_latent_voices: null voice_of");
+        const std::vector<int> T = bigvgan_lengths(t_codes, B, 3, "mi_bigvgan_forward_latent_voices: B >= 1 items of >= 3 latent rows");
+        // voice indices and counts are checked by the engine before anything reaches the device (the handle stays usable)
+        h->impl->run_latent_voices(latent, B, T.data(), n_voices, conds, (long)n_conds, (const int*)voice_of, out_f32, out_i16,
+                                   (long)out_cap, out_lens, mem);
+    });
+}
+
 int mi_aa_activation1d(const float* x, int B, int C, int T, const float* alpha_log, const float* beta_log,
                        int logscale, int post, int dtype, float* y) {
     return guard([&] {

@@ -195,6 +195,9 @@ struct ConvGemm {
     // ragged batches (padded slabs, BigVGAN::run_ragged): output rows >= lens[b] * len_mul + len_add of item b are stored as
     // zeros and tiles wholly past them skip their main loop; lens is a device table of B ints (null: every row is live)
     const int* lens = nullptr; int len_mul = 1, len_add = 0;
+    // ... with a bias row per item: item b reads bias[b * bias_bstride + col] (floats; 0: one row for all items).  Launches with
+    // lengths only — their direct epilogue is the one that indexes the bias by item; anything else refuses a non-zero stride
+    long bias_bstride = 0;
 };
 constexpr int LN_BLK = 32;        // columns per partial-statistics block of the AdaLN fold
 void launch_conv_gemm(const ConvGemm& p, hipStream_t s);

@@ -555,12 +555,12 @@ static bool buf_ok(const ConvGemmDev& d, int esz = 2) {
 }
 
 // a launch of dispatch_tiles: K is the uniform instantiation, KL the same tile with the lengths switch (LENS), which the
-// profiler files under K's name + " + lengths"
+// profiler files under K's name + " + lengths" (+ " + item bias" when the launch reads its bias by item, ConvGemm::bias_bstride)
 #define MI_LAUNCH_LN(K, KL, T_, TO_, grid, blk, lds, s, ...)                                            \
     do {                                                                                               \
         if constexpr (LENS) {                                                                          \
             mi::prof_set_kernel(#K, mi::type_label<T_>(), mi::type_label<TO_>());                      \
-            mi::prof_kernel_suffix(" + lengths");                                                      \
+            mi::prof_kernel_suffix(d.bias_bstride ? " + lengths + item bias" : " + lengths");          \
             hipLaunchKernelGGL(KL, grid, blk, lds, s, __VA_ARGS__);                                    \
         } else {                                                                                       \
             MI_LAUNCH(K, T_, TO_, grid, blk, lds, s, __VA_ARGS__);                                     \
@@ -914,6 +914,14 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
         MI_REQUIRE((p.epi == EPI_PLAIN || p.epi == EPI_CONVT) && !p.ln_stats_in && !p.ln_stats_out && !p.out_planes && !p.xp && !p.w3 &&
                        !p.gcp_w && p.G == 1 && !p.gate,
                    "conv_gemm: a launch with lengths is a plain or ConvTranspose1d convolution over padded slabs");
+    // per-item bias rows: read by the direct epilogue of the LENS instantiations only.  Every other way out of this function (LDS-staged
+    // epilogues, x3 / x3p / ph8 / stream-K, the grouped-convolution kernels, EPI_QKV_ROPE) is closed to a launch with lengths above
+    // and below, so a stride without lengths is the one case that would be ignored: refuse it
+    d.bias_bstride = p.bias_bstride;
+    if (p.bias_bstride != 0)
+        MI_REQUIRE(p.lens && p.bias && p.bias_bstride > 0 && (p.epi == EPI_PLAIN || p.epi == EPI_CONVT) && !p.xp && !p.w3 && !p.w3p &&
+                       !p.gcp_w && !p.out_planes,
+                   "conv_gemm: per-item bias rows (bias_bstride) need a launch with lengths: the direct epilogue of the length-aware kernels");
     if (p.ln_stats_in || p.ln_stats_out) {
         MI_REQUIRE(!(p.ln_stats_in && p.ln_stats_out), "conv_gemm: a launch is the producer OR the consumer of the AdaLN fold");
         MI_REQUIRE(p.B == 1 && p.G == 1 && p.taps == 1 && p.alpha == 1.f && !p.accumulate && p.gate_bstride == 0 && p.N % 64 == 0,
@@ -972,6 +980,7 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     if (!p.lens && p.dtype != MI_F32 && p.gcp_w && opt(OPT_GEMM_USE_DMA) && launch_gconv16(p, s)) return;
     if (p.lens) {
         MI_REQUIRE(odt == p.dtype, "conv_gemm: a launch with lengths writes the engine dtype");
+        MI_REQUIRE(!d.lds_epi, "conv_gemm: a launch with lengths leaves through the direct epilogue");
         if (p.dtype == MI_F32) dispatch_tiles<float, float, true>(d, p.B, s);
         else if (p.dtype == MI_F16) dispatch_tiles<f16, f16, true>(d, p.B, s);
         else dispatch_tiles<bf16, bf16, true>(d, p.B, s);

@@ -265,16 +265,16 @@ template <typename T, typename TO>
 void launch_conv_gemm_dma3(const ConvGemmDev& e, int bn, hipStream_t s) {
     const dim3 grid(e.RC == 2 ? 8 * ((e.RT * e.Tn + 7) / 8) : e.RT * e.Tn, e.G);
     if constexpr (std::is_same<T, TO>::value) if (e.lens) {
-        // ragged batches: the same tiles with the lengths switch, named as the uniform ones + " + lengths"
+        // ragged batches: the same tiles with the lengths switch, named as the uniform ones + " + lengths" (+ " + item bias": per-item bias rows)
         if (bn == 192) {
             prof_set_kernel("conv_gemm_dma3_kernel<T, TO, 256, 192, 64, 96, 2, true>", type_label<T>(), type_label<TO>());
-            prof_kernel_suffix(" + lengths");
+            prof_kernel_suffix(e.bias_bstride ? " + lengths + item bias" : " + lengths");
             hipLaunchKernelGGL((conv_gemm_dma3_kernel<T, TO, 256, 192, 64, 96, 2, true, true>), grid, dim3(512), 0, s, e);
         } else {
             // no 256x256 tile with lengths: dispatch_tiles sends those launches to 256x192 / 256x128
             MI_REQUIRE(bn == 128, "conv_gemm_dma3: no 256x256 tile with lengths");
             prof_set_kernel("conv_gemm_dma3_kernel<T, TO, 256, 128, 64, 64, 3>", type_label<T>(), type_label<TO>());
-            prof_kernel_suffix(" + lengths");
+            prof_kernel_suffix(e.bias_bstride ? " + lengths + item bias" : " + lengths");
             hipLaunchKernelGGL((conv_gemm_dma3_kernel<T, TO, 256, 128, 64, 64, 3, false, true>), grid, dim3(512), 0, s, e);
         }
         return;

@@ -55,6 +55,7 @@ struct ConvGemmDev {
     int ln_final = 0;                            // ln_stats_in = finished (rstd, mean * rstd) per row instead of partial sums
     int* sat = nullptr;                          // fp16-pair producers raise bit 0 when an operand met the fp16 range limit
     const int* lens = nullptr; int len_mul = 1, len_add = 0;   // ragged batches (ConvGemm::lens): the LENS instantiations only
+    long bias_bstride = 0;                       // ... and their per-item bias rows (ConvGemm::bias_bstride), floats; 0: one row for all items
 };
 
 // Shared epilogue: 32x32 accumulator tiles -> bias / activation / gate / residual / alpha / accumulate -> HBM,
@@ -90,7 +91,9 @@ __device__ __forceinline__ void act16(float (&v)[16]) {
 }
 
 // LENS (ragged batches, ConvGemmDev::lens): output rows >= vb (item b's live rows) are stored as zeros and read no residual /
-// accumulate operand; vb is wave-uniform.  EPI_PLAIN / EPI_CONVT only.
+// accumulate operand; vb is wave-uniform.  EPI_PLAIN / EPI_CONVT only.  They alone read the bias as a per-item table: row b (wave-
+// uniform, so the row offset is scalar arithmetic) starts bias_bstride floats after row b - 1; the uniform instantiations compile
+// the address they always had (launch_conv_gemm refuses a stride without lengths).
 template <typename TO, int TM, int TN, int WM, int WN, bool LENS = false>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int m0, int n0, int b, int g,
                                               int wm, int wn, int lr, int lk, int vb = 0) {
@@ -142,6 +145,8 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvG
     }
     TO* outp = (TO*)p.out + (long)b * p.out_bstride;
     const TO* resp = p.res ? (const TO*)p.res + (long)b * p.out_bstride : nullptr;
+    const float* biasp = p.bias;
+    if constexpr (LENS) biasp = p.bias ? p.bias + (long)b * p.bias_bstride : nullptr;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = n0 + wn * WN + j * 32 + lr;
@@ -150,7 +155,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], const ConvG
         int col, ph = 0;
         if (p.epi == EPI_CONVT) { ph = nc / p.Cout; col = nc - ph * p.Cout; }
         else col = g * p.N + nc;
-        const float bv = p.bias ? p.bias[col] : 0.f;
+        const float bv = biasp ? biasp[col] : 0.f;
         const float gv = p.gate ? p.gate[(long)b * p.gate_bstride + col] : 1.f;
         // LENS: M rows m < mlim of this column are live (output row m, or m * u + ph - padT for the ConvTranspose1d map, < vb)
         int mlim = 0;

@@ -115,6 +115,9 @@ def load() -> C.CDLL:
     L.mi_bigvgan_forward_ragged.restype = C.c_int
     L.mi_bigvgan_forward_latent_ragged.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int]
     L.mi_bigvgan_forward_latent_ragged.restype = C.c_int
+    if hasattr(L, "mi_bigvgan_forward_latent_voices"):       # absent from an older build loaded through MI355TTS_LIB (A/B runs)
+        L.mi_bigvgan_forward_latent_voices.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int]
+        L.mi_bigvgan_forward_latent_voices.restype = C.c_int
     L.mi_indextts_cond_param_count.argtypes = [C.POINTER(C.c_int32), C.c_int]; L.mi_indextts_cond_param_count.restype = C.c_int64
     L.mi_indextts_cond_create.argtypes = [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int]
     L.mi_indextts_cond_create.restype = vp

@@ -7,6 +7,7 @@ through the C-ABI.  B > 1 is this engine's extension (the reference graph is bat
 """
 from __future__ import annotations
 
+import operator
 from typing import Optional
 
 import numpy as np
@@ -37,6 +38,53 @@ def ragged_layout(cfg: BigVGANConfig, frames, latent: bool = False):
     out_lens = [f * cfg.hop + 30 for f in F]
     out_offs = [int(v) for v in np.concatenate([[0], np.cumsum(out_lens)[:-1]])]
     return F, in_offs, out_lens, out_offs, Fmax
+
+
+def flat_conds(cfg: BigVGANConfig, conds) -> np.ndarray:
+    """One voice's conditioning vectors [cond_0 .. cond_{n-1}, cond_pre] (each (1, C, 1) / (C,)) as the flat float32 row the
+    C-ABI takes (mi_bigvgan_forward_latent).  ValueError for a wrong count or size."""
+    want = [cfg.stage_channels(i) for i in range(cfg.num_upsamples)] + [cfg.upsample_initial_channel]
+    conds = list(conds)
+    if len(conds) != len(want):
+        raise ValueError(f"expected {len(want)} conditioning vectors")
+    flat = []
+    for c, n in zip(conds, want):
+        c = np.asarray(c, dtype=np.float32).reshape(-1)
+        if c.size != n:
+            raise ValueError(f"conditioning vector has {c.size} values, expected {n}")
+        flat.append(c)
+    return np.ascontiguousarray(np.concatenate(flat))
+
+
+def voices_table(cfg: BigVGANConfig, voices, voice_of, n_items: int):
+    """Host-side arguments of a several-voice graph-F forward (BigVGANVocoder.run_latent_voices, mi_bigvgan_forward_latent_voices):
+    voices = V >= 1 conditioning lists as ``run_latent`` takes them, voice_of = the voice index of each of the n_items items.
+    Returns (table, index): float32 (V, total_cond), row v = voice v flattened like ``flat_conds``, and int32 (n_items,).
+    Raises ValueError for what the engine would refuse (no voice, no item, a count or size that does not fit the config, an
+    index outside [0, V)), before the GPU is touched."""
+    if not (cfg.pre_layernorm and cfg.speaker_cond):
+        raise ValueError("this config is not an IndexTTS graph-F vocoder (no speaker conditioning)")
+    voices = list(voices)
+    if not voices:
+        raise ValueError("voices: at least one voice")
+    rows = []
+    for v, conds in enumerate(voices):
+        try:
+            rows.append(flat_conds(cfg, conds))
+        except ValueError as e:
+            raise ValueError(f"voice {v}: {e}") from None
+    if int(n_items) < 1:
+        raise ValueError("ragged batch: at least one item")
+    try:
+        index = [operator.index(x) for x in voice_of]
+    except TypeError:
+        raise ValueError("voice_of must hold integers") from None
+    if len(index) != int(n_items):
+        raise ValueError(f"voice_of has {len(index)} entries for {int(n_items)} items")
+    for b, x in enumerate(index):
+        if not 0 <= x < len(rows):
+            raise ValueError(f"item {b}: voice {x} is outside [0, {len(rows)})")
+    return np.ascontiguousarray(np.stack(rows), dtype=np.float32), np.asarray(index, dtype=np.int32)
 
 
 class BigVGANVocoder:
@@ -169,7 +217,8 @@ class BigVGANVocoder:
 
     def run_latent_ragged(self, latents, conds, return_float: bool = False):
         """IndexTTS graph F for B sentences of one speaker: latents = list of (T_b >= 3, gpt_dim) arrays, conds as in
-        ``run_latent`` (shared by all items) -> list of int16 (1, 1, (T_b - 2) * hop + 30)."""
+        ``run_latent`` (shared by all items) -> list of int16 (1, 1, (T_b - 2) * hop + 30).  The one-voice form of
+        ``run_latent_voices``."""
         cfg = self.cfg
         if not (cfg.pre_layernorm and cfg.speaker_cond):
             raise ValueError("this vocoder was not created from an IndexTTS graph-F config")
@@ -194,18 +243,77 @@ class BigVGANVocoder:
             return wav, [outf[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
         return wav
 
-    def _flat_conds(self, conds):
+    def run_latent_voices(self, latents, voices, voice_of, return_float: bool = False):
+        """IndexTTS graph F for B sentences of several speakers in one forward: latents as in ``run_latent_ragged``, voices = list
+        of V conditioning lists as ``run_latent`` takes them, voice_of[b] = the voice of sentence b.  Returns what
+        ``run_latent_ragged`` returns; item b is the waveform ``run_latent(latents[b], voices[voice_of[b]])`` gives."""
         cfg = self.cfg
-        want = [cfg.stage_channels(i) for i in range(cfg.num_upsamples)] + [cfg.upsample_initial_channel]
-        if len(conds) != len(want):
-            raise ValueError(f"expected {len(want)} conditioning vectors")
-        flat = []
-        for c, n in zip(conds, want):
-            c = np.asarray(c, dtype=np.float32).reshape(-1)
-            if c.size != n:
-                raise ValueError(f"conditioning vector has {c.size} values, expected {n}")
-            flat.append(c)
-        return np.ascontiguousarray(np.concatenate(flat))
+        if not (cfg.pre_layernorm and cfg.speaker_cond):
+            raise ValueError("this vocoder was not created from an IndexTTS graph-F config")
+        latents = [np.asarray(x) for x in latents]
+        for b, x in enumerate(latents):
+            if x.ndim != 2 or x.shape[1] != cfg.num_mels:
+                raise ValueError(f"item {b}: latent must be (T_codes, {cfg.num_mels}), got {x.shape}")
+        _, _, out_lens, out_offs, _ = ragged_layout(cfg, [x.shape[0] for x in latents], latent=True)
+        table, index = voices_table(cfg, voices, voice_of, len(latents))
+        x = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(v, np.float32) for v in latents]))
+        tc = np.asarray([v.shape[0] for v in latents], np.int64)
+        n = sum(out_lens)
+        out = np.empty(n, np.int16)
+        outf = np.empty(n, np.float32) if return_float else None
+        lens = np.zeros(len(latents), np.int64)
+        _lib.check(_lib.load().mi_bigvgan_forward_latent_voices(self._h, len(latents), x.ctypes.data, tc.ctypes.data, table.shape[0],
+                                                                table.ctypes.data, table.shape[1], index.ctypes.data, out.ctypes.data,
+                                                                None if outf is None else outf.ctypes.data, n, lens.ctypes.data,
+                                                                _lib.MI_HOST), "mi_bigvgan_forward_latent_voices")
+        assert list(lens) == out_lens, (list(lens), out_lens)
+        wav = [out[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        if return_float:
+            return wav, [outf[o:o + l].reshape(1, 1, l).copy() for o, l in zip(out_offs, out_lens)]
+        return wav
+
+    def run_latent_voices_torch(self, latent_cat, t_codes, conds_table, voice_of, out=None):
+        """Device-resident run_latent_voices: latent_cat = the items' (T_b, gpt_dim) latents concatenated (float32 CUDA tensor, e.g.
+        the hidden states a GPT queue left on the device), t_codes = the host list T_b, conds_table = (V, total_cond) float32 CUDA
+        tensor (rows as ``flat_conds``), voice_of = the host list of voice indices.  The conditioning is read where it lies.
+        Returns (wav_cat, out_lens): the int16 waveforms concatenated in one CUDA tensor and their lengths."""
+        import torch
+        cfg = self.cfg
+        if not (cfg.pre_layernorm and cfg.speaker_cond):
+            raise ValueError("this vocoder was not created from an IndexTTS graph-F config")
+        _, _, out_lens, _, _ = ragged_layout(cfg, t_codes, latent=True)
+        tc = np.asarray([int(t) for t in t_codes], np.int64)
+        if not (latent_cat.is_cuda and latent_cat.dtype == torch.float32 and latent_cat.is_contiguous()):
+            raise ValueError("latent_cat must be a contiguous float32 tensor on the GPU")
+        if latent_cat.numel() < int(tc.sum()) * cfg.num_mels:
+            raise ValueError("latent_cat holds fewer than sum(t_codes) * gpt_dim values")
+        if not (conds_table.is_cuda and conds_table.dtype == torch.float32 and conds_table.is_contiguous() and conds_table.dim() == 2):
+            raise ValueError("conds_table must be a contiguous float32 (V, total_cond) tensor on the GPU")
+        want = sum(cfg.stage_channels(i) for i in range(cfg.num_upsamples)) + cfg.upsample_initial_channel
+        V = int(conds_table.shape[0])
+        if V < 1 or int(conds_table.shape[1]) != want:
+            raise ValueError(f"conds_table must be (V >= 1, {want}), got {tuple(conds_table.shape)}")
+        try:
+            index = [operator.index(x) for x in voice_of]
+        except TypeError:
+            raise ValueError("voice_of must hold integers") from None
+        if len(index) != len(tc) or any(not 0 <= x < V for x in index):
+            raise ValueError(f"voice_of must hold {len(tc)} indices in [0, {V})")
+        index = np.asarray(index, np.int32)
+        n = sum(out_lens)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int16, device=latent_cat.device)
+        assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous()
+        lens = np.zeros(len(tc), np.int64)
+        torch.cuda.current_stream(latent_cat.device).synchronize()
+        _lib.check(_lib.load().mi_bigvgan_forward_latent_voices(self._h, len(tc), latent_cat.data_ptr(), tc.ctypes.data, V,
+                                                                conds_table.data_ptr(), want, index.ctypes.data, out.data_ptr(), None,
+                                                                out.numel(), lens.ctypes.data, _lib.MI_DEVICE),
+                   "mi_bigvgan_forward_latent_voices")
+        return out, [int(v) for v in lens]
+
+    def _flat_conds(self, conds):
+        return flat_conds(self.cfg, conds)
 
     # ---- IndexTTS graph F: latent + speaker conditioning in, waveform out ------------------------------------
     def run_latent(self, latent: np.ndarray, conds, return_float: bool = False):

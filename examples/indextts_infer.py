@@ -31,6 +31,11 @@ With `--queue`, `--prompt a.wav,b.wav,...` is a dialogue: graph A runs once per 
 `--voice-of 0,1,1,0,...`, one index per sentence), every sentence's prompt carries its own voice's conditioning rows, and ONE
 `run_latent_voices` call vocodes all of them in order, whatever the mix of voices.  One prompt file is the one-voice case of the
 same calls: the same output file as before.
+`--queue --stream` returns audio while the queue is still decoding: `stream_synthesize` drives the queue as a session and, after
+every round of decode steps, vocodes `--chunk` frames (default 32) of every sentence that has them ready, with `--halo` frames of
+context at each cut (default: the vocoder's receptive field, `BigVGANConfig.halo_frames()`, with which the samples are those of the
+whole sentence's forward; fewer trade accuracy for work), in ONE `run_latent_windows_torch` call for all sentences and voices.  The
+chunks are assembled here and the file has the layout of `--queue`; the wall time to the first chunk and to the last is printed.
 """
 import argparse
 import dataclasses
@@ -46,7 +51,7 @@ sys.path.insert(0, os.path.join(ROOT, "text-to-speech-tts-onnx_amd"))
 from mi355tts import audio_io, weights                                       # noqa: E402
 from mi355tts.bigvgan import BigVGANVocoder                                   # noqa: E402
 from mi355tts.config import BigVGANConfig, IndexCondConfig, IndexGPTConfig    # noqa: E402
-from mi355tts.indextts import IndexCond, IndexGPT, Sampling                   # noqa: E402
+from mi355tts.indextts import IndexCond, IndexGPT, Sampling, stream_synthesize    # noqa: E402
 from mi355tts.indextts_text import TextNormalizer, TextTokenizer              # noqa: E402
 
 
@@ -113,7 +118,14 @@ def parse_args(argv=None):
     ap.add_argument("--queue", action="store_true", help="decode all sentences through the batch slots (refilled as sentences end); "
                     "every sentence starts from a fresh penalty vector")
     ap.add_argument("--slots", type=int, default=8, help=f"batch slots of --queue (1..{MAX_SLOTS})")
+    ap.add_argument("--stream", action="store_true", help="with --queue: vocode windows of every sentence while the queue decodes (time to first audio)")
+    ap.add_argument("--chunk", type=int, default=32, help="frames per streamed window")
+    ap.add_argument("--halo", type=int, default=None, help="context frames at each cut of a streamed window (default: the vocoder's receptive field)")
     args = ap.parse_args(argv)
+    if args.stream and not args.queue:
+        ap.error("--stream needs --queue (it streams the sentence queue)")
+    if args.chunk < 1 or (args.halo is not None and args.halo < 0):
+        ap.error("--chunk must be >= 1 and --halo >= 0")
     args.prompts = args.prompt.split(",") if args.prompt else [None]
     if (len(args.prompts) > 1 or args.voice_of is not None) and not args.queue:
         ap.error("several --prompt files / --voice-of need --queue (one run_latent_voices call vocodes the whole dialogue)")
@@ -186,10 +198,27 @@ def main():
             budgets.append(max(gcfg.max_generate_length - int(prompt_len[0]), 0))
         t_dec = time.time()
         q_sampling = [dataclasses.replace(take_sampling[0], seed=take_sampling[0].seed + i) for i in range(len(prompts))] if sampled else None
-        results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, return_stats=True)
-        n_codes = sum(h.shape[0] for _, h in results)
-        print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "
-              f"{gcfg.max_batch} slots: {q_stats['steps']} decode steps, {q_stats['passes']} prompt passes)")
+        if args.stream:
+            chunks, t_first = {}, None
+            for i, first_sample, chunk, last in stream_synthesize(gpt, voc, prompts, budgets, [c for c, _ in speakers], voice_of,
+                                                                  chunk=args.chunk, halo=args.halo, stop_tokens=stops, sampling=q_sampling):
+                if t_first is None:
+                    t_first = time.time() - t_dec
+                assert first_sample == sum(c.size for c in chunks.get(i, []))
+                chunks.setdefault(i, []).append(chunk)
+            t_last = time.time() - t_dec
+            n_codes = sum((sum(c.size for c in chunks[i]) - 30) // vcfg.hop + 2 for i in chunks)
+            n_chunks = sum(len(c) for c in chunks.values())
+            print(f"Streamed {n_chunks} chunks of {len(chunks)} sentence(s) in {gcfg.max_batch} slots (chunk {args.chunk}, halo "
+                  f"{vcfg.halo_frames() if args.halo is None else args.halo}): first chunk after {1e3 * (t_first or 0.0):.1f} ms, last after {1e3 * t_last:.1f} ms")
+            for i in sorted(chunks):
+                pieces.append(np.concatenate([np.concatenate(chunks[i]).reshape(1, 1, -1), gap], axis=-1))
+            results = []
+        else:
+            results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, return_stats=True)
+            n_codes = sum(h.shape[0] for _, h in results)
+            print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "
+                  f"{gcfg.max_batch} slots: {q_stats['steps']} decode steps, {q_stats['passes']} prompt passes)")
         keep = [i for i, (_, h) in enumerate(results) if h.shape[0] >= 3]         # the vocoder needs three codes
         if keep:                                                     # one forward for every voice in flight
             for wav in voc.run_latent_voices([results[i][1] for i in keep], [c for c, _ in speakers], [voice_of[i] for i in keep]):

@@ -103,6 +103,25 @@ int         mi_bigvgan_forward_latent_ragged(mi_bigvgan* h, int B, const float* 
 int         mi_bigvgan_forward_latent_voices(mi_bigvgan* h, int B, const float* latent, const int64_t* t_codes, int n_voices,
                                              const float* conds, int64_t n_conds, const int32_t* voice_of, int16_t* out_i16,
                                              float* out_f32, int64_t out_cap, int64_t* out_lens, int mem);
+/* ... and for WINDOWS of latent rows, so that audio can leave before a sentence has all its rows.  latent = any (latent_rows,
+ * gpt_dim) fp32 array (follows `mem`; it may be the `hidden` output of a GPT call where it lies in HBM); item b is frames
+ * [row0[b], row0[b] + rows[b]) of it (host int64).  Items may overlap and share rows, and NO rows are dropped here: the caller
+ * leaves a sentence's last two rows out of its windows.  head[b] / tail[b] (host int32, >= 0, head + tail < rows) count the halo
+ * frames at the window's two ends: their samples are computed and discarded.  Run alone, frames [lo, hi) of a sentence give
+ * (hi - lo) * hop + 30 samples, and sample j of them stands for sample lo * hop + j of the sentence's waveform.  The samples kept
+ * are [head ? head * hop + 15 : 0, tail ? (rows - tail) * hop + 15 : rows * hop + 30), written concatenated; out_lens[b] is
+ * their count, and nothing is written outside the sum of them.  A sample is the sentence's own, to the last bit of the arithmetic,
+ * when the halo covers the generator's receptive field (BigVGANConfig.halo_frames(): 34 frames for the IndexTTS-1.5 vocoder); a
+ * shorter halo is the caller's trade of accuracy for work.  The forward is that of mi_bigvgan_forward_latent_voices (same slabs,
+ * same length-aware launches, same bias table), with row0 as the row-offset table and a windowed conv_post; with head = tail = 0
+ * and windows naming whole sentences minus their last two rows it gives that entry's waveforms bit for bit.  n_voices, conds,
+ * n_conds, voice_of: as there.  MI_EINVAL, with the handle still usable, for B < 1, rows < 1, head or tail < 0, head + tail >=
+ * rows, a window outside [0, latent_rows), a window past the ragged path's frame limit, out_cap below the sum of out_lens, a
+ * handle that is not graph F, and everything mi_bigvgan_forward_latent_voices rejects.                                      */
+int         mi_bigvgan_forward_latent_windows(mi_bigvgan* h, int B, const float* latent, int64_t latent_rows, const int64_t* row0,
+                                              const int64_t* rows, const int32_t* head, const int32_t* tail, int n_voices,
+                                              const float* conds, int64_t n_conds, const int32_t* voice_of, int16_t* out_i16,
+                                              float* out_f32, int64_t out_cap, int64_t* out_lens, int mem);
 /* unit-level entry (tests): one anti-aliased SnakeBeta Activation1d on x (B,C,T) fp32
  * channels-first host memory; post!=0 selects the pad-15 variant (out T+30).                   */
 int         mi_aa_activation1d(const float* x, int B, int C, int T, const float* alpha_log,
@@ -404,6 +423,41 @@ int         mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const 
                                   int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
                                   const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
                                   int32_t* stats /* host, 2 ints or NULL: {decode steps launched, prompt passes} */);
+
+/* ---- the sentence queue as a session: the same loop, handed back after every run of decode steps, so that rows can be used
+ * (mi_bigvgan_forward_latent_windows) while the queue is still decoding.  mi_gpt_generate_queue IS begin + advance until nothing
+ * is left + end over this loop, except for its copy policy (one copy per sentence at retirement, none per round).
+ *
+ * mi_gpt_queue_begin: arguments and validation of mi_gpt_generate_queue (all of it before anything is launched; MI_EINVAL leaves
+ * the handle usable and no session open).  The small host arrays (prompt_rows, max_new, stop ids, sampling parameters) are
+ * copied; prompts, tokens (n, cap) and hidden (n, cap, hidden) stay the caller's, follow `mem`, and must live until
+ * mi_gpt_queue_end.  Nothing is decoded yet.
+ *
+ * mi_gpt_queue_advance: ONE round of the policy above: steps 1 and 2 repeated until nothing more can be admitted, then one run
+ * of c <= 16 decode steps (step 3) and a look at the states.  Then the caller's arrays are brought up to date: for every live or
+ * just-finished sentence i its new tokens and rows [what it had, count[i]) go to tokens[i] and hidden[i].  With mem = MI_DEVICE
+ * that is one kernel launch per round over a table of at most 64 (slot, first, count, sentence) entries; with MI_HOST the same
+ * kernel packs the rows into a staging buffer and each array leaves in one device-to-host copy.  (A sentence that is retired
+ * inside the round before a decode step has run for it, e.g. one whose limit is 1, leaves in a launch of its own ahead of the
+ * pass that refills its slot.)  On return the stream is synchronised; count[i] (host, n) tokens and rows of sentence i are valid
+ * and FINAL: a row never changes afterwards; done[i] (host, n) is 1 when count[i] is the sentence's n_out (a sentence with
+ * max_new == 0 is done with count 0 from the start); *finished is 1 when no sentence is live or waiting.  stats (host, 2 ints,
+ * or NULL): as mi_gpt_generate_queue, so far.  A call after *finished does nothing and reports the same.
+ *
+ * mi_gpt_queue_end: closes the session; it may come before *finished (the rest is abandoned) and the handle is usable
+ * afterwards.  mi_gpt_destroy with an open session is fine.
+ *
+ * While a session is open every other entry on the handle that would touch the slots returns MI_ESTATE: mi_gpt_step,
+ * mi_gpt_generate*, mi_gpt_kv_write, mi_gpt_reset, mi_gpt_bench_pick and a second mi_gpt_queue_begin; advance / end without a
+ * session return MI_ESTATE too.  Beam search does not go through a session: hypothesis 0's rows are gathered along its ancestors
+ * at the end, so no row of it is final before that.                                                                          */
+int         mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                               const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
+                               float* hidden, int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p,
+                               const uint64_t* seeds);
+int         mi_gpt_queue_advance(mi_gpt* h, int32_t* count /* host, n */, int32_t* done /* host, n */, int32_t* finished /* host, 1 */,
+                                 int32_t* stats /* host, 2 ints, or NULL */);
+int         mi_gpt_queue_end(mi_gpt* h);
 
 /* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
  * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these

@@ -60,7 +60,16 @@ struct BigVGAN {
     // become one device table of B rows (cond_bias_table_kernel) that conv_pre and the upsamplers index by item.
     void run_latent_voices(const float* latent, int B, const int* T_codes, int n_voices, const float* conds, long n_conds,
                            const int* voice_of, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
-    // ... the one-voice form of it: n_voices = 1, voice_of = 0 ... 0
+    // ... windows of one (latent_rows, num_mels) array instead of whole sentences: item b = rows [row0[b], row0[b] + rows[b]), no
+    // rows dropped, head[b] / tail[b] halo frames whose samples are computed and not written (conv_post's windowed instantiation)
+    void run_latent_windows(const float* latent, long latent_rows, int B, const int64_t* row0, const int64_t* rows, const int32_t* head,
+                            const int32_t* tail, int n_voices, const float* conds, long n_conds, const int* voice_of, float* out_f32,
+                            int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
+    // what the two share once their arguments are checked (row0 / win null: sentences one after another, untrimmed tail)
+    void latent_items(const float* latent, long rows, int B, const int* F, int Fmax, const long* row0, const long* win, long total,
+                      int n_voices, const float* conds, long n_conds, const int* voice_of, float* out_f32, int16_t* out_i16,
+                      int64_t* out_lens, int mem);
+    // ... the one-voice form of run_latent_voices: n_voices = 1, voice_of = 0 ... 0
     void run_latent_ragged(const float* latent, int B, const int* T_codes, const float* conds, long n_conds, float* out_f32,
                            int16_t* out_i16, long out_cap, int64_t* out_lens, int mem);
     // IndexTTS graph F: latent (T_codes, num_mels) channels-last fp32, conds = [cond_0 .. cond_{n_up-1}, cond_pre] concatenated
@@ -75,8 +84,11 @@ struct BigVGAN {
     DevBuf d_frames, d_in_offs, d_out_offs;
     DevBuf d_voice_of, d_conds, d_bias_tab;       // run_latent_voices: voice per item, the host caller's conditioning rows, the (B, total_cond) bias table
     const long* out_offs = nullptr; long out_total = 0;
-    // uploads (voice_of, when given, goes up with them); returns the output offsets
-    std::vector<long> ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of = nullptr);
+    bool out_win = false;                         // d_out_offs holds conv_post's window table (3 values per item)
+    // uploads (voice_of, when given, goes up with them); returns the output offsets.  row0: the items' first input rows instead of
+    // running sums; win: the (first kept sample, kept count, output offset) table of a windowed call instead of the output offsets
+    std::vector<long> ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of = nullptr, const long* row0 = nullptr,
+                                    const long* win = nullptr);
     long total_cond() const;
     DevBuf ln_w, ln_b, d_latent;
 };

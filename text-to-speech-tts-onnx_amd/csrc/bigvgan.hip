@@ -288,18 +288,20 @@ void BigVGAN::run_latent(const float* latent, int T_codes, const float* conds, l
 // (mul, add) of its resolution, so that each buffer a layer writes holds exact zeros in the rows past the item's live rows
 // (F_b * prod(rates[0..i]) inside stage i, F_b * hop + 30 after the post activation).  The next layer's zero padding then sees
 // what a solo run sees at the item's end, and stale workspace never reaches a live row.  Host decisions depend on (B, Fmax) only.
-std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of) {
+std::vector<long> BigVGAN::ragged_tables(int B, const int* frames, long extra_rows, const int* voice_of, const long* row0,
+                                         const long* win) {
     std::vector<long> in_offs(B), out_offs(B + 1, 0);
     long acc = 0;
     for (int b = 0; b < B; ++b) {
-        in_offs[b] = acc;
+        in_offs[b] = row0 ? row0[b] : acc;               // windows name their first row; sentences follow each other
         acc += frames[b] + extra_rows;
-        out_offs[b + 1] = out_offs[b] + (long)frames[b] * cfg.hop + 30;
+        out_offs[b + 1] = out_offs[b] + (win ? win[3 * b + 1] : (long)frames[b] * cfg.hop + 30);
     }
-    d_frames.ensure((size_t)B * 4); d_in_offs.ensure((size_t)B * 8); d_out_offs.ensure((size_t)B * 8);
+    const size_t out_n = win ? (size_t)3 * B : (size_t)B;    // windows: (first kept sample, kept count, output offset) per item
+    d_frames.ensure((size_t)B * 4); d_in_offs.ensure((size_t)B * 8); d_out_offs.ensure(out_n * 8);
     MI_HIP(hipMemcpyAsync(d_frames.p, frames, (size_t)B * 4, hipMemcpyHostToDevice, stream));
     MI_HIP(hipMemcpyAsync(d_in_offs.p, in_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
-    MI_HIP(hipMemcpyAsync(d_out_offs.p, out_offs.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(d_out_offs.p, win ? win : out_offs.data(), out_n * 8, hipMemcpyHostToDevice, stream));
     if (voice_of) {
         d_voice_of.ensure((size_t)B * 4);
         MI_HIP(hipMemcpyAsync(d_voice_of.p, voice_of, (size_t)B * 4, hipMemcpyHostToDevice, stream));
@@ -373,12 +375,59 @@ void BigVGAN::run_latent_voices(const float* latent, int B, const int* T_codes, 
     }
     MI_REQUIRE((long)Fmax * cfg.hop < (1L << 30), "bigvgan_forward_latent_voices: too many frames");
     MI_REQUIRE(total <= out_cap, "bigvgan_forward_latent_voices: out_cap is smaller than the sum of the waveform lengths");
+    latent_items(latent, rows, B, F.data(), Fmax, nullptr, nullptr, total, n_voices, conds, n_conds, voice_of, out_f32, out_i16,
+                 out_lens, mem);
+}
+
+// Windows of one latent array (include/mi355tts.h mi_bigvgan_forward_latent_windows): item b = frames [row0[b], row0[b] + rows[b])
+// of `latent`, of which head[b] leading and tail[b] trailing frames are halo.  The forward is run_latent_voices' with row0 as the
+// row-offset table; only the tail differs: conv_post keeps samples [head ? head * hop + 15 : 0, tail ? (rows - tail) * hop + 15 :
+// rows * hop + 30) of each item.
+void BigVGAN::run_latent_windows(const float* latent, long latent_rows, int B, const int64_t* row0, const int64_t* rows,
+                                 const int32_t* head, const int32_t* tail, int n_voices, const float* conds, long n_conds,
+                                 const int* voice_of, float* out_f32, int16_t* out_i16, long out_cap, int64_t* out_lens, int mem) {
+    MI_REQUIRE(cfg.pre_ln && cfg.cond, "bigvgan_forward_latent_windows: handle was not created with the IndexTTS graph-F flags");
+    MI_REQUIRE(latent && row0 && rows && head && tail && conds && voice_of && out_lens && B > 0 && (out_f32 || out_i16),
+               "bigvgan_forward_latent_windows: bad arguments");
+    MI_REQUIRE(n_voices >= 1, "bigvgan_forward_latent_windows: at least one voice");
+    MI_REQUIRE(n_conds == total_cond(), "bigvgan_forward_latent_windows: conditioning vector length");
+    MI_REQUIRE(mel_pad == cfg.num_mels, "bigvgan_forward_latent_windows: the latent width must be a multiple of the 16-byte vector");
+    MI_REQUIRE(latent_rows >= 1, "bigvgan_forward_latent_windows: latent_rows");
+    std::vector<int> F(B);
+    std::vector<long> r0(B), win((size_t)3 * B);
+    int Fmax = 0;
+    long total = 0;
+    for (int b = 0; b < B; ++b) {
+        MI_REQUIRE(rows[b] >= 1 && head[b] >= 0 && tail[b] >= 0 && (int64_t)head[b] + tail[b] < rows[b],
+                   "bigvgan_forward_latent_windows: every window needs rows >= 1, head >= 0, tail >= 0 and head + tail < rows");
+        MI_REQUIRE(row0[b] >= 0 && row0[b] <= latent_rows && rows[b] <= latent_rows - row0[b],
+                   "bigvgan_forward_latent_windows: a window lies outside [0, latent_rows)");
+        MI_REQUIRE(rows[b] * cfg.hop < (1L << 30), "bigvgan_forward_latent_windows: too many frames");
+        MI_REQUIRE(voice_of[b] >= 0 && voice_of[b] < n_voices, "bigvgan_forward_latent_windows: voice_of holds an index outside [0, n_voices)");
+        F[b] = (int)rows[b];
+        r0[b] = (long)row0[b];
+        Fmax = std::max(Fmax, F[b]);
+        const long first = head[b] ? (long)head[b] * cfg.hop + 15 : 0;
+        const long end = tail[b] ? (long)(F[b] - tail[b]) * cfg.hop + 15 : (long)F[b] * cfg.hop + 30;
+        win[3 * b] = first; win[3 * b + 1] = end - first; win[3 * b + 2] = total;
+        total += end - first;
+    }
+    MI_REQUIRE(total <= out_cap, "bigvgan_forward_latent_windows: out_cap is smaller than the sum of the kept samples");
+    latent_items(latent, latent_rows, B, F.data(), Fmax, r0.data(), win.data(), total, n_voices, conds, n_conds, voice_of, out_f32,
+                 out_i16, out_lens, mem);
+}
+
+// the forward of the two entries above, after their checks.  `rows` = the latent rows a host caller hands over; row0 / win null:
+// whole sentences of F[b] + 2 rows one after another, untrimmed
+void BigVGAN::latent_items(const float* latent, long rows, int B, const int* Fp, int Fmax, const long* row0, const long* win,
+                           long total, int n_voices, const float* conds, long n_conds, const int* voice_of, float* out_f32,
+                           int16_t* out_i16, int64_t* out_lens, int mem) {
     MI_HIP(hipSetDevice(device));
     const int tc = (int)n_conds;
     ensure_workspace(B, Fmax);
     d_bias_tab.ensure((size_t)B * tc * 4);               // every buffer of the forward exists before its first launch
     if (mem == MI_HOST) { d_conds.ensure((size_t)n_voices * tc * 4); d_latent.ensure((size_t)rows * cfg.num_mels * 4); }
-    const std::vector<long> offs = ragged_tables(B, F.data(), 2, voice_of);      // latent rows of item b start at sum of T_codes before it
+    const std::vector<long> offs = ragged_tables(B, Fp, 2, voice_of, row0, win);     // sentences: item b starts at the sum of T_codes before it
     const float* dc = conds;
     const float* dl = latent;
     if (mem == MI_HOST) {                                // the caller's arrays outlive the call: body() ends with a synchronisation
@@ -407,11 +456,11 @@ void BigVGAN::run_latent_voices(const float* latent, int B, const int* T_codes, 
     }
     launch_rownorm_len(NORM_LN_AFFINE, dl, bT1.p, dtype, ln_w.as<float>(), ln_b.as<float>(), B, Fmax, cfg.num_mels, 1e-5f,
                        d_frames.as<int>(), d_in_offs.as<long>(), stream);
-    ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total;
+    ln = d_frames.as<int>(); out_offs = d_out_offs.as<long>(); out_total = total; out_win = win != nullptr;
     try {
         body(bT1.p, B, Fmax, nullptr, d_bias_tab.as<float>(), tc, out_f32, out_i16, mem);
-    } catch (...) { ln = nullptr; out_offs = nullptr; throw; }
-    ln = nullptr; out_offs = nullptr;
+    } catch (...) { ln = nullptr; out_offs = nullptr; out_win = false; throw; }
+    ln = nullptr; out_offs = nullptr; out_win = false;
     for (int b = 0; b < B; ++b) out_lens[b] = offs[b + 1] - offs[b];
 }
 
@@ -535,7 +584,9 @@ void BigVGAN::body(const void* x0, int B, int F, const float* const* cond, const
     float* of = out_f32 ? (mem == MI_DEVICE ? out_f32 : d_out_f32.as<float>()) : nullptr;
     int16_t* oi = out_i16 ? (mem == MI_DEVICE ? out_i16 : d_out_i16.as<int16_t>()) : nullptr;
     const long n_out = lens ? out_total : (long)B * Tout;
-    if (lens) launch_conv_post_len(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, lens, cfg.hop, 30,
+    if (lens && out_win) launch_conv_post_win(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, lens, cfg.hop,
+                                              30, out_offs, stream);
+    else if (lens) launch_conv_post_len(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, lens, cfg.hop, 30,
                                    out_offs, stream);
     else launch_conv_post(bT1.p, post_w.as<float>(), post_bias, B, (int)Tout, cl, dtype, cfg.tanh_final, of, oi, stream);
     if (mem == MI_HOST) {

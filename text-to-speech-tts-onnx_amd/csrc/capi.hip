@@ -6,6 +6,7 @@
 #include "gpt_pick.h"
 #include "cond.h"
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <exception>
 
@@ -14,7 +15,8 @@ using namespace mi;
 // calls on one handle are serialised (one HIP stream + one workspace per handle); different handles run concurrently
 struct mi_bigvgan { BigVGAN* impl; std::mutex mu; };
 struct mi_f5 { F5* impl; std::mutex mu; };
-struct mi_gpt { Gpt* impl; std::mutex mu; };
+struct GptQueue;                         // an open sentence-queue session (mi_gpt_queue_begin), defined with the queue below
+struct mi_gpt { Gpt* impl; std::mutex mu; GptQueue* session = nullptr; };
 struct mi_cond { Cond* impl; std::mutex mu; };
 
 // Every C-ABI entry runs under the SHARED side of the option lock; mi_set_option takes the exclusive side.  The dispatch options
@@ -216,6 +218,22 @@ int mi_bigvgan_forward_latent_voices(mi_bigvgan* h, int B, const float* latent, 
         // voice indices and counts are checked by the engine before anything reaches the device (the handle stays usable)
         h->impl->run_latent_voices(latent, B, T.data(), n_voices, conds, (long)n_conds, (const int*)voice_of, out_f32, out_i16,
                                    (long)out_cap, out_lens, mem);
+    });
+}
+
+int mi_bigvgan_forward_latent_windows(mi_bigvgan* h, int B, const float* latent, int64_t latent_rows, const int64_t* row0,
+                                      const int64_t* rows, const int32_t* head, const int32_t* tail, int n_voices, const float* conds,
+                                      int64_t n_conds, const int32_t* voice_of, int16_t* out_i16, float* out_f32, int64_t out_cap,
+                                      int64_t* out_lens, int mem) {
+    return guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_bigvgan_forward_latent_windows: null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, "mi_bigvgan_forward_latent_windows: bad mem kind");
+        MI_REQUIRE(out_i16, "mi_bigvgan_forward_latent_windows: null out_i16");
+        MI_REQUIRE(B >= 1 && latent_rows >= 1 && latent_rows < (1L << 40), "mi_bigvgan_forward_latent_windows: B >= 1 windows of >= 1 latent rows");
+        // windows, voices and counts are checked by the engine before anything reaches the device (the handle stays usable)
+        h->impl->run_latent_windows(latent, (long)latent_rows, B, row0, rows, head, tail, n_voices, conds, (long)n_conds,
+                                    (const int*)voice_of, out_f32, out_i16, (long)out_cap, out_lens, mem);
     });
 }
 
@@ -664,9 +682,12 @@ mi_gpt* mi_gpt_create_mem(const int32_t* cfg, int n_cfg, const float* weights, i
     return rc == MI_OK ? h : nullptr;
 }
 
+static void gpt_queue_free(GptQueue* q);
+
 void mi_gpt_destroy(mi_gpt* h) {
     if (!h) return;
-    delete h->impl;
+    delete h->impl;                          // synchronises the stream: nothing of an open session is in flight afterwards
+    gpt_queue_free(h->session);
     delete h;
 }
 
@@ -675,6 +696,12 @@ void mi_gpt_destroy(mi_gpt* h) {
     std::lock_guard<std::mutex> lk_((h)->mu);                                      \
     MI_REQUIRE((mem) == MI_HOST || (mem) == MI_DEVICE, name ": bad mem kind");     \
     MI_HIP(hipSetDevice((h)->impl->device))
+
+// after GPT_CHECK (the handle's lock is held): the entry would touch the slots an open queue session decodes in
+#define GPT_NO_SESSION(h, name)                                                    \
+    do {                                                                           \
+        if ((h)->session) throw mi::Error(MI_ESTATE, std::string(name) + ": a sentence-queue session is open on this handle (mi_gpt_queue_end)"); \
+    } while (0)
 
 // input staged to the device when it lives on the host
 static const void* stage_in(DevBuf& buf, const void* src, size_t bytes, int mem, hipStream_t s) {
@@ -775,6 +802,7 @@ int mi_gpt_reset(mi_gpt* h) {
     return guard([&] {
         MI_REQUIRE(h && h->impl, "mi_gpt_reset: null handle");
         std::lock_guard<std::mutex> lk_(h->mu);
+        GPT_NO_SESSION(h, "mi_gpt_reset");
         MI_HIP(hipSetDevice(h->impl->device));
         h->impl->reset();
     });
@@ -789,6 +817,7 @@ int mi_gpt_step(mi_gpt* h, const float* hidden_state, int ids_len, const float* 
                 float* last_hidden_state, int32_t* max_logit_id, float* logits, int mem) {
     return guard([&] {
         GPT_CHECK(h, mem, "mi_gpt_step");
+        GPT_NO_SESSION(h, "mi_gpt_step");
         Gpt& e = *h->impl;
         const GptCfg& c = e.cfg;
         MI_REQUIRE(hidden_state && ids_len >= 1, "mi_gpt_step: hidden_state must hold at least one row");
@@ -828,6 +857,7 @@ int mi_gpt_kv_read(mi_gpt* h, int layer, float* keys, float* values, int mem) {
 int mi_gpt_kv_write(mi_gpt* h, int layer, const float* keys, const float* values, int hist, int mem) {
     return guard([&] {
         GPT_CHECK(h, mem, "mi_gpt_kv_write");
+        GPT_NO_SESSION(h, "mi_gpt_kv_write");
         Gpt& e = *h->impl;
         MI_REQUIRE(hist >= 0 && hist < e.cfg.max_seq, "mi_gpt_kv_write: history does not fit the KV cache (max_seq)");
         MI_REQUIRE(hist == 0 || (keys && values), "mi_gpt_kv_write: null keys/values");
@@ -869,6 +899,7 @@ static void gpt_generate_impl(mi_gpt* h, const float* prompt, int P, int max_new
     MI_REQUIRE(h && h->impl, who + ": null handle");
     std::lock_guard<std::mutex> lk_(h->mu);
     MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+    GPT_NO_SESSION(h, who);
     MI_HIP(hipSetDevice(h->impl->device));
     Gpt& e = *h->impl;
     const GptCfg& c = e.cfg;
@@ -930,6 +961,7 @@ static void gpt_generate_batch_impl(mi_gpt* h, int nb, const float* prompts, con
     MI_REQUIRE(h && h->impl, who + ": null handle");
     std::lock_guard<std::mutex> lk_(h->mu);
     MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+    GPT_NO_SESSION(h, who);
     MI_HIP(hipSetDevice(h->impl->device));
     Gpt& e = *h->impl;
     const GptCfg& c = e.cfg;
@@ -997,7 +1029,175 @@ int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const
 }
 
 // Sentence queue (include/mi355tts.h, "sentence queue"): n sentences through S = min(max_batch, n) slots, a slot refilled as
-// soon as its sentence stops, every prompt pass packed (Gpt::forward_packed).  The policy is the header's, step by step.
+// soon as its sentence stops, every prompt pass packed (Gpt::forward_packed).  The policy is the header's, step by step.  The
+// loop lives in a session (mi_gpt_queue_begin / _advance / _end) that stops after every run of decode steps; the blocking entry
+// is a session driven to its end inside one call.
+struct GptQueue {
+    int n = 0, cap = 0, mem = MI_HOST, S = 0, penalty_range = 0;
+    bool any_samp = false;
+    bool per_round = false;          // sessions: tokens and rows leave after every round; blocking entry: at retirement only
+    bool ended = false;              // the loop has run out: nothing live, nothing waiting
+    const float* prompts = nullptr;  // the caller's, alive until the session ends
+    int32_t* tokens = nullptr;
+    float* hidden = nullptr;
+    std::vector<int32_t> prompt_rows, max_new, stops, all, n_out, copied;
+    std::vector<GptSampleRec> recs;
+    std::vector<size_t> row0;
+    std::vector<int> owner;          // the sentence in each slot, -1 = free
+    std::vector<char> retired;
+    int next = 0, live = 0;
+    long steps = 0, passes = 0;
+    Gpt::OutTable tab;               // the copy-out entries gathered since the last launch
+    int n_tab = 0;
+    std::vector<int32_t> h_tok;      // MI_HOST: what the copy-out kernel packed, on the host
+    std::vector<float> h_hid;
+};
+
+static void gpt_queue_free(GptQueue* q) { delete q; }
+
+// validation (all of it before anything is launched) and the start state: every slot finished, nothing admitted
+static void gpt_queue_setup(Gpt& e, GptQueue& q, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                            const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
+                            int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
+                            const std::string& who) {
+    const GptCfg& c = e.cfg;
+    MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
+    MI_REQUIRE(prompts && prompt_rows && max_new && cap >= 1, who + ": null argument");
+    q.stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
+    q.any_samp = temperature || top_k || top_p || seeds;
+    MI_REQUIRE(!q.any_samp || (temperature && top_k && top_p && seeds), who + ": the four sampling arrays come together or not at all");
+    gpt_check_lengths(c, n, prompt_rows, max_new, cap, who);
+    q.n = n; q.cap = cap; q.mem = mem; q.penalty_range = penalty_range;
+    q.prompts = prompts; q.tokens = tokens; q.hidden = hidden;
+    q.prompt_rows.assign(prompt_rows, prompt_rows + n);
+    q.max_new.assign(max_new, max_new + n);
+    q.row0.resize(n);
+    size_t rows_total = 0;
+    for (int i = 0; i < n; ++i) { q.row0[i] = rows_total; rows_total += (size_t)prompt_rows[i]; }
+    GptModeScope mode(e, q.any_samp);                            // (checks that the handle can sample)
+    q.recs.resize(q.any_samp ? n : 0);
+    for (int i = 0; i < (int)q.recs.size(); ++i) q.recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
+    hipStream_t s = e.stream;
+    e.set_rep_value(repeat_value);
+    q.S = std::min(c.max_batch, n);
+    // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
+    q.all.assign((size_t)q.S * GS_WORDS, 0);
+    for (int b = 0; b < q.S; ++b) q.all[(size_t)b * GS_WORDS + GS_DONE] = 1;
+    MI_HIP(hipMemcpyAsync(e.state.p, q.all.data(), q.all.size() * 4, hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+    q.owner.assign(q.S, -1);
+    q.n_out.assign(n, 0); q.copied.assign(n, 0); q.retired.assign(n, 0);
+    q.next = 0; q.live = 0; q.steps = 0; q.passes = 0; q.n_tab = 0; q.ended = false;
+    while (q.next < n && q.max_new[q.next] == 0) ++q.next;
+}
+
+// sessions: rows [copied_i, upto) of sentence i, held by slot b, join the round's copy-out table
+static void gpt_queue_note(GptQueue& q, int b, int i, int upto) {
+    if (upto <= q.copied[i]) return;
+    MI_REQUIRE(q.n_tab < GPT_MAX_BATCH, "gpt queue: copy-out table overflow");
+    Gpt::OutSeg& g = q.tab.e[q.n_tab++];
+    g.slot = b; g.first = q.copied[i]; g.count = upto - q.copied[i]; g.sentence = i;
+    g.dst_row = (int64_t)i * q.cap + q.copied[i];
+    q.copied[i] = upto;
+}
+
+// sessions: the table's rows leave in one launch.  MI_DEVICE: straight into the caller's arrays.  MI_HOST: packed into the
+// staging buffers, one device-to-host copy per array, then placed by the host (synchronises).
+static void gpt_queue_flush(Gpt& e, GptQueue& q) {
+    if (q.n_tab == 0) return;
+    const int h = e.cfg.hidden;
+    if (q.mem == MI_DEVICE) {
+        e.copy_out_rows(q.tab, q.n_tab, q.tokens, q.hidden);
+    } else {
+        Gpt::OutTable packed = q.tab;
+        size_t rows = 0;
+        for (int k = 0; k < q.n_tab; ++k) { packed.e[k].dst_row = (int64_t)rows; rows += (size_t)q.tab.e[k].count; }
+        e.io_a.ensure(rows * 4); e.io_b.ensure(rows * h * 4);
+        q.h_tok.resize(rows); q.h_hid.resize(rows * h);
+        e.copy_out_rows(packed, q.n_tab, q.tokens ? e.io_a.as<int32_t>() : nullptr, q.hidden ? e.io_b.as<float>() : nullptr);
+        if (q.tokens) MI_HIP(hipMemcpyAsync(q.h_tok.data(), e.io_a.p, rows * 4, hipMemcpyDeviceToHost, e.stream));
+        if (q.hidden) MI_HIP(hipMemcpyAsync(q.h_hid.data(), e.io_b.p, rows * h * 4, hipMemcpyDeviceToHost, e.stream));
+        MI_HIP(hipStreamSynchronize(e.stream));
+        for (int k = 0; k < q.n_tab; ++k) {
+            const Gpt::OutSeg& g = q.tab.e[k];
+            const size_t src = (size_t)packed.e[k].dst_row, dst = (size_t)g.dst_row;
+            if (q.tokens) std::memcpy(q.tokens + dst, q.h_tok.data() + src, (size_t)g.count * 4);
+            if (q.hidden) std::memcpy(q.hidden + dst * h, q.h_hid.data() + src * h, (size_t)g.count * h * 4);
+        }
+    }
+    q.n_tab = 0;
+}
+
+// One round of the policy: admit and retire until nothing more can be admitted, then one run of c <= 16 decode steps and a look
+// at the states.  Returns false when there was nothing left to decode (the queue has ended).
+static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
+    const GptCfg& c = e.cfg;
+    hipStream_t s = e.stream;
+    const int n = q.n, S = q.S;
+    const hipMemcpyKind in = q.mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    std::vector<int32_t>& all = q.all;
+    std::vector<int>& owner = q.owner;
+    auto skip_empty = [&] { while (q.next < n && q.max_new[q.next] == 0) ++q.next; };
+    for (;;) {
+        // 1. admit: passes of the waiting sentences into the free slots, in index order, lowest free slot first
+        bool ran = false;
+        while (q.live < S && q.next < n) {
+            Gpt::Seg segs[GPT_MAX_BATCH];
+            int k = 0, total = 0;
+            while (q.live < S && q.next < n) {
+                const int rows = q.prompt_rows[q.next];
+                if (k > 0 && total + rows > c.max_seq) break;        // the first sentence of a pass always fits
+                int slot = 0;
+                while (owner[slot] >= 0) ++slot;
+                owner[slot] = q.next; ++q.live;
+                e.set_state(gpt_state_words(q.stops, q.penalty_range, q.max_new[q.next], false), slot);
+                e.reset_penalty(slot);
+                if (q.any_samp) e.set_sampling_slot(&q.recs[q.next], slot);
+                MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, q.prompts + q.row0[q.next] * c.hidden,
+                                      (size_t)rows * c.hidden * 4, in, s));
+                segs[k].first = total; segs[k].rows = rows; segs[k].slot = slot; segs[k].pad = 0;
+                ++k; total += rows;
+                ++q.next;
+                skip_empty();
+            }
+            e.forward_packed(segs, k);
+            ++q.passes;
+            ran = true;
+        }
+        if (ran) gpt_read_states(e, all);
+        // 2. retire every finished slot: its tokens and rows go out, the slot is free
+        bool freed = false;
+        for (int b = 0; b < S; ++b) {
+            const int i = owner[b];
+            if (i < 0 || !all[(size_t)b * GS_WORDS + GS_DONE]) continue;
+            const int nt = std::min(all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[i]);
+            q.n_out[i] = nt;
+            if (q.per_round) {
+                gpt_queue_note(q, b, i, nt);                     // what the rounds before have not moved yet
+            } else {
+                copy_out(q.tokens ? q.tokens + (size_t)i * q.cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)nt * 4, q.mem, s);
+                copy_out(q.hidden ? q.hidden + (size_t)i * q.cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
+                         (size_t)nt * c.hidden * 4, q.mem, s);
+            }
+            q.retired[i] = 1;
+            owner[b] = -1; --q.live;
+            freed = true;
+        }
+        if (q.per_round) gpt_queue_flush(e, q);                  // in stream order before a pass can refill the slots
+        if (freed && q.next < n) continue;                       // refill before the next decode step
+        // 3. finish, or decode up to the nearest limit (at most 16 steps) and look again
+        if (q.live == 0) { q.ended = true; return false; }
+        int cs = 16;
+        for (int b = 0; b < S; ++b)
+            if (owner[b] >= 0) cs = std::min(cs, q.max_new[owner[b]] - all[(size_t)b * GS_WORDS + GS_NDEC]);
+        MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
+        e.decode_batch_steps(S, cs);
+        q.steps += cs;
+        gpt_read_states(e, all);
+        return true;
+    }
+}
+
 int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                           const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
                           float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
@@ -1005,90 +1205,82 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
     return guard([&] {
         const std::string who = "mi_gpt_generate_queue";
         GPT_CHECK(h, mem, "mi_gpt_generate_queue");
+        GPT_NO_SESSION(h, "mi_gpt_generate_queue");
         Gpt& e = *h->impl;
-        const GptCfg& c = e.cfg;
-        // everything is validated before anything is launched
-        MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
-        MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
-        const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
-        const bool any_samp = temperature || top_k || top_p || seeds;
-        MI_REQUIRE(!any_samp || (temperature && top_k && top_p && seeds), who + ": the four sampling arrays come together or not at all");
-        gpt_check_lengths(c, n, prompt_rows, max_new, cap, who);
-        std::vector<size_t> row0(n);
-        size_t rows_total = 0;
-        for (int i = 0; i < n; ++i) { row0[i] = rows_total; rows_total += (size_t)prompt_rows[i]; }
-        GptModeScope mode(e, any_samp);
-        std::vector<GptSampleRec> recs(any_samp ? n : 0);
-        for (int i = 0; i < (int)recs.size(); ++i) recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
-        hipStream_t s = e.stream;
-        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        e.set_rep_value(repeat_value);
-        const int S = std::min(c.max_batch, n);
-        // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
-        std::vector<int32_t> all((size_t)S * GS_WORDS, 0);
-        for (int b = 0; b < S; ++b) all[(size_t)b * GS_WORDS + GS_DONE] = 1;
-        MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
-        MI_HIP(hipStreamSynchronize(s));
-        std::vector<int> owner(S, -1);                               // the sentence in each slot, -1 = free
-        for (int i = 0; i < n; ++i) n_out[i] = 0;
-        int next = 0, live = 0;
-        long steps = 0, passes = 0;
-        auto skip_empty = [&] { while (next < n && max_new[next] == 0) ++next; };
-        skip_empty();
-        for (;;) {
-            // 1. admit: passes of the waiting sentences into the free slots, in index order, lowest free slot first
-            bool ran = false;
-            while (live < S && next < n) {
-                Gpt::Seg segs[GPT_MAX_BATCH];
-                int k = 0, total = 0;
-                while (live < S && next < n) {
-                    const int rows = prompt_rows[next];
-                    if (k > 0 && total + rows > c.max_seq) break;        // the first sentence of a pass always fits
-                    int slot = 0;
-                    while (owner[slot] >= 0) ++slot;
-                    owner[slot] = next; ++live;
-                    e.set_state(gpt_state_words(stops, penalty_range, max_new[next], false), slot);
-                    e.reset_penalty(slot);
-                    if (any_samp) e.set_sampling_slot(&recs[next], slot);
-                    MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, prompts + row0[next] * c.hidden,
-                                          (size_t)rows * c.hidden * 4, in, s));
-                    segs[k].first = total; segs[k].rows = rows; segs[k].slot = slot; segs[k].pad = 0;
-                    ++k; total += rows;
-                    ++next;
-                    skip_empty();
-                }
-                e.forward_packed(segs, k);
-                ++passes;
-                ran = true;
+        MI_REQUIRE(n_out != nullptr, who + ": null argument");
+        GptQueue q;
+        gpt_queue_setup(e, q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap, mem,
+                        temperature, top_k, top_p, seeds, who);
+        GptModeScope mode(e, q.any_samp);
+        while (gpt_queue_round(e, q, who)) {}
+        for (int i = 0; i < n; ++i) n_out[i] = q.n_out[i];
+        e.history = q.all[GS_HIST];
+        MI_HIP(hipStreamSynchronize(e.stream));
+        if (stats) { stats[0] = (int32_t)q.steps; stats[1] = (int32_t)q.passes; }
+    });
+}
+
+int mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                       const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
+                       int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds) {
+    return guard([&] {
+        const std::string who = "mi_gpt_queue_begin";
+        GPT_CHECK(h, mem, "mi_gpt_queue_begin");
+        GPT_NO_SESSION(h, "mi_gpt_queue_begin");
+        Gpt& e = *h->impl;
+        std::unique_ptr<GptQueue> q(new GptQueue);
+        gpt_queue_setup(e, *q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
+                        mem, temperature, top_k, top_p, seeds, who);
+        q->per_round = true;
+        h->session = q.release();
+    });
+}
+
+int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* finished, int32_t* stats) {
+    return guard([&] {
+        const std::string who = "mi_gpt_queue_advance";
+        MI_REQUIRE(h && h->impl, who + ": null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        if (!h->session) throw mi::Error(MI_ESTATE, who + ": no session is open on this handle");
+        MI_REQUIRE(count && done && finished, who + ": null argument");
+        MI_HIP(hipSetDevice(h->impl->device));
+        Gpt& e = *h->impl;
+        GptQueue& q = *h->session;
+        if (!q.ended) {
+            GptModeScope mode(e, q.any_samp);
+            if (gpt_queue_round(e, q, who)) {
+                // everything the live slots hold by now, finished ones included (they are retired by the next round)
+                for (int b = 0; b < q.S; ++b)
+                    if (q.owner[b] >= 0)
+                        gpt_queue_note(q, b, q.owner[b], std::min(q.all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[q.owner[b]]));
+                gpt_queue_flush(e, q);
             }
-            if (ran) gpt_read_states(e, all);
-            // 2. retire every finished slot: its tokens and rows go out, the slot is free
-            bool freed = false;
-            for (int b = 0; b < S; ++b) {
-                const int i = owner[b];
-                if (i < 0 || !all[(size_t)b * GS_WORDS + GS_DONE]) continue;
-                const int nt = std::min(all[(size_t)b * GS_WORDS + GS_NDEC], max_new[i]);
-                n_out[i] = nt;
-                copy_out(tokens ? tokens + (size_t)i * cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)nt * 4, mem, s);
-                copy_out(hidden ? hidden + (size_t)i * cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
-                         (size_t)nt * c.hidden * 4, mem, s);
-                owner[b] = -1; --live;
-                freed = true;
-            }
-            if (freed && next < n) continue;                         // refill before the next decode step
-            // 3. finish, or decode up to the nearest limit (at most 16 steps) and look again
-            if (live == 0) break;
-            int cs = 16;
-            for (int b = 0; b < S; ++b)
-                if (owner[b] >= 0) cs = std::min(cs, max_new[owner[b]] - all[(size_t)b * GS_WORDS + GS_NDEC]);
-            MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
-            e.decode_batch_steps(S, cs);
-            steps += cs;
-            gpt_read_states(e, all);
+            e.history = q.all[GS_HIST];
+            MI_HIP(hipStreamSynchronize(e.stream));
         }
-        e.history = all[GS_HIST];
-        MI_HIP(hipStreamSynchronize(s));
-        if (stats) { stats[0] = (int32_t)steps; stats[1] = (int32_t)passes; }
+        bool fin = q.next >= q.n;
+        for (int i = 0; i < q.n; ++i) { count[i] = q.n_out[i]; done[i] = q.retired[i] || q.max_new[i] == 0; }
+        for (int b = 0; b < q.S; ++b) {
+            const int i = q.owner[b];
+            if (i < 0) continue;
+            count[i] = q.copied[i];
+            done[i] = q.all[(size_t)b * GS_WORDS + GS_DONE] != 0;
+            fin = fin && done[i];
+        }
+        *finished = fin ? 1 : 0;
+        if (stats) { stats[0] = (int32_t)q.steps; stats[1] = (int32_t)q.passes; }
+    });
+}
+
+int mi_gpt_queue_end(mi_gpt* h) {
+    return guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_gpt_queue_end: null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        if (!h->session) throw mi::Error(MI_ESTATE, "mi_gpt_queue_end: no session is open on this handle");
+        MI_HIP(hipSetDevice(h->impl->device));
+        (void)hipStreamSynchronize(h->impl->stream);                 // nothing of the session is in flight when its arrays go
+        gpt_queue_free(h->session);
+        h->session = nullptr;
     });
 }
 
@@ -1099,6 +1291,7 @@ int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t*
     return guard([&] {
         const std::string who = "mi_gpt_generate_beam";
         GPT_CHECK(h, mem, "mi_gpt_generate_beam");
+        GPT_NO_SESSION(h, "mi_gpt_generate_beam");
         Gpt& e = *h->impl;
         const GptCfg& c = e.cfg;
         const int B = num_beams;
@@ -1201,6 +1394,7 @@ int mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* temperature, co
                       double* us) {
     return guard([&] {
         GPT_CHECK(h, MI_HOST, "mi_gpt_bench_pick");
+        GPT_NO_SESSION(h, "mi_gpt_bench_pick");
         Gpt& e = *h->impl;
         MI_REQUIRE(us && nb >= 1 && nb <= e.cfg.max_batch && iters >= 1, "mi_gpt_bench_pick: bad arguments");
         std::vector<GptSampleRec> recs;

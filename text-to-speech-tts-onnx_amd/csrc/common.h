@@ -307,5 +307,8 @@ void launch_conv_post(const void* x, const float* w /*[7][C]*/, float bias, int 
 // ragged batches: item b has lens[b] * len_mul + len_add output samples, written from out + offs[b] (the items concatenated)
 void launch_conv_post_len(const void* x, const float* w, float bias, int B, int T, int C, int dtype, int use_tanh, float* out_f32,
                           int16_t* out_i16, const int* lens, int len_mul, int len_add, const long* offs, hipStream_t s);
+// windows: win[3b ..] = (first kept sample, kept count, output offset) of item b; samples outside the kept range are not written
+void launch_conv_post_win(const void* x, const float* w, float bias, int B, int T, int C, int dtype, int use_tanh, float* out_f32,
+                          int16_t* out_i16, const int* lens, int len_mul, int len_add, const long* win, hipStream_t s);
 
 }  // namespace mi

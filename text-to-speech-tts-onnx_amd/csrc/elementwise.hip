@@ -103,7 +103,10 @@ void launch_nlc_to_ncl(const void* x, float* y, int B, int C, int T, int dtype, 
 // with an odd row stride so the per-thread row walks are bank-conflict free.
 // LENS (ragged batches): item b has Tb = lens[b] * len_mul + len_add samples (zeros after them in its slab of Tn rows), written
 // from out + offs[b]; a workgroup wholly past Tb has nothing to write
-template <typename T, bool LENS = false>
+// WIN (windows with halo frames, needs LENS): offs is a table of three values per item, (first kept sample, kept count, output
+// offset); sample t of item b goes to out + offs[3b + 2] + t - first when first <= t < first + count and nowhere otherwise.  A
+// workgroup with no kept sample returns before it stages anything.
+template <typename T, bool LENS = false, bool WIN = false>
 __global__ __launch_bounds__(256) void conv_post_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                         float bias, int Tn, int C, int use_tanh,
                                                         float* __restrict__ out_f32, int16_t* __restrict__ out_i16,
@@ -115,12 +118,19 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const T* __restrict__ x,
     float* xs = lds + 7 * C;          // 262 * LD
     const int b = blockIdx.y, t0 = blockIdx.x * 256, tid = threadIdx.x;
     const T* xb = x + (long)b * Tn * C;
-    int Tb = Tn;
+    int Tb = Tn, k0 = 0, k1 = 0;              // WIN: kept samples [k0, k1) of the item
     long ob = (long)b * Tn;
     if constexpr (LENS) {
         Tb = __builtin_amdgcn_readfirstlane(lens[b] * len_mul + len_add);
         if (t0 >= Tb) return;
-        ob = offs[b];
+        if constexpr (WIN) {
+            k0 = __builtin_amdgcn_readfirstlane((int)offs[3 * b]);
+            k1 = k0 + __builtin_amdgcn_readfirstlane((int)offs[3 * b + 1]);
+            if (t0 + 256 <= k0 || t0 >= k1) return;
+            ob = offs[3 * b + 2] - k0;
+        } else {
+            ob = offs[b];
+        }
     }
     for (int i = tid; i < 7 * C; i += 256) ws[i] = w[i];
     const int n = 262 * C;
@@ -132,6 +142,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const T* __restrict__ x,
     __syncthreads();
     const int t = t0 + tid;
     if (t >= Tb) return;
+    if constexpr (WIN) { if (t < k0 || t >= k1) return; }
     float acc = bias;
     for (int j = 0; j < 7; ++j) {
         const float* xr = xs + (tid + j) * LD;
@@ -179,6 +190,27 @@ void launch_conv_post_len(const void* x, const float* w, float bias, int B, int 
     else
         hipLaunchKernelGGL((conv_post_kernel<bf16, true>), grid, dim3(256), lds, s, (const bf16*)x, w, bias, T, C, use_tanh, out_f32, out_i16,
                            lens, len_mul, len_add, offs);
+    MI_HIP(hipGetLastError());
+}
+
+// windows: win = three longs per item (first kept sample, kept count, output offset); only kept samples are written
+void launch_conv_post_win(const void* x, const float* w, float bias, int B, int T, int C, int dtype, int use_tanh, float* out_f32,
+                          int16_t* out_i16, const int* lens, int len_mul, int len_add, const long* win, hipStream_t s) {
+    dim3 grid((T + 255) / 256, B);
+    const size_t lds = (size_t)(7 * C + 262 * (C | 1)) * 4;
+    MI_REQUIRE(lds <= 160 * 1024, "conv_post: channel count too large");
+    ProfScope ps(FAM_CONV_POST, s, (double)B * T * (C * (double)dtype_size(dtype) + 2.0), 2.0 * B * T * 7.0 * C);
+    prof_set_kernel("conv_post_kernel<T>", dtype == MI_F32 ? "float" : dtype == MI_F16 ? "_Float16" : "__bf16");
+    prof_kernel_suffix(" + lengths + window");
+    if (dtype == MI_F32)
+        hipLaunchKernelGGL((conv_post_kernel<float, true, true>), grid, dim3(256), lds, s, (const float*)x, w, bias, T, C, use_tanh, out_f32,
+                           out_i16, lens, len_mul, len_add, win);
+    else if (dtype == MI_F16)
+        hipLaunchKernelGGL((conv_post_kernel<f16, true, true>), grid, dim3(256), lds, s, (const f16*)x, w, bias, T, C, use_tanh, out_f32,
+                           out_i16, lens, len_mul, len_add, win);
+    else
+        hipLaunchKernelGGL((conv_post_kernel<bf16, true, true>), grid, dim3(256), lds, s, (const bf16*)x, w, bias, T, C, use_tanh, out_f32,
+                           out_i16, lens, len_mul, len_add, win);
     MI_HIP(hipGetLastError());
 }
 

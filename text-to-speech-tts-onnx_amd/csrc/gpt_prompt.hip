@@ -84,6 +84,37 @@ void Gpt::reset_penalty(int slot) {
     MI_HIP(hipGetLastError());
 }
 
+// Copy-out of a queue session's round: entry q moves tokens and last_hidden_state rows [first, first + count) of slot `slot` to
+// rows dst_row .. of the destination arrays (the caller's (n, cap) arrays, or a packed staging buffer).  One block per (row of
+// the longest entry, entry); the table travels as a kernel argument, so a round costs one launch and no upload.
+__global__ __launch_bounds__(256) void gpt_copy_out_kernel(Gpt::OutTable tab, const int32_t* __restrict__ toks,
+                                                           const float* __restrict__ hid, int32_t* __restrict__ tokens_dst,
+                                                           float* __restrict__ hidden_dst, int hidden, int max_seq, int max_batch) {
+    const Gpt::OutSeg g = tab.e[blockIdx.y];
+    const int r = blockIdx.x;
+    if (r >= g.count || g.slot < 0 || g.slot >= max_batch || g.first < 0 || g.first + r >= max_seq) return;      // block-uniform
+    const size_t src = (size_t)g.slot * max_seq + g.first + r;
+    const size_t dst = (size_t)(g.dst_row + r);
+    if (tokens_dst && threadIdx.x == 0) tokens_dst[dst] = toks[src];
+    if (hidden_dst)
+        for (int c = threadIdx.x; c < hidden; c += 256) hidden_dst[dst * hidden + c] = hid[src * hidden + c];
+}
+
+void Gpt::copy_out_rows(const OutTable& tab, int n, int32_t* tokens_dst, float* hidden_dst) {
+    MI_REQUIRE(n >= 0 && n <= GPT_MAX_BATCH, "gpt: copy-out table");
+    int rows = 0;
+    for (int q = 0; q < n; ++q) {
+        const OutSeg& g = tab.e[q];
+        MI_REQUIRE(g.slot >= 0 && g.slot < cfg.max_batch && g.first >= 0 && g.count >= 0 && g.first + g.count <= cfg.max_seq &&
+                       g.dst_row >= 0, "gpt: copy-out entry");
+        rows = std::max(rows, (int)g.count);
+    }
+    if (n == 0 || rows == 0 || (!tokens_dst && !hidden_dst)) return;
+    hipLaunchKernelGGL(gpt_copy_out_kernel, dim3(rows, n), dim3(256), 0, stream, tab, toks.as<int32_t>(), hid.as<float>(), tokens_dst,
+                       hidden_dst, cfg.hidden, cfg.max_seq, cfg.max_batch);
+    MI_HIP(hipGetLastError());
+}
+
 static_assert(GPT_MAX_BATCH <= 64, "forward_packed keeps the slots of a pass in a 64-bit mask");
 
 void Gpt::forward_packed(const Seg* segs, int k) {

@@ -13,6 +13,7 @@ import numpy as np
 MI_F32, MI_F16, MI_BF16 = 0, 1, 2
 MI_HOST, MI_DEVICE = 0, 1
 MI_EINVAL = -1
+MI_ESTATE = -4
 DTYPES = {"f32": MI_F32, "fp32": MI_F32, "float32": MI_F32, "f16": MI_F16, "fp16": MI_F16, "float16": MI_F16,
           "bf16": MI_BF16, "bfloat16": MI_BF16}
 
@@ -118,6 +119,10 @@ def load() -> C.CDLL:
     if hasattr(L, "mi_bigvgan_forward_latent_voices"):       # absent from an older build loaded through MI355TTS_LIB (A/B runs)
         L.mi_bigvgan_forward_latent_voices.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int]
         L.mi_bigvgan_forward_latent_voices.restype = C.c_int
+    if hasattr(L, "mi_bigvgan_forward_latent_windows"):
+        L.mi_bigvgan_forward_latent_windows.argtypes = [vp, C.c_int, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp,
+                                                        C.c_int64, vp, C.c_int]
+        L.mi_bigvgan_forward_latent_windows.restype = C.c_int
     L.mi_indextts_cond_param_count.argtypes = [C.POINTER(C.c_int32), C.c_int]; L.mi_indextts_cond_param_count.restype = C.c_int64
     L.mi_indextts_cond_create.argtypes = [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int]
     L.mi_indextts_cond_create.restype = vp
@@ -149,6 +154,12 @@ def load() -> C.CDLL:
     L.mi_gpt_generate_queue.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
                                         C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp]
     L.mi_gpt_generate_queue.restype = C.c_int
+    if hasattr(L, "mi_gpt_queue_begin"):
+        L.mi_gpt_queue_begin.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
+                                         C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.mi_gpt_queue_begin.restype = C.c_int
+        L.mi_gpt_queue_advance.argtypes = [vp, vp, vp, vp, vp]; L.mi_gpt_queue_advance.restype = C.c_int
+        L.mi_gpt_queue_end.argtypes = [vp]; L.mi_gpt_queue_end.restype = C.c_int
     L.mi_gpt_sample_logits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.mi_gpt_sample_logits.restype = C.c_int
     L.mi_gpt_generate_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,

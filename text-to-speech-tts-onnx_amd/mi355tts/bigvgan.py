@@ -40,6 +40,46 @@ def ragged_layout(cfg: BigVGANConfig, frames, latent: bool = False):
     return F, in_offs, out_lens, out_offs, Fmax
 
 
+def window_layout(cfg: BigVGANConfig, latent_rows: int, windows):
+    """Host-side plan of a windowed graph-F forward (BigVGANVocoder.run_latent_windows, mi_bigvgan_forward_latent_windows).
+    windows = (row0, rows, head, tail) each: frames [row0, row0 + rows) of a (latent_rows, gpt_dim) array, of which `head`
+    leading and `tail` trailing frames are halo.  Run alone the window gives rows * hop + 30 samples; the kept ones are
+    [first, first + out_len) with first = head * hop + 15 (0 without a head) and the end at (rows - tail) * hop + 15
+    (rows * hop + 30 without a tail).  Raises ValueError where the engine says MI_EINVAL, before the GPU is touched.
+    Returns (first, out_lens, out_offs, Fmax): per window the first kept sample, the kept count and its offset in the
+    concatenated output, and the slab height."""
+    if not (cfg.pre_layernorm and cfg.speaker_cond):
+        raise ValueError("this config is not an IndexTTS graph-F vocoder (no latent input)")
+    try:
+        n_rows = operator.index(latent_rows)
+        win = [tuple(operator.index(v) for v in w) for w in windows]
+    except TypeError:
+        raise ValueError("latent_rows and the windows must hold integers") from None
+    if not win:
+        raise ValueError("windows: at least one window")
+    if n_rows < 1:
+        raise ValueError("latent_rows must be >= 1")
+    first, out_lens = [], []
+    for b, w in enumerate(win):
+        if len(w) != 4:
+            raise ValueError(f"window {b}: expected (row0, rows, head, tail)")
+        row0, rows, head, tail = w
+        if rows < 1:
+            raise ValueError(f"window {b}: {rows} rows, needs >= 1")
+        if head < 0 or tail < 0 or head + tail >= rows:
+            raise ValueError(f"window {b}: head {head} and tail {tail} must be >= 0 and leave a frame of {rows} rows")
+        if row0 < 0 or row0 + rows > n_rows:
+            raise ValueError(f"window {b}: rows [{row0}, {row0 + rows}) lie outside [0, {n_rows})")
+        if rows * cfg.hop >= 1 << 30:
+            raise ValueError(f"window {b}: {rows} frames exceed the vocoder's limit")
+        lo = head * cfg.hop + 15 if head else 0
+        hi = (rows - tail) * cfg.hop + 15 if tail else rows * cfg.hop + 30
+        first.append(lo)
+        out_lens.append(hi - lo)
+    out_offs = [int(v) for v in np.concatenate([[0], np.cumsum(out_lens)[:-1]])]
+    return first, out_lens, out_offs, max(w[1] for w in win)
+
+
 def flat_conds(cfg: BigVGANConfig, conds) -> np.ndarray:
     """One voice's conditioning vectors [cond_0 .. cond_{n-1}, cond_pre] (each (1, C, 1) / (C,)) as the flat float32 row the
     C-ABI takes (mi_bigvgan_forward_latent).  ValueError for a wrong count or size."""
@@ -310,6 +350,87 @@ class BigVGANVocoder:
                                                                 conds_table.data_ptr(), want, index.ctypes.data, out.data_ptr(), None,
                                                                 out.numel(), lens.ctypes.data, _lib.MI_DEVICE),
                    "mi_bigvgan_forward_latent_voices")
+        return out, [int(v) for v in lens]
+
+    # ---- windows of latent rows with halo frames: audio before a sentence has all its rows ------------------------------------
+    def run_latent_windows(self, latent, windows, voices, voice_of, return_float: bool = False):
+        """IndexTTS graph F on windows of one latent array: latent (latent_rows, gpt_dim) float32 (no rows are dropped here: leave
+        a sentence's last two rows out of its windows), windows = (row0, rows, head, tail) each (``window_layout``), voices /
+        voice_of as in ``run_latent_voices`` with one entry of voice_of per window.  Returns a list of int16 (out_len,) arrays,
+        the kept samples of each window (with return_float: also the float samples, as a second list).  With halo >=
+        ``cfg.halo_frames()`` at every cut inside a sentence the pieces are the sentence's own samples."""
+        cfg = self.cfg
+        latent = np.ascontiguousarray(latent, dtype=np.float32)
+        if latent.ndim != 2 or latent.shape[1] != cfg.num_mels:
+            raise ValueError(f"latent must be (latent_rows, {cfg.num_mels}), got {latent.shape}")
+        win = [tuple(int(v) for v in w) for w in windows]
+        _, out_lens, out_offs, _ = window_layout(cfg, latent.shape[0], win)
+        table, index = voices_table(cfg, voices, voice_of, len(win))
+        n = sum(out_lens)
+        out = np.empty(n, np.int16)
+        outf = np.empty(n, np.float32) if return_float else None
+        lens = np.zeros(len(win), np.int64)
+        w = np.asarray(win, np.int64)
+        row0, rows = np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+        head, tail = np.ascontiguousarray(w[:, 2], np.int32), np.ascontiguousarray(w[:, 3], np.int32)
+        _lib.check(_lib.load().mi_bigvgan_forward_latent_windows(self._h, len(win), latent.ctypes.data, latent.shape[0], row0.ctypes.data,
+                                                                 rows.ctypes.data, head.ctypes.data, tail.ctypes.data, table.shape[0],
+                                                                 table.ctypes.data, table.shape[1], index.ctypes.data, out.ctypes.data,
+                                                                 None if outf is None else outf.ctypes.data, n, lens.ctypes.data,
+                                                                 _lib.MI_HOST), "mi_bigvgan_forward_latent_windows")
+        assert list(lens) == out_lens, (list(lens), out_lens)
+        wav = [out[o:o + l].copy() for o, l in zip(out_offs, out_lens)]
+        if return_float:
+            return wav, [outf[o:o + l].copy() for o, l in zip(out_offs, out_lens)]
+        return wav
+
+    def run_latent_windows_torch(self, latent, windows, conds_table, voice_of, out=None, out_float=None):
+        """Device-resident run_latent_windows: latent = a contiguous float32 CUDA tensor whose last dimension is gpt_dim, read as
+        (latent_rows, gpt_dim) rows where it lies (e.g. the (n, cap, hidden) `hidden` tensor of an IndexGPT queue session:
+        sentence i's rows start at i * cap); conds_table / voice_of as in ``run_latent_voices_torch``.  `out` (int16) may be
+        larger than the kept samples; nothing outside them is written.  out_float: an optional float32 tensor for the float
+        samples.  Returns (wav_cat, out_lens)."""
+        import torch
+        cfg = self.cfg
+        if not (latent.is_cuda and latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() >= 2
+                and latent.shape[-1] == cfg.num_mels):
+            raise ValueError(f"latent must be a contiguous float32 (..., {cfg.num_mels}) tensor on the GPU")
+        n_rows = latent.numel() // cfg.num_mels
+        win = [tuple(int(v) for v in w) for w in windows]
+        _, out_lens, _, _ = window_layout(cfg, n_rows, win)
+        if not (conds_table.is_cuda and conds_table.dtype == torch.float32 and conds_table.is_contiguous() and conds_table.dim() == 2):
+            raise ValueError("conds_table must be a contiguous float32 (V, total_cond) tensor on the GPU")
+        want = sum(cfg.stage_channels(i) for i in range(cfg.num_upsamples)) + cfg.upsample_initial_channel
+        V = int(conds_table.shape[0])
+        if V < 1 or int(conds_table.shape[1]) != want:
+            raise ValueError(f"conds_table must be (V >= 1, {want}), got {tuple(conds_table.shape)}")
+        try:
+            index = [operator.index(x) for x in voice_of]
+        except TypeError:
+            raise ValueError("voice_of must hold integers") from None
+        if len(index) != len(win) or any(not 0 <= x < V for x in index):
+            raise ValueError(f"voice_of must hold {len(win)} indices in [0, {V})")
+        index = np.asarray(index, np.int32)
+        n = sum(out_lens)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int16, device=latent.device)
+        if not (out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.numel() >= n):
+            raise ValueError(f"out must be a contiguous int16 CUDA tensor of at least {n} samples")
+        cap = out.numel()
+        if out_float is not None:
+            if not (out_float.is_cuda and out_float.dtype == torch.float32 and out_float.is_contiguous() and out_float.numel() >= n):
+                raise ValueError(f"out_float must be a contiguous float32 CUDA tensor of at least {n} samples")
+            cap = min(cap, out_float.numel())
+        lens = np.zeros(len(win), np.int64)
+        w = np.asarray(win, np.int64)
+        row0, rows = np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+        head, tail = np.ascontiguousarray(w[:, 2], np.int32), np.ascontiguousarray(w[:, 3], np.int32)
+        torch.cuda.current_stream(latent.device).synchronize()
+        _lib.check(_lib.load().mi_bigvgan_forward_latent_windows(self._h, len(win), latent.data_ptr(), n_rows, row0.ctypes.data,
+                                                                 rows.ctypes.data, head.ctypes.data, tail.ctypes.data, V,
+                                                                 conds_table.data_ptr(), want, index.ctypes.data, out.data_ptr(),
+                                                                 None if out_float is None else out_float.data_ptr(), cap,
+                                                                 lens.ctypes.data, _lib.MI_DEVICE), "mi_bigvgan_forward_latent_windows")
         return out, [int(v) for v in lens]
 
     def _flat_conds(self, conds):

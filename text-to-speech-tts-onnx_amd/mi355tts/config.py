@@ -60,6 +60,30 @@ class BigVGANConfig:
         # (BigVGAN/modeling_modified/bigvgan.py:370,381-382)
         return frames * self.hop + 30
 
+    def halo_frames(self) -> int:
+        """The generator's receptive field in frames: waveform samples 15 + f * hop .. 15 + (f + 1) * hop - 1 (frame f's) depend
+        on no input frame outside [f - halo, f + halo].  Found by walking one output sample back through the generator, tracking
+        the interval of indices it depends on, for every phase of the hop: conv_post +-3; the post activation's out[o] reads
+        x[o - 20 .. o - 10]; per stage the widest AMP block (per dilation d: anti-aliased activation +-5, conv (k - 1) / 2 * d,
+        activation +-5, conv (k - 1) / 2; the residual adds only the identity path), then the upsampler (stride u, kernel k,
+        padding p = (k - u) / 2: [lo, hi] -> [ceil((lo + p - k + 1) / u), floor((hi + p) / u)]); conv_pre +-3.  Windows of
+        latent rows carrying this many extra frames at each cut reproduce the whole sentence's samples exactly
+        (BigVGANVocoder.run_latent_windows)."""
+        amp = max(sum(5 + (k - 1) // 2 * d + 5 + (k - 1) // 2 for d in dils)
+                  for k, dils in zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes))
+        halo = 0
+        for phase in range(self.hop):
+            lo = hi = 15 + phase                         # a sample of frame 0
+            lo, hi = lo - 3, hi + 3                      # conv_post
+            lo, hi = lo - 20, hi - 10                    # post activation (pad 15 on both FIRs)
+            for u, k in zip(reversed(self.upsample_rates), reversed(self.upsample_kernel_sizes)):
+                lo, hi = lo - amp, hi + amp
+                p = (k - u) // 2
+                lo, hi = -((-(lo + p - k + 1)) // u), (hi + p) // u
+            lo, hi = lo - 3, hi + 3                      # conv_pre
+            halo = max(halo, -lo, hi)
+        return halo
+
     def to_int_array(self) -> List[int]:
         """Flat encoding consumed by mi_bigvgan_create (include/mi355tts.h)."""
         out = [self.num_mels, self.upsample_initial_channel, self.num_upsamples, self.num_kernels,

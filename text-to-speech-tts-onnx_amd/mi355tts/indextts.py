@@ -232,6 +232,153 @@ def _queue_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, 
     return toks, hid, cnt, stats
 
 
+class QueueSession:
+    """An open sentence-queue session (include/mi355tts.h, mi_gpt_queue_begin / _advance / _end; made by
+    ``IndexGPT.queue_session``).  ``tokens`` (n, cap) int32 and ``hidden`` (n, cap, hidden) float32 are numpy arrays, or torch
+    tensors on the engine's device with device=True; after ``advance()`` the first count[i] entries of sentence i are valid and
+    final.  A context manager: leaving it ends the session (also before everything has finished)."""
+
+    def __init__(self, gpt, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays, device):
+        self._gpt = gpt
+        self._open = False
+        c = gpt.cfg
+        n = int(rows.size)
+        self.n, self.cap = n, cap
+        self._count = np.zeros((n,), np.int32)
+        self._done = np.zeros((n,), np.int32)
+        self._fin = np.zeros((1,), np.int32)
+        self._stats = np.zeros((2,), np.int32)
+        sa = (None,) * 4 if sampling_arrays is None else tuple(sampling_arrays)
+        L = _lib.load()
+        if device:
+            import torch
+            dev = torch.device("cuda", gpt.device)
+            self._cat = torch.from_numpy(cat).to(dev)
+            self._stops = torch.from_numpy(stops).to(dev) if stops.size else None
+            self.tokens = torch.zeros((n, cap), dtype=torch.int32, device=dev)
+            self.hidden = torch.zeros((n, cap, c.hidden), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ptrs = (self._cat.data_ptr(), None if self._stops is None else self._stops.data_ptr(), self.tokens.data_ptr(),
+                    self.hidden.data_ptr())
+            mem = _lib.MI_DEVICE
+        else:
+            self._cat, self._stops = cat, stops
+            self.tokens = np.zeros((n, cap), np.int32)
+            self.hidden = np.zeros((n, cap, c.hidden), np.float32)
+            ptrs = (cat.ctypes.data, stops.ctypes.data if stops.size else None, self.tokens.ctypes.data, self.hidden.ctypes.data)
+            mem = _lib.MI_HOST
+        rc = L.mi_gpt_queue_begin(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
+                                  penalty_range, ptrs[2], ptrs[3], cap, mem, *(None if a is None else a.ctypes.data for a in sa))
+        if rc == _lib.MI_EINVAL:
+            raise ValueError("mi_gpt_queue_begin: " + L.mi_last_error().decode("utf-8", "replace"))
+        _lib.check(rc, "mi_gpt_queue_begin")
+        self._open = True
+
+    def advance(self):
+        """One round of the queue's policy: admissions and retirements, then one run of at most 16 decode steps.  Returns
+        (count, done, finished): int32 (n,) valid tokens / rows per sentence, bool (n,) whether that is all of the sentence,
+        and whether nothing is live or waiting any more."""
+        if not self._open:
+            raise _lib.MiError("the queue session has ended")
+        _lib.check(_lib.load().mi_gpt_queue_advance(self._gpt._h, self._count.ctypes.data, self._done.ctypes.data,
+                                                    self._fin.ctypes.data, self._stats.ctypes.data), "mi_gpt_queue_advance")
+        return self._count.copy(), self._done.astype(bool), bool(self._fin[0])
+
+    @property
+    def stats(self):
+        """{"steps": decode steps launched, "passes": prompt passes}, so far"""
+        return {"steps": int(self._stats[0]), "passes": int(self._stats[1])}
+
+    def end(self):
+        if self._open:
+            self._open = False
+            if getattr(self._gpt, "_h", None):
+                _lib.check(_lib.load().mi_gpt_queue_end(self._gpt._h), "mi_gpt_queue_end")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.end()
+        return False
+
+    def __del__(self):
+        try:
+            self.end()
+        except Exception:
+            pass
+
+
+def stream_plan(emitted, count, done, chunk: int, halo: int):
+    """Which vocoder windows are ready: the host model of ``stream_synthesize``.  emitted[i] = frames of sentence i already
+    emitted, count[i] / done[i] = what ``QueueSession.advance`` reported.  A sentence has A = count - 2 frames available: its F
+    when done, and safe while live (a live sentence's last two rows are not yet known to be frames).  While live a sentence emits
+    [e, e + chunk) as soon as e + chunk + halo <= A, again and again; when done it emits everything left, [e, F), as one
+    window.  Each piece [a, b) becomes the window of frames [lo, hi) = [max(0, a - halo), min(A, b + halo)) with head = a - lo
+    and tail = hi - b.  Sentences with fewer than three codes emit nothing.  Returns (windows, emitted_after): windows = list of
+    (sentence, a, b, lo, hi, last) in sentence order, pieces of a sentence in frame order."""
+    chunk, halo = int(chunk), int(halo)
+    if chunk < 1 or halo < 0:
+        raise ValueError("stream_plan: chunk must be >= 1 and halo >= 0")
+    if not (len(emitted) == len(count) == len(done)):
+        raise ValueError("stream_plan: emitted, count and done must have one entry per sentence")
+    out, after = [], [int(e) for e in emitted]
+    for i in range(len(after)):
+        A = int(count[i]) - 2
+        e = after[i]
+        if A < 1 or e >= A:
+            continue
+        if done[i]:
+            pieces = [(e, A)]
+        else:
+            pieces = []
+            while e + chunk + halo <= A:
+                pieces.append((e, e + chunk))
+                e += chunk
+        for a, b in pieces:
+            out.append((i, a, b, max(0, a - halo), min(A, b + halo), bool(done[i]) and b == A))
+            after[i] = b
+    return out, after
+
+
+def stream_synthesize(gpt, voc, prompts, max_new, voices, voice_of, *, chunk: int = 32, halo: Optional[int] = None, **decode_kw):
+    """Audio while the queue decodes: a generator over (sentence, first_sample, int16 chunk, last).  gpt = IndexGPT, voc = a
+    graph-F BigVGANVocoder, prompts / max_new / decode_kw (stop_tokens, repeat_value, penalty_range, sampling) as
+    ``IndexGPT.generate_queue``, voices / voice_of as ``BigVGANVocoder.run_latent_voices`` (one voice index per sentence).
+    Every round is one ``QueueSession.advance()`` followed by ONE ``run_latent_windows_torch`` call over all windows
+    ``stream_plan`` reports, of any sentences and voices, reading the rows from the session's device `hidden`.  The chunks of a
+    sentence tile its waveform [0, F * hop + 30) in order, `last` on the final one; a sentence of fewer than three codes yields
+    nothing.  halo: frames of context at each cut (default: ``voc.cfg.halo_frames()``, with which the samples are those of the
+    whole sentence's forward; less trades accuracy for work).  One thread: the vocoder call pauses the decode."""
+    import torch
+    from .bigvgan import voices_table
+    n = len(prompts)
+    halo = voc.cfg.halo_frames() if halo is None else int(halo)
+    table, index = voices_table(voc.cfg, voices, voice_of, n)
+    hop = voc.cfg.hop
+    with gpt.queue_session(prompts, max_new, device=True, **decode_kw) as q:
+        tab = torch.from_numpy(table).to(q.hidden.device)
+        emitted = [0] * n
+        finished = False
+        while not finished:
+            count, done, finished = q.advance()
+            plan, emitted = stream_plan(emitted, count, done, chunk, halo)
+            if not plan:
+                continue
+            wins = [(i * q.cap + lo, hi - lo, a - lo, hi - b) for i, a, b, lo, hi, _ in plan]
+            wav, lens = voc.run_latent_windows_torch(q.hidden, wins, tab, [int(index[i]) for i, *_ in plan])
+            wav = wav.cpu().numpy()
+            off = 0
+            for (i, a, b, lo, hi, last), ln in zip(plan, lens):
+                # the piece's own samples; the window's kept range is exactly that unless halo == 0 left a cut without a halo
+                # frame (an untrimmed end carries the 15 + 15 samples of the post activation's padding)
+                s0 = a * hop + 15 if a else 0
+                s1 = b * hop + (30 if last else 15)
+                k0 = lo * hop + ((a - lo) * hop + 15 if a > lo else 0)
+                yield i, s0, wav[off + s0 - k0:off + s1 - k0].copy(), last
+                off += ln
+
+
 class IndexGPT:
     def __init__(self, cfg: IndexGPTConfig, state: Optional[dict] = None, *, blob: Optional[np.ndarray] = None,
                  blob_device=None, dtype: str = "f32", device: int = 0):
@@ -493,6 +640,27 @@ class IndexGPT:
                                             int(c.penalty_range if penalty_range is None else penalty_range), cap, sa)
         res = [(toks[i, : cnt[i]].copy(), hid[i, : cnt[i]].copy()) for i in range(n)]
         return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
+
+    def queue_session(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
+                      device: bool = False) -> QueueSession:
+        """``generate_queue`` as a session that hands out rows as they appear: arguments as there; returns a ``QueueSession``
+        (a context manager) whose ``advance()`` runs one round.  device=True keeps tokens / hidden as torch tensors on the
+        engine's device (``BigVGANVocoder.run_latent_windows_torch`` reads the rows where they lie).  While the session is open
+        the other decode entries of this engine raise (MI_ESTATE)."""
+        c = self.cfg
+        n = len(prompts)
+        if n < 1 or len(max_new) != n:
+            raise ValueError(f"{n} prompts and {len(max_new)} limits: queue_session needs one limit per sentence, n >= 1")
+        samp = _batch_sampling(sampling, n)
+        ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
+        rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
+        cat = np.ascontiguousarray(np.concatenate(ps, axis=0))
+        mx = np.ascontiguousarray([int(m) for m in max_new], dtype=np.int32)
+        cap = max(int(mx.max()), 1)
+        stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
+        sa = None if samp is None else _sampling_arrays(samp)
+        return QueueSession(self, cat, rows, mx, stops, float(c.repeat_penalty if repeat_value is None else repeat_value),
+                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa, device)
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
                              repeat_value=None, penalty_range=None, sampling=None, beams: int = 1):

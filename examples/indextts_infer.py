@@ -26,7 +26,9 @@ through `--slots` batch slots (default 8, 1..64) — a slot is refilled as soon 
 together share one pass over the weights — and `run_latent_ragged` vocodes them in one forward, in order, with the same gap.
 Every queued sentence starts from a FRESH penalty vector: the sentences run concurrently, so the carry of the vector from one
 sentence to the next that the sentence-by-sentence forms keep (like the reference) does not exist there.  Sampling flags apply
-(one seed per sentence: sample-seed + its index); beams and takes do not go through the queue.
+(one seed per sentence: sample-seed + its index); takes do not go through the queue.  `--queue --num-beams N` is beam search
+through the queue: every sentence runs as a group of N slots, the queue schedules the `--slots` // N groups, and with `--stream`
+a sentence's audio leaves whole, as soon as its group is retired, while the other groups decode.
 With `--queue`, `--prompt a.wav,b.wav,...` is a dialogue: graph A runs once per file, sentence i is spoken by voice i mod V (or by
 `--voice-of 0,1,1,0,...`, one index per sentence), every sentence's prompt carries its own voice's conditioning rows, and ONE
 `run_latent_voices` call vocodes all of them in order, whatever the mix of voices.  One prompt file is the one-voice case of the
@@ -138,10 +140,12 @@ def parse_args(argv=None):
             ap.error(f"--voice-of indices must be in 0..{len(args.prompts) - 1} (one --prompt file per voice)")
     if not 1 <= args.slots <= MAX_SLOTS:
         ap.error(f"--slots must be in 1..{MAX_SLOTS} (the engine's batch slots)")
-    if args.queue and (args.takes > 1 or args.num_beams > 1 or args.device_type == "cuda"):
-        ap.error("--queue uses the host-array queue call (generate_queue): no --takes, no --num-beams, --device-type cpu")
+    if args.queue and (args.takes > 1 or args.device_type == "cuda"):
+        ap.error("--queue uses the host-array queue call (generate_queue): no --takes, --device-type cpu")
     if not 1 <= args.num_beams <= 8:
         ap.error("--num-beams must be in 1..8")
+    if args.queue and args.num_beams > args.slots:
+        ap.error("--queue --num-beams N runs every sentence in a group of N slots: --slots must be at least N")
     if not 1 <= args.takes <= MAX_SLOTS:
         ap.error(f"--takes must be in 1..{MAX_SLOTS} (the engine's batch slots)")
     args.sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
@@ -198,10 +202,12 @@ def main():
             budgets.append(max(gcfg.max_generate_length - int(prompt_len[0]), 0))
         t_dec = time.time()
         q_sampling = [dataclasses.replace(take_sampling[0], seed=take_sampling[0].seed + i) for i in range(len(prompts))] if sampled else None
+        q_beams = args.num_beams if args.num_beams > 1 else None     # a sentence in a group of N slots, the queue over slots // N groups
         if args.stream:
             chunks, t_first = {}, None
             for i, first_sample, chunk, last in stream_synthesize(gpt, voc, prompts, budgets, [c for c, _ in speakers], voice_of,
-                                                                  chunk=args.chunk, halo=args.halo, stop_tokens=stops, sampling=q_sampling):
+                                                                  chunk=args.chunk, halo=args.halo, stop_tokens=stops, sampling=q_sampling,
+                                                                  beams=q_beams):
                 if t_first is None:
                     t_first = time.time() - t_dec
                 assert first_sample == sum(c.size for c in chunks.get(i, []))
@@ -215,7 +221,9 @@ def main():
                 pieces.append(np.concatenate([np.concatenate(chunks[i]).reshape(1, 1, -1), gap], axis=-1))
             results = []
         else:
-            results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, return_stats=True)
+            results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, beams=q_beams,
+                                                  return_stats=True)
+            results = [r[:2] for r in results]                       # (tokens, hidden[, score])
             n_codes = sum(h.shape[0] for _, h in results)
             print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "
                   f"{gcfg.max_batch} slots: {q_stats['steps']} decode steps, {q_stats['passes']} prompt passes)")

@@ -449,8 +449,9 @@ int         mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const 
  *
  * While a session is open every other entry on the handle that would touch the slots returns MI_ESTATE: mi_gpt_step,
  * mi_gpt_generate*, mi_gpt_kv_write, mi_gpt_reset, mi_gpt_bench_pick and a second mi_gpt_queue_begin; advance / end without a
- * session return MI_ESTATE too.  Beam search does not go through a session: hypothesis 0's rows are gathered along its ancestors
- * at the end, so no row of it is final before that.                                                                          */
+ * session return MI_ESTATE too; all of this covers mi_gpt_generate_queue_beam and mi_gpt_queue_begin_beam as well.  Beam search
+ * goes through a session opened by mi_gpt_queue_begin_beam (below): hypothesis 0's rows are gathered along its ancestors when its
+ * sentence ends, so no row of a sentence is final before that, and count[i] stays 0 until sentence i is retired.             */
 int         mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                                const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
                                float* hidden, int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p,
@@ -458,6 +459,37 @@ int         mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int
 int         mi_gpt_queue_advance(mi_gpt* h, int32_t* count /* host, n */, int32_t* done /* host, n */, int32_t* finished /* host, 1 */,
                                  int32_t* stats /* host, 2 ints, or NULL */);
 int         mi_gpt_queue_end(mi_gpt* h);
+
+/* ---- beam search through the sentence queue: a sentence runs as a group, B = num_beams hypotheses in B consecutive slots, and
+ * the queue schedules groups where it schedules slots above.  The beam search is the one defined under "beam search" in every
+ * respect (selection 0, selection n, the end rule, ties, no finished pool, no length penalty).
+ *
+ * mi_gpt_generate_queue_beam: arguments and validation of mi_gpt_generate_queue without the sampling arrays (beams and sampling
+ * do not combine), plus mi_gpt_generate_beam's checks on num_beams: 1..8, at most mel_codes, at most max_batch.  All of it runs
+ * before anything is launched: MI_EINVAL, with the handle still usable.  scores (n) or NULL follows `mem`.  Per sentence the
+ * result is what mi_gpt_generate_beam gives for that sentence alone from a penalty vector of ones: hypothesis 0's tokens, its
+ * last_hidden_state rows along its own path, and its score.  The decode steps are the same launches; the prompt pass differs
+ * from the one-by-one pass in GEMM tiling only, as for the greedy queue; there is no repeat_penality argument and no write-back,
+ * for the reason given there.  num_beams == 1 gives the tokens of mi_gpt_generate_queue.
+ *
+ * Policy (mi355tts.indextts.queue_schedule(..., beams=B), i.e. with slots = max_batch / B, is its host model).  G = min(max_batch
+ * / B, n) groups; group g is slots gB .. gB + B - 1; slots beyond G * B are never run and the decode step runs over G * B rows.
+ * Steps 1-3 are the ones above with "slot" read as "group": admission in index order into the lowest free group, a pass ending
+ * at the first sentence whose rows would push it past max_seq packed rows; retire, then refill before the next decode step; runs
+ * of c = min(16, nearest limit of a live group) beam decode steps over the G groups.  A pass stores each prompt's keys and values
+ * once, in its group's first slot, and selection 0 of all the groups it admitted is one launch.  Every group retiring in a round
+ * leaves in one launch (tokens, rows and score, along the ancestor table) ahead of the pass that refills it.  stats: as above.
+ *
+ * mi_gpt_queue_begin_beam: the same arguments; it opens the kind of session mi_gpt_queue_advance / mi_gpt_queue_end drive, and
+ * `scores` stays the caller's until mi_gpt_queue_end like tokens and hidden.  count[i] is 0 until sentence i is retired, then it
+ * is its n_out with done[i] = 1: its tokens, rows and score all leave in that round.                                         */
+int         mi_gpt_generate_queue_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                       const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                                       int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores /* (n) or NULL */,
+                                       int mem, int32_t* stats /* host, 2 ints or NULL */);
+int         mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                    const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                                    int32_t* tokens, float* hidden, int cap, float* scores /* (n) or NULL */, int mem);
 
 /* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
  * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these

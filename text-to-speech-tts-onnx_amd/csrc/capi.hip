@@ -1032,8 +1032,14 @@ int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const
 // soon as its sentence stops, every prompt pass packed (Gpt::forward_packed).  The policy is the header's, step by step.  The
 // loop lives in a session (mi_gpt_queue_begin / _advance / _end) that stops after every run of decode steps; the blocking entry
 // is a session driven to its end inside one call.
+// With beams (B != 0; the "_beam" entries) the unit of the schedule is a group: sentence -> B consecutive slots, group g = slots
+// gB .. gB + B - 1, S = min(max_batch / B, n) groups; owner / live / the policy's "slot" count groups.  B == 0 is the greedy or
+// sampled queue and launches exactly what it launched before groups existed.
 struct GptQueue {
     int n = 0, cap = 0, mem = MI_HOST, S = 0, penalty_range = 0;
+    int B = 0;                       // beams per sentence, 0 = no beam search
+    float* scores = nullptr;         // beams: the caller's (n) scores or null, alive until the session ends
+    std::vector<float> h_sc;         // MI_HOST: the scores of a round, on the host
     bool any_samp = false;
     bool per_round = false;          // sessions: tokens and rows leave after every round; blocking entry: at retirement only
     bool ended = false;              // the loop has run out: nothing live, nothing waiting
@@ -1059,8 +1065,13 @@ static void gpt_queue_free(GptQueue* q) { delete q; }
 static void gpt_queue_setup(Gpt& e, GptQueue& q, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                             const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
                             int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
-                            const std::string& who) {
+                            const std::string& who, int B = 0, float* scores = nullptr) {
     const GptCfg& c = e.cfg;
+    if (B) {                                                     // mi_gpt_generate_beam's checks on num_beams
+        MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
+        MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
+        MI_REQUIRE(B <= c.max_batch, who + ": num_beams exceeds the handle's max_batch");
+    }
     MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
     MI_REQUIRE(prompts && prompt_rows && max_new && cap >= 1, who + ": null argument");
     q.stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
@@ -1069,6 +1080,7 @@ static void gpt_queue_setup(Gpt& e, GptQueue& q, int n, const float* prompts, co
     gpt_check_lengths(c, n, prompt_rows, max_new, cap, who);
     q.n = n; q.cap = cap; q.mem = mem; q.penalty_range = penalty_range;
     q.prompts = prompts; q.tokens = tokens; q.hidden = hidden;
+    q.B = B; q.scores = scores;
     q.prompt_rows.assign(prompt_rows, prompt_rows + n);
     q.max_new.assign(max_new, max_new + n);
     q.row0.resize(n);
@@ -1079,10 +1091,12 @@ static void gpt_queue_setup(Gpt& e, GptQueue& q, int n, const float* prompts, co
     for (int i = 0; i < (int)q.recs.size(); ++i) q.recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
     hipStream_t s = e.stream;
     e.set_rep_value(repeat_value);
-    q.S = std::min(c.max_batch, n);
+    const int W = B ? B : 1;                                     // slots per unit of the schedule
+    q.S = std::min(c.max_batch / W, n);
+    if (B) e.beam_ensure();
     // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
-    q.all.assign((size_t)q.S * GS_WORDS, 0);
-    for (int b = 0; b < q.S; ++b) q.all[(size_t)b * GS_WORDS + GS_DONE] = 1;
+    q.all.assign((size_t)q.S * W * GS_WORDS, 0);
+    for (int b = 0; b < q.S * W; ++b) q.all[(size_t)b * GS_WORDS + GS_DONE] = 1;
     MI_HIP(hipMemcpyAsync(e.state.p, q.all.data(), q.all.size() * 4, hipMemcpyHostToDevice, s));
     MI_HIP(hipStreamSynchronize(s));
     q.owner.assign(q.S, -1);
@@ -1128,12 +1142,78 @@ static void gpt_queue_flush(Gpt& e, GptQueue& q) {
     q.n_tab = 0;
 }
 
+// beams: sentence i, held by the group whose first slot is `slot`, joins the round's retirement table with all its nt tokens
+static void gpt_queue_note_beam(GptQueue& q, int slot, int i, int nt) {
+    MI_REQUIRE(q.n_tab < GPT_MAX_BATCH, "gpt queue: retirement table overflow");
+    Gpt::OutSeg& g = q.tab.e[q.n_tab++];
+    g.slot = slot; g.first = 0; g.count = nt; g.sentence = i;
+    g.dst_row = (int64_t)i * q.cap;
+    q.copied[i] = nt;
+}
+
+// beams: every group of the table leaves in one launch (Gpt::beam_out_rows): hypothesis 0's tokens and rows along its ancestors,
+// and its score.  MI_DEVICE: straight into the caller's arrays.  MI_HOST: packed into the staging buffers, one device-to-host
+// copy per array, then placed by the host (synchronises), as gpt_queue_flush does.
+static void gpt_queue_flush_beam(Gpt& e, GptQueue& q) {
+    if (q.n_tab == 0) return;
+    const int h = e.cfg.hidden;
+    if (q.mem == MI_DEVICE) {
+        e.beam_out_rows(q.tab, q.n_tab, q.B, q.tokens, q.hidden, q.scores);
+    } else {
+        Gpt::OutTable packed = q.tab;
+        size_t rows = 0;
+        for (int k = 0; k < q.n_tab; ++k) {
+            packed.e[k].dst_row = (int64_t)rows; packed.e[k].sentence = k;
+            rows += (size_t)q.tab.e[k].count;
+        }
+        e.io_a.ensure(rows * 4); e.io_b.ensure(rows * h * 4); e.io_s.ensure((size_t)q.n_tab * 4);
+        q.h_tok.resize(rows); q.h_hid.resize(rows * h); q.h_sc.resize(q.n_tab);
+        e.beam_out_rows(packed, q.n_tab, q.B, q.tokens ? e.io_a.as<int32_t>() : nullptr, q.hidden ? e.io_b.as<float>() : nullptr,
+                        q.scores ? e.io_s.as<float>() : nullptr);
+        if (q.tokens && rows) MI_HIP(hipMemcpyAsync(q.h_tok.data(), e.io_a.p, rows * 4, hipMemcpyDeviceToHost, e.stream));
+        if (q.hidden && rows) MI_HIP(hipMemcpyAsync(q.h_hid.data(), e.io_b.p, rows * h * 4, hipMemcpyDeviceToHost, e.stream));
+        if (q.scores) MI_HIP(hipMemcpyAsync(q.h_sc.data(), e.io_s.p, (size_t)q.n_tab * 4, hipMemcpyDeviceToHost, e.stream));
+        MI_HIP(hipStreamSynchronize(e.stream));
+        for (int k = 0; k < q.n_tab; ++k) {
+            const Gpt::OutSeg& g = q.tab.e[k];
+            const size_t src = (size_t)packed.e[k].dst_row, dst = (size_t)g.dst_row;
+            if (q.tokens) std::memcpy(q.tokens + dst, q.h_tok.data() + src, (size_t)g.count * 4);
+            if (q.hidden) std::memcpy(q.hidden + dst * h, q.h_hid.data() + src * h, (size_t)g.count * h * 4);
+            if (q.scores) q.scores[g.sentence] = q.h_sc[k];
+        }
+    }
+    q.n_tab = 0;
+}
+
+// beams: the B slots of a refilled group get the sentence's state words, the group's first slot its side-0 penalty row of ones
+// (selection 0 reads side 0: GS_NDEC = 0), both in stream order behind the retirement launch of the tenant before.  Nothing
+// else of that tenant can be read (checked against gpt_beam.hip):
+//   - ancestor tables: selection n copies entries [0, nprev = n) from the side it reads and writes entry n, so from nprev = 0
+//     on every entry below n of the side in use was written by this sentence; attention, the reset lookup and retirement read
+//     entries below GS_NDEC only;
+//   - scores: selection 0 (`first`) starts every candidate from 0 and never adds the scores it loaded;
+//   - penalties: selection 0 reads the first slot's side-0 row alone (parent 0) and writes all B rows of side 1; selection 1
+//     reads those and writes all B rows of side 0: side 1, and rows 1 .. B-1 of side 0, are written before they are read;
+//   - toks / hid: selection n writes row n of every slot of the group before GS_NDEC becomes n + 1, and every read is of a
+//     row below GS_NDEC, so a stale row lies at an index >= ndec;
+//   - the KV cache: the pass rewrites the prompt's rows in the first slot, a decode step writes position P + n - 1 of its own
+//     slot before its attention reads it, and no key at or beyond the history is visited.
+static void gpt_queue_admit_group(Gpt& e, GptQueue& q, int slot, int i) {
+    const std::vector<int32_t> w = gpt_state_words(q.stops, q.penalty_range, q.max_new[i], false);
+    std::vector<int32_t> ws((size_t)q.B * GS_WORDS);
+    for (int b = 0; b < q.B; ++b) std::copy(w.begin(), w.end(), ws.begin() + (size_t)b * GS_WORDS);
+    MI_REQUIRE(slot >= 0 && slot + q.B <= e.cfg.max_batch, "gpt queue: group slot");
+    MI_HIP(hipMemcpyAsync(e.state.as<int32_t>() + (size_t)slot * GS_WORDS, ws.data(), ws.size() * 4, hipMemcpyHostToDevice, e.stream));
+    MI_HIP(hipStreamSynchronize(e.stream));                      // `ws` is done with
+    e.reset_penalty(slot);
+}
+
 // One round of the policy: admit and retire until nothing more can be admitted, then one run of c <= 16 decode steps and a look
 // at the states.  Returns false when there was nothing left to decode (the queue has ended).
 static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
     const GptCfg& c = e.cfg;
     hipStream_t s = e.stream;
-    const int n = q.n, S = q.S;
+    const int n = q.n, S = q.S, B = q.B, W = B ? B : 1;          // S units (slots, or groups of B slots), unit u = slots uW ..
     const hipMemcpyKind in = q.mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     std::vector<int32_t>& all = q.all;
     std::vector<int>& owner = q.owner;
@@ -1147,12 +1227,17 @@ static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
             while (q.live < S && q.next < n) {
                 const int rows = q.prompt_rows[q.next];
                 if (k > 0 && total + rows > c.max_seq) break;        // the first sentence of a pass always fits
-                int slot = 0;
-                while (owner[slot] >= 0) ++slot;
-                owner[slot] = q.next; ++q.live;
-                e.set_state(gpt_state_words(q.stops, q.penalty_range, q.max_new[q.next], false), slot);
-                e.reset_penalty(slot);
-                if (q.any_samp) e.set_sampling_slot(&q.recs[q.next], slot);
+                int unit = 0;
+                while (owner[unit] >= 0) ++unit;
+                owner[unit] = q.next; ++q.live;
+                const int slot = unit * W;
+                if (B) {
+                    gpt_queue_admit_group(e, q, slot, q.next);
+                } else {
+                    e.set_state(gpt_state_words(q.stops, q.penalty_range, q.max_new[q.next], false), slot);
+                    e.reset_penalty(slot);
+                    if (q.any_samp) e.set_sampling_slot(&q.recs[q.next], slot);
+                }
                 MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, q.prompts + q.row0[q.next] * c.hidden,
                                       (size_t)rows * c.hidden * 4, in, s));
                 segs[k].first = total; segs[k].rows = rows; segs[k].slot = slot; segs[k].pad = 0;
@@ -1167,12 +1252,14 @@ static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
         if (ran) gpt_read_states(e, all);
         // 2. retire every finished slot: its tokens and rows go out, the slot is free
         bool freed = false;
-        for (int b = 0; b < S; ++b) {
-            const int i = owner[b];
+        for (int u = 0; u < S; ++u) {
+            const int i = owner[u], b = u * W;
             if (i < 0 || !all[(size_t)b * GS_WORDS + GS_DONE]) continue;
             const int nt = std::min(all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[i]);
             q.n_out[i] = nt;
-            if (q.per_round) {
+            if (B) {
+                gpt_queue_note_beam(q, b, i, nt);                // the whole sentence: no row of it was final before
+            } else if (q.per_round) {
                 gpt_queue_note(q, b, i, nt);                     // what the rounds before have not moved yet
             } else {
                 copy_out(q.tokens ? q.tokens + (size_t)i * q.cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)nt * 4, q.mem, s);
@@ -1180,38 +1267,54 @@ static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
                          (size_t)nt * c.hidden * 4, q.mem, s);
             }
             q.retired[i] = 1;
-            owner[b] = -1; --q.live;
+            owner[u] = -1; --q.live;
             freed = true;
         }
-        if (q.per_round) gpt_queue_flush(e, q);                  // in stream order before a pass can refill the slots
+        if (B) gpt_queue_flush_beam(e, q);                       // in stream order before a pass can refill the groups
+        else if (q.per_round) gpt_queue_flush(e, q);             // in stream order before a pass can refill the slots
         if (freed && q.next < n) continue;                       // refill before the next decode step
         // 3. finish, or decode up to the nearest limit (at most 16 steps) and look again
         if (q.live == 0) { q.ended = true; return false; }
         int cs = 16;
-        for (int b = 0; b < S; ++b)
-            if (owner[b] >= 0) cs = std::min(cs, q.max_new[owner[b]] - all[(size_t)b * GS_WORDS + GS_NDEC]);
+        for (int u = 0; u < S; ++u)
+            if (owner[u] >= 0) cs = std::min(cs, q.max_new[owner[u]] - all[(size_t)u * W * GS_WORDS + GS_NDEC]);
         MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
-        e.decode_batch_steps(S, cs);
+        if (B) e.decode_beam_steps(S, B, cs);
+        else e.decode_batch_steps(S, cs);
         q.steps += cs;
         gpt_read_states(e, all);
         return true;
     }
 }
 
-int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
-                          const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
-                          float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
-                          const float* top_p, const uint64_t* seeds, int32_t* stats) {
+// the handle runs beam groups (forward_rows / forward_packed leave the token choice to selection 0) until the scope ends
+struct GptBeamScope {
+    Gpt& e;
+    GptBeamScope(Gpt& g, int B) : e(g) { e.beams = B; }
+    ~GptBeamScope() { e.beams = 0; }
+};
+
+// the blocking entries: a session driven to its end inside one call (num_beams == 0: no beam search)
+static int gpt_generate_queue_impl(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                   const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
+                                   float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
+                                   const float* top_p, const uint64_t* seeds, int32_t* stats, const char* name, bool beam,
+                                   int num_beams, float* scores) {
     return guard([&] {
-        const std::string who = "mi_gpt_generate_queue";
-        GPT_CHECK(h, mem, "mi_gpt_generate_queue");
-        GPT_NO_SESSION(h, "mi_gpt_generate_queue");
+        const std::string who = name;
+        MI_REQUIRE(h && h->impl, who + ": null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+        MI_HIP(hipSetDevice(h->impl->device));
+        GPT_NO_SESSION(h, who);
         Gpt& e = *h->impl;
         MI_REQUIRE(n_out != nullptr, who + ": null argument");
+        MI_REQUIRE(!beam || num_beams >= 1, who + ": num_beams must be in [1, 8]");
         GptQueue q;
         gpt_queue_setup(e, q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap, mem,
-                        temperature, top_k, top_p, seeds, who);
+                        temperature, top_k, top_p, seeds, who, beam ? num_beams : 0, scores);
         GptModeScope mode(e, q.any_samp);
+        GptBeamScope group(e, q.B);
         while (gpt_queue_round(e, q, who)) {}
         for (int i = 0; i < n; ++i) n_out[i] = q.n_out[i];
         e.history = q.all[GS_HIST];
@@ -1220,20 +1323,55 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
     });
 }
 
-int mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
-                       const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
-                       int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds) {
+int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                          const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
+                          float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const uint64_t* seeds, int32_t* stats) {
+    return gpt_generate_queue_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden,
+                                   cap, n_out, mem, temperature, top_k, top_p, seeds, stats, "mi_gpt_generate_queue", false, 0, nullptr);
+}
+
+int mi_gpt_generate_queue_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                               const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                               int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem, int32_t* stats) {
+    return gpt_generate_queue_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden,
+                                   cap, n_out, mem, nullptr, nullptr, nullptr, nullptr, stats, "mi_gpt_generate_queue_beam", true,
+                                   num_beams, scores);
+}
+
+static int gpt_queue_begin_impl(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
+                                float* hidden, int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p,
+                                const uint64_t* seeds, const char* name, bool beam, int num_beams, float* scores) {
     return guard([&] {
-        const std::string who = "mi_gpt_queue_begin";
-        GPT_CHECK(h, mem, "mi_gpt_queue_begin");
-        GPT_NO_SESSION(h, "mi_gpt_queue_begin");
+        const std::string who = name;
+        MI_REQUIRE(h && h->impl, who + ": null handle");
+        std::lock_guard<std::mutex> lk_(h->mu);
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+        MI_HIP(hipSetDevice(h->impl->device));
+        GPT_NO_SESSION(h, who);
         Gpt& e = *h->impl;
+        MI_REQUIRE(!beam || num_beams >= 1, who + ": num_beams must be in [1, 8]");
         std::unique_ptr<GptQueue> q(new GptQueue);
         gpt_queue_setup(e, *q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
-                        mem, temperature, top_k, top_p, seeds, who);
+                        mem, temperature, top_k, top_p, seeds, who, beam ? num_beams : 0, scores);
         q->per_round = true;
         h->session = q.release();
     });
+}
+
+int mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                       const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
+                       int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds) {
+    return gpt_queue_begin_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
+                                mem, temperature, top_k, top_p, seeds, "mi_gpt_queue_begin", false, 0, nullptr);
+}
+
+int mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                            const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                            int32_t* tokens, float* hidden, int cap, float* scores, int mem) {
+    return gpt_queue_begin_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
+                                mem, nullptr, nullptr, nullptr, nullptr, "mi_gpt_queue_begin_beam", true, num_beams, scores);
 }
 
 int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* finished, int32_t* stats) {
@@ -1248,8 +1386,10 @@ int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* fini
         GptQueue& q = *h->session;
         if (!q.ended) {
             GptModeScope mode(e, q.any_samp);
-            if (gpt_queue_round(e, q, who)) {
-                // everything the live slots hold by now, finished ones included (they are retired by the next round)
+            GptBeamScope group(e, q.B);
+            if (gpt_queue_round(e, q, who) && !q.B) {
+                // everything the live slots hold by now, finished ones included (they are retired by the next round).  With beams
+                // nothing leaves here: no row of a live group is final, the whole sentence leaves when its group is retired.
                 for (int b = 0; b < q.S; ++b)
                     if (q.owner[b] >= 0)
                         gpt_queue_note(q, b, q.owner[b], std::min(q.all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[q.owner[b]]));
@@ -1264,7 +1404,8 @@ int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* fini
             const int i = q.owner[b];
             if (i < 0) continue;
             count[i] = q.copied[i];
-            done[i] = q.all[(size_t)b * GS_WORDS + GS_DONE] != 0;
+            // beams: unit b is a group, and a finished group is done for the caller once it has been retired (count = n_out)
+            done[i] = q.B ? 0 : q.all[(size_t)b * GS_WORDS + GS_DONE] != 0;
             fin = fin && done[i];
         }
         *finished = fin ? 1 : 0;

@@ -39,7 +39,7 @@ struct Gpt {
     int MBp = 1;              // max_batch rounded up to a batched-GEMV template width (<= 16) or to a multiple of 16 (above)
     // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams)
     std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;
-    DevBuf io_a, io_b;        // host<->device staging
+    DevBuf io_a, io_b, io_s;  // host<->device staging (io_s: scores of a queue round)
     DevBuf rep_dev;           // REPEAT_PENALITY as a device scalar (read by gpt_pick_kernel, also inside replayed graphs)
     void set_rep_value(float v);
     int history = 0;          // host mirror of state[GS_HIST] (valid outside generate())
@@ -55,7 +55,7 @@ struct Gpt {
     // slots.  What follows a hypothesis from slot to slot exists twice, the side in use being GS_NDEC & 1: the penalty vectors
     // (side 0 = pen, side 1 = pen_b) and the ancestor table anc[side][slot][n] = the slot inside the group that held this
     // hypothesis' ancestor after selection n — the cache row, token and last_hidden_state row of step n are read from there.
-    int beams = 0;            // 0 outside mi_gpt_generate_beam; forward_rows then leaves the token choice to the caller
+    int beams = 0;            // 0 outside the beam entries; forward_rows / forward_packed then leave the token choice to selection 0
     DevBuf pen_b, anc, score; // allocated by the first beam call
     void beam_ensure();
     void beam_select_first(int group, int B, int rows);                               // selection 0 after a prompt pass
@@ -63,6 +63,9 @@ struct Gpt {
     void decode_beam_steps(int nb, int B, int n);
     // hypothesis 0 of every group, gathered along its ancestors: tokens (nb, cap), hidden (nb, cap, hidden), device arrays
     void beam_gather(int nb, int B, int32_t* tokens, float* hidden, int cap);
+    // the sentence queue with beams: selection 0 of the k groups of the packed pass just run (their segments are in segtab), in
+    // one launch; retirement of the table's groups along their ancestor tables, with hypothesis 0's scores, in one launch
+    void beam_select_segs(int k, int B);
     hipGraphExec_t step_graph[2] = {nullptr, nullptr};      // by mode
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under
@@ -95,6 +98,7 @@ struct Gpt {
     struct OutSeg { int32_t slot, first, count, sentence; int64_t dst_row; };
     struct OutTable { OutSeg e[GPT_MAX_BATCH]; };
     void copy_out_rows(const OutTable& tab, int n, int32_t* tokens_dst, float* hidden_dst);
+    void beam_out_rows(const OutTable& tab, int n, int B, int32_t* tokens_dst, float* hidden_dst, float* score_dst);   // gpt_beam.hip
     // one layer's K / V cache of a slot (bytes; slots are slot_cache_elems() elements apart)
     struct LayerKV { char *k, *v; };
     LayerKV layer_cache(int layer, int slot = 0) {

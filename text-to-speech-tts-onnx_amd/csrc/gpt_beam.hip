@@ -177,23 +177,21 @@ __global__ __launch_bounds__(1024) void gpt_beam_select_rows_kernel(const float*
     }
 }
 
-// The decode step's selection: group = group0 + blockIdx.x, slots group * B .. + B - 1.  pen0 / pen1 and anc0 / anc1 are the two
-// sides of what moves with a hypothesis; the side read is GS_NDEC & 1, the other one is written.  rows = new cache rows of the
-// forward pass before (the prompt's for selection 0, else 1).  Every index that comes out of memory is clamped before it forms
-// an address.
-__global__ __launch_bounds__(1024) void gpt_beam_step_kernel(const float* __restrict__ logits, float* pen0, float* pen1,
-                                                             const float* __restrict__ last, int* st, int* toks,
-                                                             float* __restrict__ hid, int* anc0, int* anc1, float* scores,
-                                                             int codes, int hidden, int rows, const float* __restrict__ rep_dev,
-                                                             int max_tok, const float* __restrict__ emb,
-                                                             const float* __restrict__ pos, int max_pos, float* __restrict__ xb,
-                                                             int B, int first, int group0) {
+// One selection of the group whose first slot is s0, by the whole workgroup: the body of the two kernels below.  pen0 / pen1 and
+// anc0 / anc1 are the two sides of what moves with a hypothesis; the side read is GS_NDEC & 1, the other one is written.  rows =
+// new cache rows of the forward pass before (the prompt's for selection 0, else 1).  Every index that comes out of memory is
+// clamped before it forms an address.
+__device__ __forceinline__ void beam_step_body(const float* __restrict__ logits, float* pen0, float* pen1,
+                                               const float* __restrict__ last, int* st, int* toks, float* __restrict__ hid,
+                                               int* anc0, int* anc1, float* scores, int codes, int hidden, int rows,
+                                               const float* __restrict__ rep_dev, int max_tok, const float* __restrict__ emb,
+                                               const float* __restrict__ pos, int max_pos, float* __restrict__ xb, int B,
+                                               int first, size_t s0) {
     __shared__ BeamShared sh;
     __shared__ int sw[GPT_BEAM_MAX][GS_WORDS];
     __shared__ float osc[GPT_BEAM_MAX];
     __shared__ int pw_t[GPT_BEAM_MAX], pw_r[GPT_BEAM_MAX], new_reset[GPT_BEAM_MAX], s_done;
     const int tid = threadIdx.x;
-    const size_t s0 = (size_t)(group0 + blockIdx.x) * B;          // the group's first slot
     if (tid < B * GS_WORDS) sw[tid / GS_WORDS][tid % GS_WORDS] = st[s0 * GS_WORDS + tid];
     if (tid < B) osc[tid] = scores[s0 + tid];
     const float repv = rep_dev[0];
@@ -270,6 +268,36 @@ __global__ __launch_bounds__(1024) void gpt_beam_step_kernel(const float* __rest
     }
 }
 
+// The decode step's selection: group = group0 + blockIdx.x, slots group * B .. + B - 1.
+__global__ __launch_bounds__(1024) void gpt_beam_step_kernel(const float* __restrict__ logits, float* pen0, float* pen1,
+                                                             const float* __restrict__ last, int* st, int* toks,
+                                                             float* __restrict__ hid, int* anc0, int* anc1, float* scores,
+                                                             int codes, int hidden, int rows, const float* __restrict__ rep_dev,
+                                                             int max_tok, const float* __restrict__ emb,
+                                                             const float* __restrict__ pos, int max_pos, float* __restrict__ xb,
+                                                             int B, int first, int group0) {
+    beam_step_body(logits, pen0, pen1, last, st, toks, hid, anc0, anc1, scores, codes, hidden, rows, rep_dev, max_tok, emb, pos,
+                   max_pos, xb, B, first, (size_t)(group0 + blockIdx.x) * B);
+}
+
+// Selection 0 of every group a packed prompt pass admitted, in one launch: workgroup q serves segment q of the pass's table
+// (Gpt::Seg as an int4: first packed row, rows, slot, pad), the one the pass's KV scatter and attention read.  The group is
+// slot / B — the groups of a pass need not be neighbours — and `rows` is the segment's.  A segment whose slot does not name a
+// whole group inside the handle's slots is left alone (block-uniform).
+__global__ __launch_bounds__(1024) void gpt_beam_first_segs_kernel(const int4* __restrict__ segs, const float* __restrict__ logits,
+                                                                   float* pen0, float* pen1, const float* __restrict__ last,
+                                                                   int* st, int* toks, float* __restrict__ hid, int* anc0,
+                                                                   int* anc1, float* scores, int codes, int hidden,
+                                                                   const float* __restrict__ rep_dev, int max_tok,
+                                                                   const float* __restrict__ emb, const float* __restrict__ pos,
+                                                                   int max_pos, float* __restrict__ xb, int B, int max_batch) {
+    const int4 g = segs[blockIdx.x];
+    const int group = g.z / B;
+    if (g.z < 0 || (group + 1) * B > max_batch) return;
+    beam_step_body(logits, pen0, pen1, last, st, toks, hid, anc0, anc1, scores, codes, hidden, min(max(g.y, 0), max_tok), rep_dev,
+                   max_tok, emb, pos, max_pos, xb, B, 1, (size_t)group * B);
+}
+
 // Decode-step attention of a hypothesis: gpt_attn1_body (gpt_attn.h) with the slot of every key / value row read from the
 // ancestor table.  blockIdx.y = slot; its group's first slot holds the prompt's rows.  A lane's key j >= P sits in slot
 // anc[j - P] of the group; the value rows of a pass take their slots from the lanes that hold the same keys.
@@ -306,6 +334,32 @@ __global__ __launch_bounds__(256) void gpt_beam_gather_kernel(const int* __restr
     if (hidden_out)
         for (int c = threadIdx.x; c < hidden; c += 256)
             hidden_out[((size_t)blockIdx.y * cap + n) * hidden + c] = hid[(src * max_tok + n) * hidden + c];
+}
+
+// Retirement of the queue's groups by table, in the style of gpt_copy_out_kernel and of the gather above: entry q = (slot = the
+// group's first slot, sentence, count, dst_row).  Token n and last_hidden_state row n of hypothesis 0 were stored by slot anc[n]
+// of the group, on the side GS_NDEC & 1 of the state the group still holds; they go to row dst_row + n of the destination arrays
+// and hypothesis 0's score to score_dst[sentence] (the caller's (n, cap) arrays and (n) scores, or packed staging buffers).  One
+// block per (row of the longest entry, entry); the table travels as a kernel argument.
+__global__ __launch_bounds__(256) void gpt_beam_out_kernel(Gpt::OutTable tab, const int* __restrict__ st,
+                                                           const int* __restrict__ anc0, const int* __restrict__ anc1,
+                                                           const int* __restrict__ toks, const float* __restrict__ hid,
+                                                           const float* __restrict__ score, int32_t* __restrict__ tokens_dst,
+                                                           float* __restrict__ hidden_dst, float* __restrict__ score_dst, int B,
+                                                           int max_tok, int hidden, int max_batch) {
+    const Gpt::OutSeg g = tab.e[blockIdx.y];
+    const int n = blockIdx.x;
+    if (g.slot < 0 || g.slot % B != 0 || g.slot + B > max_batch || g.sentence < 0) return;      // block-uniform
+    const size_t s0 = (size_t)g.slot;
+    if (n == 0 && threadIdx.x == 0 && score_dst) score_dst[g.sentence] = score[s0];
+    const int ndec = st[s0 * GS_WORDS + GS_NDEC];
+    if (n >= g.count || n >= ndec || n >= max_tok) return;
+    const int* anc = ((ndec & 1) ? anc1 : anc0) + s0 * max_tok;
+    const size_t src = s0 + min(max(anc[n], 0), B - 1);
+    const size_t dst = (size_t)(g.dst_row + n);
+    if (tokens_dst && threadIdx.x == 0) tokens_dst[dst] = toks[src * max_tok + n];
+    if (hidden_dst)
+        for (int c = threadIdx.x; c < hidden; c += 256) hidden_dst[dst * hidden + c] = hid[(src * max_tok + n) * hidden + c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -370,6 +424,36 @@ void Gpt::beam_gather(int nb, int B, int32_t* tokens, float* hidden, int cap) {
     hipLaunchKernelGGL(gpt_beam_gather_kernel, dim3(rows, nb), dim3(256), 0, stream, state.as<int>(), anc0,
                        anc0 + (size_t)MBp * cfg.max_seq, toks.as<int>(), hid.as<float>(), tokens, hidden, B, cfg.max_seq,
                        cfg.hidden, cap);
+    MI_HIP(hipGetLastError());
+}
+
+// selection 0 of the k groups whose segments forward_packed left in segtab, one launch
+void Gpt::beam_select_segs(int k, int B) {
+    const GptCfg& c = cfg;
+    MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX && B <= c.mel_codes && k >= 1 && k * B <= c.max_batch && pen_b.p && segtab.p,
+               "gpt beam: selection launch over a pass's segments");
+    int* anc0 = anc.as<int>();
+    hipLaunchKernelGGL(gpt_beam_first_segs_kernel, dim3(k), dim3(1024), 0, stream, segtab.as<int4>(), logits.as<float>(),
+                       pen.as<float>(), pen_b.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(), hid.as<float>(), anc0,
+                       anc0 + (size_t)MBp * c.max_seq, score.as<float>(), c.mel_codes, c.hidden, rep_dev.as<float>(), c.max_seq,
+                       mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, Xd.as<float>(), B, c.max_batch);
+    MI_HIP(hipGetLastError());
+}
+
+void Gpt::beam_out_rows(const OutTable& tab, int n, int B, int32_t* tokens_dst, float* hidden_dst, float* score_dst) {
+    MI_REQUIRE(n >= 0 && n <= GPT_MAX_BATCH && B >= 1 && B <= GPT_BEAM_MAX && pen_b.p, "gpt beam: retirement table");
+    int rows = 1;                                                 // the score leaves in row 0's block
+    for (int q = 0; q < n; ++q) {
+        const OutSeg& g = tab.e[q];
+        MI_REQUIRE(g.slot >= 0 && g.slot % B == 0 && g.slot + B <= cfg.max_batch && g.count >= 0 && g.count <= cfg.max_seq &&
+                       g.sentence >= 0 && g.dst_row >= 0, "gpt beam: retirement entry");
+        rows = std::max(rows, (int)g.count);
+    }
+    if (n == 0 || (!tokens_dst && !hidden_dst && !score_dst)) return;
+    const int* anc0 = anc.as<int>();
+    hipLaunchKernelGGL(gpt_beam_out_kernel, dim3(rows, n), dim3(256), 0, stream, tab, state.as<int>(), anc0,
+                       anc0 + (size_t)MBp * cfg.max_seq, toks.as<int>(), hid.as<float>(), score.as<float>(), tokens_dst, hidden_dst,
+                       score_dst, B, cfg.max_seq, cfg.hidden, cfg.max_batch);
     MI_HIP(hipGetLastError());
 }
 

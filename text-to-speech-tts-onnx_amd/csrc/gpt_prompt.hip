@@ -10,6 +10,8 @@
 //     attention body of gpt_attn.h, which gpt_attn_kernel (gpt.hip) runs for a lone prompt.  It never reads a cache row
 //     beyond rows_g: a refilled slot still holds the rows of the sentence before.
 // The tail (ln_f + final_norm + lm_head on each segment's last row, then the token choice) is forward_rows' own, per segment.
+// With beams (Gpt::beams != 0) a segment's slot is its group's first slot and the token choice is replaced by selection 0 of all
+// the pass's groups in one launch (gpt_beam_first_segs_kernel, gpt_beam.hip, over the same segment table).
 #include "gpt.h"
 #include "gpt_attn.h"
 #include "gpt_pick.h"
@@ -123,18 +125,21 @@ void Gpt::forward_packed(const Seg* segs, int k) {
     hipStream_t s = stream;
     const size_t es = dtype_size(dtype);
     MI_REQUIRE(segs && k >= 1 && k <= c.max_batch, "gpt: packed pass segments");
-    MI_REQUIRE(!beams, "gpt: the packed prompt pass does not serve beam search");
+    // beam search: a segment's slot is its group's first slot — the prompt's keys and values are stored once per sentence there
+    if (beams) MI_REQUIRE(beams <= GPT_BEAM_MAX && pen_b.p, "gpt: the packed prompt pass of a beam queue needs the beam state");
     int total = 0;
     uint64_t used = 0;                         // one bit per slot (GPT_MAX_BATCH = 64)
     for (int g = 0; g < k; ++g) {
         MI_REQUIRE(segs[g].first == total && segs[g].rows >= 1, "gpt: packed segments must be ascending and gap-free");
         MI_REQUIRE(segs[g].slot >= 0 && segs[g].slot < c.max_batch && !(used >> segs[g].slot & 1u), "gpt: packed segment slot");
+        MI_REQUIRE(!beams || (segs[g].slot % beams == 0 && segs[g].slot + beams <= c.max_batch), "gpt: packed segment group");
         used |= (uint64_t)1 << segs[g].slot;
         total += segs[g].rows;
         MI_REQUIRE(total <= S, "gpt: packed rows exceed the prompt scratch (max_seq)");
     }
     if (total == 1) {                          // linear() is the multi-row path: a lone one-row prompt is the single-row pass
         forward_rows(1, 1, segs[0].slot);
+        if (beams) beam_select_first(segs[0].slot / beams, beams, 1);        // as mi_gpt_generate_beam's one-by-one pass
         return;
     }
     const int lds = (((S + 3) & ~3) + 64 + 512 + 4) * 4;
@@ -184,8 +189,10 @@ void Gpt::forward_packed(const Seg* segs, int k) {
         gemv(head, xl, fn_w.as<float>(), fn_b.as<float>(), logits.as<float>() + (size_t)slot * c.mel_codes, MI_F32, ACT_NONE,
              nullptr, nullptr, nullptr, 0, lnf_w.as<float>(), lnf_b.as<float>(), last.as<float>() + (size_t)slot * h);
         // X still holds the other segments' rows: the token's graph C goes to the slot's batched decode row only
-        choose_token(segs[g].rows, slot, false);
+        if (!beams) choose_token(segs[g].rows, slot, false);
     }
+    // beam search: selection 0 of all admitted groups from the segment table the pass left on the device, one launch
+    if (beams) beam_select_segs(k, beams);
 }
 
 }  // namespace mi

@@ -160,6 +160,13 @@ def load() -> C.CDLL:
         L.mi_gpt_queue_begin.restype = C.c_int
         L.mi_gpt_queue_advance.argtypes = [vp, vp, vp, vp, vp]; L.mi_gpt_queue_advance.restype = C.c_int
         L.mi_gpt_queue_end.argtypes = [vp]; L.mi_gpt_queue_end.restype = C.c_int
+    if hasattr(L, "mi_gpt_generate_queue_beam"):
+        L.mi_gpt_generate_queue_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int,
+                                                 C.c_float, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), vp, C.c_int, vp]
+        L.mi_gpt_generate_queue_beam.restype = C.c_int
+        L.mi_gpt_queue_begin_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
+                                              C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+        L.mi_gpt_queue_begin_beam.restype = C.c_int
     L.mi_gpt_sample_logits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.mi_gpt_sample_logits.restype = C.c_int
     L.mi_gpt_generate_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,

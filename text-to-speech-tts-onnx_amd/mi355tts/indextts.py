@@ -95,14 +95,19 @@ def sample_logits(logits, *, temperature, top_k, top_p, seeds, positions, pen=No
     return (toks, u, probs) if return_probs else (toks, u)
 
 
-def queue_schedule(prompt_rows, max_new, lengths, slots, max_seq):
+def queue_schedule(prompt_rows, max_new, lengths, slots, max_seq, *, beams: int = 1):
     """Host model of ``mi_gpt_generate_queue``'s scheduling policy (include/mi355tts.h, "sentence queue") -> (steps, passes).
 
     prompt_rows / max_new: per sentence, as given to the entry; lengths: what each sentence actually produced (<= max_new; 0
     where max_new is 0); slots = the handle's max_batch; max_seq = the packed-row capacity of a prompt pass.  ``steps`` is
     the number of batched decode steps the entry launches (its stats[0]); ``passes`` lists every prompt pass as a list of
-    (sentence, slot) in packing order.  Pure host code: it documents the policy, feeds tools/gpt_queue_bench.py and is what the
+    (sentence, slot) in packing order.  beams = B: the schedule of the queue with beam search, which is this one over groups —
+    ``slots // B`` units, a pass entry naming (sentence, group), group g being slots gB .. gB + B - 1.  Pure host code: it documents the policy, feeds tools/gpt_queue_bench.py and is what the
     tests hold the entry's stats against."""
+    beams = int(beams)
+    if beams < 1:
+        raise ValueError("queue_schedule: beams must be >= 1")
+    slots = int(slots) // beams
     rows = [int(r) for r in prompt_rows]
     limit = [int(m) for m in max_new]
     length = [int(x) for x in lengths]
@@ -212,6 +217,42 @@ def beam_select(logits, prev_scores=None, *, beams: int, first: bool = False, pe
     return par.reshape(g, beams), tok.reshape(g, beams), sc.reshape(g, beams)
 
 
+def _check_queue_beams(beams, cfg, sampling):
+    """The ``beams`` keyword of the queue entries: None (no beam search) or an integer in [1, 8], not above the code count or the
+    engine's max_batch (one group must fit), and never together with ``sampling``."""
+    if beams is None:
+        return None
+    if isinstance(beams, bool) or int(beams) != beams or not 1 <= beams <= MAX_BEAMS:
+        raise ValueError(f"beams must be an integer in [1, {MAX_BEAMS}], got {beams}")
+    if sampling is not None:
+        raise ValueError("beams and sampling do not combine: beam search is deterministic")
+    if beams > cfg.mel_codes:
+        raise ValueError(f"beams = {beams} exceeds the {cfg.mel_codes} mel codes")
+    if beams > cfg.max_batch:
+        raise ValueError(f"{beams} beams need {beams} slots; this engine was created with max_batch = {cfg.max_batch}")
+    return int(beams)
+
+
+def _queue_beam_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, cap, beams):
+    """mi_gpt_generate_queue_beam on host arrays -> (tokens, hidden, counts, scores, stats).  What the entry rejects before
+    launching anything (MI_EINVAL) is a ValueError; the handle stays usable."""
+    n = int(rows.size)
+    toks = np.zeros((n, cap), np.int32)
+    hid = np.zeros((n, cap, cfg.hidden), np.float32)
+    cnt = np.zeros((n,), np.int32)
+    sc = np.zeros((n,), np.float32)
+    stats = np.zeros((2,), np.int32)
+    L = _lib.load()
+    rc = L.mi_gpt_generate_queue_beam(handle, n, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx),
+                                      stops.ctypes.data if stops.size else None, stops.size, repeat_value, penalty_range,
+                                      int(beams), toks.ctypes.data, hid.ctypes.data, cap, _lib.i32p(cnt), sc.ctypes.data,
+                                      _lib.MI_HOST, stats.ctypes.data)
+    if rc == _lib.MI_EINVAL:
+        raise ValueError("mi_gpt_generate_queue_beam: " + L.mi_last_error().decode("utf-8", "replace"))
+    _lib.check(rc, "mi_gpt_generate_queue_beam")
+    return toks, hid, cnt, sc, stats
+
+
 def _queue_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays):
     """mi_gpt_generate_queue on host arrays.  sampling_arrays: None or (temperature, top_k, top_p, seeds), an item of which may
     be None.  What the entry rejects before launching anything (MI_EINVAL) is a ValueError; the handle stays usable."""
@@ -236,9 +277,11 @@ class QueueSession:
     """An open sentence-queue session (include/mi355tts.h, mi_gpt_queue_begin / _advance / _end; made by
     ``IndexGPT.queue_session``).  ``tokens`` (n, cap) int32 and ``hidden`` (n, cap, hidden) float32 are numpy arrays, or torch
     tensors on the engine's device with device=True; after ``advance()`` the first count[i] entries of sentence i are valid and
-    final.  A context manager: leaving it ends the session (also before everything has finished)."""
+    final.  With ``beams`` (mi_gpt_queue_begin_beam) a sentence's count stays 0 until it is retired and is then all of it;
+    ``scores`` (n,) float32 holds hypothesis 0's score of every retired sentence (None without beams).  A context manager:
+    leaving it ends the session (also before everything has finished)."""
 
-    def __init__(self, gpt, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays, device):
+    def __init__(self, gpt, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays, device, beams=None):
         self._gpt = gpt
         self._open = False
         c = gpt.cfg
@@ -257,27 +300,36 @@ class QueueSession:
             self._stops = torch.from_numpy(stops).to(dev) if stops.size else None
             self.tokens = torch.zeros((n, cap), dtype=torch.int32, device=dev)
             self.hidden = torch.zeros((n, cap, c.hidden), dtype=torch.float32, device=dev)
+            self.scores = None if beams is None else torch.zeros((n,), dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()
             ptrs = (self._cat.data_ptr(), None if self._stops is None else self._stops.data_ptr(), self.tokens.data_ptr(),
-                    self.hidden.data_ptr())
+                    self.hidden.data_ptr(), None if beams is None else self.scores.data_ptr())
             mem = _lib.MI_DEVICE
         else:
             self._cat, self._stops = cat, stops
             self.tokens = np.zeros((n, cap), np.int32)
             self.hidden = np.zeros((n, cap, c.hidden), np.float32)
-            ptrs = (cat.ctypes.data, stops.ctypes.data if stops.size else None, self.tokens.ctypes.data, self.hidden.ctypes.data)
+            self.scores = None if beams is None else np.zeros((n,), np.float32)
+            ptrs = (cat.ctypes.data, stops.ctypes.data if stops.size else None, self.tokens.ctypes.data, self.hidden.ctypes.data,
+                    None if beams is None else self.scores.ctypes.data)
             mem = _lib.MI_HOST
-        rc = L.mi_gpt_queue_begin(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
-                                  penalty_range, ptrs[2], ptrs[3], cap, mem, *(None if a is None else a.ctypes.data for a in sa))
+        if beams is None:
+            name = "mi_gpt_queue_begin"
+            rc = L.mi_gpt_queue_begin(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
+                                      penalty_range, ptrs[2], ptrs[3], cap, mem, *(None if a is None else a.ctypes.data for a in sa))
+        else:
+            name = "mi_gpt_queue_begin_beam"
+            rc = L.mi_gpt_queue_begin_beam(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
+                                           penalty_range, int(beams), ptrs[2], ptrs[3], cap, ptrs[4], mem)
         if rc == _lib.MI_EINVAL:
-            raise ValueError("mi_gpt_queue_begin: " + L.mi_last_error().decode("utf-8", "replace"))
-        _lib.check(rc, "mi_gpt_queue_begin")
+            raise ValueError(name + ": " + L.mi_last_error().decode("utf-8", "replace"))
+        _lib.check(rc, name)
         self._open = True
 
     def advance(self):
         """One round of the queue's policy: admissions and retirements, then one run of at most 16 decode steps.  Returns
         (count, done, finished): int32 (n,) valid tokens / rows per sentence, bool (n,) whether that is all of the sentence,
-        and whether nothing is live or waiting any more."""
+        and whether nothing is live or waiting any more.  With beams a sentence's count is 0 until the round that retires it."""
         if not self._open:
             raise _lib.MiError("the queue session has ended")
         _lib.check(_lib.load().mi_gpt_queue_advance(self._gpt._h, self._count.ctypes.data, self._done.ctypes.data,
@@ -343,12 +395,13 @@ def stream_plan(emitted, count, done, chunk: int, halo: int):
 
 def stream_synthesize(gpt, voc, prompts, max_new, voices, voice_of, *, chunk: int = 32, halo: Optional[int] = None, **decode_kw):
     """Audio while the queue decodes: a generator over (sentence, first_sample, int16 chunk, last).  gpt = IndexGPT, voc = a
-    graph-F BigVGANVocoder, prompts / max_new / decode_kw (stop_tokens, repeat_value, penalty_range, sampling) as
+    graph-F BigVGANVocoder, prompts / max_new / decode_kw (stop_tokens, repeat_value, penalty_range, sampling, beams) as
     ``IndexGPT.generate_queue``, voices / voice_of as ``BigVGANVocoder.run_latent_voices`` (one voice index per sentence).
     Every round is one ``QueueSession.advance()`` followed by ONE ``run_latent_windows_torch`` call over all windows
     ``stream_plan`` reports, of any sentences and voices, reading the rows from the session's device `hidden`.  The chunks of a
     sentence tile its waveform [0, F * hop + 30) in order, `last` on the final one; a sentence of fewer than three codes yields
-    nothing.  halo: frames of context at each cut (default: ``voc.cfg.halo_frames()``, with which the samples are those of the
+    nothing.  With ``beams=B`` no row of a sentence is final before it ends, so every sentence leaves as ONE chunk (its whole
+    waveform) in the round that retires it, while the other groups go on decoding.  halo: frames of context at each cut (default: ``voc.cfg.halo_frames()``, with which the samples are those of the
     whole sentence's forward; less trades accuracy for work).  One thread: the vocoder call pauses the decode."""
     import torch
     from .bigvgan import voices_table
@@ -616,13 +669,16 @@ class IndexGPT:
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy()) for b in range(nb)], pen
 
     def generate_queue(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
-                       return_stats: bool = False):
+                       beams=None, return_stats: bool = False):
         """Any number of sentences through the engine's max_batch slots (include/mi355tts.h, "sentence queue"): a slot is
         refilled as soon as its sentence stops, and the prompts admitted together run as one packed pass over the weights.
         prompts = list of (1, P_i, hidden) graph-D outputs, max_new = list of per-sentence limits.  Every sentence starts from a
         penalty vector of ones (nothing is carried between sentences: they run concurrently).  sampling: None (greedy), one
-        ``Sampling`` for every sentence, or a list of n ``Sampling`` / None.  Beam search does not go through the queue.
-        Returns a list of (tokens, hidden) per sentence[, {"steps": decode steps launched, "passes": prompt passes}]."""
+        ``Sampling`` for every sentence, or a list of n ``Sampling`` / None.  beams = B (1..8, not with sampling): beam search
+        through the queue (mi_gpt_generate_queue_beam): a sentence runs as a group of B slots, the queue schedules the
+        max_batch // B groups, and each result is (tokens, hidden, score) of the best hypothesis, as ``generate_beam`` gives for
+        the sentence alone.  Returns a list of (tokens, hidden) per sentence[, {"steps": decode steps launched, "passes": prompt
+        passes}]."""
         c = self.cfg
         n = len(prompts)
         if n < 1 or len(max_new) != n:
@@ -634,6 +690,13 @@ class IndexGPT:
         mx = np.ascontiguousarray([int(m) for m in max_new], dtype=np.int32)
         cap = max(int(mx.max()), 1)
         stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
+        beams = _check_queue_beams(beams, c, sampling)
+        if beams is not None:
+            toks, hid, cnt, sc, stats = _queue_beam_call(self._h, c, cat, rows, mx, stops,
+                                                         float(c.repeat_penalty if repeat_value is None else repeat_value),
+                                                         int(c.penalty_range if penalty_range is None else penalty_range), cap, beams)
+            res = [(toks[i, : cnt[i]].copy(), hid[i, : cnt[i]].copy(), float(sc[i])) for i in range(n)]
+            return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
         sa = None if samp is None else _sampling_arrays(samp)
         toks, hid, cnt, stats = _queue_call(self._h, c, cat, rows, mx, stops,
                                             float(c.repeat_penalty if repeat_value is None else repeat_value),
@@ -642,10 +705,11 @@ class IndexGPT:
         return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
 
     def queue_session(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
-                      device: bool = False) -> QueueSession:
+                      beams=None, device: bool = False) -> QueueSession:
         """``generate_queue`` as a session that hands out rows as they appear: arguments as there; returns a ``QueueSession``
         (a context manager) whose ``advance()`` runs one round.  device=True keeps tokens / hidden as torch tensors on the
-        engine's device (``BigVGANVocoder.run_latent_windows_torch`` reads the rows where they lie).  While the session is open
+        engine's device (``BigVGANVocoder.run_latent_windows_torch`` reads the rows where they lie).  beams = B: beam search, a
+        sentence's tokens, rows and score (``QueueSession.scores``) appearing all at once when it is retired.  While the session is open
         the other decode entries of this engine raise (MI_ESTATE)."""
         c = self.cfg
         n = len(prompts)
@@ -659,8 +723,9 @@ class IndexGPT:
         cap = max(int(mx.max()), 1)
         stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
         sa = None if samp is None else _sampling_arrays(samp)
+        beams = _check_queue_beams(beams, c, sampling)
         return QueueSession(self, cat, rows, mx, stops, float(c.repeat_penalty if repeat_value is None else repeat_value),
-                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa, device)
+                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa, device, beams)
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
                              repeat_value=None, penalty_range=None, sampling=None, beams: int = 1):

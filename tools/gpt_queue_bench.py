@@ -2,6 +2,7 @@
 """The sentence queue of the IndexTTS GPT against lock-step batches of the same sentences, in one run.
 
     python tools/gpt_queue_bench.py [--sentences 64] [--slots 16] [--rows 100] [--lo 60] [--hi 240] [--dtype f16] [--small]
+                                    [--beams B]
 
 Full IndexTTS-1.5 size (24 x 1280, 8194 mel codes), synthetic weights, --sentences prompts of --rows rows each, max_new seeded-
 uniform in [--lo, --hi], no stop token, so every sentence decodes exactly its limit.  Three measurements on one handle, each the
@@ -11,6 +12,10 @@ median wall time of three calls after one warm call (eager steps and graph captu
   (c) prompt passes only, --slots sentences with max_new = 1: through generate_queue (packed) and generate_batch (one by one).
 Beside (a) and (b): the decode steps the host model of each schedule predicts (queue_schedule / lockstep_steps) and, for (a),
 the steps the entry reports.  One JSON line per measurement and a summary line.
+
+--beams B: beam search.  (a) is generate_queue(beams=B): the queue over the --slots // B groups; (b) is generate_beam over
+index-order groups of --slots // B sentences; the host models are queue_schedule(..., beams=B) and lockstep_steps over
+--slots // B; (c) compares the packed pass with one selection-0 launch against generate_beam's one-by-one prompt passes.
 """
 import argparse
 import json
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--hi", type=int, default=240)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--beams", type=int, default=None, help="beam search with B hypotheses per sentence (1..8): groups of B slots")
     ap.add_argument("--small", action="store_true", help="the reduced model (a functional check of this tool, not a measurement)")
     a = ap.parse_args()
     cfg = IndexGPTConfig.small() if a.small else IndexGPTConfig()
@@ -66,32 +72,44 @@ def main():
     limits = np.random.default_rng(a.seed).integers(a.lo, a.hi + 1, a.sentences).tolist()
     rows = [a.rows] * a.sentences
     base = {"dtype": a.dtype, "sentences": a.sentences, "slots": a.slots, "rows": a.rows, "tokens": int(sum(limits))}
+    B = a.beams
+    if B is not None:
+        assert 1 <= B <= 8 and B <= a.slots, "--beams must be in 1..8 and at most --slots"
+        base["beams"] = B
+    per = a.slots if B is None else a.slots // B       # sentences decoding together
+    qkw = {} if B is None else {"beams": B}
 
     stats = {}
 
     def run_queue():
-        _, s = eng.generate_queue(prompts, limits, stop_tokens=[], return_stats=True)
+        _, s = eng.generate_queue(prompts, limits, stop_tokens=[], return_stats=True, **qkw)
         stats.update(s)
 
+    def batch(ps, ls):
+        if B is None:
+            eng.generate_batch(ps, ls, stop_tokens=[])
+        else:
+            eng.generate_beam(ps, ls, B, stop_tokens=[])
+
     def run_groups():
-        for g in range(0, a.sentences, a.slots):
-            eng.generate_batch(prompts[g:g + a.slots], limits[g:g + a.slots], stop_tokens=[])
+        for g in range(0, a.sentences, per):
+            batch(prompts[g:g + per], limits[g:g + per])
 
     t_q, sp_q = timed(run_queue)
-    q_steps, q_passes = queue_schedule(rows, limits, limits, a.slots, cfg.max_seq)
+    q_steps, q_passes = queue_schedule(rows, limits, limits, a.slots, cfg.max_seq, beams=B or 1)
     ra = dict(base, what="a: generate_queue", seconds=round(t_q, 4), spread=round(sp_q, 4), codes_per_s=round(sum(limits) / t_q, 1),
               model_steps=q_steps, model_passes=len(q_passes), steps=stats["steps"], passes=stats["passes"])
     print(json.dumps(ra), flush=True)
     t_b, sp_b = timed(run_groups)
-    b_steps = lockstep_steps(limits, a.slots)
-    rb = dict(base, what="b: generate_batch, index-order groups", seconds=round(t_b, 4), spread=round(sp_b, 4),
+    b_steps = lockstep_steps(limits, per)
+    rb = dict(base, what="b: generate_batch, index-order groups" if B is None else "b: generate_beam, index-order groups", seconds=round(t_b, 4), spread=round(sp_b, 4),
               codes_per_s=round(sum(limits) / t_b, 1), model_steps=b_steps, prompt_passes=a.sentences)
     print(json.dumps(rb), flush=True)
-    k = min(a.slots, a.sentences)
-    t_pp, sp_pp = timed(lambda: eng.generate_queue(prompts[:k], [1] * k, stop_tokens=[]))
-    t_p1, sp_p1 = timed(lambda: eng.generate_batch(prompts[:k], [1] * k, stop_tokens=[]))
+    k = min(per, a.sentences)
+    t_pp, sp_pp = timed(lambda: eng.generate_queue(prompts[:k], [1] * k, stop_tokens=[], **qkw))
+    t_p1, sp_p1 = timed(lambda: batch(prompts[:k], [1] * k))
     rc = dict(base, what="c: prompt passes only", prompts=k, packed_seconds=round(t_pp, 5), packed_spread=round(sp_pp, 4),
-              packed_passes=len(queue_schedule(rows[:k], [1] * k, [1] * k, a.slots, cfg.max_seq)[1]),
+              packed_passes=len(queue_schedule(rows[:k], [1] * k, [1] * k, a.slots, cfg.max_seq, beams=B or 1)[1]),
               one_by_one_seconds=round(t_p1, 5), one_by_one_spread=round(sp_p1, 4), ratio=round(t_p1 / t_pp, 3))
     print(json.dumps(rc), flush=True)
     print(json.dumps(dict(base, what="summary", speedup_a_over_b=round(t_b / t_q, 3), model_step_ratio=round(b_steps / q_steps, 3),

@@ -385,6 +385,31 @@ int         mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const 
 int         mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_scores, int groups, int beams, int codes,
                                int first, int32_t* parents, int32_t* tokens, float* scores, int mem);
 
+/* unit entries (tests, no handle): ONE launch of each of the GPT's four attention kernels, through the launcher the engine
+ * calls (same kernel, grid, block and dynamic LDS).  softmax(q K^T [+ mask]) V per head of 64 columns, no scale (the engine's q
+ * is pre-scaled by the folded weights).  qkv (rows, 3 * hidden), hidden = 64 * heads, of which only the q third is read; kc /
+ * vc: K and V caches in the engine's layout [slot][head][max_seq][64]; out (rows, hidden).  All fp32 and following `mem`; the
+ * inputs are rounded to `dtype` (MI_F32 | MI_F16 | MI_BF16) on the device, the output widened back (exact).  The integer tables
+ * are HOST arrays.  1 <= heads <= 64, 1 <= max_seq <= 8192, 1 <= nslots <= 64.  A cache row the launch must not read may hold
+ * anything, NaN included.
+ *   decode       row r = slot r attends to keys 0 .. kv-1 of its own slot, kv = min(hist[r] + 1, max_seq); 0 <= hist <= max_seq.
+ *   decode_beam  slots in groups of `beams` (1..8, dividing nslots).  P = hist - ndec + 1 (0 <= ndec <= hist + 1): key j < P is
+ *                read from the group's first slot, key P + n from slot anc[ndec & 1][r][n] of the group; anc (2, nslots,
+ *                max_seq), every entry in [0, beams).
+ *   prompt       ONE slot (kc / vc: [head][max_seq][64]) holding hist + rows keys; row i of the `rows` new ones sees all of
+ *                them, key j > i (j absolute, i inside the new block) with -128 * flag added; hist + rows <= max_seq.
+ *   prompt_packed  segs (nseg, 3) = (first, rows, slot): ascending, gap-free, distinct slots, the rows summing to total <=
+ *                max_seq; packed row first + i of a segment is row i of a prompt of `rows` rows in `slot`, history 0, mask on. */
+int         mi_gpt_attn_decode(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int nslots,
+                               const int32_t* hist, float* out, int mem);
+int         mi_gpt_attn_decode_beam(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq,
+                                    int nslots, const int32_t* hist, const int32_t* ndec, int beams, const int32_t* anc, float* out,
+                                    int mem);
+int         mi_gpt_attn_prompt(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int hist,
+                               int rows, int flag, float* out, int mem);
+int         mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq,
+                                      int nslots, const int32_t* segs, int nseg, int total, float* out, int mem);
+
 /* ---- sentence queue: any number of sentences through the handle's slots, a slot refilled as soon as its sentence stops ---------
  * A decode step costs little more for 16 live slots than for 1, and 64 cost far less than four times 16,
  * so throughput is the number of LIVE slots.  mi_gpt_generate_batch takes

@@ -288,6 +288,48 @@ def test_greedy_sampled_beam_on_one_handle(eng, small):
     assert int(tok[0, 0]) == int(np.argmax(lg)) == int(fresh[0][0][0])
 
 
+# Beyond 64 keys.  Everything above runs at max_seq = 64: one 64-key pass in wave 0 of gpt_attn1_body.  Here the cache holds 352
+# rows, so the ancestor lookup runs in all four waves, through both halves of a wave's double buffer (keys >= 256) and the merge.
+@pytest.fixture(scope="module")
+def long_eng(small):
+    cfg = IndexGPTConfig(**{**small[0].__dict__, "max_seq": 352, "max_mel_pos": 352, "max_batch": 3})
+    e = IndexGPT(cfg, W.synth_state(W.gpt_spec(cfg), SEED), dtype="f32")
+    yield e
+    e.close()
+
+
+def test_one_beam_is_greedy_over_300_tokens(long_eng):
+    """include/mi355tts.h: "num_beams == 1 is greedy exactly" — a 40-row prompt, 300 tokens, 339 keys at the end"""
+    e = long_eng
+    p = _prompt(e, 1, n_text=6, n_cond=31)
+    assert p.shape[1] == 40
+    rb, pb = e.generate_batch([p], [300], stop_tokens=[], **KW)
+    res, p1 = e.generate_beam([p], [300], 1, stop_tokens=[], **KW)
+    t1, h1, _ = res[0]
+    assert len(t1) == 300 and t1.tolist() == rb[0][0].tolist()
+    print(f"one beam, 300 tokens: max |d hidden| against generate_batch {np.abs(h1 - rb[0][1]).max():.3g}")
+    # the same launches but for the attention, and in fp32 gpt_attn1_beam_kernel gives gpt_attn1_kernel's bits: equal rows
+    np.testing.assert_array_equal(h1, rb[0][1])
+    np.testing.assert_array_equal(p1[0], pb[0])
+
+
+def test_device_beam_vs_host_driven_300_row_prompt(long_eng):
+    """three beams over a 300-row prompt, 8 selections (P = 300: every later key is found through the table, in wave 0's and wave
+    1's second pass), against the host-driven beam; the seed is the first of (1, 2, 3) whose host-side margin reaches MARGIN"""
+    e = long_eng
+    for seed in (1, 2, 3):
+        p = _prompt(e, seed, n_text=6, n_cond=291)
+        assert p.shape[1] == 300
+        ref = R.beam_generate(R.EngineModel(e), p, 3, 8, stop_tokens=(), **KW)
+        if min(ref["margins"]) >= MARGIN:
+            break
+        print(f"beam (300 rows, seed {seed}): host-side margin {min(ref['margins']):.3g} below {MARGIN}, next seed")
+    assert min(ref["margins"]) >= MARGIN and len(ref["tokens"]) == 8
+    res, pen = e.generate_beam([p], [8], 3, stop_tokens=[], **KW)
+    assert len(res[0][0]) == 8
+    _compare(res[0], pen[0], ref, (seed, 3, "300-row prompt"))
+
+
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_beam_16_bit_engines(small, dtype):
     e = _engine(small, 3, dtype)

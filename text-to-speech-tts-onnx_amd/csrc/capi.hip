@@ -1587,6 +1587,143 @@ int mi_gpt_sample_logits(const float* logits, const float* pen, int rows, int co
     });
 }
 
+}  // extern "C"
+
+// The unit entries of the four attention launches share this: fp32 inputs staged and rounded to `dtype` on the device, the
+// GS_* state words built from the host tables, the engine's launcher (gpt.h), the output back as fp32.  The output is preset
+// to NaN bytes, so a row the launch does not write shows.
+namespace {
+struct AttnUnit {
+    hipStream_t s = nullptr;
+    int dtype, heads, hidden, max_seq;
+    DevBuf in_q, in_k, in_v, q, k, v, o, o32, st;
+    AttnUnit(const std::string& who, int dt, int heads_, int max_seq_, int mem) : dtype(dt), heads(heads_), hidden(64 * heads_), max_seq(max_seq_) {
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+        MI_REQUIRE(dt == MI_F32 || dt == MI_F16 || dt == MI_BF16, who + ": dtype must be MI_F32, MI_F16 or MI_BF16");
+        MI_REQUIRE(heads_ >= 1 && heads_ <= 64, who + ": heads must be in [1, 64] (hidden = 64 * heads)");
+        // the dynamic LDS of the prompt kernels stays below what a launch may ask for without raising the function attribute
+        MI_REQUIRE(max_seq_ >= 1 && max_seq_ <= 8192, who + ": max_seq must be in [1, 8192]");
+        MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    }
+    ~AttnUnit() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    size_t slot_elems() const { return (size_t)hidden * max_seq; }
+    void inputs(const float* qkv, int rows, const float* kc, const float* vc, int nslots, int mem) {
+        const size_t es = dtype_size(dtype), nq = (size_t)rows * 3 * hidden, nc = (size_t)nslots * slot_elems();
+        q.ensure(nq * es); k.ensure(nc * es); v.ensure(nc * es); o.ensure((size_t)rows * hidden * es);
+        launch_copy2d((const float*)stage_in(in_q, qkv, nq * 4, mem, s), 3 * hidden, q.p, 3 * hidden, rows, 3 * hidden, dtype, s);
+        launch_copy2d((const float*)stage_in(in_k, kc, nc * 4, mem, s), 64, k.p, 64, (long)(nc / 64), 64, dtype, s);
+        launch_copy2d((const float*)stage_in(in_v, vc, nc * 4, mem, s), 64, v.p, 64, (long)(nc / 64), 64, dtype, s);
+        MI_HIP(hipMemsetAsync(o.p, 0xFF, (size_t)rows * hidden * es, s));
+    }
+    // words[slot] = (GS_HIST, GS_NDEC)
+    void state(const std::vector<std::pair<int, int>>& words) {
+        std::vector<int32_t> w(words.size() * GS_WORDS, 0);
+        for (size_t b = 0; b < words.size(); ++b) { w[b * GS_WORDS + GS_HIST] = words[b].first; w[b * GS_WORDS + GS_NDEC] = words[b].second; }
+        st.ensure(w.size() * 4);
+        MI_HIP(hipMemcpyAsync(st.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));       // `w` is a local
+    }
+    void result(float* out, int rows, int mem) {
+        const size_t n = (size_t)rows * hidden;
+        float* dst = out;
+        if (mem == MI_HOST) { o32.ensure(n * 4); dst = o32.as<float>(); }
+        launch_cast_to_f32(o.p, dtype, dst, (long)n, s);
+        if (mem == MI_HOST) copy_out(out, dst, n * 4, mem, s);
+        MI_HIP(hipStreamSynchronize(s));
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int mi_gpt_attn_decode(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int nslots,
+                       const int32_t* hist, float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_attn_decode";
+        AttnUnit u(who, dtype, heads, max_seq, mem);
+        MI_REQUIRE(qkv && kc && vc && hist && out, who + ": null argument");
+        MI_REQUIRE(nslots >= 1 && nslots <= GPT_MAX_BATCH, who + ": nslots must be in [1, 64]");
+        std::vector<std::pair<int, int>> w(nslots);
+        for (int b = 0; b < nslots; ++b) {
+            MI_REQUIRE(hist[b] >= 0 && hist[b] <= max_seq, who + ": hist must be in [0, max_seq]");
+            w[b] = {hist[b], 0};
+        }
+        u.inputs(qkv, nslots, kc, vc, nslots, mem);
+        u.state(w);
+        launch_gpt_attn1(dtype, u.q.p, u.k.p, u.v.p, u.o.p, u.st.as<int>(), heads, nslots, u.hidden, max_seq, 1, u.slot_elems(), u.s);
+        u.result(out, nslots, mem);
+    });
+}
+
+int mi_gpt_attn_decode_beam(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int nslots,
+                            const int32_t* hist, const int32_t* ndec, int beams, const int32_t* anc, float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_attn_decode_beam";
+        AttnUnit u(who, dtype, heads, max_seq, mem);
+        MI_REQUIRE(qkv && kc && vc && hist && ndec && anc && out, who + ": null argument");
+        MI_REQUIRE(nslots >= 1 && nslots <= GPT_MAX_BATCH, who + ": nslots must be in [1, 64]");
+        MI_REQUIRE(beams >= 1 && beams <= GPT_BEAM_MAX && nslots % beams == 0, who + ": beams must be in [1, 8] and divide nslots");
+        std::vector<std::pair<int, int>> w(nslots);
+        for (int b = 0; b < nslots; ++b) {
+            MI_REQUIRE(hist[b] >= 0 && hist[b] <= max_seq, who + ": hist must be in [0, max_seq]");
+            MI_REQUIRE(ndec[b] >= 0 && ndec[b] <= hist[b] + 1, who + ": ndec must be in [0, hist + 1]");
+            w[b] = {hist[b], ndec[b]};
+        }
+        const size_t na = (size_t)2 * nslots * max_seq;
+        for (size_t i = 0; i < na; ++i) MI_REQUIRE(anc[i] >= 0 && anc[i] < beams, who + ": ancestor table entries must be in [0, beams)");
+        u.inputs(qkv, nslots, kc, vc, nslots, mem);
+        u.state(w);
+        DevBuf tab;
+        tab.ensure(na * 4);
+        MI_HIP(hipMemcpyAsync(tab.p, anc, na * 4, hipMemcpyHostToDevice, u.s));
+        launch_gpt_attn1_beam(dtype, u.q.p, u.k.p, u.v.p, u.o.p, u.st.as<int>(), tab.as<int>(), tab.as<int>() + (size_t)nslots * max_seq,
+                              heads, nslots, u.hidden, max_seq, u.slot_elems(), beams, u.s);
+        u.result(out, nslots, mem);
+    });
+}
+
+int mi_gpt_attn_prompt(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int hist, int rows,
+                       int flag, float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_attn_prompt";
+        AttnUnit u(who, dtype, heads, max_seq, mem);
+        MI_REQUIRE(qkv && kc && vc && out, who + ": null argument");
+        MI_REQUIRE(hist >= 0 && rows >= 1 && hist + rows <= max_seq, who + ": hist + rows exceeds max_seq");
+        MI_REQUIRE(flag == 0 || flag == 1, who + ": flag must be 0 or 1");
+        u.inputs(qkv, rows, kc, vc, 1, mem);
+        u.state({{hist, 0}});
+        launch_gpt_attn_prompt(dtype, u.q.p, u.k.p, u.v.p, u.o.p, u.st.as<int>(), heads, rows, flag, u.hidden, max_seq, u.s);
+        u.result(out, rows, mem);
+    });
+}
+
+int mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq, int nslots,
+                              const int32_t* segs, int nseg, int total, float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_attn_prompt_packed";
+        AttnUnit u(who, dtype, heads, max_seq, mem);
+        MI_REQUIRE(qkv && kc && vc && segs && out, who + ": null argument");
+        MI_REQUIRE(nslots >= 1 && nslots <= GPT_MAX_BATCH && nseg >= 1 && nseg <= nslots, who + ": nslots must be in [1, 64], nseg in [1, nslots]");
+        std::vector<Gpt::Seg> tab(nseg);
+        int sum = 0;
+        uint64_t used = 0;
+        for (int g = 0; g < nseg; ++g) {
+            const int32_t first = segs[3 * g], rows = segs[3 * g + 1], slot = segs[3 * g + 2];
+            MI_REQUIRE(first == sum && rows >= 1 && rows <= max_seq - sum, who + ": segments must be ascending and gap-free within max_seq");
+            MI_REQUIRE(slot >= 0 && slot < nslots && !(used >> slot & 1u), who + ": segment slot out of range or used twice");
+            used |= (uint64_t)1 << slot;
+            sum += rows;
+            tab[g] = {first, rows, slot, 0};
+        }
+        MI_REQUIRE(sum == total, who + ": total must be the sum of the segments' rows");
+        u.inputs(qkv, total, kc, vc, nslots, mem);
+        DevBuf dtab;
+        dtab.ensure(tab.size() * sizeof(Gpt::Seg));
+        MI_HIP(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * sizeof(Gpt::Seg), hipMemcpyHostToDevice, u.s));
+        launch_gpt_attn_packed(dtype, u.q.p, u.k.p, u.v.p, u.o.p, dtab.p, nseg, total, heads, u.hidden, max_seq, nslots, u.slot_elems(), u.s);
+        u.result(out, total, mem);
+    });
+}
 
 int mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int iters, double* ms) {
     return guard([&] {

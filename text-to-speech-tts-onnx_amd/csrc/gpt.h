@@ -105,8 +105,6 @@ struct Gpt {
         const size_t off = ((size_t)slot * slot_cache_elems() + (size_t)layer * cfg.hidden * cfg.max_seq) * dtype_size(dtype);
         return {(char*)kc.p + off, (char*)vc.p + off};
     }
-    // dynamic LDS of gpt_attn_kernel: the score buffer, the query and the merge scratch (max_seq + 64 + 512 floats)
-    int prompt_attn_lds() const { return (cfg.max_seq + 64 + 512) * 4; }
     void set_state(const std::vector<int32_t>& words, int slot = 0);
     std::vector<int32_t> get_state(int slot = 0);
     // the greedy or sampled token choice (by `sampled`) of slots slot0 .. slot0 + nb - 1 from their logits / last rows, with
@@ -190,6 +188,30 @@ template <typename F> void Gpt::replay(hipGraphExec_t& exec, int n, F&& step) {
     }
     for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
 }
+
+// The four attention launches of the GPT, each defined beside its kernel and called by the engine and by the unit entries of
+// capi.hip (mi_gpt_attn_*): arrays of `dtype` on the device, st = GS_* state words, kc / vc = one layer's cache.
+//   decode step (gpt.hip): rows 0 .. nrows-1 of qkv / out.  batched: row r is slot r (its state words, its cache slot_stride
+//   elements on); otherwise one row against st / kc / vc as given
+void launch_gpt_attn1(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, int heads, int nrows,
+                      int hidden, int max_seq, int batched, size_t slot_stride, hipStream_t s);
+//   decode step of nr hypotheses in groups of B slots (gpt_beam.hip): kc / vc = slot 0's layer, anc0 / anc1 = the two sides of
+//   the ancestor table, [slot][max_seq] each
+void launch_gpt_attn1_beam(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, const int* anc0,
+                           const int* anc1, int heads, int nr, int hidden, int max_seq, size_t slot_stride, int B, hipStream_t s);
+//   a lone prompt's `rows` new rows behind st[GS_HIST] cached ones (gpt.hip); dynamic LDS = gpt_prompt_attn_lds(max_seq)
+void launch_gpt_attn_prompt(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, int heads,
+                            int rows, int flag, int hidden, int max_seq, hipStream_t s);
+//   `total` packed rows over the nseg segments of the device table segs (gpt_prompt.hip): kc / vc = slot 0's layer; dynamic
+//   LDS = gpt_packed_attn_lds(max_seq)
+void launch_gpt_attn_packed(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const void* segs, int nseg,
+                            int total, int heads, int hidden, int max_seq, int max_batch, size_t slot_stride, hipStream_t s);
+// dynamic LDS of the two prompt kernels, in bytes.  Above the 64 KiB a launch may ask for by default the caller raises
+// hipFuncAttributeMaxDynamicSharedMemorySize first (gpt_attn_prompt_reserve / gpt_attn_packed_reserve, all three types).
+inline int gpt_prompt_attn_lds(int max_seq) { return (max_seq + 64 + 512) * 4; }                  // sc | qs | red
+inline int gpt_packed_attn_lds(int max_seq) { return (((max_seq + 3) & ~3) + 64 + 512 + 4) * 4; } // sc | qs | red | bc
+void gpt_attn_prompt_reserve(int lds);
+void gpt_attn_packed_reserve(int lds);
 
 constexpr int GPT_BEAM_MAX = 8;                  // hypotheses per sentence
 constexpr int GPT_BEAM_MAX_CODES = 16384;        // the unit entry's documented range

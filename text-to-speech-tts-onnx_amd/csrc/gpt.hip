@@ -611,6 +611,27 @@ __global__ __launch_bounds__(256) void gpt_attn1_kernel(const T* __restrict__ qk
     gpt_attn1_body<T>(qkv, kc, vc, out, slot, head, hidden, max_seq, kv, AttnRowsOwn{});
 }
 
+void launch_gpt_attn1(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, int heads, int nrows,
+                      int hidden, int max_seq, int batched, size_t slot_stride, hipStream_t s) {
+#define ATT1(T, ...) hipLaunchKernelGGL(gpt_attn1_kernel<T>, dim3(heads, nrows), dim3(256), 0, s, (const T*)qkv, (const T*)kc, (const T*)vc, (T*)out, st, hidden, max_seq, batched, slot_stride)
+    GPT_DISPATCH(ATT1, 0);
+#undef ATT1
+}
+
+void launch_gpt_attn_prompt(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, int heads,
+                            int rows, int flag, int hidden, int max_seq, hipStream_t s) {
+    const int lds = gpt_prompt_attn_lds(max_seq);
+#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn_kernel<T>, dim3(heads, rows), dim3(512), lds, s, (const T*)qkv, (const T*)kc, (const T*)vc, (T*)out, st, rows, flag, hidden, max_seq, 0, (size_t)0)
+    GPT_DISPATCH(ATT, 0);
+#undef ATT
+}
+
+void gpt_attn_prompt_reserve(int lds) {
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+}
+
 __global__ __launch_bounds__(256) void gpt_text_embed_kernel(const int* __restrict__ ids, const float* __restrict__ emb,
                                                              const float* __restrict__ pos, float* __restrict__ out,
                                                              int n, int hidden, int vocab) {
@@ -751,10 +772,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     MI_HIP(hipStreamSynchronize(s));
     set_rep_value(0.7f);
     use_graph = !env_first_is("MI355TTS_NO_GRAPH", '1');
-    const int lds = prompt_attn_lds();
-    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    gpt_attn_prompt_reserve(gpt_prompt_attn_lds(c.max_seq));
 }
 
 Gpt::~Gpt() {
@@ -864,7 +882,6 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
     MI_REQUIRE(slot >= 0 && slot < c.max_batch, "gpt: slot");
     const int* st = state.as<int>() + (size_t)slot * GS_WORDS;
     float* x = X.as<float>();
-    const int lds = prompt_attn_lds();
     float* last_s = last.as<float>() + (size_t)slot * h;
     float* logits_s = logits.as<float>() + (size_t)slot * c.mel_codes;
     for (int li = 0; li < c.layers; ++li) {
@@ -884,11 +901,8 @@ void Gpt::forward_rows(int rows, int flag, int slot) {
         }
         {
             ProfScope ps(FAM_ATTN, s, 2.0 * (double)h * (history + rows) * es, 4.0 * (double)h * rows * (history + rows));
-#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn_kernel<T>, dim3(c.heads, rows), dim3(512), lds, s, (const T*)qkv.p, (const T*)kcl, (const T*)vcl, (T*)att.p, st, rows, flag, h, S, 0, (size_t)0)
-#define ATT1(T, ...) hipLaunchKernelGGL(gpt_attn1_kernel<T>, dim3(c.heads, 1), dim3(256), 0, s, (const T*)qkv.p, (const T*)kcl, (const T*)vcl, (T*)att.p, st, h, S, 0, (size_t)0)
-            if (rows == 1 && !flag) GPT_DISPATCH(ATT1, 0); else GPT_DISPATCH(ATT, 0);
-#undef ATT1
-#undef ATT
+            if (rows == 1 && !flag) launch_gpt_attn1(dtype, qkv.p, kcl, vcl, att.p, st, c.heads, 1, h, S, 0, 0, s);
+            else launch_gpt_attn_prompt(dtype, qkv.p, kcl, vcl, att.p, st, c.heads, rows, flag, h, S, s);
         }
         if (rows == 1) {
             gemv(l.proj, att.p, nullptr, nullptr, x, MI_F32, ACT_NONE, x, nullptr, nullptr);
@@ -1046,9 +1060,8 @@ void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int 
 void Gpt::decode_batch_eager(int nb) {
     MI_REQUIRE(nb >= 1 && nb <= cfg.max_batch, "gpt: batch exceeds max_batch");
     decode_rows_eager(nb, [&](char* kcl, char* vcl) {
-#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_kernel<T>, dim3(cfg.heads, nb), dim3(256), 0, stream, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), cfg.hidden, cfg.max_seq, 1, slot_cache_elems())
-        GPT_DISPATCH(ATT, 0);
-#undef ATT
+        launch_gpt_attn1(dtype, qkvd.p, kcl, vcl, attd.p, state.as<int>(), cfg.heads, nb, cfg.hidden, cfg.max_seq, 1,
+                         slot_cache_elems(), stream);
     }, [&] { launch_choice(nb, 0, 1, nullptr); });
 }
 

@@ -318,6 +318,13 @@ __global__ __launch_bounds__(256) void gpt_attn1_beam_kernel(const T* __restrict
                       AttnRowsAncestor{anc, P, B, max_seq, slot_stride});
 }
 
+void launch_gpt_attn1_beam(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const int* st, const int* anc0,
+                           const int* anc1, int heads, int nr, int hidden, int max_seq, size_t slot_stride, int B, hipStream_t s) {
+#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_beam_kernel<T>, dim3(heads, nr), dim3(256), 0, s, (const T*)qkv, (const T*)kc, (const T*)vc, (T*)out, st, anc0, anc1, hidden, max_seq, slot_stride, B)
+    GPT_DISPATCH(ATT, 0);
+#undef ATT
+}
+
 // hypothesis 0 of every group along its ancestors: token n and last_hidden_state row n were stored by slot anc[n]
 __global__ __launch_bounds__(256) void gpt_beam_gather_kernel(const int* __restrict__ st, const int* __restrict__ anc0,
                                                               const int* __restrict__ anc1, const int* __restrict__ toks,
@@ -406,9 +413,8 @@ void Gpt::decode_beam_eager(int nb, int B) {
     const int* anc0 = anc.as<int>();
     const int* anc1 = anc0 + (size_t)MBp * cfg.max_seq;
     decode_rows_eager(nr, [&](char* kcl, char* vcl) {
-#define ATT(T, ...) hipLaunchKernelGGL(gpt_attn1_beam_kernel<T>, dim3(cfg.heads, nr), dim3(256), 0, stream, (const T*)qkvd.p, (const T*)kcl, (const T*)vcl, (T*)attd.p, state.as<int>(), anc0, anc1, cfg.hidden, cfg.max_seq, slot_cache_elems(), B)
-        GPT_DISPATCH(ATT, 0);
-#undef ATT
+        launch_gpt_attn1_beam(dtype, qkvd.p, kcl, vcl, attd.p, state.as<int>(), anc0, anc1, cfg.heads, nr, cfg.hidden, cfg.max_seq,
+                              slot_cache_elems(), B, stream);
     }, [&] { beam_step_launch(*this, nb, 0, B, 1, 0); });
 }
 

@@ -73,6 +73,20 @@ __global__ __launch_bounds__(512) void gpt_attn_packed_kernel(const T* __restric
     gpt_prompt_attn_body<T>(i, kv, 1, qkv, kc, vc, out, row, head, hidden, max_seq, sc, qs, red, bc);
 }
 
+void launch_gpt_attn_packed(int dtype, const void* qkv, const void* kc, const void* vc, void* out, const void* segs, int nseg,
+                            int total, int heads, int hidden, int max_seq, int max_batch, size_t slot_stride, hipStream_t s) {
+    const int lds = gpt_packed_attn_lds(max_seq);
+#define ATTP(T, ...) hipLaunchKernelGGL(gpt_attn_packed_kernel<T>, dim3(heads, total), dim3(512), lds, s, (const T*)qkv, (const T*)kc, (const T*)vc, (T*)out, (const int4*)segs, nseg, hidden, max_seq, max_batch, slot_stride)
+    GPT_DISPATCH(ATTP, 0);
+#undef ATTP
+}
+
+void gpt_attn_packed_reserve(int lds) {
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+}
+
 __global__ __launch_bounds__(256) void gpt_fill_kernel(float* __restrict__ p, float v, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = v;
@@ -142,12 +156,9 @@ void Gpt::forward_packed(const Seg* segs, int k) {
         if (beams) beam_select_first(segs[0].slot / beams, beams, 1);        // as mi_gpt_generate_beam's one-by-one pass
         return;
     }
-    const int lds = (((S + 3) & ~3) + 64 + 512 + 4) * 4;
     if (!packed_ready) {
         segtab.ensure((size_t)c.max_batch * sizeof(Seg));
-        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MI_HIP(hipFuncSetAttribute((const void*)gpt_attn_packed_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        gpt_attn_packed_reserve(gpt_packed_attn_lds(S));
         packed_ready = true;
     }
     static_assert(sizeof(Seg) == sizeof(int4), "Seg is one int4 on the device");
@@ -173,9 +184,7 @@ void Gpt::forward_packed(const Seg* segs, int k) {
             double keys = 0.0;
             for (int g = 0; g < k; ++g) keys += (double)segs[g].rows * segs[g].rows;
             ProfScope ps(FAM_ATTN, s, 2.0 * (double)h * total * es, 4.0 * (double)h * keys);
-#define ATTP(T, ...) hipLaunchKernelGGL(gpt_attn_packed_kernel<T>, dim3(c.heads, total), dim3(512), lds, s, (const T*)qkv.p, (const T*)kcl, (const T*)vcl, (T*)att.p, tab, k, h, S, c.max_batch, sstride)
-            GPT_DISPATCH(ATTP, 0);
-#undef ATTP
+            launch_gpt_attn_packed(dtype, qkv.p, kcl, vcl, att.p, tab, k, total, c.heads, h, S, c.max_batch, sstride, s);
         }
         linear(l.proj, att.p, total, x, MI_F32, ACT_NONE, x);
         launch_rownorm(NORM_LN_AFFINE, x, xn.p, dtype, l.ln2_w.as<float>(), l.ln2_b.as<float>(), total, h, 1e-5f, s);

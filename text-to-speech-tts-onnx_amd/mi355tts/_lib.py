@@ -174,6 +174,15 @@ def load() -> C.CDLL:
     L.mi_gpt_generate_beam.restype = C.c_int
     L.mi_gpt_beam_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int]
     L.mi_gpt_beam_select.restype = C.c_int
+    if hasattr(L, "mi_gpt_attn_decode"):
+        L.mi_gpt_attn_decode.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, vp, C.c_int]
+        L.mi_gpt_attn_decode.restype = C.c_int
+        L.mi_gpt_attn_decode_beam.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, vp, C.c_int, vp, vp, C.c_int]
+        L.mi_gpt_attn_decode_beam.restype = C.c_int
+        L.mi_gpt_attn_prompt.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp, C.c_int]
+        L.mi_gpt_attn_prompt.restype = C.c_int
+        L.mi_gpt_attn_prompt_packed.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int, C.c_int, vp, C.c_int]
+        L.mi_gpt_attn_prompt_packed.restype = C.c_int
     L.mi_gpt_bench_pick.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_double)]
     L.mi_gpt_bench_pick.restype = C.c_int
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]

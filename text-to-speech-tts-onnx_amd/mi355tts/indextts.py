@@ -217,6 +217,70 @@ def beam_select(logits, prev_scores=None, *, beams: int, first: bool = False, pe
     return par.reshape(g, beams), tok.reshape(g, beams), sc.reshape(g, beams)
 
 
+def _attn_inputs(q, K, V, slots: bool):
+    """q (rows, hidden) -> a qkv array whose k / v thirds are zero (the kernels read q alone); K / V caches as float32"""
+    q = np.asarray(q, np.float32)
+    K = np.ascontiguousarray(K, dtype=np.float32)
+    V = np.ascontiguousarray(V, dtype=np.float32)
+    if q.ndim != 2 or q.shape[1] % 64 or K.shape != V.shape or K.ndim != (4 if slots else 3) or K.shape[-1] != 64 \
+            or K.shape[-3] * 64 != q.shape[1]:
+        raise ValueError("q must be (rows, 64 * heads), K / V " + ("(slots, heads, max_seq, 64)" if slots else "(heads, max_seq, 64)"))
+    qkv = np.zeros((q.shape[0], 3 * q.shape[1]), np.float32)
+    qkv[:, :q.shape[1]] = q
+    return qkv, K, V, np.zeros(q.shape, np.float32)
+
+
+def attention_decode(q, K, V, hist, *, dtype: str = "f32"):
+    """The decode step's attention launch (unit entry mi_gpt_attn_decode): row r of q (slots, hidden) against keys
+    0 .. min(hist[r] + 1, max_seq) - 1 of slot r of the caches K / V (slots, heads, max_seq, 64) -> (slots, hidden) float32."""
+    qkv, K, V, out = _attn_inputs(q, K, V, True)
+    h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+    if h.size != K.shape[0] or qkv.shape[0] != K.shape[0]:
+        raise ValueError("one q row and one hist entry per slot")
+    _lib.check(_lib.load().mi_gpt_attn_decode(qkv.ctypes.data, K.ctypes.data, V.ctypes.data, _lib.DTYPES[dtype], K.shape[1],
+                                              K.shape[2], K.shape[0], h.ctypes.data, out.ctypes.data, _lib.MI_HOST),
+               "mi_gpt_attn_decode")
+    return out
+
+
+def attention_decode_beam(q, K, V, hist, ndec, anc, *, beams: int, dtype: str = "f32"):
+    """The beam step's attention launch (unit entry mi_gpt_attn_decode_beam): as attention_decode, with key j of slot r read
+    from the group's first slot below P = hist[r] - ndec[r] + 1 and from slot anc[ndec[r] & 1, r, j - P] of the group from
+    there on; anc (2, slots, max_seq) int32 with entries in [0, beams)."""
+    qkv, K, V, out = _attn_inputs(q, K, V, True)
+    ns, S = K.shape[0], K.shape[2]
+    h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+    n = np.ascontiguousarray(ndec, dtype=np.int32).reshape(-1)
+    a = np.ascontiguousarray(anc, dtype=np.int32)
+    if h.size != ns or n.size != ns or qkv.shape[0] != ns or a.shape != (2, ns, S):
+        raise ValueError("one q row, hist and ndec entry per slot; anc must be (2, slots, max_seq)")
+    _lib.check(_lib.load().mi_gpt_attn_decode_beam(qkv.ctypes.data, K.ctypes.data, V.ctypes.data, _lib.DTYPES[dtype], K.shape[1], S,
+                                                   ns, h.ctypes.data, n.ctypes.data, int(beams), a.ctypes.data, out.ctypes.data,
+                                                   _lib.MI_HOST), "mi_gpt_attn_decode_beam")
+    return out
+
+
+def attention_prompt(q, K, V, hist: int, *, flag: int = 1, dtype: str = "f32"):
+    """A lone prompt pass's attention launch (unit entry mi_gpt_attn_prompt): the rows of q (rows, hidden) are the new block
+    behind ``hist`` cached rows of ONE slot's K / V (heads, max_seq, 64); additive mask -128 * flag on keys j > i."""
+    qkv, K, V, out = _attn_inputs(q, K, V, False)
+    _lib.check(_lib.load().mi_gpt_attn_prompt(qkv.ctypes.data, K.ctypes.data, V.ctypes.data, _lib.DTYPES[dtype], K.shape[0],
+                                              K.shape[1], int(hist), qkv.shape[0], int(flag), out.ctypes.data, _lib.MI_HOST),
+               "mi_gpt_attn_prompt")
+    return out
+
+
+def attention_prompt_packed(q, K, V, segs, *, dtype: str = "f32"):
+    """The packed prompt pass's attention launch (unit entry mi_gpt_attn_prompt_packed): q (total, hidden) holds the segments
+    ``segs`` = [(first, rows, slot)] back to back, each a prompt of its own in its slot of K / V (slots, heads, max_seq, 64)."""
+    qkv, K, V, out = _attn_inputs(q, K, V, True)
+    sg = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 3)
+    _lib.check(_lib.load().mi_gpt_attn_prompt_packed(qkv.ctypes.data, K.ctypes.data, V.ctypes.data, _lib.DTYPES[dtype], K.shape[1],
+                                                     K.shape[2], K.shape[0], sg.ctypes.data, sg.shape[0], qkv.shape[0],
+                                                     out.ctypes.data, _lib.MI_HOST), "mi_gpt_attn_prompt_packed")
+    return out
+
+
 def _check_queue_beams(beams, cfg, sampling):
     """The ``beams`` keyword of the queue entries: None (no beam search) or an integer in [1, 8], not above the code count or the
     engine's max_batch (one group must fit), and never together with ``sampling``."""

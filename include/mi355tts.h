@@ -442,7 +442,9 @@ int         mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const f
  *      with no decode step in between.
  *   3. Finish or decode.  No live slot: finished.  Otherwise c = min(16, min over live slots of (max_new - tokens so far))
  *      batched decode steps over slots 0..S-1 are replayed (finished and empty slots are no-ops), the states are read: step 2.
- * stats (host, 2 ints, or NULL): {sum of the c values = decode steps launched, number of prompt passes}.               */
+ * stats (host, 2 ints, or NULL): {sum of the c values = decode steps launched, number of prompt passes}.
+ * In the library these three steps are decided by one object, mi::QueuePolicy (csrc/gpt_queue.h), and mi_gpt_queue_schedule
+ * (below) drives that same object on the host alone.                                                                    */
 int         mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                                   const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
                                   int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
@@ -515,6 +517,17 @@ int         mi_gpt_generate_queue_beam(mi_gpt* h, int n, const float* prompts, c
 int         mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                                     const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
                                     int32_t* tokens, float* hidden, int cap, float* scores /* (n) or NULL */, int mem);
+
+/* Tests and tools, no handle, no GPU: the schedule the policy above gives n sentences that will produce lengths[i] tokens each
+ * (host arrays of n; 1 <= lengths[i] <= max_new[i], or 0 where max_new[i] is 0) on a handle of `slots` slots and max_seq packed
+ * rows, in units of `beams` slots (1: no beam search).  The library's own policy object is driven as the engine drives it: the
+ * prompt pass gives token 0 and a unit is done when its sentence holds lengths[i] tokens.  *steps / *n_passes: what stats would
+ * report; pass_of[i]: the pass that admitted sentence i, counted from 0; unit_of[i]: the slot (beams > 1: the group) it was
+ * admitted into; both -1 where max_new[i] is 0.  Inside a pass sentences are in index order, so this is the whole of
+ * mi355tts.indextts.queue_schedule's result, and its argument errors are the ones reported here (MI_EINVAL).             */
+int         mi_gpt_queue_schedule(int n, const int32_t* prompt_rows, const int32_t* max_new, const int32_t* lengths, int slots,
+                                  int max_seq, int beams, int32_t* steps, int32_t* n_passes, int32_t* pass_of /* n */,
+                                  int32_t* unit_of /* n */);
 
 /* tuning hook: microseconds per launch (HIP events around `iters` launches) of the decode step's token-choosing kernel over nb
  * slots, on the logits the handle's last step left: the greedy kernel when temperature is NULL, else the sampler with these

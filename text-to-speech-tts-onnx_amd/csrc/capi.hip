@@ -3,7 +3,7 @@
 #include "bigvgan.h"
 #include "f5.h"
 #include "gpt.h"
-#include "gpt_pick.h"
+#include "gpt_queue.h"
 #include "cond.h"
 #include <algorithm>
 #include <memory>
@@ -15,8 +15,7 @@ using namespace mi;
 // calls on one handle are serialised (one HIP stream + one workspace per handle); different handles run concurrently
 struct mi_bigvgan { BigVGAN* impl; std::mutex mu; };
 struct mi_f5 { F5* impl; std::mutex mu; };
-struct GptQueue;                         // an open sentence-queue session (mi_gpt_queue_begin), defined with the queue below
-struct mi_gpt { Gpt* impl; std::mutex mu; GptQueue* session = nullptr; };
+struct mi_gpt { Gpt* impl; std::mutex mu; std::unique_ptr<GptQueue> session; };     // session: open from mi_gpt_queue_begin to _end
 struct mi_cond { Cond* impl; std::mutex mu; };
 
 // Every C-ABI entry runs under the SHARED side of the option lock; mi_set_option takes the exclusive side.  The dispatch options
@@ -322,11 +321,6 @@ struct F5Recover {
     F5Recover rec_((h)->impl);                                                     \
     ArithScope arith_((h)->impl->arith);                                           \
     MI_REQUIRE((mem) == MI_HOST || (mem) == MI_DEVICE, name ": bad mem kind")
-
-static void copy_out(void* dst, const void* src, size_t bytes, int mem, hipStream_t s) {
-    if (!dst) return;
-    MI_HIP(hipMemcpyAsync(dst, src, bytes, mem == MI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-}
 
 int mi_f5_tables(mi_f5* h, float* time_expand, float* delta_t) {
     return guard([&] {
@@ -682,26 +676,22 @@ mi_gpt* mi_gpt_create_mem(const int32_t* cfg, int n_cfg, const float* weights, i
     return rc == MI_OK ? h : nullptr;
 }
 
-static void gpt_queue_free(GptQueue* q);
-
 void mi_gpt_destroy(mi_gpt* h) {
     if (!h) return;
     delete h->impl;                          // synchronises the stream: nothing of an open session is in flight afterwards
-    gpt_queue_free(h->session);
-    delete h;
+    delete h;                                // (an open session goes with it; it holds host memory only)
 }
 
-#define GPT_CHECK(h, mem, name)                                                    \
-    MI_REQUIRE((h) && (h)->impl, name ": null handle");                            \
-    std::lock_guard<std::mutex> lk_((h)->mu);                                      \
-    MI_REQUIRE((mem) == MI_HOST || (mem) == MI_DEVICE, name ": bad mem kind");     \
-    MI_HIP(hipSetDevice((h)->impl->device))
-
-// after GPT_CHECK (the handle's lock is held): the entry would touch the slots an open queue session decodes in
-#define GPT_NO_SESSION(h, name)                                                    \
-    do {                                                                           \
-        if ((h)->session) throw mi::Error(MI_ESTATE, std::string(name) + ": a sentence-queue session is open on this handle (mi_gpt_queue_end)"); \
-    } while (0)
+// Every entry on a GPT handle starts here, `who` being its name: the handle's lock, held while the result lives, the mem kind,
+// the device.  no_session: the entry would touch the slots an open queue session decodes in.
+static std::unique_lock<std::mutex> gpt_enter(mi_gpt* h, int mem, const std::string& who, bool no_session = false) {
+    MI_REQUIRE(h && h->impl, who + ": null handle");
+    std::unique_lock<std::mutex> lk(h->mu);
+    MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+    MI_HIP(hipSetDevice(h->impl->device));
+    if (no_session && h->session) throw mi::Error(MI_ESTATE, who + ": a sentence-queue session is open on this handle (mi_gpt_queue_end)");
+    return lk;
+}
 
 // input staged to the device when it lives on the host
 static const void* stage_in(DevBuf& buf, const void* src, size_t bytes, int mem, hipStream_t s) {
@@ -711,63 +701,9 @@ static const void* stage_in(DevBuf& buf, const void* src, size_t bytes, int mem,
     return buf.p;
 }
 
-// what the generate entries share -----------------------------------------------------------------------------------------
-// per-sentence lengths against the caller's row capacity, the KV cache and the mel position table
-static void gpt_check_lengths(const GptCfg& c, int n, const int32_t* prompt_rows, const int32_t* max_new, int cap,
-                              const std::string& who) {
-    for (int i = 0; i < n; ++i) {
-        MI_REQUIRE(prompt_rows[i] >= 1 && max_new[i] >= 0 && max_new[i] <= cap, who + ": prompt_rows / max_new");
-        MI_REQUIRE(max_new[i] == 0 || prompt_rows[i] + max_new[i] - 1 <= c.max_seq, who + ": prompt + max_new exceeds the KV cache (max_seq)");
-        MI_REQUIRE(max_new[i] <= c.max_mel_pos, who + ": max_new exceeds the mel position table");
-    }
-}
-
-// the stop ids on the host, from the host or the device
-static std::vector<int32_t> gpt_fetch_stops(const int32_t* stop_ids, int n_stop, int mem, const std::string& who) {
-    MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
-    std::vector<int32_t> stops(n_stop);
-    if (n_stop) {
-        if (mem == MI_HOST) std::copy(stop_ids, stop_ids + n_stop, stops.begin());
-        else MI_HIP(hipMemcpy(stops.data(), stop_ids, (size_t)n_stop * 4, hipMemcpyDeviceToHost));
-    }
-    return stops;
-}
-
-// the state words of a sentence about to start: limit = its max_new (0: none), done = it generates nothing
-static std::vector<int32_t> gpt_state_words(const std::vector<int32_t>& stops, int penalty_range, int limit, bool done) {
-    std::vector<int32_t> w(GS_WORDS, 0);
-    w[GS_NSTOP] = (int32_t)stops.size(); w[GS_RANGE] = penalty_range; w[GS_UPDATE_PEN] = 1; w[GS_LIMIT] = limit;
-    std::copy(stops.begin(), stops.end(), w.begin() + GS_STOP0);
-    if (done) w[GS_DONE] = 1;
-    return w;
-}
-
-// penalty rows := the caller's `rows` vectors, or ones; row r goes to slot r * stride (beam search: a group's first slot)
-static void gpt_fill_penalty(Gpt& e, int rows, const float* src, hipMemcpyKind in_kind, int stride = 1) {
-    const int copies = stride == 1 ? 1 : rows;             // adjacent rows go in one copy
-    const size_t n = e.cfg.mel_codes, len = (size_t)rows / copies * n;
-    std::vector<float> ones;
-    if (!src) ones.assign(len, 1.f);
-    for (size_t r = 0; r < (size_t)copies; ++r) {
-        float* dst = e.pen.as<float>() + r * stride * n;
-        if (src) MI_HIP(hipMemcpyAsync(dst, src + r * len, len * 4, in_kind, e.stream));
-        else MI_HIP(hipMemcpyAsync(dst, ones.data(), len * 4, hipMemcpyHostToDevice, e.stream));
-    }
-    if (!src) MI_HIP(hipStreamSynchronize(e.stream));      // `ones` is done with
-}
-
-// the state words of slots 0 .. all.size() / GS_WORDS - 1 -> all; true when every stride-th slot is done
-static bool gpt_read_states(Gpt& e, std::vector<int32_t>& all, int stride = 1) {
-    MI_HIP(hipMemcpyAsync(all.data(), e.state.p, all.size() * 4, hipMemcpyDeviceToHost, e.stream));
-    MI_HIP(hipStreamSynchronize(e.stream));
-    bool done = true;
-    for (size_t b = 0; b < all.size() / GS_WORDS; b += stride) done &= all[b * GS_WORDS + GS_DONE] != 0;
-    return done;
-}
-
 int mi_gpt_text_embed(mi_gpt* h, const int32_t* text_ids, int n, float* out, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_text_embed");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_text_embed");
         Gpt& e = *h->impl;
         MI_REQUIRE(out && n >= 0 && (n == 0 || text_ids), "mi_gpt_text_embed: null argument");
         MI_REQUIRE(n + 2 <= e.cfg.max_text_pos, "mi_gpt_text_embed: text is longer than the text position table");
@@ -786,7 +722,7 @@ int mi_gpt_text_embed(mi_gpt* h, const int32_t* text_ids, int n, float* out, int
 
 int mi_gpt_mel_embed(mi_gpt* h, int32_t gpt_id, int64_t gen_len, float* out, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_mel_embed");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_mel_embed");
         Gpt& e = *h->impl;
         MI_REQUIRE(out != nullptr, "mi_gpt_mel_embed: null output");
         const size_t ob = (size_t)e.cfg.hidden * 4;
@@ -800,10 +736,7 @@ int mi_gpt_mel_embed(mi_gpt* h, int32_t gpt_id, int64_t gen_len, float* out, int
 
 int mi_gpt_reset(mi_gpt* h) {
     return guard([&] {
-        MI_REQUIRE(h && h->impl, "mi_gpt_reset: null handle");
-        std::lock_guard<std::mutex> lk_(h->mu);
-        GPT_NO_SESSION(h, "mi_gpt_reset");
-        MI_HIP(hipSetDevice(h->impl->device));
+        const auto lk_ = gpt_enter(h, MI_HOST, "mi_gpt_reset", true);
         h->impl->reset();
     });
 }
@@ -816,8 +749,7 @@ int64_t mi_gpt_history_len(mi_gpt* h) {
 int mi_gpt_step(mi_gpt* h, const float* hidden_state, int ids_len, const float* repeat_penality, int attention_mask,
                 float* last_hidden_state, int32_t* max_logit_id, float* logits, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_step");
-        GPT_NO_SESSION(h, "mi_gpt_step");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_step", true);
         Gpt& e = *h->impl;
         const GptCfg& c = e.cfg;
         MI_REQUIRE(hidden_state && ids_len >= 1, "mi_gpt_step: hidden_state must hold at least one row");
@@ -839,7 +771,7 @@ int mi_gpt_step(mi_gpt* h, const float* hidden_state, int ids_len, const float* 
 
 int mi_gpt_kv_read(mi_gpt* h, int layer, float* keys, float* values, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_kv_read");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_kv_read");
         Gpt& e = *h->impl;
         const size_t n = (size_t)e.cfg.hidden * e.history * 4;
         if (n == 0) return;
@@ -856,8 +788,7 @@ int mi_gpt_kv_read(mi_gpt* h, int layer, float* keys, float* values, int mem) {
 
 int mi_gpt_kv_write(mi_gpt* h, int layer, const float* keys, const float* values, int hist, int mem) {
     return guard([&] {
-        GPT_CHECK(h, mem, "mi_gpt_kv_write");
-        GPT_NO_SESSION(h, "mi_gpt_kv_write");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_kv_write", true);
         Gpt& e = *h->impl;
         MI_REQUIRE(hist >= 0 && hist < e.cfg.max_seq, "mi_gpt_kv_write: history does not fit the KV cache (max_seq)");
         MI_REQUIRE(hist == 0 || (keys && values), "mi_gpt_kv_write: null keys/values");
@@ -868,39 +799,10 @@ int mi_gpt_kv_write(mi_gpt* h, int layer, const float* keys, const float* values
     });
 }
 
-// the calls that follow on the handle choose tokens by sampling (off: greedy); greedy again when the scope ends.  With `recs`
-// the records of slots 0 .. nb-1 are uploaded as well (null: greedy); the queue uploads a slot's record when it admits a sentence.
-struct GptModeScope {
-    Gpt& e;
-    GptModeScope(Gpt& g, bool on) : e(g) {
-        if (on) MI_REQUIRE(e.cfg.mel_codes <= GPT_SAMPLE_MAX_CODES, "gpt: sampling supports at most 16384 mel codes");
-        e.sampled = on ? 1 : 0;
-    }
-    GptModeScope(Gpt& g, const GptSampleRec* recs, int nb) : GptModeScope(g, recs != nullptr) {
-        if (recs) e.set_sampling(recs, nb);
-    }
-    ~GptModeScope() { e.sampled = 0; }
-};
-
-// one sentence's parameters, validated -> the device record
-static GptSampleRec gpt_sample_rec(float temperature, int top_k, float top_p, uint64_t seed) {
-    MI_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "gpt sampling: temperature must be finite and > 0");
-    MI_REQUIRE(top_k >= 0, "gpt sampling: top_k must be >= 0 (0 = every code)");
-    MI_REQUIRE(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "gpt sampling: top_p must be in (0, 1]");
-    GptSampleRec r{};
-    r.inv_T = 1.0f / temperature; r.top_p = top_p; r.top_k = top_k;
-    r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
-    return r;
-}
-
 static void gpt_generate_impl(mi_gpt* h, const float* prompt, int P, int max_new, const int32_t* stop_ids, int n_stop,
                               float repeat_value, int penalty_range, float* repeat_penality, int32_t* tokens, float* hidden,
                               int32_t* n_out, int mem, const GptSampleRec* rec, const std::string& who) {
-    MI_REQUIRE(h && h->impl, who + ": null handle");
-    std::lock_guard<std::mutex> lk_(h->mu);
-    MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
-    GPT_NO_SESSION(h, who);
-    MI_HIP(hipSetDevice(h->impl->device));
+    const auto lk_ = gpt_enter(h, mem, who, true);
     Gpt& e = *h->impl;
     const GptCfg& c = e.cfg;
     GptModeScope mode(e, rec, 1);
@@ -958,11 +860,7 @@ static void gpt_generate_batch_impl(mi_gpt* h, int nb, const float* prompts, con
                                     const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
                                     float* repeat_penality, int32_t* tokens, float* hidden, int cap, int32_t* n_out, int mem,
                                     const GptSampleRec* recs, const std::string& who) {
-    MI_REQUIRE(h && h->impl, who + ": null handle");
-    std::lock_guard<std::mutex> lk_(h->mu);
-    MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
-    GPT_NO_SESSION(h, who);
-    MI_HIP(hipSetDevice(h->impl->device));
+    const auto lk_ = gpt_enter(h, mem, who, true);
     Gpt& e = *h->impl;
     const GptCfg& c = e.cfg;
     MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
@@ -1028,298 +926,27 @@ int mi_gpt_generate_batch_sampled(mi_gpt* h, int nb, const float* prompts, const
     });
 }
 
-// Sentence queue (include/mi355tts.h, "sentence queue"): n sentences through S = min(max_batch, n) slots, a slot refilled as
-// soon as its sentence stops, every prompt pass packed (Gpt::forward_packed).  The policy is the header's, step by step.  The
-// loop lives in a session (mi_gpt_queue_begin / _advance / _end) that stops after every run of decode steps; the blocking entry
-// is a session driven to its end inside one call.
-// With beams (B != 0; the "_beam" entries) the unit of the schedule is a group: sentence -> B consecutive slots, group g = slots
-// gB .. gB + B - 1, S = min(max_batch / B, n) groups; owner / live / the policy's "slot" count groups.  B == 0 is the greedy or
-// sampled queue and launches exactly what it launched before groups existed.
-struct GptQueue {
-    int n = 0, cap = 0, mem = MI_HOST, S = 0, penalty_range = 0;
-    int B = 0;                       // beams per sentence, 0 = no beam search
-    float* scores = nullptr;         // beams: the caller's (n) scores or null, alive until the session ends
-    std::vector<float> h_sc;         // MI_HOST: the scores of a round, on the host
-    bool any_samp = false;
-    bool per_round = false;          // sessions: tokens and rows leave after every round; blocking entry: at retirement only
-    bool ended = false;              // the loop has run out: nothing live, nothing waiting
-    const float* prompts = nullptr;  // the caller's, alive until the session ends
-    int32_t* tokens = nullptr;
-    float* hidden = nullptr;
-    std::vector<int32_t> prompt_rows, max_new, stops, all, n_out, copied;
-    std::vector<GptSampleRec> recs;
-    std::vector<size_t> row0;
-    std::vector<int> owner;          // the sentence in each slot, -1 = free
-    std::vector<char> retired;
-    int next = 0, live = 0;
-    long steps = 0, passes = 0;
-    Gpt::OutTable tab;               // the copy-out entries gathered since the last launch
-    int n_tab = 0;
-    std::vector<int32_t> h_tok;      // MI_HOST: what the copy-out kernel packed, on the host
-    std::vector<float> h_hid;
-};
-
-static void gpt_queue_free(GptQueue* q) { delete q; }
-
-// validation (all of it before anything is launched) and the start state: every slot finished, nothing admitted
-static void gpt_queue_setup(Gpt& e, GptQueue& q, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
-                            const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
-                            int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
-                            const std::string& who, int B = 0, float* scores = nullptr) {
-    const GptCfg& c = e.cfg;
-    if (B) {                                                     // mi_gpt_generate_beam's checks on num_beams
-        MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
-        MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
-        MI_REQUIRE(B <= c.max_batch, who + ": num_beams exceeds the handle's max_batch");
-    }
-    MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
-    MI_REQUIRE(prompts && prompt_rows && max_new && cap >= 1, who + ": null argument");
-    q.stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
-    q.any_samp = temperature || top_k || top_p || seeds;
-    MI_REQUIRE(!q.any_samp || (temperature && top_k && top_p && seeds), who + ": the four sampling arrays come together or not at all");
-    gpt_check_lengths(c, n, prompt_rows, max_new, cap, who);
-    q.n = n; q.cap = cap; q.mem = mem; q.penalty_range = penalty_range;
-    q.prompts = prompts; q.tokens = tokens; q.hidden = hidden;
-    q.B = B; q.scores = scores;
-    q.prompt_rows.assign(prompt_rows, prompt_rows + n);
-    q.max_new.assign(max_new, max_new + n);
-    q.row0.resize(n);
-    size_t rows_total = 0;
-    for (int i = 0; i < n; ++i) { q.row0[i] = rows_total; rows_total += (size_t)prompt_rows[i]; }
-    GptModeScope mode(e, q.any_samp);                            // (checks that the handle can sample)
-    q.recs.resize(q.any_samp ? n : 0);
-    for (int i = 0; i < (int)q.recs.size(); ++i) q.recs[i] = gpt_sample_rec(temperature[i], top_k[i], top_p[i], seeds[i]);
-    hipStream_t s = e.stream;
-    e.set_rep_value(repeat_value);
-    const int W = B ? B : 1;                                     // slots per unit of the schedule
-    q.S = std::min(c.max_batch / W, n);
-    if (B) e.beam_ensure();
-    // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
-    q.all.assign((size_t)q.S * W * GS_WORDS, 0);
-    for (int b = 0; b < q.S * W; ++b) q.all[(size_t)b * GS_WORDS + GS_DONE] = 1;
-    MI_HIP(hipMemcpyAsync(e.state.p, q.all.data(), q.all.size() * 4, hipMemcpyHostToDevice, s));
-    MI_HIP(hipStreamSynchronize(s));
-    q.owner.assign(q.S, -1);
-    q.n_out.assign(n, 0); q.copied.assign(n, 0); q.retired.assign(n, 0);
-    q.next = 0; q.live = 0; q.steps = 0; q.passes = 0; q.n_tab = 0; q.ended = false;
-    while (q.next < n && q.max_new[q.next] == 0) ++q.next;
-}
-
-// sessions: rows [copied_i, upto) of sentence i, held by slot b, join the round's copy-out table
-static void gpt_queue_note(GptQueue& q, int b, int i, int upto) {
-    if (upto <= q.copied[i]) return;
-    MI_REQUIRE(q.n_tab < GPT_MAX_BATCH, "gpt queue: copy-out table overflow");
-    Gpt::OutSeg& g = q.tab.e[q.n_tab++];
-    g.slot = b; g.first = q.copied[i]; g.count = upto - q.copied[i]; g.sentence = i;
-    g.dst_row = (int64_t)i * q.cap + q.copied[i];
-    q.copied[i] = upto;
-}
-
-// sessions: the table's rows leave in one launch.  MI_DEVICE: straight into the caller's arrays.  MI_HOST: packed into the
-// staging buffers, one device-to-host copy per array, then placed by the host (synchronises).
-static void gpt_queue_flush(Gpt& e, GptQueue& q) {
-    if (q.n_tab == 0) return;
-    const int h = e.cfg.hidden;
-    if (q.mem == MI_DEVICE) {
-        e.copy_out_rows(q.tab, q.n_tab, q.tokens, q.hidden);
-    } else {
-        Gpt::OutTable packed = q.tab;
-        size_t rows = 0;
-        for (int k = 0; k < q.n_tab; ++k) { packed.e[k].dst_row = (int64_t)rows; rows += (size_t)q.tab.e[k].count; }
-        e.io_a.ensure(rows * 4); e.io_b.ensure(rows * h * 4);
-        q.h_tok.resize(rows); q.h_hid.resize(rows * h);
-        e.copy_out_rows(packed, q.n_tab, q.tokens ? e.io_a.as<int32_t>() : nullptr, q.hidden ? e.io_b.as<float>() : nullptr);
-        if (q.tokens) MI_HIP(hipMemcpyAsync(q.h_tok.data(), e.io_a.p, rows * 4, hipMemcpyDeviceToHost, e.stream));
-        if (q.hidden) MI_HIP(hipMemcpyAsync(q.h_hid.data(), e.io_b.p, rows * h * 4, hipMemcpyDeviceToHost, e.stream));
-        MI_HIP(hipStreamSynchronize(e.stream));
-        for (int k = 0; k < q.n_tab; ++k) {
-            const Gpt::OutSeg& g = q.tab.e[k];
-            const size_t src = (size_t)packed.e[k].dst_row, dst = (size_t)g.dst_row;
-            if (q.tokens) std::memcpy(q.tokens + dst, q.h_tok.data() + src, (size_t)g.count * 4);
-            if (q.hidden) std::memcpy(q.hidden + dst * h, q.h_hid.data() + src * h, (size_t)g.count * h * 4);
-        }
-    }
-    q.n_tab = 0;
-}
-
-// beams: sentence i, held by the group whose first slot is `slot`, joins the round's retirement table with all its nt tokens
-static void gpt_queue_note_beam(GptQueue& q, int slot, int i, int nt) {
-    MI_REQUIRE(q.n_tab < GPT_MAX_BATCH, "gpt queue: retirement table overflow");
-    Gpt::OutSeg& g = q.tab.e[q.n_tab++];
-    g.slot = slot; g.first = 0; g.count = nt; g.sentence = i;
-    g.dst_row = (int64_t)i * q.cap;
-    q.copied[i] = nt;
-}
-
-// beams: every group of the table leaves in one launch (Gpt::beam_out_rows): hypothesis 0's tokens and rows along its ancestors,
-// and its score.  MI_DEVICE: straight into the caller's arrays.  MI_HOST: packed into the staging buffers, one device-to-host
-// copy per array, then placed by the host (synchronises), as gpt_queue_flush does.
-static void gpt_queue_flush_beam(Gpt& e, GptQueue& q) {
-    if (q.n_tab == 0) return;
-    const int h = e.cfg.hidden;
-    if (q.mem == MI_DEVICE) {
-        e.beam_out_rows(q.tab, q.n_tab, q.B, q.tokens, q.hidden, q.scores);
-    } else {
-        Gpt::OutTable packed = q.tab;
-        size_t rows = 0;
-        for (int k = 0; k < q.n_tab; ++k) {
-            packed.e[k].dst_row = (int64_t)rows; packed.e[k].sentence = k;
-            rows += (size_t)q.tab.e[k].count;
-        }
-        e.io_a.ensure(rows * 4); e.io_b.ensure(rows * h * 4); e.io_s.ensure((size_t)q.n_tab * 4);
-        q.h_tok.resize(rows); q.h_hid.resize(rows * h); q.h_sc.resize(q.n_tab);
-        e.beam_out_rows(packed, q.n_tab, q.B, q.tokens ? e.io_a.as<int32_t>() : nullptr, q.hidden ? e.io_b.as<float>() : nullptr,
-                        q.scores ? e.io_s.as<float>() : nullptr);
-        if (q.tokens && rows) MI_HIP(hipMemcpyAsync(q.h_tok.data(), e.io_a.p, rows * 4, hipMemcpyDeviceToHost, e.stream));
-        if (q.hidden && rows) MI_HIP(hipMemcpyAsync(q.h_hid.data(), e.io_b.p, rows * h * 4, hipMemcpyDeviceToHost, e.stream));
-        if (q.scores) MI_HIP(hipMemcpyAsync(q.h_sc.data(), e.io_s.p, (size_t)q.n_tab * 4, hipMemcpyDeviceToHost, e.stream));
-        MI_HIP(hipStreamSynchronize(e.stream));
-        for (int k = 0; k < q.n_tab; ++k) {
-            const Gpt::OutSeg& g = q.tab.e[k];
-            const size_t src = (size_t)packed.e[k].dst_row, dst = (size_t)g.dst_row;
-            if (q.tokens) std::memcpy(q.tokens + dst, q.h_tok.data() + src, (size_t)g.count * 4);
-            if (q.hidden) std::memcpy(q.hidden + dst * h, q.h_hid.data() + src * h, (size_t)g.count * h * 4);
-            if (q.scores) q.scores[g.sentence] = q.h_sc[k];
-        }
-    }
-    q.n_tab = 0;
-}
-
-// beams: the B slots of a refilled group get the sentence's state words, the group's first slot its side-0 penalty row of ones
-// (selection 0 reads side 0: GS_NDEC = 0), both in stream order behind the retirement launch of the tenant before.  Nothing
-// else of that tenant can be read (checked against gpt_beam.hip):
-//   - ancestor tables: selection n copies entries [0, nprev = n) from the side it reads and writes entry n, so from nprev = 0
-//     on every entry below n of the side in use was written by this sentence; attention, the reset lookup and retirement read
-//     entries below GS_NDEC only;
-//   - scores: selection 0 (`first`) starts every candidate from 0 and never adds the scores it loaded;
-//   - penalties: selection 0 reads the first slot's side-0 row alone (parent 0) and writes all B rows of side 1; selection 1
-//     reads those and writes all B rows of side 0: side 1, and rows 1 .. B-1 of side 0, are written before they are read;
-//   - toks / hid: selection n writes row n of every slot of the group before GS_NDEC becomes n + 1, and every read is of a
-//     row below GS_NDEC, so a stale row lies at an index >= ndec;
-//   - the KV cache: the pass rewrites the prompt's rows in the first slot, a decode step writes position P + n - 1 of its own
-//     slot before its attention reads it, and no key at or beyond the history is visited.
-static void gpt_queue_admit_group(Gpt& e, GptQueue& q, int slot, int i) {
-    const std::vector<int32_t> w = gpt_state_words(q.stops, q.penalty_range, q.max_new[i], false);
-    std::vector<int32_t> ws((size_t)q.B * GS_WORDS);
-    for (int b = 0; b < q.B; ++b) std::copy(w.begin(), w.end(), ws.begin() + (size_t)b * GS_WORDS);
-    MI_REQUIRE(slot >= 0 && slot + q.B <= e.cfg.max_batch, "gpt queue: group slot");
-    MI_HIP(hipMemcpyAsync(e.state.as<int32_t>() + (size_t)slot * GS_WORDS, ws.data(), ws.size() * 4, hipMemcpyHostToDevice, e.stream));
-    MI_HIP(hipStreamSynchronize(e.stream));                      // `ws` is done with
-    e.reset_penalty(slot);
-}
-
-// One round of the policy: admit and retire until nothing more can be admitted, then one run of c <= 16 decode steps and a look
-// at the states.  Returns false when there was nothing left to decode (the queue has ended).
-static bool gpt_queue_round(Gpt& e, GptQueue& q, const std::string& who) {
-    const GptCfg& c = e.cfg;
-    hipStream_t s = e.stream;
-    const int n = q.n, S = q.S, B = q.B, W = B ? B : 1;          // S units (slots, or groups of B slots), unit u = slots uW ..
-    const hipMemcpyKind in = q.mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    std::vector<int32_t>& all = q.all;
-    std::vector<int>& owner = q.owner;
-    auto skip_empty = [&] { while (q.next < n && q.max_new[q.next] == 0) ++q.next; };
-    for (;;) {
-        // 1. admit: passes of the waiting sentences into the free slots, in index order, lowest free slot first
-        bool ran = false;
-        while (q.live < S && q.next < n) {
-            Gpt::Seg segs[GPT_MAX_BATCH];
-            int k = 0, total = 0;
-            while (q.live < S && q.next < n) {
-                const int rows = q.prompt_rows[q.next];
-                if (k > 0 && total + rows > c.max_seq) break;        // the first sentence of a pass always fits
-                int unit = 0;
-                while (owner[unit] >= 0) ++unit;
-                owner[unit] = q.next; ++q.live;
-                const int slot = unit * W;
-                if (B) {
-                    gpt_queue_admit_group(e, q, slot, q.next);
-                } else {
-                    e.set_state(gpt_state_words(q.stops, q.penalty_range, q.max_new[q.next], false), slot);
-                    e.reset_penalty(slot);
-                    if (q.any_samp) e.set_sampling_slot(&q.recs[q.next], slot);
-                }
-                MI_HIP(hipMemcpyAsync(e.X.as<float>() + (size_t)total * c.hidden, q.prompts + q.row0[q.next] * c.hidden,
-                                      (size_t)rows * c.hidden * 4, in, s));
-                segs[k].first = total; segs[k].rows = rows; segs[k].slot = slot; segs[k].pad = 0;
-                ++k; total += rows;
-                ++q.next;
-                skip_empty();
-            }
-            e.forward_packed(segs, k);
-            ++q.passes;
-            ran = true;
-        }
-        if (ran) gpt_read_states(e, all);
-        // 2. retire every finished slot: its tokens and rows go out, the slot is free
-        bool freed = false;
-        for (int u = 0; u < S; ++u) {
-            const int i = owner[u], b = u * W;
-            if (i < 0 || !all[(size_t)b * GS_WORDS + GS_DONE]) continue;
-            const int nt = std::min(all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[i]);
-            q.n_out[i] = nt;
-            if (B) {
-                gpt_queue_note_beam(q, b, i, nt);                // the whole sentence: no row of it was final before
-            } else if (q.per_round) {
-                gpt_queue_note(q, b, i, nt);                     // what the rounds before have not moved yet
-            } else {
-                copy_out(q.tokens ? q.tokens + (size_t)i * q.cap : nullptr, e.toks.as<int32_t>() + (size_t)b * c.max_seq, (size_t)nt * 4, q.mem, s);
-                copy_out(q.hidden ? q.hidden + (size_t)i * q.cap * c.hidden : nullptr, e.hid.as<float>() + (size_t)b * c.max_seq * c.hidden,
-                         (size_t)nt * c.hidden * 4, q.mem, s);
-            }
-            q.retired[i] = 1;
-            owner[u] = -1; --q.live;
-            freed = true;
-        }
-        if (B) gpt_queue_flush_beam(e, q);                       // in stream order before a pass can refill the groups
-        else if (q.per_round) gpt_queue_flush(e, q);             // in stream order before a pass can refill the slots
-        if (freed && q.next < n) continue;                       // refill before the next decode step
-        // 3. finish, or decode up to the nearest limit (at most 16 steps) and look again
-        if (q.live == 0) { q.ended = true; return false; }
-        int cs = 16;
-        for (int u = 0; u < S; ++u)
-            if (owner[u] >= 0) cs = std::min(cs, q.max_new[owner[u]] - all[(size_t)u * W * GS_WORDS + GS_NDEC]);
-        MI_REQUIRE(cs >= 1, who + ": a live slot is at its limit");
-        if (B) e.decode_beam_steps(S, B, cs);
-        else e.decode_batch_steps(S, cs);
-        q.steps += cs;
-        gpt_read_states(e, all);
-        return true;
-    }
-}
-
-// the handle runs beam groups (forward_rows / forward_packed leave the token choice to selection 0) until the scope ends
-struct GptBeamScope {
-    Gpt& e;
-    GptBeamScope(Gpt& g, int B) : e(g) { e.beams = B; }
-    ~GptBeamScope() { e.beams = 0; }
-};
-
-// the blocking entries: a session driven to its end inside one call (num_beams == 0: no beam search)
-static int gpt_generate_queue_impl(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
-                                   const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
-                                   float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
-                                   const float* top_p, const uint64_t* seeds, int32_t* stats, const char* name, bool beam,
-                                   int num_beams, float* scores) {
+// Sentence queue (gpt_queue.h; include/mi355tts.h, "sentence queue"): the four entries that open one list their arguments as
+// GptQueueArgs.  The blocking entries: a session driven to its end inside one call
+static int gpt_queue_run(mi_gpt* h, const GptQueueArgs& a, int32_t* n_out, int32_t* stats) {
     return guard([&] {
-        const std::string who = name;
-        MI_REQUIRE(h && h->impl, who + ": null handle");
-        std::lock_guard<std::mutex> lk_(h->mu);
-        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
-        MI_HIP(hipSetDevice(h->impl->device));
-        GPT_NO_SESSION(h, who);
+        const auto lk_ = gpt_enter(h, a.mem, a.who, true);
+        MI_REQUIRE(n_out != nullptr, std::string(a.who) + ": null argument");
         Gpt& e = *h->impl;
-        MI_REQUIRE(n_out != nullptr, who + ": null argument");
-        MI_REQUIRE(!beam || num_beams >= 1, who + ": num_beams must be in [1, 8]");
-        GptQueue q;
-        gpt_queue_setup(e, q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap, mem,
-                        temperature, top_k, top_p, seeds, who, beam ? num_beams : 0, scores);
-        GptModeScope mode(e, q.any_samp);
-        GptBeamScope group(e, q.B);
-        while (gpt_queue_round(e, q, who)) {}
-        for (int i = 0; i < n; ++i) n_out[i] = q.n_out[i];
-        e.history = q.all[GS_HIST];
-        MI_HIP(hipStreamSynchronize(e.stream));
-        if (stats) { stats[0] = (int32_t)q.steps; stats[1] = (int32_t)q.passes; }
+        GptQueue q(e, a);
+        GptModeScope mode(e, q.sampled());
+        GptBeamScope group(e, q.beams());
+        while (q.round()) {}
+        q.settle();
+        q.report(n_out, nullptr, nullptr, stats);
+    });
+}
+
+static int gpt_queue_open(mi_gpt* h, GptQueueArgs a) {
+    return guard([&] {
+        const auto lk_ = gpt_enter(h, a.mem, a.who, true);
+        a.per_round = true;
+        h->session.reset(new GptQueue(*h->impl, a));
     });
 }
 
@@ -1327,102 +954,62 @@ int mi_gpt_generate_queue(mi_gpt* h, int n, const float* prompts, const int32_t*
                           const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
                           float* hidden, int cap, int32_t* n_out, int mem, const float* temperature, const int32_t* top_k,
                           const float* top_p, const uint64_t* seeds, int32_t* stats) {
-    return gpt_generate_queue_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden,
-                                   cap, n_out, mem, temperature, top_k, top_p, seeds, stats, "mi_gpt_generate_queue", false, 0, nullptr);
+    return gpt_queue_run(h, {"mi_gpt_generate_queue", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                             tokens, hidden, cap, mem, temperature, top_k, top_p, seeds}, n_out, stats);
 }
 
 int mi_gpt_generate_queue_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                                const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
                                int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem, int32_t* stats) {
-    return gpt_generate_queue_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden,
-                                   cap, n_out, mem, nullptr, nullptr, nullptr, nullptr, stats, "mi_gpt_generate_queue_beam", true,
-                                   num_beams, scores);
-}
-
-static int gpt_queue_begin_impl(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
-                                const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens,
-                                float* hidden, int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p,
-                                const uint64_t* seeds, const char* name, bool beam, int num_beams, float* scores) {
-    return guard([&] {
-        const std::string who = name;
-        MI_REQUIRE(h && h->impl, who + ": null handle");
-        std::lock_guard<std::mutex> lk_(h->mu);
-        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
-        MI_HIP(hipSetDevice(h->impl->device));
-        GPT_NO_SESSION(h, who);
-        Gpt& e = *h->impl;
-        MI_REQUIRE(!beam || num_beams >= 1, who + ": num_beams must be in [1, 8]");
-        std::unique_ptr<GptQueue> q(new GptQueue);
-        gpt_queue_setup(e, *q, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
-                        mem, temperature, top_k, top_p, seeds, who, beam ? num_beams : 0, scores);
-        q->per_round = true;
-        h->session = q.release();
-    });
+    return gpt_queue_run(h, {"mi_gpt_generate_queue_beam", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                             tokens, hidden, cap, mem, nullptr, nullptr, nullptr, nullptr, true, num_beams, scores}, n_out, stats);
 }
 
 int mi_gpt_queue_begin(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                        const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int32_t* tokens, float* hidden,
                        int cap, int mem, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds) {
-    return gpt_queue_begin_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
-                                mem, temperature, top_k, top_p, seeds, "mi_gpt_queue_begin", false, 0, nullptr);
+    return gpt_queue_open(h, {"mi_gpt_queue_begin", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                              tokens, hidden, cap, mem, temperature, top_k, top_p, seeds});
 }
 
 int mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                             const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
                             int32_t* tokens, float* hidden, int cap, float* scores, int mem) {
-    return gpt_queue_begin_impl(h, n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range, tokens, hidden, cap,
-                                mem, nullptr, nullptr, nullptr, nullptr, "mi_gpt_queue_begin_beam", true, num_beams, scores);
+    return gpt_queue_open(h, {"mi_gpt_queue_begin_beam", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                              tokens, hidden, cap, mem, nullptr, nullptr, nullptr, nullptr, true, num_beams, scores});
 }
 
 int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* finished, int32_t* stats) {
     return guard([&] {
         const std::string who = "mi_gpt_queue_advance";
-        MI_REQUIRE(h && h->impl, who + ": null handle");
-        std::lock_guard<std::mutex> lk_(h->mu);
+        const auto lk_ = gpt_enter(h, MI_HOST, who);
         if (!h->session) throw mi::Error(MI_ESTATE, who + ": no session is open on this handle");
         MI_REQUIRE(count && done && finished, who + ": null argument");
-        MI_HIP(hipSetDevice(h->impl->device));
         Gpt& e = *h->impl;
         GptQueue& q = *h->session;
-        if (!q.ended) {
-            GptModeScope mode(e, q.any_samp);
-            GptBeamScope group(e, q.B);
-            if (gpt_queue_round(e, q, who) && !q.B) {
-                // everything the live slots hold by now, finished ones included (they are retired by the next round).  With beams
-                // nothing leaves here: no row of a live group is final, the whole sentence leaves when its group is retired.
-                for (int b = 0; b < q.S; ++b)
-                    if (q.owner[b] >= 0)
-                        gpt_queue_note(q, b, q.owner[b], std::min(q.all[(size_t)b * GS_WORDS + GS_NDEC], q.max_new[q.owner[b]]));
-                gpt_queue_flush(e, q);
-            }
-            e.history = q.all[GS_HIST];
-            MI_HIP(hipStreamSynchronize(e.stream));
+        if (!q.ended()) {
+            GptModeScope mode(e, q.sampled());
+            GptBeamScope group(e, q.beams());
+            if (q.round()) q.publish_live();
+            q.settle();
         }
-        bool fin = q.next >= q.n;
-        for (int i = 0; i < q.n; ++i) { count[i] = q.n_out[i]; done[i] = q.retired[i] || q.max_new[i] == 0; }
-        for (int b = 0; b < q.S; ++b) {
-            const int i = q.owner[b];
-            if (i < 0) continue;
-            count[i] = q.copied[i];
-            // beams: unit b is a group, and a finished group is done for the caller once it has been retired (count = n_out)
-            done[i] = q.B ? 0 : q.all[(size_t)b * GS_WORDS + GS_DONE] != 0;
-            fin = fin && done[i];
-        }
-        *finished = fin ? 1 : 0;
-        if (stats) { stats[0] = (int32_t)q.steps; stats[1] = (int32_t)q.passes; }
+        q.report(count, done, finished, stats);
     });
 }
 
 int mi_gpt_queue_end(mi_gpt* h) {
     return guard([&] {
-        MI_REQUIRE(h && h->impl, "mi_gpt_queue_end: null handle");
-        std::lock_guard<std::mutex> lk_(h->mu);
+        const auto lk_ = gpt_enter(h, MI_HOST, "mi_gpt_queue_end");
         if (!h->session) throw mi::Error(MI_ESTATE, "mi_gpt_queue_end: no session is open on this handle");
-        MI_HIP(hipSetDevice(h->impl->device));
         (void)hipStreamSynchronize(h->impl->stream);                 // nothing of the session is in flight when its arrays go
-        gpt_queue_free(h->session);
-        h->session = nullptr;
+        h->session.reset();
     });
+}
+
+// tests and tools: the queue's policy object driven on the host alone; no handle, no GPU
+int mi_gpt_queue_schedule(int n, const int32_t* prompt_rows, const int32_t* max_new, const int32_t* lengths, int slots, int max_seq,
+                          int beams, int32_t* steps, int32_t* n_passes, int32_t* pass_of, int32_t* unit_of) {
+    return guard([&] { gpt_queue_schedule(n, prompt_rows, max_new, lengths, slots, max_seq, beams, steps, n_passes, pass_of, unit_of); });
 }
 
 // beam search (gpt_beam.hip): gpt_generate_batch_impl's loop over nb groups of B slots
@@ -1431,8 +1018,7 @@ int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t*
                          int num_beams, int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem) {
     return guard([&] {
         const std::string who = "mi_gpt_generate_beam";
-        GPT_CHECK(h, mem, "mi_gpt_generate_beam");
-        GPT_NO_SESSION(h, "mi_gpt_generate_beam");
+        const auto lk_ = gpt_enter(h, mem, "mi_gpt_generate_beam", true);
         Gpt& e = *h->impl;
         const GptCfg& c = e.cfg;
         const int B = num_beams;
@@ -1444,8 +1030,7 @@ int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t*
         const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
         const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
         gpt_check_lengths(c, nb, prompt_rows, max_new, cap, who);
-        struct BeamScope { Gpt& e; ~BeamScope() { e.beams = 0; } } scope{e};
-        e.beams = B;
+        GptBeamScope group(e, B);
         e.sampled = 0;
         e.beam_ensure();
         const int nr = nb * B;
@@ -1534,8 +1119,7 @@ int mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_
 int mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* temperature, const int32_t* top_k, const float* top_p,
                       double* us) {
     return guard([&] {
-        GPT_CHECK(h, MI_HOST, "mi_gpt_bench_pick");
-        GPT_NO_SESSION(h, "mi_gpt_bench_pick");
+        const auto lk_ = gpt_enter(h, MI_HOST, "mi_gpt_bench_pick", true);
         Gpt& e = *h->impl;
         MI_REQUIRE(us && nb >= 1 && nb <= e.cfg.max_batch && iters >= 1, "mi_gpt_bench_pick: bad arguments");
         std::vector<GptSampleRec> recs;

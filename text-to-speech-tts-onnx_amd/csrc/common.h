@@ -81,6 +81,12 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// a result to the caller's array (host or device by `mem`; a null array is not wanted), in stream order
+inline void copy_out(void* dst, const void* src, size_t bytes, int mem, hipStream_t s) {
+    if (!dst) return;
+    MI_HIP(hipMemcpyAsync(dst, src, bytes, mem == MI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+}
+
 // host fp32 -> device tensor of dtype dt
 void upload_as(DevBuf& dst, const float* src, size_t n, int dt, hipStream_t s);
 void upload_f32(DevBuf& dst, const float* src, size_t n, hipStream_t s);

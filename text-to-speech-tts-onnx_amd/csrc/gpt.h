@@ -93,7 +93,7 @@ struct Gpt {
     DevBuf segtab;            // the pass's segments on the device (max_batch entries)
     bool packed_ready = false;
     void forward_packed(const Seg* segs, int k);
-    // queue sessions (capi.hip): tokens and last_hidden_state rows [first, first + count) of `slot` -> rows dst_row .. of the
+    // queue sessions (gpt_queue.hip): tokens and last_hidden_state rows [first, first + count) of `slot` -> rows dst_row .. of the
     // destination arrays (either may be null), every entry of the table in ONE launch, in stream order (gpt_prompt.hip)
     struct OutSeg { int32_t slot, first, count, sentence; int64_t dst_row; };
     struct OutTable { OutSeg e[GPT_MAX_BATCH]; };

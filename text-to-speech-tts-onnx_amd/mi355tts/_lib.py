@@ -167,6 +167,9 @@ def load() -> C.CDLL:
         L.mi_gpt_queue_begin_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
                                               C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
         L.mi_gpt_queue_begin_beam.restype = C.c_int
+    if hasattr(L, "mi_gpt_queue_schedule"):
+        L.mi_gpt_queue_schedule.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.mi_gpt_queue_schedule.restype = C.c_int
     L.mi_gpt_sample_logits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.mi_gpt_sample_logits.restype = C.c_int
     L.mi_gpt_generate_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,

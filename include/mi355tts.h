@@ -540,6 +540,15 @@ int         mi_gpt_bench_pick(mi_gpt* h, int nb, int iters, const float* tempera
 int         mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int iters,
                                double* ms);
 
+/* host only, no device needed: the launch plan of that same convolution (the arguments of mi_bench_conv_gemm, at the process's
+ * options) on a device of `cus` compute units.  *n_launches = 1, or 2 when the rows are split; plans[launch][MI_GEMM_PLAN_INTS] =
+ * kind, Tm, Tn, RT, RC, lds_epi, use_buf, grid x, y, z.  kind counts from 1 in this order: direct 256x32, direct 128x64, direct
+ * 128x128, DMA 64x64, DMA 64x64 with fp16 pairs, DMA 128 two-buffer, DMA 128 four-stage ring, ph8, x3p, x3, stream-K, dma3 at
+ * 192, at 256, at 128.  (The grouped-convolution kernels are tried before the plan and decide for themselves.)            */
+#define MI_GEMM_PLAN_INTS 10
+int         mi_conv_gemm_plan(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int cus,
+                              int32_t* plans /* [2][MI_GEMM_PLAN_INTS] */, int* n_launches);
+
 /* ---- IndexTTS graph A: prompt audio -> conditioning (cond.hip) -----------------------------------------------------------
  * Replaces ort_session_A of IndexTTS/Inference_IndexTTS_ONNX.py:700-712 (graph definition: IndexTTS_A,
  * IndexTTS/Export_IndexTTS.py:74-200): mel front end (0.1 s constant noise pad + 'constant'-padded STFT + HTK mel + log) ->

@@ -1309,14 +1309,61 @@ int mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc
     });
 }
 
+// The ConvGemm of mi_bench_conv_gemm's arguments, its operands from buf(which, bytes): device memory to launch it, aligned dummies
+// that nobody dereferences to plan it (mi_conv_gemm_plan).  Decides which operands exist: the weight planes w3 (bf16x3 kernel), the
+// panel planes xp / w3p (gemm_x3p.hip), the stream-K workspace of 1024 slots.
+extern "C++" {
+enum { BG_X, BG_W, BG_BIAS, BG_OUT, BG_RES, BG_W3, BG_XP, BG_W3P, BG_SK_WS, BG_SK_FLAGS, BG_COUNT };
+template <typename F> static ConvGemm bench_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, F&& buf) {
+    const size_t es = dtype_size(dtype), nx = (size_t)B * T * Cin, nw = (size_t)N * taps * Cin, no = (size_t)B * T * N;
+    ConvGemm p;
+    p.dtype = dtype; p.x = buf(BG_X, nx * es); p.w = buf(BG_W, nw * es); p.bias = (const float*)buf(BG_BIAS, (size_t)N * 4); p.out = buf(BG_OUT, no * es);
+    p.res = with_res ? buf(BG_RES, no * es) : nullptr;
+    p.B = B; p.T_in = T; p.M = T; p.N = N; p.Cin = Cin; p.taps = taps; p.dil = dil; p.pad = (taps * dil - dil) / 2;
+    p.x_bstride = (long)T * Cin; p.x_rstride = Cin; p.out_bstride = (long)T * N; p.out_rstride = N;
+    p.sk_slots = 1024; p.sk_ws = (float*)buf(BG_SK_WS, (size_t)p.sk_slots * 128 * 128 * 4); p.sk_flags = (int*)buf(BG_SK_FLAGS, (size_t)p.sk_slots * 4);
+    if (dtype == MI_F32 && taps == 1 && gemm_x3_enabled()) p.w3 = buf(BG_W3, (size_t)3 * nw * 2);      // the bf16x3 kernel needs the weight planes
+    if (p.w3 && gemm_x3p_enabled() && N % 128 == 0 && Cin % 32 == 0 && p.pad == 0) {       // ... and the panel-plane form (gemm_x3p.hip)
+        p.np = x3p_planes();
+        p.xp = buf(BG_XP, (size_t)x3p_bytes((long)B * T, Cin, p.np)); p.w3p = buf(BG_W3P, (size_t)x3p_bytes(N, Cin, p.np));
+    }
+    return p;
+}
+}  // extern "C++"
+
+int mi_conv_gemm_plan(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int cus, int32_t* plans, int* n_launches) {
+    return guard([&] {
+        MI_REQUIRE(plans && n_launches && (dtype == MI_F32 || dtype == MI_F16 || dtype == MI_BF16) && B > 0 && T > 0 && Cin > 0 && N > 0 && taps > 0 && dil > 0 && cus > 0,
+                   "mi_conv_gemm_plan: bad arguments");
+        ConvGemm p = bench_gemm(dtype, B, T, Cin, N, taps, dil, with_res, [](int which, size_t) { return (void*)(uintptr_t)(4096 * (which + 1)); });
+        gemm_one_m_axis(p);
+        int n = 0;
+        for (;;) {
+            const GemmPlan g = gemm_plan(p, cus);
+            const int32_t row[MI_GEMM_PLAN_INTS] = {g.kind, g.Tm, g.Tn, g.RT, g.RC, g.lds_epi, g.use_buf, (int32_t)g.grid[0], (int32_t)g.grid[1], (int32_t)g.grid[2]};
+            std::memcpy(plans + (size_t)n++ * MI_GEMM_PLAN_INTS, row, sizeof(row));
+            if (!g.split_rows || n == 2) break;
+            p.M = p.T_in = p.M - g.split_rows;        // the rest of a row split is a problem of its own (pointers: nobody reads them here)
+        }
+        *n_launches = n;
+    });
+}
+
 int mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int dil, int with_res, int iters, double* ms) {
     return guard([&] {
         MI_REQUIRE(ms && B > 0 && T > 0 && Cin > 0 && N > 0 && taps > 0 && iters > 0, "mi_bench_conv_gemm: bad arguments");
         hipStream_t s;
         MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         const size_t es = dtype_size(dtype);
-        DevBuf x, w, o, r, bias;
         const size_t nx = (size_t)B * T * Cin, nw = (size_t)N * taps * Cin, no = (size_t)B * T * N;
+        DevBuf bufs[BG_COUNT];
+        SkWorkspace skw;
+        ConvGemm p = bench_gemm(dtype, B, T, Cin, N, taps, dil, with_res, [&](int which, size_t bytes) -> void* {
+            if (which == BG_SK_WS || which == BG_SK_FLAGS) { skw.ensure(1024, s); return which == BG_SK_WS ? skw.ws.p : skw.flags.p; }
+            bufs[which].ensure(bytes);
+            return bufs[which].p;
+        });
+        DevBuf &x = bufs[BG_X], &w = bufs[BG_W], &w3p = bufs[BG_W3P];
         std::vector<float> hx(nx), hw(nw), hb(N, 0.01f);
         uint32_t st = 12345;
         auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; };
@@ -1326,35 +1373,18 @@ int mi_bench_conv_gemm(int dtype, int B, int T, int Cin, int N, int taps, int di
         // MI355TTS_BENCH_WSETS=n: cycle through n copies of the weights (n * bytes > 256 MiB MALL => every launch
         // streams cold weights from HBM, like consecutive layers of a real model)
         const int nsets = std::max(1, (int)env_int("MI355TTS_BENCH_WSETS", 1));
-        upload_as(x, hx.data(), nx, dtype, s); upload_as(w, hw.data(), nw, dtype, s); upload_f32(bias, hb.data(), N, s);
+        upload_as(x, hx.data(), nx, dtype, s); upload_as(w, hw.data(), nw, dtype, s); upload_f32(bufs[BG_BIAS], hb.data(), N, s);
         DevBuf wsets;
         if (nsets > 1) {
             wsets.ensure((size_t)nsets * nw * es);
             for (int i = 0; i < nsets; ++i)
                 MI_HIP(hipMemcpyAsync((char*)wsets.p + (size_t)i * nw * es, w.p, nw * es, hipMemcpyDeviceToDevice, s));
         }
-        o.ensure(no * es); r.ensure(no * es);
-        MI_HIP(hipMemsetAsync(r.p, 0, no * es, s));
-        ConvGemm p;
-        p.dtype = dtype; p.x = x.p; p.w = w.p; p.bias = bias.as<float>(); p.out = o.p; p.res = with_res ? r.p : nullptr;
-        p.B = B; p.T_in = T; p.M = T; p.N = N; p.Cin = Cin; p.taps = taps; p.dil = dil; p.pad = (taps * dil - dil) / 2;
-        p.x_bstride = (long)T * Cin; p.x_rstride = Cin; p.out_bstride = (long)T * N; p.out_rstride = N;
-        SkWorkspace skw;
-        skw.ensure(1024, s);
-        skw.attach(p);
-        DevBuf w3;
-        if (dtype == MI_F32 && taps == 1 && gemm_x3_enabled()) {      // the bf16x3 kernel needs the weight planes
-            w3.ensure((size_t)3 * nw * 2);
-            split3_planes((const float*)w.p, w3.p, (long)nw, s);
-            p.w3 = w3.p;
-        }
-        DevBuf xp, w3p;
-        if (p.w3 && gemm_x3p_enabled() && N % 128 == 0 && Cin % 32 == 0 && p.pad == 0) {       // ... and the panel-plane form (gemm_x3p.hip)
-            const int np = x3p_planes();
-            xp.ensure((size_t)x3p_bytes((long)B * T, Cin, np)); w3p.ensure((size_t)x3p_bytes(N, Cin, np));
-            x3p_split_rows((const float*)x.p, Cin, xp.p, B * T, Cin, s, np);
-            x3p_split_rows((const float*)w.p, Cin, w3p.p, N, Cin, s, np);
-            p.xp = xp.p; p.w3p = w3p.p; p.np = np;
+        if (p.res) MI_HIP(hipMemsetAsync(bufs[BG_RES].p, 0, no * es, s));
+        if (p.w3) split3_planes((const float*)w.p, bufs[BG_W3].p, (long)nw, s);
+        if (p.xp) {
+            x3p_split_rows((const float*)x.p, Cin, bufs[BG_XP].p, B * T, Cin, s, p.np);
+            x3p_split_rows((const float*)w.p, Cin, w3p.p, N, Cin, s, p.np);
         }
         // panel-plane launches with MI355TTS_BENCH_WSETS: n copies of the weight PLANES (the kernel never reads p.w)
         DevBuf w3psets;

@@ -207,7 +207,23 @@ struct ConvGemm {
 };
 constexpr int LN_BLK = 32;        // columns per partial-statistics block of the AdaLN fold
 void launch_conv_gemm(const ConvGemm& p, hipStream_t s);
-bool gemm_ln_fold_ok(const ConvGemm& p);           // will launch_conv_gemm(p) run on a kernel whose epilogue has the fold (ln_* fields)?
+// The launch plan of launch_conv_gemm(p) on a device of `cus` compute units (gemm_conv.hip): the one decision that the dispatch
+// switches on and the queries below read.  One kind per family of launch statements.
+enum GemmKind { GEMM_NONE = 0, GEMM_DIRECT_256x32, GEMM_DIRECT_128x64, GEMM_DIRECT_128x128, GEMM_DMA64, GEMM_DMA64_PAIRS, GEMM_DMA128,
+                GEMM_DMA128_RING4, GEMM_PH8, GEMM_X3P, GEMM_X3, GEMM_SK, GEMM_DMA3_192, GEMM_DMA3_256, GEMM_DMA3_128 };
+struct GemmPlan {
+    int kind;                                  // GemmKind
+    int Tm, Tn, RT, RC, use_buf, lds_epi;      // what ConvGemmDev carries to the kernel under these names (x3p: its launcher tiles it)
+    int sk_stages;                             // GEMM_SK: option gemm_sk_stages
+    unsigned grid[3];                          // ph8 / x3p / x3 / stream-K size theirs in their own launchers from the CU count: for those kinds a
+                                               // mirror that no launch reads (mi_conv_gemm_plan reports it), held by the census fixture only (no ph8 split tail there)
+    bool fold_epi;                             // the kind's epilogue carries the AdaLN fold (ln_* fields)
+    bool planes_out;                           // ... and may be given out_planes
+    int split_rows;                            // > 0: the plan covers the first split_rows rows; the rest is a problem planned by itself
+};
+void gemm_one_m_axis(ConvGemm& p);              // a one-tap batch over contiguous items becomes one M axis (B = 1): launch_conv_gemm's first step
+GemmPlan gemm_plan(const ConvGemm& p, int cus);    // p as given: flatten a batch with gemm_one_m_axis first, as the launch does
+bool gemm_ln_fold_ok(const ConvGemm& p, int cus);  // will launch_conv_gemm(p), given the fold's operands, run on kernels whose epilogue has the fold?
 // gemm_x3p.hip panel planes: [panel = row / 128][chunk = k / 32][plane 0..2][row % 128][32 bf16], the four 16-byte k-slots of a
 // 64-byte row XOR-swizzled by (row >> 2) & 3
 constexpr int X3P_PLANE = 128 * 32 * 2;          // one plane of one (panel, chunk): 128 rows x 64 bytes
@@ -232,8 +248,8 @@ size_t gconv16_image_bytes(int G, int taps);
 void gconv16_build_weights(const void* w, int dtype, void* img, int G, int taps, hipStream_t s);
 int x3p_planes();                                  // option "gemm_f32_planes": the format new planes are built in (3 or 2)
 bool gemm_x3p_enabled();
-bool gemm_x3p_would_run(const ConvGemm& p);        // p.xp / p.w3p set: will launch_conv_gemm(p) take the panel-plane kernel?
-bool gemm_x3p_can_write_planes(const ConvGemm& p); // ... and may it be given out_planes (needs the LDS-staged epilogue: N >= 1024)?
+bool gemm_x3p_would_run(const ConvGemm& p, int cus);        // p.xp / p.w3p set: will launch_conv_gemm(p) take the panel-plane kernel?
+bool gemm_x3p_can_write_planes(const ConvGemm& p, int cus); // ... and may it be given out_planes (needs the LDS-staged epilogue: N >= 1024)?
 // owner of a stream-K workspace (one per engine handle / stream)
 struct SkWorkspace {
     DevBuf ws, flags; int slots = 0;

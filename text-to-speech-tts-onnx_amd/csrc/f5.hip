@@ -578,7 +578,7 @@ void F5::gemm(int dt, const void* x, long xb, long xr, int K, const Lin& L, void
     if (dt == MI_F32 && L.w3p.p && g.B == 1 && Ap.p && gemm_x3p_enabled()) {
         DevBuf& ab = K <= cfg.dim ? Ap : Ap2;                      // Ap holds dim columns, Ap2 ap2_cols() (ff, or the input projection's K)
         g.xp = ab.p; g.w3p = L.w3p.p; g.np = np;
-        if (gemm_x3p_would_run(g)) {
+        if (gemm_x3p_would_run(g, device_cus())) {
             MI_REQUIRE(x3p_bytes(g.M, K, np) <= (long)ab.bytes, "F5::gemm: the panel planes of the rows do not fit their buffer");
             x3p_split_rows((const float*)x, xr, const_cast<void*>(g.xp), g.M, K, stream, np, d_sat.as<int>());
         } else {
@@ -803,6 +803,7 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
     };
     // which form: decided on block 0's layers (every block has the same shapes and the same weight formats)
     bool planes = false, fold = false;
+    const int cus = device_cus();
     {
         const Block& b0 = blocks[0];
         ConvGemm gq = qkv_gemm(b0);
@@ -811,11 +812,11 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
         ConvGemm g2 = lin(b0.ff2, ff, MI_F32, X.p); g2.x = Hff.p; g2.res = X.p; g2.gate = modk;
         if (f32 && Ap.p && gemm_x3p_enabled() && b0.qkv.w3p.p && b0.o.w3p.p && b0.ff1.w3p.p && b0.ff2.w3p.p && ap.o_planes) {
             with_planes(gq, b0.qkv, Ap.p); with_planes(go, b0.o, Ap.p); with_planes(g1, b0.ff1, Ap.p); with_planes(g2, b0.ff2, Ap2.p);
-            planes = gemm_x3p_would_run(gq) && gemm_x3p_would_run(go) && gemm_x3p_can_write_planes(g1) && gemm_x3p_would_run(g2);
+            planes = gemm_x3p_would_run(gq, cus) && gemm_x3p_would_run(go, cus) && gemm_x3p_can_write_planes(g1, cus) && gemm_x3p_would_run(g2, cus);
         }
         if (fold_built && cfg.ln_fold != 0 && (planes || !f32) && (!f32 || ApN.p) && ln_stats.p && (f32 || ln_fin.p)) {
             if (f32) { with_planes(gq, b0.qkv, ApN.p); with_planes(g1, b0.ff1, ApN.p); }
-            fold = gemm_ln_fold_ok(gq) && gemm_ln_fold_ok(go) && gemm_ln_fold_ok(g1) && gemm_ln_fold_ok(g2);
+            fold = gemm_ln_fold_ok(gq, cus) && gemm_ln_fold_ok(go, cus) && gemm_ln_fold_ok(g1, cus) && gemm_ln_fold_ok(g2, cus);
         }
     }
     if (f32 && (fold || planes)) ap = attn_plan(true);
@@ -840,7 +841,7 @@ void F5::dit_eval(int U, int N, int k, const int* lens) {
     // epilogue left in ApN; PLANES: what the row norm left in Ap), O reads the attention's planes, FF2 reads FF1's (Ap2)
     const void* normed = fold ? ApN.p : Ap.p;
     auto layer = [&](ConvGemm& g, const Lin& L, const void* xp, const char* left) {
-        if (f32) { with_planes(g, L, xp); MI_REQUIRE(gemm_x3p_would_run(g), left); }
+        if (f32) { with_planes(g, L, xp); MI_REQUIRE(gemm_x3p_would_run(g, cus), left); }
         launch_conv_gemm(g, s);
     };
     for (int i = 0; i < c.depth; ++i) {

@@ -548,251 +548,14 @@ int x3p_planes() {
 bool gemm_x3p_enabled() { return opt_x3() != 0 && opt_x3p() != 0; }
 static DevBuf g_zero_page[16];
 
-// buffer-descriptor DMA (BUF kernels): whole 64-deep chunks only, and every byte offset must fit the 32-bit range check
-static bool buf_ok(const ConvGemmDev& d, int esz = 2) {
-    const long a_bytes = (((long)d.T_in - 1) * d.x_rstride + d.Cin) * esz, b_bytes = (long)d.N * d.K * esz;
-    return opt(OPT_GEMM_BUF) && d.Cin % (128 / esz) == 0 && a_bytes + (long)512 * d.x_rstride * esz < 0x7fff0000L && b_bytes < 0x7fff0000L;
-}
-
-// a launch of dispatch_tiles: K is the uniform instantiation, KL the same tile with the lengths switch (LENS), which the
-// profiler files under K's name + " + lengths" (+ " + item bias" when the launch reads its bias by item, ConvGemm::bias_bstride)
-#define MI_LAUNCH_LN(K, KL, T_, TO_, grid, blk, lds, s, ...)                                            \
-    do {                                                                                               \
-        if constexpr (LENS) {                                                                          \
-            mi::prof_set_kernel(#K, mi::type_label<T_>(), mi::type_label<TO_>());                      \
-            mi::prof_kernel_suffix(d.bias_bstride ? " + lengths + item bias" : " + lengths");          \
-            hipLaunchKernelGGL(KL, grid, blk, lds, s, __VA_ARGS__);                                    \
-        } else {                                                                                       \
-            MI_LAUNCH(K, T_, TO_, grid, blk, lds, s, __VA_ARGS__);                                     \
-        }                                                                                              \
-    } while (0)
-
-// LENS: ragged batches (ConvGemmDev::lens) — only the kernels with the direct epilogue take them; the planner's choice of tile is the
-// uniform one, so (B, M) alone decides it
-template <typename T, typename TO, bool LENS>
-static void dispatch_tiles(const ConvGemmDev& d, int B, hipStream_t s) {
-    constexpr int KC = sizeof(T) == 4 ? 16 : 64;
-    dim3 blk(256);
-    // the AdaLN fold exists in the epilogues of linear_x3p / linear_ph8 / the 16-bit conv_gemm_dma_kernel only: anything else refuses
-    auto no_fold = [&] { MI_REQUIRE(!d.ln_stats_in && !d.ln_stats_out, "conv_gemm: this launch lands on a kernel without the AdaLN fold epilogues (gemm_ln_fold_ok disagrees with the dispatch)"); };
-    if (d.N <= 32) {
-        no_fold();
-        dim3 grid((d.M + 255) / 256, (d.N + 31) / 32, B * d.G);
-        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC>), (conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC, true>), T, TO, grid, blk, 0, s, d);
-    } else if (d.N <= 64) {
-        no_fold();
-        {
-            // N = 64 per group (the DiT position convolution: k = 31, 16 groups of 64 channels): 64x64 tiles of the LDS-DMA kernel
-            // instead of the register-staged 128x64 one (fp32: 186 -> 120 us per launch)
-            constexpr int VEC_ = 16 / (int)sizeof(T);
-            const long lim = sizeof(T) == 4 ? opt(OPT_GEMM_F32_N64_DMA) : opt(OPT_GEMM_N64_DMA16);
-            if (lim && d.N == 64 && opt(OPT_GEMM_USE_DMA) && (sizeof(T) != 4 || opt(OPT_GEMM_F32_DMA)) && d.Cin % VEC_ == 0 && d.K % d.Cin == 0) {
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 63) / 64; e.Tn = 1; e.RT = B * e.Tm; e.RC = 0;
-                e.use_buf = buf_ok(d, (int)sizeof(T));
-                dim3 g2(e.RT * e.Tn, d.G);
-                if constexpr (sizeof(T) == 4) {
-                    // fp32 with many taps (the DiT's grouped k = 31 position convolution): operands as fp16 pairs split in registers
-                    if (!LENS && opt_x3() != 0 && opt_n64_pairs() != 0 && d.K / d.Cin >= 8 && d.Cin % 32 == 0) {
-                        if (e.lds_epi) { prof_set_kernel("conv_gemm_dma_kernel<float, float, true, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, true, 2, 64, true>), g2, blk, 0, s, e); }
-                        else { prof_set_kernel("conv_gemm_dma_kernel<float, float, false, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, false, 2, 64, true>), g2, blk, 0, s, e); }
-                        MI_HIP(hipGetLastError());
-                        return;
-                    }
-                }
-                if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
-                MI_HIP(hipGetLastError());
-                return;
-            }
-        }
-        dim3 grid((d.M + 127) / 128, (d.N + 63) / 64, B * d.G);
-        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
-    } else {
-        dim3 grid((d.M + 127) / 128, (d.N + 127) / 128, B * d.G);
-        // a launch that carries the AdaLN fold (gemm_ln_fold_ok said yes) skips the 16-bit kernels without fold epilogues (dma3<192 |
-        // 256 | 128>, 16-bit stream-K) instead of refusing in the middle of an inference: e.g. dim = 1152 at ~4 utterances would
-        // otherwise land O / FF2 on dma3<192>; the fold kernels (ph8, conv_gemm_dma) take every shape those take
-        const bool fold = d.ln_stats_in || d.ln_stats_out;
-        if constexpr (sizeof(T) == 2) {
-            // many row tiles (a batch of utterances): the 8-wave 256x256 eight-phase main loop
-            const long tiles256 = (long)((d.M + 255) / 256) * ((d.N + 255) / 256);
-            if (!LENS && opt(OPT_GEMM_PH8) && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % 64 == 0 && d.pad == 0 && d.N % 64 == 0 && buf_ok(d, 2) &&
-                d.lds_epi && (d.epi == EPI_PLAIN || d.epi == EPI_QKV_ROPE) && tiles256 >= opt(OPT_GEMM_PH8_MIN_TILES)) {
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = e.Tm; e.RC = (int)opt(OPT_GEMM_PH8_ORDER);
-                launch_linear_ph8<T, TO>(e, s);
-                return;
-            }
-        }
-        if constexpr (sizeof(T) == 4) {
-            const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-            if (!LENS && d.xp && d.w3p && B == 1) {                      // both kept only when x3p_eligible() said yes (launch_conv_gemm)
-                ConvGemmDev e = d;
-                e.x = d.xp; e.w3 = d.w3p;
-                launch_linear_x3p(e, s);
-                return;
-            }
-            if (!LENS && d.w3 && B == 1 && tiles >= 64) {                // d.w3 is only kept when x3_eligible() said yes (launch_conv_gemm)
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
-                e.RC = 0;       // row tiles fastest: neighbouring ranges share the weight planes, the heavier operand here (24 of the 40 KB per chunk): 62.9 -> 61.0 us
-                if (opt(OPT_GEMM_SK_ORDER) >= 0) e.RC = (int)opt(OPT_GEMM_SK_ORDER);
-                no_fold();
-                launch_linear_x3(e, s);
-                return;
-            }
-        }
-        {
-            // plain linear layer (one tap, one group, one M axis, whole K chunks): stream-K over persistent workgroups
-            constexpr int KCB = 128 / (int)sizeof(T);
-            const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
-            if (!LENS && !(sizeof(T) == 2 && fold) && opt(OPT_GEMM_SK) >= (sizeof(T) == 4 ? 1 : 2) && d.sk_ws && d.sk_slots >= 256 && B == 1 && d.G == 1 && d.K == d.Cin && d.Cin % KCB == 0 &&
-                (d.epi == EPI_PLAIN || (d.epi == EPI_QKV_ROPE && (sizeof(T) == 2 || opt(OPT_GEMM_SK_QKV32)))) && buf_ok(d, (int)sizeof(T)) && d.M > 128 && tiles >= g_sk_min_tiles && tiles <= g_sk_max_tiles && d.pad == 0) {
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = e.Tm;
-                e.RC = d.M <= d.N ? 0 : 1;      // per-XCD groups: whole weight panels (x re-read 8x) when x is the smaller operand, else whole row tiles
-                if (opt(OPT_GEMM_SK_ORDER) >= 0) e.RC = (int)opt(OPT_GEMM_SK_ORDER);
-                e.tail_tiles = 0;
-                no_fold();
-                launch_linear_sk<T, TO>(e, (int)opt(OPT_GEMM_SK_STAGES), s);
-                return;
-            }
-        }
-        if constexpr (sizeof(T) == 2) {
-            // measured on gfx950 (tools/gemm_bench.py): with <= 32 K-chunks the 4-wave 128x128 kernel (two workgroups
-            // per CU, short prologue/epilogue) wins; deeper K favours the 8-wave 256-row tiles.
-            // N divisible by both 192 and 256 (BigVGAN stage 0, N = 768 at B = 8: 192 tiles of 256x256 leave a quarter of
-            // the CUs idle for the whole launch, 256 tiles of 256x192 fill the chip): compare rounds x tile width
-            const long rt256 = (long)B * ((d.M + 255) / 256);
-            const long rounds192 = (rt256 * (d.N / 192) + 255) / 256, rounds256 = (rt256 * ((d.N + 255) / 256) + 255) / 256;
-            bool n192_wins = d.N % 256 != 0 || (d.K > opt(OPT_GEMM_DMA3_K_MIN) && rounds192 * 192 < rounds256 * 256);
-            // LENS: there is no 256x256 instantiation with lengths (its epilogue would spill: the uniform one already spills 108
-            // VGPRs).  Where the uniform plan takes that tile below, a ragged launch takes the 256x192 tile when N allows and the
-            // 256x128 one otherwise — still a choice of (B, M) alone
-            const bool big256 = opt(OPT_GEMM_USE_DMA3) && opt(OPT_GEMM_BIG_TILES) && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > opt(OPT_GEMM_DMA3_K_MIN) && buf_ok(d) &&
-                                rt256 * ((d.N + 255) / 256) >= opt(OPT_GEMM_BIG_TILE_MIN) && (((d.N + 255) / 256) * 256 - d.N) * 4 <= d.N;
-            if (LENS && big256) n192_wins = true;
-            if (!fold && opt(OPT_GEMM_USE_DMA3) && opt(OPT_GEMM_N192) && buf_ok(d) && d.K % d.Cin == 0 && d.M > 128 && d.N % 192 == 0 && n192_wins &&
-                d.K >= 576 && (long)B * ((d.M + 255) / 256) * (d.N / 192) >= opt(OPT_GEMM_N192_MIN)) {
-                // N = 192 / 384 (BigVGAN stages 2 and 1): a 192-wide tile has no padded columns (128-wide tiles waste 25 %
-                // of the MFMAs and DMA bytes at N = 192) and the fewest DMA bytes per useful flop after 256x256
-                ConvGemmDev e = d;
-                e.RC = 0; e.Tm = (d.M + 255) / 256; e.Tn = d.N / 192; e.RT = B * e.Tm;
-                no_fold();
-                launch_conv_gemm_dma3<T, TO>(e, 192, s);
-                MI_HIP(hipGetLastError());
-                return;
-            }
-            if (!fold && opt(OPT_GEMM_USE_DMA3) && d.Cin % 8 == 0 && d.K % d.Cin == 0 && d.M > 128 && d.K > opt(OPT_GEMM_DMA3_K_MIN)) {
-                ConvGemmDev e = d;
-                e.RC = 0;
-                const long blocks_128 = (long)B * ((d.M + 127) / 128) * ((d.N + 127) / 128);
-                const long blocks_256x128 = (long)B * ((d.M + 255) / 256) * ((d.N + 127) / 128);
-                const long blocks_256x256 = (long)B * ((d.M + 255) / 256) * ((d.N + 255) / 256);
-                const int n_waste_256 = ((d.N + 255) / 256) * 256 - d.N;
-                if (!LENS && opt(OPT_GEMM_BIG_TILES) && buf_ok(d) && blocks_256x256 >= opt(OPT_GEMM_BIG_TILE_MIN) && n_waste_256 * 4 <= d.N) {
-                    // every CU busy for >= 2 rounds: the tile with the fewest DMA bytes per flop
-                    e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 255) / 256; e.RT = B * e.Tm;
-                    no_fold();
-                    launch_conv_gemm_dma3<T, TO>(e, 256, s);
-                    MI_HIP(hipGetLastError());
-                    return;
-                }
-                if (blocks_256x128 >= opt(OPT_GEMM_MID_TILE_MIN) || blocks_128 < blocks_256x128 + 32) {
-                    e.Tm = (d.M + 255) / 256; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
-                    no_fold();
-                    launch_conv_gemm_dma3<T, TO>(e, 128, s);
-                    MI_HIP(hipGetLastError());
-                    return;
-                }
-                // few tiles: fall through to the 128x128 kernel so that more CUs pull data
-            }
-            if (opt(OPT_GEMM_USE_DMA) && d.Cin % 8 == 0 && d.K % d.Cin == 0) {
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
-                e.RC = opt(OPT_GEMM_XCD_ORDER) ? (e.RT + 7) / 8 : 0;
-                e.use_buf = buf_ok(d, 2);
-                dim3 g1(e.RC > 0 ? 8 * e.RC * e.Tn : e.RT * e.Tn, d.G);
-                const int nchunks = (d.K / d.Cin) * ((d.Cin + 63) / 64);
-                if (d.epi == EPI_PLAIN && (long)g1.x * g1.y <= opt(OPT_GEMM_SMALL16_MAX)) {
-                    // at most one 128x128 tile per CU (the O / FF2 projections of one utterance: 144 tiles): 64x64 tiles put
-                    // four times as many, shorter workgroups on ALL CUs (O 15.6 -> 12.1 us, FF2 24.6 -> 21.4 us; with 288
-                    // tiles, FF1, the doubled DMA bytes per flop already cost more than the balance gains)
-                    e.Tm = (d.M + 63) / 64; e.Tn = (d.N + 63) / 64; e.RT = B * e.Tm; e.RC = 0;
-                    dim3 g2(e.RT * e.Tn, d.G);
-                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
-                    MI_HIP(hipGetLastError());
-                    return;
-                }
-                if (opt(OPT_GEMM_RING4) && (long)g1.x * g1.y <= opt(OPT_GEMM_RING4_MAX) && nchunks >= 6) {
-                    // at most one workgroup per CU: the four-stage ring hides the DMA round trip that the two-buffer
-                    // loop exposes when a CU has no second workgroup to switch to
-                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 4>), T, TO, g1, blk, 0, s, e);
-                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 4>), (conv_gemm_dma_kernel<T, TO, false, 4, 128, false, true>), T, TO, g1, blk, 0, s, e);
-                } else if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
-                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false>), (conv_gemm_dma_kernel<T, TO, false, 2, 128, false, true>), T, TO, g1, blk, 0, s, e);
-                MI_HIP(hipGetLastError());
-                return;
-            }
-        }
-        if constexpr (sizeof(T) == 4) {
-            // fp32: the same 128x128 LDS-DMA kernel with 32-float K chunks (MFMA-bound: 8x the MFMA cycles per DMA byte)
-            if (opt(OPT_GEMM_USE_DMA) && opt(OPT_GEMM_F32_DMA) && d.Cin % 4 == 0 && d.K % d.Cin == 0) {
-                no_fold();
-                ConvGemmDev e = d;
-                e.Tm = (d.M + 127) / 128; e.Tn = (d.N + 127) / 128; e.RT = B * e.Tm;
-                e.RC = opt(OPT_GEMM_XCD_ORDER) ? (e.RT + 7) / 8 : 0;
-                e.use_buf = buf_ok(d, 4);
-                if (opt(OPT_GEMM_F32_SMALL) && (long)e.RT * e.Tn * d.G < opt(OPT_GEMM_F32_SMALL_MAX)) {
-                    // fewer than a few 128x128 tiles per CU (one utterance: 144 / 288 / 432 tiles on 256 CUs): 64x64 tiles
-                    // balance the chip (O projection 144 -> 576 workgroups: makespan 3 quarter-tiles instead of 4)
-                    e.Tm = (d.M + 63) / 64; e.Tn = (d.N + 63) / 64; e.RT = B * e.Tm; e.RC = 0;
-                    dim3 g2(e.RT * e.Tn, d.G);
-                    if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true, 2, 64>), T, TO, g2, blk, 0, s, e);
-                    else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>), T, TO, g2, blk, 0, s, e);
-                    MI_HIP(hipGetLastError());
-                    return;
-                }
-                dim3 g1(e.RC > 0 ? 8 * e.RC * e.Tn : e.RT * e.Tn, d.G);
-                if (!LENS && e.lds_epi) MI_LAUNCH((conv_gemm_dma_kernel<T, TO, true>), T, TO, g1, blk, 0, s, e);
-                else MI_LAUNCH_LN((conv_gemm_dma_kernel<T, TO, false>), (conv_gemm_dma_kernel<T, TO, false, 2, 128, false, true>), T, TO, g1, blk, 0, s, e);
-                MI_HIP(hipGetLastError());
-                return;
-            }
-        }
-        no_fold();
-        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
+// one-tap GEMM over contiguous batch items: a single M axis.  launch_conv_gemm does this first; whoever asks gemm_plan about a problem
+// with B > 1 does it first too, so that the plan (and its split_rows) speaks of the rows that are launched
+void gemm_one_m_axis(ConvGemm& p) {
+    if (!p.lens && p.B > 1 && p.taps == 1 && p.G == 1 && p.pad == 0 && p.epi == EPI_PLAIN && p.M == p.T_in && p.gate_bstride == 0 &&
+        p.x_bstride == (long)p.M * p.x_rstride && p.out_bstride == (long)p.M * p.out_rstride) {
+        p.T_in = p.M = p.B * p.M; p.B = 1;
     }
-    MI_HIP(hipGetLastError());
 }
-
-// the bf16x3 kernel (gemm_x3.hip) takes this launch: decided ONCE here, because the epilogue kind depends on it
-static bool x3_eligible(const ConvGemm& p) {
-    if (!opt_x3() || !p.w3 || p.dtype != MI_F32 || (p.out_dtype >= 0 && p.out_dtype != MI_F32)) return false;
-    if (!p.sk_ws || !p.sk_flags || p.sk_slots < 256 || p.B != 1 || p.G != 1 || p.taps != 1 || p.pad != 0 || p.Cin % 32 != 0 || p.M <= 128) return false;
-    if (p.epi != EPI_PLAIN && p.epi != EPI_QKV_ROPE) return false;
-    if (p.epi == EPI_QKV_ROPE && !(p.head_dim == 64 && p.rope_pack && (p.rows_per_item == 0 ? p.M : p.rows_per_item) >= 64 &&
-                                   ((uintptr_t)p.out % 16) == 0 && ((uintptr_t)p.out2 % 16) == 0 && ((uintptr_t)p.out3 % 16) == 0)) return false;
-    const long tiles = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if (tiles < 64 || tiles > g_sk_max_tiles) return false;
-    const long a_bytes = (((long)p.T_in - 1) * p.x_rstride + p.Cin) * 4, b_bytes = (long)3 * p.N * p.Cin * 2;
-    return opt(OPT_GEMM_BUF) && a_bytes + (long)512 * p.x_rstride * 4 < 0x7fff0000L && b_bytes < 0x7fff0000L;
-}
-
-// ... and the panel-plane form of it (gemm_x3p.hip): whole 128-column weight panels, whole 32-deep chunks
-static bool x3p_eligible(const ConvGemm& p) {
-    if (!opt_x3p() || !p.xp || !p.w3p) return false;
-    ConvGemm q = p;
-    q.w3 = p.w3p;                                     // same conditions as the round-2 kernel (q.w3 only has to be non-null)
-    if (!x3_eligible(q)) return false;
-    const long nch = p.Cin / 32;
-    const long chb = x3p_chunk_bytes(p.np);
-    return (p.np == 2 || p.np == 3) && p.N % 128 == 0 && ((long)(p.M + 127) / 128) * nch * chb < 0x7fff0000L && ((long)p.N / 128) * nch * chb < 0x7fff0000L;
-}
-
-bool gemm_x3p_would_run(const ConvGemm& p) { return x3p_eligible(p) && p.B == 1 && p.G == 1; }
 
 // outputs leave through the LDS-staged, 16-byte-store epilogues (decided once per launch: the kernels instantiate either kind)
 static bool lds_epi_for(const ConvGemm& p, int odt, bool use_x3) {
@@ -809,46 +572,32 @@ static bool lds_epi_for(const ConvGemm& p, int odt, bool use_x3) {
            p.out_bstride % ch == 0 && ((uintptr_t)p.out % 16) == 0 && (!p.res || ((uintptr_t)p.res % 16) == 0);
 }
 
-// ... and can it leave its output as panel planes (ConvGemm::out_planes)?  Only the LDS-staged epilogue writes them, and that one is
-// chosen for wide outputs only (N >= 1024): a narrow model (dim 256: FF1 has N = 512) at a large M is eligible for the kernel but
-// not for plane output — found by the N = 4096 limit tests of round 4 (the launch refused loudly; the caller now asks first)
-bool gemm_x3p_can_write_planes(const ConvGemm& p) {
-    return gemm_x3p_would_run(p) && p.epi == EPI_PLAIN && !p.res && !p.gate && !p.accumulate && p.alpha == 1.f && p.N % 32 == 0 &&
-           lds_epi_for(p, MI_F32, true);
-}
-
-// The AdaLN fold (ConvGemm::ln_*) lives in the LDS-staged epilogues of three kernels: linear_x3p (fp32 engines), linear_ph8 and
-// conv_gemm_dma_kernel (16-bit engines).  This answers, for the caller that has to choose between the fold and a row-norm launch,
-// whether launch_conv_gemm(p) ends up on one of them; dispatch_tiles() refuses (loudly) if the two ever disagree.
-bool gemm_ln_fold_ok(const ConvGemm& p) {
-    const int odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
-    if (p.B != 1 || p.G != 1 || p.taps != 1 || p.pad != 0 || p.alpha != 1.f || p.accumulate || p.gate_bstride != 0 || p.N % 64 != 0 || p.M <= 128) return false;
-    if (p.epi != EPI_PLAIN && p.epi != EPI_QKV_ROPE) return false;
-    if (p.dtype == MI_F32) return gemm_x3p_would_run(p) && lds_epi_for(p, odt, true);
-    if (!lds_epi_for(p, odt, false) || !opt(OPT_GEMM_USE_DMA) || p.Cin % 64 != 0 || p.N <= 64) return false;
-    if (opt(OPT_GEMM_USE_DMA3) && p.Cin > opt(OPT_GEMM_DMA3_K_MIN)) return false;                    // K > 2048: the 256-row dma3 kernels are the faster choice (a preference, not a constraint: dispatch_tiles keeps fold launches off the kernels without fold epilogues)
-    return true;
-}
-
-void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
-    ConvGemm p = p_in;
-    if (!p.lens && p.B > 1 && p.taps == 1 && p.G == 1 && p.pad == 0 && p.epi == EPI_PLAIN && p.M == p.T_in && p.gate_bstride == 0 &&
-        p.x_bstride == (long)p.M * p.x_rstride && p.out_bstride == (long)p.M * p.out_rstride) {
-        p.T_in = p.M = p.B * p.M; p.B = 1;          // one-tap GEMM over contiguous batch items: a single M axis
-    }
-    const int odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
+// The launch plan: which kernel takes launch_conv_gemm(p), with which tiles, grid and epilogue.  The ONE place that reads the tile
+// options and does tile / round arithmetic: the dispatch switches on the kind, the queries below read the fields.  Pure host code
+// (no HIP call, nothing allocated, cannot throw), so it can be asked without a device: cus is the device's compute unit count.
+// p is planned as given: a batch that launch_conv_gemm would flatten goes through gemm_one_m_axis before it comes here.
+// LENS (ragged batches, ConvGemm::lens): only the kernels with the direct epilogue take them; the choice of tile is the uniform
+// one, so (B, M) alone decides it.
+GemmPlan gemm_plan(const ConvGemm& p_in, int cus) {
+    ConvGemm p = p_in;                                            // (the row split below plans the first part: M shrinks)
+    GemmPlan g = {};
+    const bool f32 = p.dtype == MI_F32, lens = p.lens != nullptr;
+    const int esz = (int)dtype_size(p.dtype), odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
+    // a launch that carries the AdaLN fold skips the 16-bit kernels without fold epilogues (dma3<192 | 256 | 128>, 16-bit stream-K)
+    // instead of being refused in the middle of an inference: e.g. dim = 1152 at ~4 utterances would otherwise land O / FF2 on
+    // dma3<192>; the fold kernels (ph8, conv_gemm_dma) take every shape those take
+    const bool fold = p.ln_stats_in || p.ln_stats_out;
     // Row split of a 16-bit linear layer whose 256x256 tiles spill into a nearly empty last round.  A batch of 8 utterances is
     // M = 18016 rows = 70.4 row tiles: N = 1024 gives 284 tiles on 256 CUs — a full round and then 28 tiles with 228 CUs idle for
     // as long again (O / FF2 ran at 312 TFLOP/s against ~600 for QKV / FF1); N = 2048: 568 = two rounds + 56.  The rows of whole
-    // rounds (M1 = a multiple of 256 * CUs / column tiles) go to the eight-phase kernel as before, the remaining rows (1632
-    // here) are a second launch that the dispatch below hands to the 128x128 kernels: 104 / 208 small tiles instead of a round
-    // of big ones.  Rows are independent in every EPI_PLAIN epilogue (bias, activation, gate per column, residual per element).
+    // rounds (a multiple of 256 * CUs / column tiles) are planned here, for the eight-phase kernel as before; the remaining rows
+    // (1632 here) are a second problem, planned by itself, that lands on the 128x128 kernels: 104 / 208 small tiles instead of a
+    // round of big ones.  Rows are independent in every EPI_PLAIN epilogue (bias, activation, gate per column, residual per element).
     const bool split_plain = p.epi == EPI_PLAIN && p.gate_bstride == 0 && !p.out_planes && !p.accumulate;
     const bool split_qkv = p.epi == EPI_QKV_ROPE && p.rows_per_item >= 32 && !p.kv_planes && p.m_off == 0;   // the epilogue indexes
                                                       // tokens from the flattened row: the second launch carries its row offset (m_off)
-    if (!p.lens && opt(OPT_GEMM_ROW_SPLIT) != 0 && opt(OPT_GEMM_PH8) != 0 && dtype_size(p.dtype) == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
+    if (!lens && cus > 0 && opt(OPT_GEMM_ROW_SPLIT) != 0 && opt(OPT_GEMM_PH8) != 0 && esz == 2 && p.B == 1 && p.G == 1 && p.taps == 1 && p.pad == 0 &&
         (split_plain || split_qkv) && p.M == p.T_in && p.N % 256 == 0 && !p.xp) {
-        const int cus = device_cus();
         const long ntn = p.N / 256;
         long gc = cus, t = ntn;
         while (t) { const long u = gc % t; gc = t; t = u; }       // gcd(cus, ntn)
@@ -856,35 +605,242 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
         const long r = (p.M / 256) / rstep * rstep;               // N = 1024 / 2048 / 3072 on 256 CUs: multiples of 64 / 32 / 64
         const long rem = p.M - 256 * r;
         const long rem_tiles = (rem + 255) / 256 * ntn;
-        if (r >= 1 && rem > 0 && rem_tiles * 2 < cus && r * ntn >= opt(OPT_GEMM_PH8_MIN_TILES)) {
-            ConvGemm a = p, b = p;
-            a.M = a.T_in = (int)(256 * r);
-            b.M = b.T_in = (int)rem;
-            b.x = (const char*)p.x + (size_t)(256 * r) * p.x_rstride * dtype_size(p.dtype);
-            if (split_qkv) b.m_off = (int)(256 * r);       // (the fold's statistics are indexed by the flattened row there too)
-            else {
-                b.out = (char*)p.out + (size_t)(256 * r) * p.out_rstride * dtype_size(odt);
-                if (p.res) b.res = (const char*)p.res + (size_t)(256 * r) * p.out_rstride * dtype_size(odt);
-                // AdaLN fold: the per-row operands of the second launch start at its first row (16-bit engines: ln_out is rows [M][N])
-                if (p.ln_stats_in) b.ln_stats_in = p.ln_stats_in + (size_t)(256 * r) * (p.ln_final ? 1 : p.ln_dim / LN_BLK) * 2;
-                if (p.ln_stats_out) {
-                    b.ln_stats_out = p.ln_stats_out + (size_t)(256 * r) * (p.N / LN_BLK) * 2;
-                    b.ln_out = (char*)p.ln_out + (size_t)(256 * r) * p.N * dtype_size(p.dtype);
-                }
+        if (r >= 1 && rem > 0 && rem_tiles * 2 < cus && r * ntn >= opt(OPT_GEMM_PH8_MIN_TILES)) p.M = p.T_in = g.split_rows = (int)(256 * r);
+    }
+    const int B = p.B, G = p.G, M = p.M, N = p.N, Cin = p.Cin, K = p.taps * p.Cin;
+    const long m64 = (M + 63) / 64, m128 = (M + 127) / 128, m256 = (M + 255) / 256, n128 = (N + 127) / 128, n256 = (N + 255) / 256;
+    const long tiles = m128 * n128, LIM = 0x7fff0000L;
+    const bool plain_or_qkv = p.epi == EPI_PLAIN || p.epi == EPI_QKV_ROPE;
+    // buffer-descriptor DMA (BUF kernels): whole 64-deep chunks only, and every byte offset must fit the 32-bit range check
+    const long a_elems = ((long)p.T_in - 1) * p.x_rstride + Cin + (long)512 * p.x_rstride;
+    const bool buf = opt(OPT_GEMM_BUF) && Cin % (128 / esz) == 0 && a_elems * esz < LIM && (long)N * K * esz < LIM;
+    // fp32 linear layers on the 16-bit pipes.  x3: the bf16x3 kernel (gemm_x3.hip), weights as planes; x3p: its panel-plane form
+    // (gemm_x3p.hip), both operands as planes: whole 128-column weight panels, whole 32-deep chunks.  Decided before the epilogue
+    // kind, which depends on it
+    const bool x3_shape = !lens && f32 && opt_x3() && odt == MI_F32 && p.sk_ws && p.sk_flags && p.sk_slots >= 256 && B == 1 && G == 1 && p.taps == 1 &&
+                          p.pad == 0 && Cin % 32 == 0 && M > 128 && tiles >= 64 && tiles <= g_sk_max_tiles &&
+                          (p.epi == EPI_PLAIN || (p.epi == EPI_QKV_ROPE && p.head_dim == 64 && p.rope_pack && (p.rows_per_item == 0 ? M : p.rows_per_item) >= 64 &&
+                                                  ((uintptr_t)p.out % 16) == 0 && ((uintptr_t)p.out2 % 16) == 0 && ((uintptr_t)p.out3 % 16) == 0)) &&
+                          opt(OPT_GEMM_BUF) && a_elems * 4 < LIM && (long)3 * N * Cin * 2 < LIM;
+    const long nch = Cin / 32, chb = x3p_chunk_bytes(p.np);
+    const bool x3p = x3_shape && opt_x3p() && p.xp && p.w3p && (p.np == 2 || p.np == 3) && N % 128 == 0 && m128 * nch * chb < LIM && (N / 128) * nch * chb < LIM;
+    const bool x3 = x3_shape && p.w3 && !x3p;
+    g.lds_epi = !lens && lds_epi_for(p, odt, x3 || x3p);          // the LENS kernels have the direct epilogue only
+
+    auto tile = [&](int kind, long Tm, long Tn, long RT, long RC) { g.kind = kind; g.Tm = (int)Tm; g.Tn = (int)Tn; g.RT = (int)RT; g.RC = (int)RC; };
+    auto grid = [&](long x, long y, long z) { g.grid[0] = (unsigned)x; g.grid[1] = (unsigned)y; g.grid[2] = (unsigned)z; };
+    if (N <= 32) {
+        tile(GEMM_DIRECT_256x32, 0, 0, 0, 0);
+        grid(m256, (N + 31) / 32, B * G);
+    } else if (N <= 64) {
+        // N = 64 per group (the DiT position convolution: k = 31, 16 groups of 64 channels): 64x64 tiles of the LDS-DMA kernel
+        // instead of the register-staged 128x64 one (fp32: 186 -> 120 us per launch)
+        if ((f32 ? opt(OPT_GEMM_F32_N64_DMA) : opt(OPT_GEMM_N64_DMA16)) && N == 64 && opt(OPT_GEMM_USE_DMA) && (!f32 || opt(OPT_GEMM_F32_DMA)) && Cin % (16 / esz) == 0) {
+            // fp32 with many taps (the DiT's grouped k = 31 position convolution): operands as fp16 pairs split in registers
+            const bool pairs = f32 && !lens && opt_x3() != 0 && opt_n64_pairs() != 0 && p.taps >= 8 && Cin % 32 == 0;
+            tile(pairs ? GEMM_DMA64_PAIRS : GEMM_DMA64, m64, 1, B * m64, 0);
+            g.use_buf = buf;
+            grid(g.RT * g.Tn, G, 1);
+        } else {
+            tile(GEMM_DIRECT_128x64, 0, 0, 0, 0);
+            grid(m128, (N + 63) / 64, B * G);
+        }
+    } else if (esz == 2 && !lens && opt(OPT_GEMM_PH8) && B == 1 && G == 1 && p.taps == 1 && Cin % 64 == 0 && p.pad == 0 && N % 64 == 0 && buf && g.lds_epi &&
+               plain_or_qkv && m256 * n256 >= opt(OPT_GEMM_PH8_MIN_TILES)) {
+        // many row tiles (a batch of utterances): the 8-wave 256x256 eight-phase main loop
+        tile(GEMM_PH8, m256, n256, m256, opt(OPT_GEMM_PH8_ORDER));
+        g.fold_epi = true;
+        // the grid as launch_linear_ph8 sizes it: whole tiles in groups of 8, the tiles of a mostly empty last round cut into S K-slices
+        const int T_all = g.Tm * g.Tn, nk = K / 64, rem = T_all % cus;
+        int S = 1;
+        if (T_all > cus && rem > 0 && rem * 2 <= cus && p.sk_ws && p.sk_flags && nk >= opt(OPT_GEMM_PH8_SPLIT_MIN_NK))
+            for (int c = 2; c <= (int)opt(OPT_GEMM_PH8_SPLIT_MAX); ++c)
+                if (rem * c <= cus && nk / c >= 4 && (long)rem * (c - 1) * 4 <= p.sk_slots) S = c;
+        const int tail = S > 1 ? rem : 0;
+        grid(8 * ((T_all - tail + 7) / 8) + tail * S, 1, 1);
+    } else if (x3p) {
+        tile(GEMM_X3P, 0, 0, 0, 0);                                // launch_linear_x3p tiles it: exact fit (gemm_x3d.hip) or stream-K over XCD bands
+        g.fold_epi = g.lds_epi;
+        g.planes_out = g.lds_epi && p.epi == EPI_PLAIN && !p.res && !p.gate && !p.accumulate && p.alpha == 1.f && N % 32 == 0;
+        ConvGemmDev e = {};
+        e.np = p.np; e.lds_epi = g.lds_epi; e.M = M; e.N = N; e.K = K; e.epi = p.epi;
+        int tw, rgn, cgn, band;
+        if (x3d_plan(e, cus, tw, rgn, cgn, band)) grid(((long)rgn * cgn + 7) / 8 * 8, 1, 1);
+        else grid(std::min(cus, p.sk_slots - 8) & ~7, 1, 1);
+    } else if (x3) {
+        // row tiles fastest: neighbouring ranges share the weight planes, the heavier operand here (24 of the 40 KB per chunk): 62.9 -> 61.0 us
+        tile(GEMM_X3, m128, n128, m128, opt(OPT_GEMM_SK_ORDER) >= 0 ? opt(OPT_GEMM_SK_ORDER) : 0);
+        grid(std::min(cus, p.sk_slots) & ~7, 1, 1);
+    } else if (!lens && !(esz == 2 && fold) && opt(OPT_GEMM_SK) >= (f32 ? 1 : 2) && p.sk_ws && p.sk_slots >= 256 && B == 1 && G == 1 && p.taps == 1 && Cin % (128 / esz) == 0 &&
+               (p.epi == EPI_PLAIN || (p.epi == EPI_QKV_ROPE && (esz == 2 || opt(OPT_GEMM_SK_QKV32)))) && buf && M > 128 && tiles >= g_sk_min_tiles && tiles <= g_sk_max_tiles && p.pad == 0) {
+        // plain linear layer (one tap, one group, one M axis, whole K chunks): stream-K over persistent workgroups.
+        // per-XCD groups: whole weight panels (x re-read 8x) when x is the smaller operand, else whole row tiles
+        tile(GEMM_SK, m128, n128, m128, opt(OPT_GEMM_SK_ORDER) >= 0 ? opt(OPT_GEMM_SK_ORDER) : (M <= N ? 0 : 1));
+        g.sk_stages = (int)opt(OPT_GEMM_SK_STAGES);
+        const int nst = g.sk_stages ? g.sk_stages : (f32 ? 3 : 2);
+        grid(std::min(cus * (nst <= 2 ? 2 : 1), p.sk_slots) & ~7, 1, 1);
+    } else {
+        if (esz == 2) {
+            // measured on gfx950 (tools/gemm_bench.py): with <= 32 K-chunks the 4-wave 128x128 kernel (two workgroups
+            // per CU, short prologue/epilogue) wins; deeper K favours the 8-wave 256-row tiles.
+            // N divisible by both 192 and 256 (BigVGAN stage 0, N = 768 at B = 8: 192 tiles of 256x256 leave a quarter of
+            // the CUs idle for the whole launch, 256 tiles of 256x192 fill the chip): compare rounds x tile width
+            const long rt256 = B * m256;
+            const bool deep = K > opt(OPT_GEMM_DMA3_K_MIN);
+            const long rounds192 = (rt256 * (N / 192) + 255) / 256, rounds256 = (rt256 * n256 + 255) / 256;
+            bool n192_wins = N % 256 != 0 || (deep && rounds192 * 192 < rounds256 * 256);
+            const bool dma3 = !fold && opt(OPT_GEMM_USE_DMA3) && M > 128;
+            // every CU busy for >= 2 rounds: the tile with the fewest DMA bytes per flop
+            const bool big256 = opt(OPT_GEMM_USE_DMA3) && opt(OPT_GEMM_BIG_TILES) && Cin % 8 == 0 && M > 128 && deep && buf && rt256 * n256 >= opt(OPT_GEMM_BIG_TILE_MIN) &&
+                                (n256 * 256 - N) * 4 <= N;
+            // LENS: there is no 256x256 instantiation with lengths (its epilogue would spill: the uniform one already spills 108
+            // VGPRs).  Where the uniform plan takes that tile below, a ragged launch takes the 256x192 tile when N allows and the
+            // 256x128 one otherwise — still a choice of (B, M) alone
+            if (lens && big256) n192_wins = true;
+            if (dma3 && opt(OPT_GEMM_N192) && buf && N % 192 == 0 && n192_wins && K >= 576 && rt256 * (N / 192) >= opt(OPT_GEMM_N192_MIN)) {
+                // N = 192 / 384 (BigVGAN stages 2 and 1): a 192-wide tile has no padded columns (128-wide tiles waste 25 %
+                // of the MFMAs and DMA bytes at N = 192) and the fewest DMA bytes per useful flop after 256x256
+                tile(GEMM_DMA3_192, m256, N / 192, rt256, 0);
+            } else if (dma3 && Cin % 8 == 0 && deep) {
+                if (!lens && big256) tile(GEMM_DMA3_256, m256, n256, rt256, 0);
+                else if (rt256 * n128 >= opt(OPT_GEMM_MID_TILE_MIN) || B * tiles < rt256 * n128 + 32) tile(GEMM_DMA3_128, m256, n128, rt256, 0);
+                // else few tiles: fall through to the 128x128 kernel so that more CUs pull data
             }
-            launch_conv_gemm(a, s);
-            launch_conv_gemm(b, s);
-            return;
+            if (g.kind != GEMM_NONE) { grid(g.RT * g.Tn, G, 1); return g; }
+        }
+        // the 128x128 LDS-DMA kernel (fp32: 32-float K chunks, MFMA-bound: 8x the MFMA cycles per DMA byte)
+        if (opt(OPT_GEMM_USE_DMA) && (f32 ? opt(OPT_GEMM_F32_DMA) && Cin % 4 == 0 : Cin % 8 == 0)) {
+            const long RT = B * m128, RC = opt(OPT_GEMM_XCD_ORDER) ? (RT + 7) / 8 : 0, g1 = (RC > 0 ? 8 * RC : RT) * n128;
+            // 16-bit: at most one 128x128 tile per CU (the O / FF2 projections of one utterance: 144 tiles): 64x64 tiles put
+            // four times as many, shorter workgroups on ALL CUs (O 15.6 -> 12.1 us, FF2 24.6 -> 21.4 us; with 288
+            // tiles, FF1, the doubled DMA bytes per flop already cost more than the balance gains).
+            // fp32: fewer than a few 128x128 tiles per CU (one utterance: 144 / 288 / 432 tiles on 256 CUs): 64x64 tiles
+            // balance the chip (O projection 144 -> 576 workgroups: makespan 3 quarter-tiles instead of 4)
+            const bool small = f32 ? opt(OPT_GEMM_F32_SMALL) && RT * n128 * G < opt(OPT_GEMM_F32_SMALL_MAX) : p.epi == EPI_PLAIN && g1 * G <= opt(OPT_GEMM_SMALL16_MAX);
+            // at most one workgroup per CU: the four-stage ring hides the DMA round trip that the two-buffer
+            // loop exposes when a CU has no second workgroup to switch to
+            const bool ring = !f32 && opt(OPT_GEMM_RING4) && g1 * G <= opt(OPT_GEMM_RING4_MAX) && p.taps * ((Cin + 63) / 64) >= 6;
+            if (small) tile(GEMM_DMA64, m64, (N + 63) / 64, B * m64, 0);
+            else tile(ring ? GEMM_DMA128_RING4 : GEMM_DMA128, m128, n128, RT, RC);
+            g.use_buf = buf;
+            g.fold_epi = !f32 && g.lds_epi;
+            grid(small ? (long)g.RT * g.Tn : g1, G, 1);
+        } else {
+            tile(GEMM_DIRECT_128x128, 0, 0, 0, 0);
+            grid(m128, n128, B * G);
         }
     }
+    return g;
+}
+
+bool gemm_x3p_would_run(const ConvGemm& p, int cus) { return p.B == 1 && gemm_plan(p, cus).kind == GEMM_X3P; }
+// ... and can it leave its output as panel planes (ConvGemm::out_planes)?  Only the LDS-staged epilogue writes them, and that one is
+// chosen for wide outputs only (N >= 1024): a narrow model (dim 256: FF1 has N = 512) at a large M is eligible for the kernel but
+// not for plane output — found by the N = 4096 limit tests of round 4 (the launch refused loudly; the caller now asks first)
+bool gemm_x3p_can_write_planes(const ConvGemm& p, int cus) { return p.B == 1 && gemm_plan(p, cus).planes_out; }
+
+// The AdaLN fold (ConvGemm::ln_*) lives in the LDS-staged epilogues of three kernels: linear_x3p (fp32 engines), linear_ph8 and
+// conv_gemm_dma_kernel (16-bit engines).  This answers, for the caller that has to choose between the fold and a row-norm launch,
+// whether launch_conv_gemm(p) with the fold's operands set ends up on them (every part of it, when its rows are split).
+bool gemm_ln_fold_ok(const ConvGemm& p, int cus) {
+    if (p.B != 1 || p.G != 1 || p.taps != 1 || p.pad != 0 || p.alpha != 1.f || p.accumulate || p.gate_bstride != 0 || p.N % 64 != 0 || p.M <= 128) return false;
+    if (p.dtype != MI_F32 && (p.Cin % 64 != 0 || !opt(OPT_GEMM_USE_DMA))) return false;                  // 16-bit engines: whole 64-deep K chunks, on the LDS-DMA kernels
+    if (p.dtype != MI_F32 && opt(OPT_GEMM_USE_DMA3) && p.Cin > opt(OPT_GEMM_DMA3_K_MIN)) return false;   // K > 2048: the 256-row dma3 kernels are the faster choice (a preference, not a constraint: the plan keeps fold launches off the kernels without fold epilogues)
+    ConvGemm q = p;
+    static const float carried = 0.f;
+    if (!q.ln_stats_in && !q.ln_stats_out) q.ln_stats_in = &carried;             // the plan only asks whether the launch carries the fold
+    const GemmPlan g = gemm_plan(q, cus);
+    if (!g.fold_epi || !g.split_rows) return g.fold_epi;
+    q.M = q.T_in = p.M - g.split_rows;                                           // the rest of a row split is a problem of its own
+    return gemm_plan(q, cus).fold_epi;
+}
+
+// a launch of dispatch_tiles: K is the uniform instantiation, KL the same tile with the lengths switch (LENS), which the
+// profiler files under K's name + " + lengths" (+ " + item bias" when the launch reads its bias by item, ConvGemm::bias_bstride)
+#define MI_LAUNCH_LN(K, KL, T_, TO_, grid, blk, lds, s, ...)                                            \
+    do {                                                                                               \
+        if constexpr (LENS) {                                                                          \
+            mi::prof_set_kernel(#K, mi::type_label<T_>(), mi::type_label<TO_>());                      \
+            mi::prof_kernel_suffix(d.bias_bstride ? " + lengths + item bias" : " + lengths");          \
+            hipLaunchKernelGGL(KL, grid, blk, lds, s, __VA_ARGS__);                                    \
+        } else {                                                                                       \
+            MI_LAUNCH(K, T_, TO_, grid, blk, lds, s, __VA_ARGS__);                                     \
+        }                                                                                              \
+    } while (0)
+// the DMA kernels: LEPI instantiation K1 when the outputs leave through the LDS-staged epilogue, else K0 (or its lengths form K0L)
+#define MI_LAUNCH_DMA(K1, K0, K0L)                                                                      \
+    do {                                                                                               \
+        if (!LENS && d.lds_epi) MI_LAUNCH(K1, T, TO, grid, blk, 0, s, d);                              \
+        else MI_LAUNCH_LN(K0, K0L, T, TO, grid, blk, 0, s, d);                                         \
+    } while (0)
+
+// d carries the plan's geometry (launch_conv_gemm); every case is the launch statement of its kind
+template <typename T, typename TO, bool LENS>
+static void dispatch_tiles(const GemmPlan& g, const ConvGemmDev& d, hipStream_t s) {
+    constexpr int KC = sizeof(T) == 4 ? 16 : 64;
+    constexpr bool F32 = sizeof(T) == 4;
+    const dim3 blk(256), grid(g.grid[0], g.grid[1], g.grid[2]);
+    // every kind ends in a launch: a kind whose kernels do not exist for T is refused, never skipped
+    auto wrong_type = [] { MI_REQUIRE(false, "conv_gemm: the plan names a kernel that does not exist for this element type"); };
+    switch (g.kind) {
+    case GEMM_DIRECT_256x32:
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC>), (conv_gemm_kernel<T, TO, 256, 32, 4, 1, KC, true>), T, TO, grid, blk, 0, s, d);
+        break;
+    case GEMM_DIRECT_128x64:
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 64, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
+        break;
+    case GEMM_DIRECT_128x128:
+        MI_LAUNCH_LN((conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC>), (conv_gemm_kernel<T, TO, 128, 128, 2, 2, KC, true>), T, TO, grid, blk, 0, s, d);
+        break;
+    case GEMM_DMA64:
+        MI_LAUNCH_DMA((conv_gemm_dma_kernel<T, TO, true, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64>), (conv_gemm_dma_kernel<T, TO, false, 2, 64, false, true>));
+        break;
+    case GEMM_DMA64_PAIRS:
+        if constexpr (!F32) wrong_type();
+        else {
+            if (d.lds_epi) { prof_set_kernel("conv_gemm_dma_kernel<float, float, true, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, true, 2, 64, true>), grid, blk, 0, s, d); }
+            else { prof_set_kernel("conv_gemm_dma_kernel<float, float, false, 2, 64, fp16 pairs>", "", ""); hipLaunchKernelGGL((conv_gemm_dma_kernel<T, TO, false, 2, 64, true>), grid, blk, 0, s, d); }
+        }
+        break;
+    case GEMM_DMA128:
+        MI_LAUNCH_DMA((conv_gemm_dma_kernel<T, TO, true>), (conv_gemm_dma_kernel<T, TO, false>), (conv_gemm_dma_kernel<T, TO, false, 2, 128, false, true>));
+        break;
+    case GEMM_DMA128_RING4:
+        if constexpr (F32) wrong_type(); else MI_LAUNCH_DMA((conv_gemm_dma_kernel<T, TO, true, 4>), (conv_gemm_dma_kernel<T, TO, false, 4>), (conv_gemm_dma_kernel<T, TO, false, 4, 128, false, true>));
+        break;
+    case GEMM_PH8:
+        if constexpr (F32) wrong_type(); else launch_linear_ph8<T, TO>(d, s);
+        break;
+    case GEMM_X3P:
+        if constexpr (!F32) wrong_type(); else launch_linear_x3p(d, s);
+        break;
+    case GEMM_X3:
+        if constexpr (!F32) wrong_type(); else launch_linear_x3(d, s);
+        break;
+    case GEMM_SK:
+        launch_linear_sk<T, TO>(d, g.sk_stages, s);
+        break;
+    case GEMM_DMA3_192: case GEMM_DMA3_256: case GEMM_DMA3_128:
+        if constexpr (F32) wrong_type(); else launch_conv_gemm_dma3<T, TO>(d, g.kind == GEMM_DMA3_192 ? 192 : g.kind == GEMM_DMA3_256 ? 256 : 128, s);
+        break;
+    default:
+        MI_REQUIRE(false, "conv_gemm: the plan names no kernel");
+    }
+    MI_HIP(hipGetLastError());
+}
+
+// argument checks, the device-side description and the launch of ONE planned problem: a whole launch, or one part of a row split
+static void launch_planned(const ConvGemm& p, const GemmPlan& plan, hipStream_t s) {
+    const int odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
     const int vec = 16 / (int)dtype_size(p.dtype);
     MI_REQUIRE(p.Cin % vec == 0, "conv_gemm: Cin must be a multiple of the 16-byte vector");
     MI_REQUIRE(p.x_rstride % vec == 0 && p.x_bstride % vec == 0 && p.x_goff % vec == 0, "conv_gemm: x strides");
     MI_REQUIRE(((uintptr_t)p.x % 16) == 0 && ((uintptr_t)p.w % 16) == 0, "conv_gemm: 16-byte alignment");
     MI_REQUIRE(odt == p.dtype || odt == MI_F32, "conv_gemm: out dtype");
     MI_REQUIRE(p.M > 0 && p.N > 0 && p.B > 0 && p.G > 0, "conv_gemm: empty problem");
+    const bool x3p = plan.kind == GEMM_X3P;
     ConvGemmDev d;
-    d.x = p.x; d.w = p.w; d.bias = p.bias; d.out = p.out; d.res = p.res; d.gate = p.gate;
+    d.x = x3p ? p.xp : p.x; d.w = p.w; d.bias = p.bias; d.out = p.out; d.res = p.res; d.gate = p.gate;
     d.gate_bstride = p.gate_bstride;
     d.G = p.G; d.T_in = p.T_in; d.M = p.M; d.N = p.N; d.Cin = p.Cin; d.K = p.taps * p.Cin; d.dil = p.dil; d.pad = p.pad;
     d.x_bstride = p.x_bstride; d.x_rstride = p.x_rstride; d.out_bstride = p.out_bstride; d.out_rstride = p.out_rstride;
@@ -896,13 +852,11 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     MI_REQUIRE(p.m_off == 0 || (p.epi == EPI_QKV_ROPE && p.rows_per_item >= 32), "conv_gemm: a row offset needs the flattened QKV epilogue");
     d.kv_planes = p.kv_planes; d.k_ld = p.k_ld; d.v_rows = p.kv_planes ? p.v_rows : 0;
     d.sk_ws = p.sk_ws; d.sk_flags = p.sk_flags; d.sk_slots = p.sk_slots;
-    const bool use_x3p = x3p_eligible(p);
-    const bool use_x3 = use_x3p || x3_eligible(p);
-    d.w3 = use_x3 ? p.w3 : nullptr;
-    d.xp = use_x3p ? p.xp : nullptr; d.w3p = use_x3p ? p.w3p : nullptr; d.np = p.np;
+    d.w3 = x3p ? p.w3p : plan.kind == GEMM_X3 ? p.w3 : nullptr;     // the plane operands reach the kernel that the plan names, nothing else
+    d.xp = x3p ? p.xp : nullptr; d.w3p = x3p ? p.w3p : nullptr; d.np = p.np;
     d.out_planes = nullptr;
     if (p.out_planes) {
-        MI_REQUIRE(use_x3p && p.epi == EPI_PLAIN && !p.res && !p.gate && !p.accumulate && p.alpha == 1.f && p.N % 32 == 0,
+        MI_REQUIRE(x3p && p.epi == EPI_PLAIN && !p.res && !p.gate && !p.accumulate && p.alpha == 1.f && p.N % 32 == 0,
                    "conv_gemm: out_planes needs the panel-plane kernel and a plain bias + activation epilogue");
         d.out_planes = p.out_planes;
     }
@@ -935,29 +889,26 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
             MI_REQUIRE(p.ln_p && p.ln_c && p.ln_dim >= 128 && p.ln_dim % 128 == 0 && !p.res && !p.gate && ((uintptr_t)p.ln_stats_in % 8) == 0 && (p.ln_final || ((uintptr_t)p.ln_stats_in % 16) == 0) &&
                            ((uintptr_t)p.ln_p % 16) == 0 && ((uintptr_t)p.ln_c % 16) == 0 && (odt != MI_F32 || p.epi == EPI_QKV_ROPE || p.out_planes),
                        "conv_gemm: AdaLN fold consumer: statistics, W(1 + scale) and W shift + b vectors");
+        // the fold exists in the epilogues of linear_x3p / linear_ph8 / the 16-bit conv_gemm_dma_kernel only: anything else refuses
+        MI_REQUIRE(plan.fold_epi, "conv_gemm: the AdaLN fold lives in the LDS-staged epilogues of linear_x3p / linear_ph8 / conv_gemm_dma (gemm_ln_fold_ok)");
     }
     d.tail_tiles = 0; d.tail_split = 1;
-    d.use_buf = 0;
+    d.Tm = plan.Tm; d.Tn = plan.Tn; d.RT = plan.RT; d.RC = plan.RC; d.use_buf = plan.use_buf; d.lds_epi = plan.lds_epi;
     {
         int dev = 0;
         MI_HIP(hipGetDevice(&dev));
-        {
-            static std::mutex zero_mu;
-            std::lock_guard<std::mutex> lk(zero_mu);
-            DevBuf& z = g_zero_page[dev & 15];
-            if (!z.p) { z.ensure(4096); MI_HIP(hipMemset(z.p, 0, 4096)); MI_HIP(hipDeviceSynchronize()); }
-            d.zero = z.p;
-        }
-        d.dbg = (int)env_int("MI355TTS_GEMM_DBG", 0);
-        // K-loop order of the DMA kernels is (channel chunk, tap), not (tap, channel chunk): sweeping all Cin channels
-        // of a block's rows once per tap overflowed the 4 MiB XCD L2 between taps at C = 384 (32 resident blocks x 196 KB
-        // of rows) and every tap re-fetched its rows from the fabric (PMC: 341 MB per launch against 100 MB algorithmic);
-        // consecutive taps now re-read the same rows x 64 channels.  fp32 accumulation: only the summation order changes.
-        // (A run-time switch between the two orders cost 12 % by itself, so the order is fixed.)
-        d.lds_epi = (!p.lens && lds_epi_for(p, odt, use_x3)) ? 1 : 0;     // the LENS kernels have the direct epilogue only
+        static std::mutex zero_mu;
+        std::lock_guard<std::mutex> lk(zero_mu);
+        DevBuf& z = g_zero_page[dev & 15];
+        if (!z.p) { z.ensure(4096); MI_HIP(hipMemset(z.p, 0, 4096)); MI_HIP(hipDeviceSynchronize()); }
+        d.zero = z.p;
     }
-    if (p.ln_stats_in || p.ln_stats_out)
-        MI_REQUIRE(d.lds_epi && (p.dtype != MI_F32 || use_x3p), "conv_gemm: the AdaLN fold lives in the LDS-staged epilogues of linear_x3p / linear_ph8 / conv_gemm_dma (gemm_ln_fold_ok)");
+    d.dbg = (int)env_int("MI355TTS_GEMM_DBG", 0);
+    // K-loop order of the DMA kernels is (channel chunk, tap), not (tap, channel chunk): sweeping all Cin channels
+    // of a block's rows once per tap overflowed the 4 MiB XCD L2 between taps at C = 384 (32 resident blocks x 196 KB
+    // of rows) and every tap re-fetched its rows from the fabric (PMC: 341 MB per launch against 100 MB algorithmic);
+    // consecutive taps now re-read the same rows x 64 channels.  fp32 accumulation: only the summation order changes.
+    // (A run-time switch between the two orders cost 12 % by itself, so the order is fixed.)
     if (p.kv_planes) MI_REQUIRE(p.epi == EPI_QKV_ROPE && p.dtype == MI_F32 && d.lds_epi && p.v_ld > 0 && p.k_ld > 0 && p.v_ld % 8 == 0,
                                 "conv_gemm: kv_planes needs the fp32 LDS-staged QKV epilogue and the padded key axes k_ld / v_ld");
     if (p.epi == EPI_CONVT) MI_REQUIRE(p.Cout > 0 && p.N == p.u * p.Cout, "conv_gemm: convT shape");
@@ -981,21 +932,50 @@ void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
     if (p.lens) {
         MI_REQUIRE(odt == p.dtype, "conv_gemm: a launch with lengths writes the engine dtype");
         MI_REQUIRE(!d.lds_epi, "conv_gemm: a launch with lengths leaves through the direct epilogue");
-        if (p.dtype == MI_F32) dispatch_tiles<float, float, true>(d, p.B, s);
-        else if (p.dtype == MI_F16) dispatch_tiles<f16, f16, true>(d, p.B, s);
-        else dispatch_tiles<bf16, bf16, true>(d, p.B, s);
+        if (p.dtype == MI_F32) dispatch_tiles<float, float, true>(plan, d, s);
+        else if (p.dtype == MI_F16) dispatch_tiles<f16, f16, true>(plan, d, s);
+        else dispatch_tiles<bf16, bf16, true>(plan, d, s);
         return;
     }
     if (p.dtype == MI_F32) {
-        dispatch_tiles<float, float, false>(d, p.B, s);
+        dispatch_tiles<float, float, false>(plan, d, s);
     } else if (p.dtype == MI_F16) {
-        if (odt == MI_F32) dispatch_tiles<f16, float, false>(d, p.B, s);
-        else dispatch_tiles<f16, f16, false>(d, p.B, s);
+        if (odt == MI_F32) dispatch_tiles<f16, float, false>(plan, d, s);
+        else dispatch_tiles<f16, f16, false>(plan, d, s);
     } else {
-        if (odt == MI_F32) dispatch_tiles<bf16, float, false>(d, p.B, s);
-        else dispatch_tiles<bf16, bf16, false>(d, p.B, s);
+        if (odt == MI_F32) dispatch_tiles<bf16, float, false>(plan, d, s);
+        else dispatch_tiles<bf16, bf16, false>(plan, d, s);
     }
 }
+
+void launch_conv_gemm(const ConvGemm& p_in, hipStream_t s) {
+    ConvGemm p = p_in;
+    gemm_one_m_axis(p);
+    const int cus = device_cus();
+    const GemmPlan plan = gemm_plan(p, cus);
+    if (!plan.split_rows) { launch_planned(p, plan, s); return; }
+    // the plan splits the rows: the first split_rows of them are the problem it planned, the rest a problem of their own
+    const int odt = p.out_dtype < 0 ? p.dtype : p.out_dtype;
+    const size_t r = (size_t)plan.split_rows;
+    ConvGemm a = p, b = p;
+    a.M = a.T_in = plan.split_rows;
+    b.M = b.T_in = p.M - plan.split_rows;
+    b.x = (const char*)p.x + r * p.x_rstride * dtype_size(p.dtype);
+    if (p.epi == EPI_QKV_ROPE) b.m_off = plan.split_rows;       // (the fold's statistics are indexed by the flattened row there too)
+    else {
+        b.out = (char*)p.out + r * p.out_rstride * dtype_size(odt);
+        if (p.res) b.res = (const char*)p.res + r * p.out_rstride * dtype_size(odt);
+        // AdaLN fold: the per-row operands of the second launch start at its first row (16-bit engines: ln_out is rows [M][N])
+        if (p.ln_stats_in) b.ln_stats_in = p.ln_stats_in + r * (p.ln_final ? 1 : p.ln_dim / LN_BLK) * 2;
+        if (p.ln_stats_out) {
+            b.ln_stats_out = p.ln_stats_out + r * (p.N / LN_BLK) * 2;
+            b.ln_out = (char*)p.ln_out + r * p.N * dtype_size(p.dtype);
+        }
+    }
+    launch_planned(a, plan, s);
+    launch_planned(b, gemm_plan(b, cus), s);
+}
+
 
 void SkWorkspace::ensure(int n_slots, hipStream_t s) {
     if (n_slots <= slots) return;

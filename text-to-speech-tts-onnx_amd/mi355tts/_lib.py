@@ -190,6 +190,9 @@ def load() -> C.CDLL:
     L.mi_gpt_bench_pick.restype = C.c_int
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]
     L.mi_bench_conv_gemm.restype = C.c_int
+    if hasattr(L, "mi_conv_gemm_plan"):
+        L.mi_conv_gemm_plan.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_int32), C.POINTER(C.c_int)]
+        L.mi_conv_gemm_plan.restype = C.c_int
     L.mi_set_option.argtypes = [C.c_char_p, C.c_int64]; L.mi_set_option.restype = C.c_int
     L.mi_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]; L.mi_get_option.restype = C.c_int
     L.mi_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_int]; L.mi_device_pci_bus_id.restype = C.c_int
@@ -272,6 +275,20 @@ def bench_conv_gemm(dtype: str, B: int, T: int, Cin: int, N: int, taps: int = 1,
     check(load().mi_bench_conv_gemm(DTYPES[dtype], B, T, Cin, N, taps, dil, int(with_res), iters, C.byref(ms)),
           "mi_bench_conv_gemm")
     return ms.value
+
+
+GEMM_KINDS = ("none", "direct 256x32", "direct 128x64", "direct 128x128", "dma 64x64", "dma 64x64 fp16 pairs", "dma 128", "dma 128 ring4",
+              "ph8", "x3p", "x3", "stream-k", "dma3 192", "dma3 256", "dma3 128")
+
+
+def conv_gemm_plan(dtype: str, B: int, T: int, Cin: int, N: int, taps: int = 1, dil: int = 1, with_res: bool = False,
+                   cus: int = 256) -> list:
+    """Host only: what launch_conv_gemm would launch for bench_conv_gemm's arguments on a device of ``cus`` compute units, at the
+    process's options.  One dict per launch (two when the rows are split): kind, Tm, Tn, RT, RC, lds_epi, use_buf, grid."""
+    plans, n = (C.c_int32 * 20)(), C.c_int(0)
+    check(load().mi_conv_gemm_plan(DTYPES.get(dtype, -1), B, T, Cin, N, taps, dil, int(with_res), cus, plans, C.byref(n)), "mi_conv_gemm_plan")
+    keys = ("Tm", "Tn", "RT", "RC", "lds_epi", "use_buf")
+    return [dict(zip(keys, plans[10 * i + 1:10 * i + 7]), kind=GEMM_KINDS[plans[10 * i]], grid=list(plans[10 * i + 7:10 * i + 10])) for i in range(n.value)]
 
 
 def device_pci_bus_id(device: int) -> str:

@@ -597,6 +597,10 @@ int         mi_indextts_cond_run(mi_cond* h, const int16_t* audio, int64_t L, fl
  *   "gpt_mfma_min" (sentences from which mi_gpt_generate_batch runs its linears on MFMA; default 9)
  *   "bigvgan_streams" (default 3): the AMP blocks of a BigVGAN stage on side streams of the handle — 1: one stream; 2: only
  *     the stages whose AMP halves are separate AA and conv launches (C > 96); 3: every stage.  Bit-identical in all three.
+ *   BigVGAN's anti-aliased activation kernels in 16-bit storage (A/B and test switches; every setting gives the same bits):
+ *     "aa_tile" (elements per tile, rows x channels; default 8192), "aa_pipe" (0: one tile per workgroup instead of persistent
+ *     workgroups with LDS-DMA), "aa_r" (16 | 8 outputs per work item of the pipelined kernel), "aaconv_lds_min" (bytes of LDS the
+ *     fused AA + conv kernel asks for at least; 83968: one workgroup per CU instead of two)
  * Removed in round 4 (variants that lost their A/B, nothing used them): "gemm_sk_min_tiles", "gemm_sk_max_tiles", "gemm_sk_qkv32",
  * "gemm_f32_n64_dma", "gemm_n64_dma16", "attn_z_max", "attn_z16_max",
  * "aa_conv_deterministic".  Changing an option invalidates the hipGraphs captured by existing handles.   */

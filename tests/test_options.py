@@ -23,9 +23,10 @@ DEFAULTS = {
     "gconv_two_taps": 1, "gconv16": 1,
     "attn_f32_x3": 2, "attn_f32_planes": 2, "attn_split": 2, "attn_xcd_map": 1, "attn_kv_planes": 1, "attn_lpt": 1,
     "attn_z_force": 0, "gpt_mfma_min": 9, "bigvgan_streams": 3,
+    "aa_tile": 8192, "aa_pipe": 1, "aa_r": 16, "aaconv_lds_min": 0,
 }
 ON_OFF = ["gemm_use_dma3", "gemm_use_dma", "gemm_big_tiles", "gemm_n192", "gemm_f32_dma", "gemm_ring4", "gemm_buf",
-          "gemm_f32_small", "gconv_two_taps", "gconv16", "attn_xcd_map", "attn_kv_planes", "attn_lpt"]       # store value != 0
+          "gemm_f32_small", "gconv_two_taps", "gconv16", "attn_xcd_map", "attn_kv_planes", "attn_lpt", "aa_pipe"]       # store value != 0
 CLAMP = {"attn_f32_x3": (0, 2), "attn_split": (0, 2), "attn_z_force": (0, 4), "bigvgan_streams": (1, 3), "gemm_ph8_split_max": (1, 4)}
 REJECT = {"gemm_f32_planes": (2, 3), "attn_f32_planes": (2, 3)}
 AS_GIVEN = sorted(set(DEFAULTS) - set(ON_OFF) - set(CLAMP) - set(REJECT))

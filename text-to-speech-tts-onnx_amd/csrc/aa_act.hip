@@ -348,6 +348,7 @@ static void launch_t(const AAAct& p, hipStream_t s) {
             if (per_cu >= 1 && lds2 <= 64 * 1024 && ntiles < 0x7fffffffL) {
                 const int grid_p = (int)std::min<long>(ntiles, (long)cus * per_cu);
                 prof_set_kernel("aa_act_pipe_kernel<T>", type_label<T>());
+                if (RP == 8) prof_kernel_suffix(", runs of 8");
                 if (p.lens) {
                     prof_kernel_suffix(" + lengths");
                     if (RP == 16)

@@ -90,10 +90,10 @@ namespace mi {
     /* BigVGAN (bigvgan.hip, aa_act.hip, aa_conv.hip) */                                                                \
     X(BIGVGAN_STREAMS, "bigvgan_streams", nullptr, ENV_INT, 3, CLAMP, 1, 3)                                             \
     X(BV_SYNC, nullptr, "MI355TTS_BV_SYNC", ENV_ONE_ON, 0, BOOL, 0, 1)                                                  \
-    X(AA_TILE, nullptr, "MI355TTS_AA_TILE", ENV_INT, 8192, STORE, 0, 0) /* tile size in elements (rows x channels) */   \
-    X(AA_PIPE, nullptr, "MI355TTS_AA_PIPE", ENV_ZERO_OFF, 1, BOOL, 0, 1)                                                \
-    X(AA_R, nullptr, "MI355TTS_AA_R", ENV_INT, 16, STORE, 0, 0) /* outputs per work item of the pipelined kernel; 8: the A/B switch */ \
-    X(AACONV_LDS_MIN, nullptr, "MI355TTS_AACONV_LDS_MIN", ENV_INT, 0, STORE, 0, 0) /* > 80 KB: one workgroup per CU (a diagnostic) */
+    X(AA_TILE, "aa_tile", "MI355TTS_AA_TILE", ENV_INT, 8192, STORE, 0, 0) /* tile size in elements (rows x channels) */   \
+    X(AA_PIPE, "aa_pipe", "MI355TTS_AA_PIPE", ENV_ZERO_OFF, 1, BOOL, 0, 1) /* 0: one tile per workgroup (aa_act_kernel) */   \
+    X(AA_R, "aa_r", "MI355TTS_AA_R", ENV_INT, 16, STORE, 0, 0) /* outputs per work item of the pipelined kernel; 8: the A/B switch */ \
+    X(AACONV_LDS_MIN, "aaconv_lds_min", "MI355TTS_AACONV_LDS_MIN", ENV_INT, 0, STORE, 0, 0) /* > 80 KB: one workgroup per CU (a diagnostic) */
 
 #define MI_OPT_ENUM(name, key, env, conv, dflt, policy, lo, hi) OPT_##name,
 enum Opt : int { MI_OPTIONS(MI_OPT_ENUM) OPT_COUNT };

@@ -410,6 +410,28 @@ int         mi_gpt_attn_prompt(const float* qkv, const float* kc, const float* v
 int         mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc, int dtype, int heads, int max_seq,
                                       int nslots, const int32_t* segs, int nseg, int total, float* out, int mem);
 
+/* unit entries (tests, no handle): ONE launch of a decode-step linear layer of the GPT, through the launchers the engine calls
+ * (csrc/gpt.h launch_gpt_gemv / launch_gpt_gemv_b: same dispatch, kernel and grid).  out = act(w x' + bias) + res.  Arrays are
+ * fp32 and follow `mem`; w (n, k), x and the caches are rounded to `dtype` (MI_F32 | MI_F16 | MI_BF16) on the device, outputs are
+ * widened back (exact); bias, res and the LayerNorm vectors stay fp32, as in the engine.  hist is a HOST value / array.  act: 0 or
+ * 1 (gelu_new).  out_f32 != 0: the launch stores fp32, otherwise `dtype`.  `out` and `pre_out` are preset to NaN bytes on the
+ * device, so an element the launch does not write comes back NaN.  k a multiple of 8, at most 16384; bias, res may be NULL.
+ *   decode  one row: x (k), out (n), res (n).  ln_w, ln_b (k) given: x stays fp32 and x' = LayerNorm(x), eps 1e-5 (k <= 2048 at
+ *           MI_F32, <= 4096 at 16 bits; no res).  pre_w, pre_b (k, with ln_w; k <= 2048): x' = LayerNorm(LayerNorm_pre(x)), the
+ *           inner row also to pre_out (k) or NULL.  qkv != 0 (with ln_w, n == 3 * k, k a multiple of 64): columns [k, 3k) go to row
+ *           `hist` of kc then vc — ONE layer's caches [k / 64][max_seq][64], in and out — when hist < max_seq, and not to out;
+ *           0 <= hist <= max_seq <= 8192.
+ *   batch   nb rows (1..64): x (nb, k), res (nb, n), hist[nb], kc / vc [nb][k / 64][max_seq][64] in and out (qkv needs no
+ *           LayerNorm here).  The device x array has the engine's padded row count P = mi_gpt_linear_batch_rows(nb) (2, 4, 8, then
+ *           multiples of 16); rows nb .. P-1 are copies of x_dead (k), zeros if NULL.  out (P, n): rows >= nb are never written. */
+int         mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int dtype, int n, int k, const float* ln_w,
+                                 const float* ln_b, const float* pre_w, const float* pre_b, float* pre_out, const float* res,
+                                 int act, int out_f32, int qkv, int hist, int max_seq, float* kc, float* vc, float* out, int mem);
+int         mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const float* x_dead, int dtype, int n, int k,
+                                int nb, const float* res, int act, int out_f32, int qkv, const int32_t* hist, int max_seq,
+                                float* kc, float* vc, float* out, int mem);
+int         mi_gpt_linear_batch_rows(int nb);       /* P above; < 0 (MI_EINVAL) outside 1..64 */
+
 /* ---- sentence queue: any number of sentences through the handle's slots, a slot refilled as soon as its sentence stops ---------
  * A decode step costs little more for 16 live slots than for 1, and 64 cost far less than four times 16,
  * so throughput is the number of LIVE slots.  mi_gpt_generate_batch takes

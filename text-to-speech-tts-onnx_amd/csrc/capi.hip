@@ -1216,6 +1216,54 @@ struct AttnUnit {
         MI_HIP(hipStreamSynchronize(s));
     }
 };
+
+// The unit entries of the decode-step linear launches share this: a stream of their own, fp32 arrays staged (and rounded to
+// `dtype` where the engine holds them so), NaN-preset outputs, results widened back.
+struct LinUnit {
+    hipStream_t s = nullptr;
+    int dtype, mem;
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    LinUnit(const std::string& who, int dt, int mem_) : dtype(dt), mem(mem_) {
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+        MI_REQUIRE(dt == MI_F32 || dt == MI_F16 || dt == MI_BF16, who + ": dtype must be MI_F32, MI_F16 or MI_BF16");
+        MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    }
+    ~LinUnit() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    DevBuf& buf(size_t bytes) { bufs.emplace_back(new DevBuf); bufs.back()->ensure(bytes); return *bufs.back(); }
+    // n fp32 values of the caller, on the device (null stays null)
+    const float* f32(const float* p, size_t n) {
+        if (!p || mem == MI_DEVICE) return p;
+        bufs.emplace_back(new DevBuf);
+        return (const float*)stage_in(*bufs.back(), p, n * 4, mem, s);
+    }
+    // (rows, cols) fp32 of the caller -> rows [0, rows) of a device array of `dt` with alloc_rows >= rows rows
+    void* typed(const float* p, long rows, int cols, int dt, long alloc_rows = 0) {
+        DevBuf& d = buf((size_t)std::max(rows, alloc_rows) * cols * dtype_size(dt));
+        launch_copy2d(f32(p, (size_t)rows * cols), cols, d.p, cols, rows, cols, dt, s);
+        return d.p;
+    }
+    // n elements of `dt`, every byte 0xFF (a NaN in all three types)
+    void* nan_out(size_t n, int dt) {
+        DevBuf& d = buf(n * dtype_size(dt));
+        MI_HIP(hipMemsetAsync(d.p, 0xFF, n * dtype_size(dt), s));
+        return d.p;
+    }
+    // n elements of `dt` on the device -> the caller's fp32 array (null: not wanted)
+    void give(float* dst, const void* src, size_t n, int dt) {
+        if (!dst) return;
+        float* d = mem == MI_HOST ? (float*)buf(n * 4).p : dst;
+        launch_cast_to_f32(src, dt, d, (long)n, s);
+        if (mem == MI_HOST) copy_out(dst, d, n * 4, mem, s);
+    }
+    const int* state(const int32_t* hist, int nslots, int rows) {
+        std::vector<int32_t> w((size_t)rows * GS_WORDS, 0);
+        for (int b = 0; b < nslots; ++b) w[(size_t)b * GS_WORDS + GS_HIST] = hist ? hist[b] : 0;
+        DevBuf& d = buf(w.size() * 4);
+        MI_HIP(hipMemcpyAsync(d.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));       // `w` is a local
+        return d.as<int>();
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -1306,6 +1354,81 @@ int mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc
         MI_HIP(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * sizeof(Gpt::Seg), hipMemcpyHostToDevice, u.s));
         launch_gpt_attn_packed(dtype, u.q.p, u.k.p, u.v.p, u.o.p, dtab.p, nseg, total, heads, u.hidden, max_seq, nslots, u.slot_elems(), u.s);
         u.result(out, total, mem);
+    });
+}
+
+int mi_gpt_linear_batch_rows(int nb) { return nb >= 1 && nb <= GPT_MAX_BATCH ? gpt_padded_rows(nb) : MI_EINVAL; }
+
+int mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int dtype, int n, int k, const float* ln_w,
+                         const float* ln_b, const float* pre_w, const float* pre_b, float* pre_out, const float* res, int act,
+                         int out_f32, int qkv, int hist, int max_seq, float* kc, float* vc, float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_linear_decode";
+        LinUnit u(who, dtype, mem);
+        MI_REQUIRE(w && x && out, who + ": null argument");
+        MI_REQUIRE(n >= 1 && n <= (1 << 20) && k >= 1 && k <= 16384, who + ": n must be in [1, 2^20], k in [1, 16384]");
+        MI_REQUIRE(k % 8 == 0, who + ": k must be a multiple of 8");
+        MI_REQUIRE(!ln_w == !ln_b && !pre_w == !pre_b, who + ": a LayerNorm needs both its vectors");
+        MI_REQUIRE(act == ACT_NONE || act == ACT_GELU_TANH, who + ": act must be 0 or 1 (gelu_new)");
+        if (qkv) {
+            MI_REQUIRE(n % 3 == 0 && n == 3 * k && k % 64 == 0, who + ": qkv needs n == 3 * k (a multiple of 3), k a multiple of 64");
+            MI_REQUIRE(kc && vc, who + ": qkv needs kc and vc");
+            MI_REQUIRE(max_seq >= 1 && max_seq <= 8192 && hist >= 0 && hist <= max_seq, who + ": 0 <= hist <= max_seq <= 8192");
+        }
+        const int odt = out_f32 ? MI_F32 : dtype;
+        const size_t nc = qkv ? (size_t)k * max_seq : 0;
+        const GptLin l{dtype, u.typed(w, n, k, dtype), u.f32(bias, n), n, k};
+        const void* xd = ln_w ? (const void*)u.f32(x, k) : u.typed(x, 1, k, dtype);
+        void* kd = qkv ? u.typed(kc, (long)(nc / 64), 64, dtype) : nullptr;
+        void* vd = qkv ? u.typed(vc, (long)(nc / 64), 64, dtype) : nullptr;
+        void* od = u.nan_out(n, odt);
+        float* pd = pre_w ? (float*)u.nan_out(k, MI_F32) : nullptr;
+        const int* st = u.state(&hist, 1, 1);
+        launch_gpt_gemv(l, xd, u.f32(ln_w, k), u.f32(ln_b, k), u.f32(pre_w, k), u.f32(pre_b, k), pd, od, odt, act, u.f32(res, n), kd,
+                        vd, st, qkv ? max_seq : 1, u.s);
+        u.give(out, od, n, odt);
+        if (pd) u.give(pre_out, pd, k, MI_F32);
+        if (qkv) { u.give(kc, kd, nc, dtype); u.give(vc, vd, nc, dtype); }
+        MI_HIP(hipStreamSynchronize(u.s));
+    });
+}
+
+int mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const float* x_dead, int dtype, int n, int k, int nb,
+                        const float* res, int act, int out_f32, int qkv, const int32_t* hist, int max_seq, float* kc, float* vc,
+                        float* out, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_linear_batch";
+        LinUnit u(who, dtype, mem);
+        MI_REQUIRE(w && x && out, who + ": null argument");
+        MI_REQUIRE(nb >= 1 && nb <= GPT_MAX_BATCH, who + ": nb must be in [1, 64]");
+        MI_REQUIRE(n >= 1 && n <= (1 << 20) && k >= 1 && k <= 16384, who + ": n must be in [1, 2^20], k in [1, 16384]");
+        MI_REQUIRE(k % 8 == 0, who + ": k must be a multiple of 8");
+        MI_REQUIRE(act == ACT_NONE || act == ACT_GELU_TANH, who + ": act must be 0 or 1 (gelu_new)");
+        if (qkv) {
+            MI_REQUIRE(n % 3 == 0 && n == 3 * k && k % 64 == 0, who + ": qkv needs n == 3 * k (a multiple of 3), k a multiple of 64");
+            MI_REQUIRE(kc && vc && hist, who + ": qkv needs kc, vc and hist");
+            MI_REQUIRE(max_seq >= 1 && max_seq <= 8192, who + ": max_seq must be in [1, 8192]");
+            for (int b = 0; b < nb; ++b) MI_REQUIRE(hist[b] >= 0 && hist[b] <= max_seq, who + ": hist must be in [0, max_seq]");
+        }
+        const int odt = out_f32 ? MI_F32 : dtype, P = gpt_padded_rows(nb);
+        const size_t sstride = qkv ? (size_t)k * max_seq : 0, nc = (size_t)nb * sstride;
+        const GptLin l{dtype, u.typed(w, n, k, dtype), u.f32(bias, n), n, k};
+        char* xd = (char*)u.typed(x, nb, k, dtype, P);
+        const size_t row = (size_t)k * dtype_size(dtype);
+        if (x_dead) {
+            const float* dead = u.f32(x_dead, k);
+            for (int b = nb; b < P; ++b) launch_copy2d(dead, k, xd + b * row, k, 1, k, dtype, u.s);
+        } else if (P > nb) {
+            MI_HIP(hipMemsetAsync(xd + nb * row, 0, (P - nb) * row, u.s));
+        }
+        void* kd = qkv ? u.typed(kc, (long)(nc / 64), 64, dtype) : nullptr;
+        void* vd = qkv ? u.typed(vc, (long)(nc / 64), 64, dtype) : nullptr;
+        void* od = u.nan_out((size_t)P * n, odt);
+        const int* st = u.state(qkv ? hist : nullptr, nb, P);
+        launch_gpt_gemv_b(l, xd, nb, P, od, odt, act, u.f32(res, (size_t)nb * n), kd, vd, st, qkv ? max_seq : 1, sstride, u.s);
+        u.give(out, od, (size_t)P * n, odt);
+        if (qkv) { u.give(kc, kd, nc, dtype); u.give(vc, vd, nc, dtype); }
+        MI_HIP(hipStreamSynchronize(u.s));
     });
 }
 

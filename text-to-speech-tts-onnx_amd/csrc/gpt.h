@@ -20,12 +20,20 @@ int64_t gpt_param_count(const GptCfg& c);
 enum { GS_HIST = 0, GS_TOKEN = 1, GS_GEN_LEN = 2, GS_NDEC = 3, GS_RESET = 4, GS_DONE = 5, GS_NSTOP = 6, GS_RANGE = 7,
        GS_UPDATE_PEN = 8, GS_LIMIT = 9, GS_STOP0 = 10, GS_WORDS = 16 };
 
+// rows of the batched decode scratch for mb slots: a batched-GEMV template width (2, 4, 8, 16) or a multiple of 16 (above).
+// Never 1: gemv_b_kernel stages whole template widths of x rows, and its narrowest width is 2
+inline int gpt_padded_rows(int mb) { return mb <= 2 ? 2 : mb <= 4 ? 4 : mb <= 8 ? 8 : (mb + 15) / 16 * 16; }
+
+// a decode-step linear layer as its launchers see it: weights (n, k) of `dtype`, fp32 bias (n) or null, both on the device
+struct GptLin { int dtype; const void* w; const float* bias; int n, k; };
+
 struct Gpt {
     GptCfg cfg;
     int dtype, device;
     hipStream_t stream = nullptr;
 
     struct GLin { DevBuf w, b; int n = 0, k = 0; };
+    GptLin lin(const GLin& l) const { return {dtype, l.w.p, l.b.as<float>(), l.n, l.k}; }
     struct Layer { DevBuf ln1_w, ln1_b, ln2_w, ln2_b; GLin qkv, proj, fc, fc2; };
     std::vector<Layer> L;
     DevBuf text_emb, text_pos, mel_emb, mel_pos;       // fp32 tables
@@ -36,7 +44,7 @@ struct Gpt {
     DevBuf X, xn, qkv, att, ff;                       // prompt-pass scratch (max_seq rows), shared by the slots
     DevBuf logits, last, pen, toks, hid, state;       // per slot: [slot][codes] / [slot][h] / [slot][max_seq](x h) / words
     DevBuf Xd, xnd, qkvd, attd, ffd, zd;              // batched decode step: one row per slot
-    int MBp = 1;              // max_batch rounded up to a batched-GEMV template width (<= 16) or to a multiple of 16 (above)
+    int MBp = 2;              // gpt_padded_rows(max_batch)
     // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams)
     std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;
     DevBuf io_a, io_b, io_s;  // host<->device staging (io_s: scores of a queue round)
@@ -188,6 +196,22 @@ template <typename F> void Gpt::replay(hipGraphExec_t& exec, int n, F&& step) {
     }
     for (int i = 0; i < n; ++i) MI_HIP(hipGraphLaunch(exec, stream));
 }
+
+// The decode-step linear launches (gpt.hip), called by Gpt::gemv / gemv_b / gemv_b16 and by the unit entries of capi.hip
+// (mi_gpt_linear_*): x, out, res, kcl / vcl (one layer's cache of the first slot, null = no QKV epilogue) on the device, st = the
+// GS_* state words of the first row's slot.  odt = MI_F32 or the layer's dtype.
+//   one row (gemv_d_kernel): x of l.dtype, or the fp32 residual row when ln_w / ln_b are given (LayerNorm fused in; pre_w / pre_b:
+//   a LayerNorm in front of that one, its fp32 row also stored to pre_out)
+void launch_gpt_gemv(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b,
+                     float* pre_out, void* out, int odt, int act, const float* res, void* kcl, void* vcl, const int* st,
+                     int max_seq, hipStream_t s);
+//   nb rows, row b = slot b (state words st + b * GS_WORDS, cache slot_stride elements on).  The kernels read whole template widths
+//   of x rows: x holds max_rows >= nb rows, max_rows as Gpt::MBp
+void launch_gpt_gemv_b(const GptLin& l, const void* x, int nb, int max_rows, void* out, int odt, int act, const float* res,
+                       void* kcl, void* vcl, const int* st, int max_seq, size_t slot_stride, hipStream_t s);
+//   nb <= 16 rows (a 16-slot group of a wider batch passes its own bases); of = the output is fp32
+void launch_gpt_gemv_b16(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                         const int* st, int max_seq, size_t slot_stride, hipStream_t s);
 
 // The four attention launches of the GPT, each defined beside its kernel and called by the engine and by the unit entries of
 // capi.hip (mi_gpt_attn_*): arrays of `dtype` on the device, st = GS_* state words, kc / vc = one layer's cache.

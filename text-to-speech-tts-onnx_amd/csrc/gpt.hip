@@ -754,7 +754,7 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     MI_REQUIRE(p - w == nw, "gpt: blob walk mismatch");
 
     const size_t es = dtype_size(dt), S = c.max_seq, MB = c.max_batch;
-    MBp = c.max_batch <= 1 ? 1 : c.max_batch <= 2 ? 2 : c.max_batch <= 4 ? 4 : c.max_batch <= 8 ? 8 : (c.max_batch + 15) / 16 * 16;
+    MBp = gpt_padded_rows(c.max_batch);
     kc.ensure(MB * slot_cache_elems() * es); vc.ensure(MB * slot_cache_elems() * es);
     X.ensure(S * h * 4); xn.ensure(S * h * es); qkv.ensure(S * 3 * h * es); att.ensure(S * h * es); ff.ensure(S * n * es);
     const size_t P = MBp;                       // padded slot rows of the batched decode scratch
@@ -813,23 +813,33 @@ void Gpt::linear(const GLin& l, const void* x, int rows, void* out, int odt, int
 // LayerNorm fused in (pre_w: a first LayerNorm in front of it, its row also stored to pre_out).  kcl != nullptr: QKV
 // epilogue (k and v rows go to the cache).
 template <typename T, int R, int KI, bool LN, bool QKV>
-static void gemv_d_launch(const Gpt::GLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w,
+static void gemv_d_launch(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w,
                           const float* pre_b, float* pre_out, const float* res, void* out, int of, int act, void* kcl,
                           void* vcl, const int* st, int max_seq, hipStream_t s) {
     constexpr int WAVES = LN ? 8 : 4;
     const dim3 grid((unsigned)((l.n + WAVES * R - 1) / (WAVES * R)));
-    hipLaunchKernelGGL((gemv_d_kernel<T, R, KI, WAVES, LN, QKV>), grid, dim3(WAVES * 64), 0, s, (const T*)l.w.p, x, ln_w,
-                       ln_b, pre_w, pre_b, pre_out, l.b.as<float>(), res, out, of, act, l.n, l.k, (T*)kcl, (T*)vcl, st, max_seq);
+    if (prof_mask()) {      // the template-id as a kernel trace prints it
+        char nm[96];
+        std::snprintf(nm, sizeof nm, "gemv_d_kernel<%s, %d, %d, %d, %s, %s>", type_label<T>(), R, KI, WAVES, LN ? "true" : "false",
+                      QKV ? "true" : "false");
+        prof_set_kernel(nm);
+    }
+    hipLaunchKernelGGL((gemv_d_kernel<T, R, KI, WAVES, LN, QKV>), grid, dim3(WAVES * 64), 0, s, (const T*)l.w, x, ln_w,
+                       ln_b, pre_w, pre_b, pre_out, l.bias, res, out, of, act, l.n, l.k, (T*)kcl, (T*)vcl, st, max_seq);
 }
 template <typename T>
-static void gemv_d_dispatch(const Gpt::GLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w,
+static void gemv_d_dispatch(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w,
                             const float* pre_b, float* pre_out, const float* res, void* out, int of, int act, void* kcl,
                             void* vcl, const int* st, int max_seq, hipStream_t s) {
     constexpr int V = 16 / (int)sizeof(T);
     const int ki = (l.k + 64 * V - 1) / (64 * V);
 #define GD(RR, KK, LNN, QK) gemv_d_launch<T, RR, KK, LNN, QK>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, max_seq, s)
     if (ln_w) {
-        MI_REQUIRE(ki <= 8, "gemv: the fused LayerNorm supports K <= 2048");
+        // the normalised row lives in LDS as 8 iterations of 64 lanes x 16 bytes of T; the leading LayerNorm holds the fp32 row in
+        // 8 float4 per lane of one wave, whatever T
+        MI_REQUIRE(ki <= 8, sizeof(T) == 4 ? "gemv: the fused LayerNorm supports K <= 2048 at fp32 (8 x 64 lanes x 4 elements)"
+                                           : "gemv: the fused LayerNorm supports K <= 4096 at 16 bits (8 x 64 lanes x 8 elements)");
+        MI_REQUIRE(!pre_w || l.k <= 2048, "gemv: the leading LayerNorm supports K <= 2048 (8 float4 per lane of one wave)");
         // rows per wave: the fewest (most waves in flight) for which the launch is one round of 512-thread blocks, one per CU
         // (5120 rows at R = 2 are 320 blocks on 256 CUs: the 64 CUs that get two set the time — 6.1 us against 4.7 for the
         // 3840-row layer; R = 3: 214 blocks, 5.4 us)
@@ -858,20 +868,26 @@ static void gemv_d_dispatch(const Gpt::GLin& l, const void* x, const float* ln_w
 #undef GD
 }
 
-void Gpt::gemv(const GLin& l, const void* x, const float* ln_w, const float* ln_b, void* out, int odt, int act,
-               const float* res, void* kcl, void* vcl, int slot, const float* pre_w, const float* pre_b, float* pre_out) {
+void launch_gpt_gemv(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b,
+                     float* pre_out, void* out, int odt, int act, const float* res, void* kcl, void* vcl, const int* st,
+                     int max_seq, hipStream_t s) {
     MI_REQUIRE(l.k % 8 == 0, "gemv: K must be a multiple of 8");
     const int of = odt == MI_F32;
-    MI_REQUIRE(of || odt == dtype, "gemv: output dtype");
+    MI_REQUIRE(of || odt == l.dtype, "gemv: output dtype");
     MI_REQUIRE(!kcl || ln_w, "gemv: the QKV epilogue comes with the fused LayerNorm");
     MI_REQUIRE(!ln_w || !res, "gemv: the fused-LayerNorm variant has no residual input");
     MI_REQUIRE(!pre_w || ln_w, "gemv: the leading LayerNorm comes with the fused one");
-    ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * dtype_size(dtype), 2.0 * l.n * l.k);
-    const int* st = state.as<int>() + (size_t)slot * GS_WORDS;
-    if (dtype == MI_F32) gemv_d_dispatch<float>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, cfg.max_seq, stream);
-    else if (dtype == MI_F16) gemv_d_dispatch<f16>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, cfg.max_seq, stream);
-    else gemv_d_dispatch<bf16>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, cfg.max_seq, stream);
+    ProfScope ps(FAM_CONV_GEMM, s, (double)l.n * l.k * dtype_size(l.dtype), 2.0 * l.n * l.k);
+    if (l.dtype == MI_F32) gemv_d_dispatch<float>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, max_seq, s);
+    else if (l.dtype == MI_F16) gemv_d_dispatch<f16>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, max_seq, s);
+    else gemv_d_dispatch<bf16>(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, res, out, of, act, kcl, vcl, st, max_seq, s);
     MI_HIP(hipGetLastError());
+}
+
+void Gpt::gemv(const GLin& l, const void* x, const float* ln_w, const float* ln_b, void* out, int odt, int act,
+               const float* res, void* kcl, void* vcl, int slot, const float* pre_w, const float* pre_b, float* pre_out) {
+    launch_gpt_gemv(lin(l), x, ln_w, ln_b, pre_w, pre_b, pre_out, out, odt, act, res, kcl, vcl,
+                    state.as<int>() + (size_t)slot * GS_WORDS, cfg.max_seq, stream);
 }
 
 void Gpt::forward_rows(int rows, int flag, int slot) {
@@ -979,16 +995,18 @@ void Gpt::decode_steps(int n) {
     replay(step_graph[sampled ? 1 : 0], n, [&] { decode_step_eager(); });
 }
 
-// batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N).  Up to 16 rows: gemv_b16.  Above: 16-bit engines
-// run the wide matrix-core kernel where the 16-row one would run; everything else (fp32, gpt_mfma = 0, a K that does not
-// split) goes group by group — slots [16g, 16g + 16) through gemv_b16 with their own row count and every per-slot base moved
-// by 16g rows or slots, the weights streamed once per group.
-void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int act, const float* res, void* kcl, void* vcl) {
-    MI_REQUIRE(l.k % 8 == 0 && nb >= 1 && nb <= MBp, "gemv_b: shape");
+// batched GEMV dispatch: x (nb rows of K, engine dtype) -> out (nb rows of N).  Up to 16 rows: launch_gpt_gemv_b16.  Above: 16-bit
+// engines run the wide matrix-core kernel where the 16-row one would run; everything else (fp32, gpt_mfma = 0, a K that does not
+// split) goes group by group — slots [16g, 16g + 16) through launch_gpt_gemv_b16 with their own row count and every per-slot base
+// moved by 16g rows or slots, the weights streamed once per group.
+void launch_gpt_gemv_b(const GptLin& l, const void* x, int nb, int max_rows, void* out, int odt, int act, const float* res,
+                       void* kcl, void* vcl, const int* st, int max_seq, size_t sstride, hipStream_t stream) {
+    MI_REQUIRE(l.k % 8 == 0 && nb >= 1 && nb <= max_rows, "gemv_b: shape");
+    const int dtype = l.dtype;
     const int of = odt == MI_F32;
     MI_REQUIRE(of || odt == dtype, "gemv_b: output dtype");
-    if (nb <= 16) { gemv_b16(l, x, nb, out, of, act, res, kcl, vcl, state.as<int>()); return; }
-    const size_t es = dtype_size(dtype), sstride = slot_cache_elems();
+    if (nb <= 16) { launch_gpt_gemv_b16(l, x, nb, out, of, act, res, kcl, vcl, st, max_seq, sstride, stream); return; }
+    const size_t es = dtype_size(dtype);
     const int KS = l.k > 2048 ? 8 : 4;
     if (opt(OPT_GPT_MFMA) && dtype != MI_F32 && nb >= opt(OPT_GPT_MFMA_MIN) && l.k % (KS * 64) == 0) {
         ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * es, 2.0 * l.n * l.k * nb);
@@ -998,7 +1016,7 @@ void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int a
         const int TR = KS == 4 && (l.n + 15) / 16 <= device_cus() ? 1 : 8 / KS;
         const dim3 gs((unsigned)((l.n + 16 * TR - 1) / (16 * TR)));
         const bool u5 = (l.k / KS) % 320 == 0;
-#define GW1(T, QK, U, C) hipLaunchKernelGGL((gemm_skinny_wide_kernel<T, QK, U, C>), gs, dim3(64 * KS * TR), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, state.as<int>(), cfg.max_seq, sstride)
+#define GW1(T, QK, U, C) do { prof_set_kernel("gemm_skinny_wide_kernel<T, " #QK ", " #U ", " #C ">", type_label<T>()); hipLaunchKernelGGL((gemm_skinny_wide_kernel<T, QK, U, C>), gs, dim3(64 * KS * TR), 0, stream, (const T*)l.w, (const T*)x, l.bias, res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, st, max_seq, sstride); } while (0)
 #define GW2(T, QK, U) do { if (CT == 2) GW1(T, QK, U, 2); else if (CT == 3) GW1(T, QK, U, 3); else GW1(T, QK, U, 4); } while (0)
 #define GW(T, QK) do { if (u5) GW2(T, QK, 5); else GW2(T, QK, 1); } while (0)
         if (dtype == MI_F16) { if (kcl) GW(f16, true); else GW(f16, false); }
@@ -1010,18 +1028,18 @@ void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int a
         return;
     }
     for (int b0 = 0; b0 < nb; b0 += 16)
-        gemv_b16(l, (const char*)x + (size_t)b0 * l.k * es, std::min(16, nb - b0), (char*)out + (size_t)b0 * l.n * (of ? 4 : es), of, act,
-                 res ? res + (size_t)b0 * l.n : nullptr, kcl ? (char*)kcl + (size_t)b0 * sstride * es : nullptr,
-                 vcl ? (char*)vcl + (size_t)b0 * sstride * es : nullptr, state.as<int>() + (size_t)b0 * GS_WORDS);
+        launch_gpt_gemv_b16(l, (const char*)x + (size_t)b0 * l.k * es, std::min(16, nb - b0), (char*)out + (size_t)b0 * l.n * (of ? 4 : es),
+                            of, act, res ? res + (size_t)b0 * l.n : nullptr, kcl ? (char*)kcl + (size_t)b0 * sstride * es : nullptr,
+                            vcl ? (char*)vcl + (size_t)b0 * sstride * es : nullptr, st + (size_t)b0 * GS_WORDS, max_seq, sstride, stream);
 }
 
 // up to 16 rows: the batched GEMV at the template width that holds nb, or the matrix-core kernel.  st = the state words of row 0
-void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
-                   const int* st) {
+void launch_gpt_gemv_b16(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                         const int* st, int max_seq, size_t sstride, hipStream_t stream) {
+    const int dtype = l.dtype;
     const int BB = nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 8 ? 8 : 16;
     const int R = l.n >= 4096 ? 2 : 1;
     ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * dtype_size(dtype), 2.0 * l.n * l.k * nb);
-    const size_t sstride = slot_cache_elems();
     {   // matrix-core path: 16-bit engines, nine or more sentences, K splits into 64-wide blocks per wave
         const int KS = l.k > 2048 ? 8 : 4;
         // measured (1280-wide model): the MFMA kernel costs ~9.5 us per launch whatever the batch, the v_dot2 GEMV
@@ -1030,7 +1048,7 @@ void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int 
             const int TR = 8 / KS;
             const dim3 gs((unsigned)((l.n + 16 * TR - 1) / (16 * TR)));
             const bool u5 = (l.k / KS) % 320 == 0;
-#define GS1(T, QK, U) hipLaunchKernelGGL((gemm_skinny_kernel<T, QK, U>), gs, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, st, cfg.max_seq, sstride)
+#define GS1(T, QK, U) do { prof_set_kernel("gemm_skinny_kernel<T, " #QK ", " #U ">", type_label<T>()); hipLaunchKernelGGL((gemm_skinny_kernel<T, QK, U>), gs, dim3(512), 0, stream, (const T*)l.w, (const T*)x, l.bias, res, out, of, act, l.n, l.k, nb, KS, (T*)kcl, (T*)vcl, st, max_seq, sstride); } while (0)
 #define GS(T, QK) do { if (u5) GS1(T, QK, 5); else GS1(T, QK, 1); } while (0)
             if (dtype == MI_F16) { if (kcl) GS(f16, true); else GS(f16, false); }
             else { if (kcl) GS(bf16, true); else GS(bf16, false); }
@@ -1041,7 +1059,7 @@ void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int 
         }
     }
     const dim3 grid((unsigned)((l.n + 8 * R - 1) / (8 * R)));
-#define GB(T, RR, B_, QK) hipLaunchKernelGGL((gemv_b_kernel<T, RR, B_, QK>), grid, dim3(512), 0, stream, (const T*)l.w.p, (const T*)x, l.b.as<float>(), res, out, of, act, l.n, l.k, nb, (T*)kcl, (T*)vcl, st, cfg.max_seq, sstride)
+#define GB(T, RR, B_, QK) do { prof_set_kernel("gemv_b_kernel<T, " #RR ", " #B_ ", " #QK ">", type_label<T>()); hipLaunchKernelGGL((gemv_b_kernel<T, RR, B_, QK>), grid, dim3(512), 0, stream, (const T*)l.w, (const T*)x, l.bias, res, out, of, act, l.n, l.k, nb, (T*)kcl, (T*)vcl, st, max_seq, sstride); } while (0)
 #define GB_B(T, RR, QK) do { if (BB == 2) GB(T, RR, 2, QK); else if (BB == 4) GB(T, RR, 4, QK); else if (BB == 8) GB(T, RR, 8, QK); else GB(T, RR, 16, QK); } while (0)
 #define GB_T(T)                                                                 \
     do {                                                                        \
@@ -1053,6 +1071,14 @@ void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int 
 #undef GB_B
 #undef GB
     MI_HIP(hipGetLastError());
+}
+
+void Gpt::gemv_b(const GLin& l, const void* x, int nb, void* out, int odt, int act, const float* res, void* kcl, void* vcl) {
+    launch_gpt_gemv_b(lin(l), x, nb, MBp, out, odt, act, res, kcl, vcl, state.as<int>(), cfg.max_seq, slot_cache_elems(), stream);
+}
+void Gpt::gemv_b16(const GLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                   const int* st) {
+    launch_gpt_gemv_b16(lin(l), x, nb, out, of, act, res, kcl, vcl, st, cfg.max_seq, slot_cache_elems(), stream);
 }
 
 // one decode step for slots 0..nb-1 together: graph C from each slot's state, graph E with every weight row streamed

@@ -186,6 +186,13 @@ def load() -> C.CDLL:
         L.mi_gpt_attn_prompt.restype = C.c_int
         L.mi_gpt_attn_prompt_packed.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int, C.c_int, vp, C.c_int]
         L.mi_gpt_attn_prompt_packed.restype = C.c_int
+    if hasattr(L, "mi_gpt_linear_decode"):
+        L.mi_gpt_linear_decode.argtypes = [vp, vp, vp] + [C.c_int] * 3 + [vp] * 6 + [C.c_int] * 5 + [vp, vp, vp, C.c_int]
+        L.mi_gpt_linear_decode.restype = C.c_int
+        L.mi_gpt_linear_batch.argtypes = [vp, vp, vp, vp] + [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, vp, vp, vp, C.c_int]
+        L.mi_gpt_linear_batch.restype = C.c_int
+        L.mi_gpt_linear_batch_rows.argtypes = [C.c_int]
+        L.mi_gpt_linear_batch_rows.restype = C.c_int
     L.mi_gpt_bench_pick.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_double)]
     L.mi_gpt_bench_pick.restype = C.c_int
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]

@@ -281,6 +281,94 @@ def attention_prompt_packed(q, K, V, segs, *, dtype: str = "f32"):
     return out
 
 
+def _f32(a, shape=None, what=""):
+    """None stays None; otherwise a contiguous float32 array (of ``shape`` when given)"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if shape is not None and a.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, not {a.shape}")
+    return a
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def linear_decode(w, x, *, bias=None, ln=None, pre=None, res=None, act: bool = False, out_f32: bool = True, cache=None,
+                  hist: int = 0, dtype: str = "f32"):
+    """One decode-step linear launch of ONE sentence (unit entry mi_gpt_linear_decode, csrc/gpt.hip gemv_d_kernel):
+    act(w x' + bias) + res for w (n, k), x (k).  ``ln`` = (gain, shift): x stays float32 and x' = LayerNorm(x); ``pre`` = (gain,
+    shift) of a LayerNorm in front of that one, whose row is returned too.  ``cache`` = (K, V), one layer's caches
+    (k / 64, max_seq, 64): the QKV form (n = 3 k) — columns [k, 3k) go to row ``hist`` of copies of K and V, not to the output.
+    Returns a dict: "out" (n) float32, NaN where the launch wrote nothing; "pre_out" (k) with ``pre``; "K", "V" with ``cache``."""
+    w = _f32(w)
+    if w.ndim != 2:
+        raise ValueError("w must be (n, k)")
+    n, k = w.shape
+    x = _f32(x, (k,), "x")
+    bias, res = _f32(bias, (n,), "bias"), _f32(res, (n,), "res")
+    lw, lb = (_f32(ln[0], (k,), "ln gain"), _f32(ln[1], (k,), "ln shift")) if ln is not None else (None, None)
+    pw, pb = (_f32(pre[0], (k,), "pre gain"), _f32(pre[1], (k,), "pre shift")) if pre is not None else (None, None)
+    out = np.zeros(n, np.float32)
+    pre_out = np.zeros(k, np.float32) if pre is not None else None
+    K = V = None
+    S = 1
+    if cache is not None:
+        K, V = (np.array(c, dtype=np.float32, order="C") for c in cache)
+        if K.shape != V.shape or K.ndim != 3 or K.shape[2] != 64:
+            raise ValueError("cache = (K, V), each (heads, max_seq, 64)")
+        S = K.shape[1]
+    _lib.check(_lib.load().mi_gpt_linear_decode(_ptr(w), _ptr(bias), _ptr(x), _lib.DTYPES[dtype], n, k, _ptr(lw), _ptr(lb), _ptr(pw),
+                                                _ptr(pb), _ptr(pre_out), _ptr(res), int(bool(act)), int(bool(out_f32)),
+                                                int(cache is not None), int(hist), S, _ptr(K), _ptr(V), _ptr(out), _lib.MI_HOST),
+               "mi_gpt_linear_decode")
+    r = {"out": out}
+    if pre is not None:
+        r["pre_out"] = pre_out
+    if cache is not None:
+        r["K"], r["V"] = K, V
+    return r
+
+
+def linear_batch_rows(nb: int) -> int:
+    """Rows of the batched decode scratch an engine of ``nb`` slots allocates (2, 4, 8, then multiples of 16)"""
+    p = _lib.load().mi_gpt_linear_batch_rows(int(nb))
+    if p < 0:
+        raise ValueError("nb must be in [1, 64]")
+    return p
+
+
+def linear_batch(w, x, *, bias=None, res=None, act: bool = False, out_f32: bool = True, cache=None, hist=None, x_dead=None,
+                 dtype: str = "f32"):
+    """One batched decode-step linear launch (unit entry mi_gpt_linear_batch, csrc/gpt.hip gemv_b_kernel / gemm_skinny_kernel /
+    gemm_skinny_wide_kernel by the engine's dispatch): row b of x (nb, k) is slot b.  ``cache`` = (K, V), (nb, k / 64, max_seq, 64)
+    with ``hist`` (nb): the QKV form.  ``x_dead`` (k): what the device x array holds in its rows nb .. linear_batch_rows(nb) - 1.
+    Returns a dict: "out" (linear_batch_rows(nb), n) float32 — rows >= nb are never written and come back NaN; "K", "V"."""
+    w = _f32(w)
+    x = _f32(x)
+    if w.ndim != 2 or x.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("w must be (n, k), x (nb, k)")
+    (n, k), nb = w.shape, x.shape[0]
+    bias, res, x_dead = _f32(bias, (n,), "bias"), _f32(res, (nb, n), "res"), _f32(x_dead, (k,), "x_dead")
+    K = V = h = None
+    S = 1
+    if cache is not None:
+        K, V = (np.array(c, dtype=np.float32, order="C") for c in cache)
+        h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+        if K.shape != V.shape or K.ndim != 4 or K.shape[0] != nb or K.shape[3] != 64 or h.size != nb:
+            raise ValueError("cache = (K, V), each (nb, heads, max_seq, 64), with one hist entry per row")
+        S = K.shape[2]
+    out = np.zeros((linear_batch_rows(nb), n), np.float32)
+    _lib.check(_lib.load().mi_gpt_linear_batch(_ptr(w), _ptr(bias), _ptr(x), _ptr(x_dead), _lib.DTYPES[dtype], n, k, nb, _ptr(res),
+                                               int(bool(act)), int(bool(out_f32)), int(cache is not None), _ptr(h), S, _ptr(K), _ptr(V),
+                                               _ptr(out), _lib.MI_HOST), "mi_gpt_linear_batch")
+    r = {"out": out}
+    if cache is not None:
+        r["K"], r["V"] = K, V
+    return r
+
+
 def _check_queue_beams(beams, cfg, sampling):
     """The ``beams`` keyword of the queue entries: None (no beam search) or an integer in [1, 8], not above the code count or the
     engine's max_batch (one group must fit), and never together with ``sampling``."""

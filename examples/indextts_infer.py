@@ -21,6 +21,11 @@ code is drawn on the device (`Sampling`, upstream IndexTTS's temperature 1.0 / t
 `--num-beams N` decodes every sentence by beam search instead (upstream IndexTTS runs 3 beams): N hypotheses in N batch slots
 over one shared KV cache, the most probable one goes to the vocoder.  Beam search is deterministic and does not combine with the
 sampling flags.
+`--num-beams N --beam-pool [--length-penalty x] [--early-stopping]` is upstream's own beam search: finished hypotheses are kept
+in a pool, the search goes on while a running one can still beat them, and the best of the pool goes to the vocoder.  With
+`--beam-pool` the sampling flags ARE accepted together with `--num-beams` (beam sampling: `--num-beams 3 --beam-pool --top-k 30
+--top-p 0.8` is what upstream runs).  Every sentence starts from a fresh penalty vector; not with --queue, --takes or
+--device-type cuda.
 `--queue` decodes the whole text at once instead of sentence by sentence: every sentence is embedded, `generate_queue` runs them
 through `--slots` batch slots (default 8, 1..64) — a slot is refilled as soon as its sentence stops and the prompts admitted
 together share one pass over the weights — and `run_latent_ragged` vocodes them in one forward, in order, with the same gap.
@@ -41,6 +46,7 @@ chunks are assembled here and the file has the layout of `--queue`; the wall tim
 """
 import argparse
 import dataclasses
+import math
 import os
 import sys
 import time
@@ -117,6 +123,9 @@ def parse_args(argv=None):
     ap.add_argument("--sample-seed", type=int, default=None, help="seed of the draws (--seed is the synthetic weights')")
     ap.add_argument("--takes", type=int, default=1, help="decode every sentence N times in one batch, seeds sample-seed .. + N - 1; writes <out>_<i>.wav")
     ap.add_argument("--num-beams", type=int, default=1, help="beam search with N hypotheses per sentence (1..8; 1 = greedy)")
+    ap.add_argument("--beam-pool", action="store_true", help="with --num-beams: beam search with a pool of finished hypotheses; the sampling flags then combine with it")
+    ap.add_argument("--length-penalty", type=float, default=0.0, help="with --beam-pool: a finished hypothesis scores log-probability / length ** x")
+    ap.add_argument("--early-stopping", action="store_true", help="with --beam-pool: end as soon as the pool holds --num-beams finished hypotheses")
     ap.add_argument("--queue", action="store_true", help="decode all sentences through the batch slots (refilled as sentences end); "
                     "every sentence starts from a fresh penalty vector")
     ap.add_argument("--slots", type=int, default=8, help=f"batch slots of --queue (1..{MAX_SLOTS})")
@@ -149,7 +158,13 @@ def parse_args(argv=None):
     if not 1 <= args.takes <= MAX_SLOTS:
         ap.error(f"--takes must be in 1..{MAX_SLOTS} (the engine's batch slots)")
     args.sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
-    if args.num_beams > 1 and args.sampled:
+    if args.beam_pool and (args.queue or args.takes > 1 or args.device_type == "cuda"):
+        ap.error("--beam-pool decodes sentence by sentence through the host-array beam call: no --queue, no --takes, --device-type cpu")
+    if not args.beam_pool and (args.length_penalty != 0.0 or args.early_stopping):
+        ap.error("--length-penalty and --early-stopping belong to --beam-pool")
+    if not math.isfinite(args.length_penalty):
+        ap.error("--length-penalty must be finite")
+    if args.num_beams > 1 and args.sampled and not args.beam_pool:
         ap.error("--num-beams does not combine with --temperature / --top-k / --top-p / --sample-seed / --takes: beam search is deterministic")
     if args.takes > 1 and args.device_type == "cuda":
         ap.error("--takes uses the host-array batch call (generate_batch); run it with --device-type cpu")
@@ -247,7 +262,15 @@ def main():
                 if hidden.shape[0] >= 3:
                     take_pieces[i].append(np.concatenate([voc.run_latent(hidden, list(stage_conds) + [embed_cond]), gap], axis=-1))
             continue
-        if on_device:
+        if args.beam_pool:
+            prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
+            budget = gcfg.max_generate_length - int(prompt_len[0])
+            res, _ = gpt.generate_beam([prompt_rows], [budget], args.num_beams, stop_tokens=stops, pool=True,
+                                       length_penalty=args.length_penalty, early_stopping=args.early_stopping,
+                                       sampling=take_sampling[0] if sampled else None)
+            hidden = res[0][1]
+            n = hidden.shape[0]
+        elif on_device:
             prompt_rows, prompt_len = gpt.concat(conds_latent[None], gpt.text_embed(ids), gpt.mel_embed(gcfg.start_mel_token, 0)[0])
             budget = gcfg.max_generate_length - int(prompt_len[0])
             codes = torch.zeros(max(budget, 1), dtype=torch.int32, device=dev)

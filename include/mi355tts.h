@@ -366,7 +366,8 @@ int         mi_gpt_sample_logits(const float* logits, const float* pen, int rows
  * batch and graph replay), so scores hold to a tolerance against another evaluation order and the choice holds wherever
  * rounding cannot decide.  Nothing is copied when hypotheses change slots: cache rows written so far never change, so the
  * prompt's keys and values are stored once per sentence (in the group's first slot) and every later position is read from the
- * slot a small per-hypothesis ancestor table names.  Beams and sampling do not combine: beam search is deterministic.
+ * slot a small per-hypothesis ancestor table names.  Beams and sampling do not combine here: this search is deterministic
+ * (the pool mode below draws).
  *
  * MI_EINVAL, with the handle still usable: num_beams < 1 or > 8, nb * num_beams above the handle's max_batch (<= 64: a
  * group of hypotheses may lie across a 16-slot boundary, the decode linears do not know about groups), num_beams >
@@ -384,6 +385,74 @@ int         mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const 
  * beams <= codes. */
 int         mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_scores, int groups, int beams, int codes,
                                int first, int32_t* parents, int32_t* tokens, float* scores, int mem);
+
+/* ---- beam search with a finished pool, and beam sampling: the second, opt-in beam mode ("pool" mode) ----------------------------
+ * What upstream IndexTTS asks of generate() (num_beams = 3, do_sample, top_k = 30, top_p = 0.8, length_penalty = 0): finished
+ * hypotheses are kept aside, the search goes on while a running one can still beat them, the best of the pool is returned, and
+ * the candidates may be drawn.  It follows transformers' _beam_search for one sentence; the entries above keep their results.
+ * One sentence has B = num_beams hypotheses in B consecutive slots, a stop set of n_stop ids, a limit max_new, a starting penalty
+ * vector pen0, length_penalty (float), early_stopping (0 or 1) and optionally a sampling record (temperature, top_k, top_p, seed).
+ * K = (n_stop + 1) * B candidates are kept per selection (transformers' beams_to_keep): B of them are sure not to stop.
+ * State: running scores s_0 .. s_{B-1} (fp32); a pool of B entries (score, initially -1e9; a finished flag; length, tokens and
+ * ancestry); one flag `open`, initially true.  Selection n (n = 0 reads only row 0 of the prompt pass, as above):
+ *   1. z = L * pen (one rounded fp32 multiply, as above), lp = z - lse(z).
+ *   2. Warp.  Deterministic mode: w = lp.  Sampling mode: w = lp * inv_T (transformers' order: the temperature on
+ *      log-probabilities, not renormalised), then top-k and top-p per row by steps 2-4 of "sampling" applied to w, except that
+ *      the K best codes of a row (ties to the lower code) are always kept: min_tokens_to_keep = K.  (transformers uses
+ *      n_stop + 1, which can leave fewer candidates than it draws and then raises.)  Codes outside get -inf.
+ *   3. acc(b, c) = s_b + w_b[c]; flat index i = b * codes + c.
+ *   4. Candidates, in "candidate order".  Deterministic: the K largest acc, descending, ties to the lower i.  Sampling:
+ *      key(i) = acc(i) + g(i), g = -log(-log u), u = ((word >> 8) + 0.5) * 2^-24, word = output word (i & 3) of Philox4x32-10
+ *      with the sentence's seed as key and counter (n, i >> 2, 1, 0) (the 1 keeps the stream apart from the sampler's
+ *      (n, 0, 0, 0)); the K largest keys, descending, ties to the lower i.  This is Gumbel-top-K: exactly K draws without
+ *      replacement from softmax(acc), in draw order, which is what torch.multinomial(softmax(acc), K) does; no renormalised
+ *      sequential pass, and the choice does not depend on any summation order.
+ *   5. stop(i): the candidate's code is a stop id, or n + 1 == max_new.
+ *   6. Next running hypotheses: the B candidates of largest acc among those with stop false, descending, ties to the earlier
+ *      candidate.  They inherit from their parent exactly as above (penalty vector, reset index, KV and token history, rows)
+ *      and do the greedy loop's bookkeeping with their own token; a running hypothesis never holds a stop id.
+ *   7. Pool.  Only while `open`, and not (early_stopping and every pool entry finished): each of the first B candidates in
+ *      candidate order with stop true enters at score acc / (n + 1)^length_penalty.  The pool keeps the B best of old and new,
+ *      an old entry before a new one on ties, then candidate order.  An entry freezes its parent's history plus its own token.
+ *   8. If every pool entry is finished: open := open and s'_0 / (n + 1)^length_penalty > the lowest pool score (s'_0: the best
+ *      new running score).  Otherwise `open` is unchanged.
+ *   9. The sentence ends after selection n when `open` is false, or early_stopping is set and every pool entry is finished, or
+ *      n + 1 == max_new.
+ * The result is pool entry 0: its tokens (the stop id stored and counted as above), its last_hidden_state rows along its own
+ * path (row n = the row of the pass whose logits produced token n) and its score.  repeat_penality is read and not written
+ * back: pool entries keep no vector.  The penalty stays the engine's (logits * pen before the log-softmax, with its range
+ * reset); transformers' RepetitionPenaltyLogitsProcessor is not part of this, and early_stopping = "never" is not offered.
+ *   Property: B = 1, deterministic, length_penalty = 0 gives the tokens of mi_gpt_generate wherever rounding cannot decide a
+ *      selection.
+ * Scores hold to a tolerance and choices wherever rounding cannot decide, as above; sampled results are the same bits from
+ * every launch, slot, batch and graph replay.  Not offered yet: pool mode through the sentence queue, and streaming of it (a
+ * group's retirement there needs the frozen list).
+ *
+ * MI_EINVAL, before anything is launched and with the handle still usable: what mi_gpt_generate_beam rejects; K > 64 or
+ * K > mel_codes; length_penalty not finite; early_stopping outside {0, 1}; an invalid sampling record; top_k not 0 and below K;
+ * more than 16384 mel codes with sampling; only some of the four sampling arrays.
+ *
+ * mi_gpt_generate_beam_pool: the arguments of mi_gpt_generate_beam (repeat_penality (nb, mel_codes) or NULL, read only), then
+ * length_penalty, early_stopping and four HOST arrays of nb sampling parameters (all four NULL: deterministic).  scores (nb) or
+ * NULL = the returned entry's score (0 for a sentence with max_new == 0, which returns nothing). */
+int         mi_gpt_generate_beam_pool(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                      const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                                      const float* repeat_penality, int num_beams, float length_penalty, int early_stopping,
+                                      const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
+                                      int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem);
+/* unit entry (tests, no handle): one selection of one sentence with the whole state passed in and out.  logits, pen (or NULL =
+ * ones): (beams, codes), following `mem`; everything else is a HOST array.  prev_scores (beams; ignored at n == 0);
+ * pool_scores / pool_finished (beams) and *open in / out; temperature / top_k / top_p / seed point to one value each (all four
+ * NULL: deterministic).  Outputs: cand / cand_acc / cand_stop (K = (n_stop + 1) * beams) = flat index, acc and stop flag in
+ * candidate order; parents / tokens / scores (beams) = the next running hypotheses (-1 where no live candidate is left);
+ * pool_src (beams): -1 - j = the entry that was at place j, q >= 0 = candidate q; *done = step 9.  1 <= codes <= 16384,
+ * 0 <= n < max_new, K <= 64 and <= codes. */
+int         mi_gpt_beam_pool_select(const float* logits, const float* pen, const float* prev_scores, int beams, int codes, int n,
+                                    int max_new, const int32_t* stop_ids, int n_stop, float* pool_scores, int32_t* pool_finished,
+                                    int32_t* open, float length_penalty, int early_stopping, const float* temperature,
+                                    const int32_t* top_k, const float* top_p, const uint64_t* seed, int32_t* cand, float* cand_acc,
+                                    int32_t* cand_stop, int32_t* parents, int32_t* tokens, float* scores, int32_t* pool_src,
+                                    int32_t* done, int mem);
 
 /* unit entries (tests, no handle): ONE launch of each of the GPT's four attention kernels, through the launcher the engine
  * calls (same kernel, grid, block and dynamic LDS).  softmax(q K^T [+ mask]) V per head of 64 columns, no scale (the engine's q

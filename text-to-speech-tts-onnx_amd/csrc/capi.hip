@@ -4,6 +4,7 @@
 #include "f5.h"
 #include "gpt.h"
 #include "gpt_queue.h"
+#include "gpt_pool.h"
 #include "cond.h"
 #include <algorithm>
 #include <memory>
@@ -1012,75 +1013,124 @@ int mi_gpt_queue_schedule(int n, const int32_t* prompt_rows, const int32_t* max_
     return guard([&] { gpt_queue_schedule(n, prompt_rows, max_new, lengths, slots, max_seq, beams, steps, n_passes, pass_of, unit_of); });
 }
 
-// beam search (gpt_beam.hip): gpt_generate_batch_impl's loop over nb groups of B slots
+// beam search (gpt_beam.hip, gpt_beam_pool.hip): gpt_generate_batch_impl's loop over nb groups of B slots, behind both beam
+// entries.  pool == null: hypothesis 0 is the result and its penalty vector is written back; else the pool-mode selection runs
+// and pool entry 0 is the result.
+struct GptPoolCall { float length_penalty; int early_stopping; const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seeds; };
+
+static void gpt_beam_run(mi_gpt* h, const std::string& who, int nb, const float* prompts, const int32_t* prompt_rows,
+                         const int32_t* max_new, const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                         const float* pen_in, float* pen_out, int num_beams, const GptPoolCall* pool, int32_t* tokens, float* hidden,
+                         int cap, int32_t* n_out, float* scores, int mem) {
+    const auto lk_ = gpt_enter(h, mem, who, true);
+    Gpt& e = *h->impl;
+    const GptCfg& c = e.cfg;
+    const int B = num_beams;
+    MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
+    MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
+    MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
+    MI_REQUIRE(nb >= 1 && (long)nb * B <= c.max_batch, who + ": nb * num_beams exceeds the handle's max_batch");
+    bool sampling = false;
+    if (pool) {
+        MI_REQUIRE(std::isfinite(pool->length_penalty), who + ": length_penalty must be finite");
+        MI_REQUIRE(pool->early_stopping == 0 || pool->early_stopping == 1, who + ": early_stopping must be 0 or 1");
+        sampling = pool->temperature || pool->top_k || pool->top_p || pool->seeds;
+        MI_REQUIRE(!sampling || (pool->temperature && pool->top_k && pool->top_p && pool->seeds), who + ": the four sampling arrays go together");
+    }
+    hipStream_t s = e.stream;
+    const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
+    std::vector<GptSampleRec> recs;
+    if (pool) {
+        const int K = ((int)stops.size() + 1) * B;
+        MI_REQUIRE(K <= GPT_POOL_MAX_CAND && K <= c.mel_codes, who + ": (n_stop + 1) * num_beams must be <= 64 and <= mel_codes");
+        if (sampling) {
+            MI_REQUIRE(c.mel_codes <= GPT_SAMPLE_MAX_CODES, who + ": sampling supports at most 16384 mel codes");
+            for (int g = 0; g < nb; ++g) {
+                recs.push_back(gpt_sample_rec(pool->temperature[g], pool->top_k[g], pool->top_p[g], pool->seeds[g]));
+                MI_REQUIRE(pool->top_k[g] == 0 || pool->top_k[g] >= K, who + ": top_k must be 0 or at least (n_stop + 1) * num_beams");
+            }
+        }
+    }
+    gpt_check_lengths(c, nb, prompt_rows, max_new, cap, who);
+    GptBeamScope group(e, B);
+    e.sampled = 0;
+    if (pool) e.pool_ensure(); else e.beam_ensure();
+    const int nr = nb * B;
+    // pen0 of sentence g -> side 0 of the group's first slot (selection 0 reads it there)
+    gpt_fill_penalty(e, nb, pen_in, in, B);
+    e.set_rep_value(repeat_value);
+    if (pool) e.pool_begin(nb, B, GptPoolCfg{pool->length_penalty, pool->early_stopping, sampling ? 1 : 0, 0}, sampling ? recs.data() : nullptr);
+    std::vector<int32_t> all((size_t)nr * GS_WORDS, 0);
+    for (int g = 0; g < nb; ++g) {
+        const std::vector<int32_t> w = gpt_state_words(stops, penalty_range, max_new[g], max_new[g] == 0);
+        for (int i = 0; i < B; ++i) std::copy(w.begin(), w.end(), all.begin() + ((size_t)g * B + i) * GS_WORDS);
+    }
+    MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+    e.history = 0;
+    bool any = false;
+    size_t row0 = 0;
+    for (int g = 0; g < nb; ++g) {                               // prompt passes, one per sentence, into the group's first slot
+        if (max_new[g] > 0) {
+            MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[g] * c.hidden * 4, in, s));
+            e.forward_rows(prompt_rows[g], 1, g * B);
+            if (pool) e.pool_select_first(g, B, prompt_rows[g]); else e.beam_select_first(g, B, prompt_rows[g]);
+            any = true;
+        }
+        row0 += prompt_rows[g];
+    }
+    int guard_steps = 0;
+    while (any && !gpt_read_states(e, all, B)) {
+        if (pool) e.decode_pool_steps(nb, B, 16); else e.decode_beam_steps(nb, B, 16);
+        guard_steps += 16;
+        MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
+    }
+    if (!any) gpt_read_states(e, all, B);
+    e.history = all[GS_HIST];
+    // the result of every group (hypothesis 0 along its ancestors, or pool entry 0 along its frozen list), gathered into
+    // staging, then out like the batched entry's rows
+    std::vector<int32_t> meta;
+    if (pool) {
+        meta.resize((size_t)nr * GPT_POOL_META);
+        MI_HIP(hipMemcpyAsync(meta.data(), e.pool_meta.p, meta.size() * 4, hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+    }
+    e.io_a.ensure((size_t)nb * cap * 4);
+    if (hidden) e.io_b.ensure((size_t)nb * cap * c.hidden * 4);
+    if (pool) e.pool_gather(nb, B, e.io_a.as<int32_t>(), hidden ? e.io_b.as<float>() : nullptr, cap);
+    else e.beam_gather(nb, B, e.io_a.as<int32_t>(), hidden ? e.io_b.as<float>() : nullptr, cap);
+    for (int g = 0; g < nb; ++g) {
+        const size_t s0 = (size_t)g * B;
+        int n = all[s0 * GS_WORDS + GS_NDEC];
+        if (pool) {
+            const int32_t* mw = meta.data() + s0 * GPT_POOL_META;
+            n = mw[PM_FIN] ? std::min(std::max(mw[PM_LEN], 0), cap) : 0;
+        }
+        n_out[g] = n;
+        copy_out(tokens ? tokens + (size_t)g * cap : nullptr, e.io_a.as<int32_t>() + (size_t)g * cap, (size_t)n * 4, mem, s);
+        if (hidden)
+            copy_out(hidden + (size_t)g * cap * c.hidden, e.io_b.as<float>() + (size_t)g * cap * c.hidden,
+                     (size_t)n * c.hidden * 4, mem, s);
+        if (pool) {
+            if (n == 0) MI_HIP(hipMemsetAsync(e.pool_score.as<float>() + s0, 0, 4, s));      // nothing returned: score 0, not the empty pool's -1e9
+            copy_out(scores ? scores + g : nullptr, e.pool_score.as<float>() + s0, 4, mem, s);
+        } else {
+            const int nd = all[s0 * GS_WORDS + GS_NDEC];
+            const float* pen_side = ((nd & 1) ? e.pen_b.as<float>() : e.pen.as<float>()) + s0 * c.mel_codes;
+            copy_out(pen_out ? pen_out + (size_t)g * c.mel_codes : nullptr, pen_side, (size_t)c.mel_codes * 4, mem, s);
+            copy_out(scores ? scores + g : nullptr, e.score.as<float>() + s0, 4, mem, s);
+        }
+    }
+    MI_HIP(hipStreamSynchronize(s));
+}
+
 int mi_gpt_generate_beam(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                          const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, float* repeat_penality,
                          int num_beams, int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem) {
     return guard([&] {
-        const std::string who = "mi_gpt_generate_beam";
-        const auto lk_ = gpt_enter(h, mem, "mi_gpt_generate_beam", true);
-        Gpt& e = *h->impl;
-        const GptCfg& c = e.cfg;
-        const int B = num_beams;
-        MI_REQUIRE(prompts && prompt_rows && max_new && n_out && cap >= 1, who + ": null argument");
-        MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX, who + ": num_beams must be in [1, 8]");
-        MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
-        MI_REQUIRE(nb >= 1 && (long)nb * B <= c.max_batch, who + ": nb * num_beams exceeds the handle's max_batch");
-        hipStream_t s = e.stream;
-        const hipMemcpyKind in = mem == MI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        const std::vector<int32_t> stops = gpt_fetch_stops(stop_ids, n_stop, mem, who);
-        gpt_check_lengths(c, nb, prompt_rows, max_new, cap, who);
-        GptBeamScope group(e, B);
-        e.sampled = 0;
-        e.beam_ensure();
-        const int nr = nb * B;
-        // pen0 of sentence g -> side 0 of the group's first slot (selection 0 reads it there)
-        gpt_fill_penalty(e, nb, repeat_penality, in, B);
-        e.set_rep_value(repeat_value);
-        std::vector<int32_t> all((size_t)nr * GS_WORDS, 0);
-        for (int g = 0; g < nb; ++g) {
-            const std::vector<int32_t> w = gpt_state_words(stops, penalty_range, max_new[g], max_new[g] == 0);
-            for (int i = 0; i < B; ++i) std::copy(w.begin(), w.end(), all.begin() + ((size_t)g * B + i) * GS_WORDS);
-        }
-        MI_HIP(hipMemcpyAsync(e.state.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
-        MI_HIP(hipStreamSynchronize(s));
-        e.history = 0;
-        bool any = false;
-        size_t row0 = 0;
-        for (int g = 0; g < nb; ++g) {                               // prompt passes, one per sentence, into the group's first slot
-            if (max_new[g] > 0) {
-                MI_HIP(hipMemcpyAsync(e.X.p, prompts + row0 * c.hidden, (size_t)prompt_rows[g] * c.hidden * 4, in, s));
-                e.forward_rows(prompt_rows[g], 1, g * B);
-                e.beam_select_first(g, B, prompt_rows[g]);
-                any = true;
-            }
-            row0 += prompt_rows[g];
-        }
-        int guard_steps = 0;
-        while (any && !gpt_read_states(e, all, B)) {
-            e.decode_beam_steps(nb, B, 16);
-            guard_steps += 16;
-            MI_REQUIRE(guard_steps <= c.max_seq + 32, who + ": decode loop did not terminate");
-        }
-        if (!any) gpt_read_states(e, all, B);
-        e.history = all[GS_HIST];
-        // hypothesis 0 of every group, gathered along its ancestors into staging, then out like the batched entry's rows
-        e.io_a.ensure((size_t)nb * cap * 4);
-        if (hidden) e.io_b.ensure((size_t)nb * cap * c.hidden * 4);
-        e.beam_gather(nb, B, e.io_a.as<int32_t>(), hidden ? e.io_b.as<float>() : nullptr, cap);
-        for (int g = 0; g < nb; ++g) {
-            const size_t s0 = (size_t)g * B;
-            const int n = all[s0 * GS_WORDS + GS_NDEC];
-            n_out[g] = n;
-            copy_out(tokens ? tokens + (size_t)g * cap : nullptr, e.io_a.as<int32_t>() + (size_t)g * cap, (size_t)n * 4, mem, s);
-            if (hidden)
-                copy_out(hidden + (size_t)g * cap * c.hidden, e.io_b.as<float>() + (size_t)g * cap * c.hidden,
-                         (size_t)n * c.hidden * 4, mem, s);
-            const float* pen_side = ((n & 1) ? e.pen_b.as<float>() : e.pen.as<float>()) + s0 * c.mel_codes;
-            copy_out(repeat_penality ? repeat_penality + (size_t)g * c.mel_codes : nullptr, pen_side, (size_t)c.mel_codes * 4, mem, s);
-            copy_out(scores ? scores + g : nullptr, e.score.as<float>() + s0, 4, mem, s);
-        }
-        MI_HIP(hipStreamSynchronize(s));
+        gpt_beam_run(h, "mi_gpt_generate_beam", nb, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                     repeat_penality, repeat_penality, num_beams, nullptr, tokens, hidden, cap, n_out, scores, mem);
     });
 }
 
@@ -1113,6 +1163,86 @@ int mi_gpt_beam_select(const float* logits, const float* pen, const float* prev_
             copy_out(scores, sc, rows * 4, mem, s);
         }
         MI_HIP(hipStreamSynchronize(s));
+    });
+}
+
+// beam search with a finished pool (gpt_beam_pool.hip): the same loop with the pool-mode selection
+int mi_gpt_generate_beam_pool(mi_gpt* h, int nb, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                              const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range,
+                              const float* repeat_penality, int num_beams, float length_penalty, int early_stopping,
+                              const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seeds,
+                              int32_t* tokens, float* hidden, int cap, int32_t* n_out, float* scores, int mem) {
+    return guard([&] {
+        const GptPoolCall pc{length_penalty, early_stopping, temperature, top_k, top_p, seeds};
+        gpt_beam_run(h, "mi_gpt_generate_beam_pool", nb, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value, penalty_range,
+                     repeat_penality, nullptr, num_beams, &pc, tokens, hidden, cap, n_out, scores, mem);
+    });
+}
+
+int mi_gpt_beam_pool_select(const float* logits, const float* pen, const float* prev_scores, int beams, int codes, int n,
+                            int max_new, const int32_t* stop_ids, int n_stop, float* pool_scores, int32_t* pool_finished,
+                            int32_t* open, float length_penalty, int early_stopping, const float* temperature,
+                            const int32_t* top_k, const float* top_p, const uint64_t* seed, int32_t* cand, float* cand_acc,
+                            int32_t* cand_stop, int32_t* parents, int32_t* tokens, float* scores, int32_t* pool_src,
+                            int32_t* done, int mem) {
+    return guard([&] {
+        const std::string who = "mi_gpt_beam_pool_select";
+        MI_REQUIRE(mem == MI_HOST || mem == MI_DEVICE, who + ": bad mem kind");
+        MI_REQUIRE(logits && (n == 0 || prev_scores) && pool_scores && pool_finished && open && cand && cand_acc && cand_stop &&
+                   parents && tokens && scores && pool_src && done, who + ": null argument");
+        MI_REQUIRE(codes >= 1 && codes <= GPT_BEAM_MAX_CODES, who + ": supports 1..16384 codes");
+        MI_REQUIRE(beams >= 1 && beams <= GPT_BEAM_MAX, who + ": beams must be in [1, 8]");
+        MI_REQUIRE(n_stop >= 0 && n_stop <= GS_WORDS - GS_STOP0 && (n_stop == 0 || stop_ids), who + ": at most 6 stop ids");
+        MI_REQUIRE(n >= 0 && max_new >= 1 && n < max_new, who + ": 0 <= n < max_new");
+        MI_REQUIRE(std::isfinite(length_penalty), who + ": length_penalty must be finite");
+        MI_REQUIRE(early_stopping == 0 || early_stopping == 1, who + ": early_stopping must be 0 or 1");
+        const int B = beams, K = (n_stop + 1) * B;
+        MI_REQUIRE(K <= GPT_POOL_MAX_CAND && K <= codes, who + ": (n_stop + 1) * beams must be <= 64 and <= codes");
+        const bool sampling = temperature || top_k || top_p || seed;
+        MI_REQUIRE(!sampling || (temperature && top_k && top_p && seed), who + ": the four sampling parameters go together");
+        GptPoolSelect p{};
+        p.B = B; p.codes = codes; p.n = n; p.max_new = max_new; p.n_stop = n_stop;
+        for (int q = 0; q < n_stop; ++q) p.stops[q] = stop_ids[q];
+        p.length_penalty = length_penalty; p.early_stopping = early_stopping; p.sampling = sampling ? 1 : 0;
+        p.rec = GptSampleRec{1.f, 1.f, 0, 0u, 0u, {0u, 0u, 0u}};
+        if (sampling) {
+            p.rec = gpt_sample_rec(*temperature, *top_k, *top_p, *seed);
+            MI_REQUIRE(*top_k == 0 || *top_k >= K, who + ": top_k must be 0 or at least (n_stop + 1) * beams");
+        }
+        hipStream_t s;
+        MI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        struct Fin { hipStream_t s; ~Fin() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } fin{s};
+        DevBuf dl, dp, dkeys, dsmall;
+        const size_t nl = (size_t)B * codes;
+        const float* l = (const float*)stage_in(dl, logits, nl * 4, mem, s);
+        const float* pn = pen ? (const float*)stage_in(dp, pen, nl * 4, mem, s) : nullptr;
+        dkeys.ensure(nl * 4);
+        // the small arrays are HOST arrays: one staging block, words [prev B | pool_score B | pool_fin B | open, done | cand K |
+        // cand_acc K | cand_stop K | parents B | tokens B | scores B | pool_src B]
+        const size_t words = 7 * (size_t)B + 2 + 3 * (size_t)K;
+        std::vector<int32_t> hb(words, 0);
+        float* hf = reinterpret_cast<float*>(hb.data());
+        for (int b = 0; b < B; ++b) {
+            hf[b] = n == 0 ? 0.f : prev_scores[b];
+            hf[B + b] = pool_scores[b];
+            hb[2 * B + b] = pool_finished[b] != 0;
+        }
+        hb[3 * B] = *open != 0;
+        dsmall.ensure(words * 4);
+        MI_HIP(hipMemcpyAsync(dsmall.p, hb.data(), words * 4, hipMemcpyHostToDevice, s));
+        int32_t* d = dsmall.as<int32_t>();
+        float* df = dsmall.as<float>();
+        const size_t oc = 3 * (size_t)B + 2, ob = oc + 3 * (size_t)K;
+        launch_gpt_pool_select(l, pn, dkeys.as<unsigned>(), p, df, df + B, d + 2 * B, d + 3 * B, d + oc, df + oc + K, d + oc + 2 * K,
+                               d + ob, d + ob + B, df + ob + 2 * B, d + ob + 3 * B, s);
+        MI_HIP(hipMemcpyAsync(hb.data(), dsmall.p, words * 4, hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+        for (int b = 0; b < B; ++b) {
+            pool_scores[b] = hf[B + b]; pool_finished[b] = hb[2 * B + b];
+            parents[b] = hb[ob + b]; tokens[b] = hb[ob + B + b]; scores[b] = hf[ob + 2 * B + b]; pool_src[b] = hb[ob + 3 * B + b];
+        }
+        *open = hb[3 * B]; *done = hb[3 * B + 1];
+        for (int q = 0; q < K; ++q) { cand[q] = hb[oc + q]; cand_acc[q] = hf[oc + K + q]; cand_stop[q] = hb[oc + 2 * K + q]; }
     });
 }
 

@@ -27,6 +27,10 @@ inline int gpt_padded_rows(int mb) { return mb <= 2 ? 2 : mb <= 4 ? 4 : mb <= 8 
 // a decode-step linear layer as its launchers see it: weights (n, k) of `dtype`, fp32 bias (n) or null, both on the device
 struct GptLin { int dtype; const void* w; const float* bias; int n, k; };
 
+struct GptSampleRec;      // gpt_pick.h
+struct GptPoolCfg;        // gpt_pool.h
+struct GptPoolDev;
+
 struct Gpt {
     GptCfg cfg;
     int dtype, device;
@@ -45,7 +49,7 @@ struct Gpt {
     DevBuf logits, last, pen, toks, hid, state;       // per slot: [slot][codes] / [slot][h] / [slot][max_seq](x h) / words
     DevBuf Xd, xnd, qkvd, attd, ffd, zd;              // batched decode step: one row per slot
     int MBp = 2;              // gpt_padded_rows(max_batch)
-    // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams)
+    // decode step over nb slots, keyed by (nb, sampled); beam steps: (nb * beams, 1 + beams), in pool mode (nb * beams, 9 + beams)
     std::map<std::pair<int, int>, hipGraphExec_t> batch_graphs;
     DevBuf io_a, io_b, io_s;  // host<->device staging (io_s: scores of a queue round)
     DevBuf rep_dev;           // REPEAT_PENALITY as a device scalar (read by gpt_pick_kernel, also inside replayed graphs)
@@ -74,6 +78,16 @@ struct Gpt {
     // the sentence queue with beams: selection 0 of the k groups of the packed pass just run (their segments are in segtab), in
     // one launch; retirement of the table's groups along their ancestor tables, with hypothesis 0's scores, in one launch
     void beam_select_segs(int k, int B);
+    // beam search with a finished pool (gpt_beam_pool.hip): the decode step and attention above with a selection kernel of its
+    // own; the pool of every group, its frozen ancestor lists and last rows, the key scratch and the call's parameters
+    DevBuf pool_score, pool_meta, pool_anc, pool_hid, pool_keys, pool_cfg, pool_rec;      // allocated by the first pool call
+    void pool_ensure();
+    GptPoolDev pool_dev();
+    void pool_begin(int nb, int B, const GptPoolCfg& cf, const GptSampleRec* recs);      // empty pools; recs: nb records or null
+    void pool_select_first(int group, int B, int rows);
+    void decode_pool_eager(int nb, int B);
+    void decode_pool_steps(int nb, int B, int n);
+    void pool_gather(int nb, int B, int32_t* tokens, float* hidden, int cap);          // pool entry 0 of every group
     hipGraphExec_t step_graph[2] = {nullptr, nullptr};      // by mode
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under

@@ -99,6 +99,51 @@ __device__ __forceinline__ void gpt_pick_finish(int idx, GptPickLoads& L, float*
     }
 }
 
+// ---- shared by the sampler (gpt_sample.hip) and pool-mode beam search (gpt_beam_pool.hip) ------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): the four output words for counter (c0, c1, c2, c3) and key (k0, k1).  The sampler reads
+// word 0 of counter (n, 0, 0, 0); pool-mode beam sampling reads word (i & 3) of counter (n, i >> 2, 1, 0) (gpt_beam_pool.hip)
+__device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+// float -> uint whose unsigned order is the float order (-0 and +0 share a key, as they compare equal)
+__device__ __forceinline__ unsigned order_key(float z) {
+    unsigned b = __float_as_uint(z);
+    if (b == 0x80000000u) b = 0;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+// wave 0: bins of h[0..256) walked from the top; the bin in which the running sum from above reaches `need`, and what of
+// `need` is left for that bin, go to *bin / *rest (and the bin's own total to *cnt)
+template <typename T>
+__device__ __forceinline__ void select_from_top(const T* h, T need, int lane, unsigned* bin, T* rest, T* cnt = nullptr) {
+    T v[4];
+    T s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[i] = h[255 - 4 * lane - i]; s += v[i]; }
+    T b = wave_incl_scan(s, lane) - s;                      // everything in bins above this lane's four
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (b < need && need <= b + v[i]) { *bin = (unsigned)(255 - 4 * lane - i); *rest = need - b; if (cnt) *cnt = v[i]; }
+        b += v[i];
+    }
+}
+
 // gpt_sample.hip
 // one token per slot by the header's sampling definition (include/mi355tts.h); grid = slots, arguments as gpt_pick_kernel's
 void launch_gpt_sample(int nb, const float* logits, float* pen, const float* last, int* st, int* toks, float* hid, int codes,

@@ -27,54 +27,10 @@ struct GptSampleShared {
     int token;
 };
 
-// first output word of Philox4x32-10 (Salmon et al., SC'11), counter (c0, c1, 0, 0), key (k0, k1)
-__device__ __forceinline__ unsigned philox4x32_10_w0(unsigned c0, unsigned c1, unsigned k0, unsigned k1) {
-    unsigned c2 = 0, c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
-// float -> uint whose unsigned order is the float order (-0 and +0 share a key, as they compare equal)
-__device__ __forceinline__ unsigned order_key(float z) {
-    unsigned b = __float_as_uint(z);
-    if (b == 0x80000000u) b = 0;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// wave 0: bins of h[0..256) walked from the top; the bin in which the running sum from above reaches `need`, and what of
-// `need` is left for that bin, go to *bin / *rest
-template <typename T>
-__device__ __forceinline__ void select_from_top(const T* h, T need, int lane, unsigned* bin, T* rest) {
-    T v[4];
-    T s = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = h[255 - 4 * lane - i]; s += v[i]; }
-    T b = wave_incl_scan(s, lane) - s;                      // everything in bins above this lane's four
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (b < need && need <= b + v[i]) { *bin = (unsigned)(255 - 4 * lane - i); *rest = need - b; }
-        b += v[i];
-    }
 }
 
 // The token for decode index n = (n_lo, n_hi) of one row.  Called by all 1024 threads; the result is valid in every thread.
@@ -97,7 +53,7 @@ __device__ int gpt_sample_token(const float* __restrict__ logits, const float* _
             z[j] = greedy ? v : v * inv_T;
         }
     }
-    const unsigned u24 = philox4x32_10_w0(n_lo, n_hi, r.seed_lo, r.seed_hi) >> 8;
+    const unsigned u24 = philox4x32_10(n_lo, n_hi, 0u, 0u, r.seed_lo, r.seed_hi).x >> 8;
     if (u_out && tid == 0) *u_out = (float)u24 * 0x1p-24f;
     if (tid == 0) { sh.sel_bin = 0; sh.sel_need = 1; sh.sel_mass = 1; sh.token = 0; }
 

@@ -177,6 +177,14 @@ def load() -> C.CDLL:
     L.mi_gpt_generate_beam.restype = C.c_int
     L.mi_gpt_beam_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int]
     L.mi_gpt_beam_select.restype = C.c_int
+    if hasattr(L, "mi_gpt_generate_beam_pool"):
+        L.mi_gpt_generate_beam_pool.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
+                                                C.c_int, vp, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
+                                                C.POINTER(C.c_int32), vp, C.c_int]
+        L.mi_gpt_generate_beam_pool.restype = C.c_int
+        L.mi_gpt_beam_pool_select.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_float,
+                                              C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+        L.mi_gpt_beam_pool_select.restype = C.c_int
     if hasattr(L, "mi_gpt_attn_decode"):
         L.mi_gpt_attn_decode.argtypes = [vp, vp, vp] + [C.c_int] * 4 + [vp, vp, C.c_int]
         L.mi_gpt_attn_decode.restype = C.c_int

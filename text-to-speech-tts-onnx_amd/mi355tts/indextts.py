@@ -176,15 +176,15 @@ def lockstep_steps(lengths, slots):
 MAX_BEAMS = 8
 
 
-def _check_beams(beams, nb, cfg, sampling=None):
+def _check_beams(beams, nb, cfg, sampling=None, pool=False):
     """The ``beams`` keyword of ``IndexGPT.generate*`` (include/mi355tts.h, "beam search"): an integer in [1, 8], not above the
-    code count, nb * beams slots within the engine's max_batch, and never together with ``sampling``."""
+    code count, nb * beams slots within the engine's max_batch, and together with ``sampling`` only in pool mode."""
     if isinstance(beams, bool) or int(beams) != beams or not 1 <= beams <= MAX_BEAMS:
         raise ValueError(f"beams must be an integer in [1, {MAX_BEAMS}], got {beams}")
     beams = int(beams)
     if beams > 1:
-        if sampling is not None:
-            raise ValueError("beams and sampling do not combine: beam search is deterministic")
+        if sampling is not None and not pool:
+            raise ValueError("beams and sampling do not combine without pool=True: that beam search is deterministic")
         if beams > cfg.mel_codes:
             raise ValueError(f"beams = {beams} exceeds the {cfg.mel_codes} mel codes")
         if nb * beams > cfg.max_batch:
@@ -215,6 +215,42 @@ def beam_select(logits, prev_scores=None, *, beams: int, first: bool = False, pe
         codes, int(bool(first)), par.ctypes.data, tok.ctypes.data, sc.ctypes.data, _lib.MI_HOST), "mi_gpt_beam_select")
     g = rows // beams
     return par.reshape(g, beams), tok.reshape(g, beams), sc.reshape(g, beams)
+
+
+def beam_pool_select(logits, prev_scores, *, beams: int, n: int, max_new: int, stop_tokens=(), pool_scores, pool_finished,
+                     open: bool = True, length_penalty: float = 0.0, early_stopping: bool = False, sampling=None, pen=None):
+    """One pool-mode selection of one sentence (unit entry mi_gpt_beam_pool_select; include/mi355tts.h, "beam search with a
+    finished pool").  logits (beams, codes), pen likewise or None, prev_scores (beams,) (ignored at n == 0), pool_scores /
+    pool_finished (beams,), sampling a Sampling or None.  Returns a dict: cand / cand_acc / cand_stop (K,) in candidate order,
+    parents / tokens / scores (beams,) of the next running hypotheses, pool_scores / pool_finished / pool_src (beams,) after
+    the merge (pool_src: -1 - j = the entry that was at place j, q >= 0 = candidate q), open, done."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim != 2 or lg.shape[0] != beams:
+        raise ValueError("logits must be (beams, codes)")
+    B, codes = lg.shape
+    pn = None if pen is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pen, np.float32), lg.shape))
+    pv = None if prev_scores is None else np.ascontiguousarray(np.asarray(prev_scores, np.float32).reshape(-1))
+    if pv is not None and pv.size != B:
+        raise ValueError(f"prev_scores must hold {B} values")
+    stops = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
+    K = (stops.size + 1) * B
+    ps = np.ascontiguousarray(np.asarray(pool_scores, np.float32).reshape(-1)).copy()
+    pf = np.ascontiguousarray(np.asarray(pool_finished).reshape(-1).astype(np.int32))
+    if ps.size != B or pf.size != B:
+        raise ValueError(f"pool_scores and pool_finished must hold {B} values")
+    op, dn = np.array([int(bool(open))], np.int32), np.zeros((1,), np.int32)
+    sa = None if sampling is None else _sampling_arrays([sampling])
+    cand, cacc, cstop = np.zeros((max(K, 1),), np.int32), np.zeros((max(K, 1),), np.float32), np.zeros((max(K, 1),), np.int32)
+    par, tok, src = np.zeros((B,), np.int32), np.zeros((B,), np.int32), np.zeros((B,), np.int32)
+    sc = np.zeros((B,), np.float32)
+    _lib.check(_lib.load().mi_gpt_beam_pool_select(
+        lg.ctypes.data, None if pn is None else pn.ctypes.data, None if pv is None else pv.ctypes.data, B, codes, int(n),
+        int(max_new), stops.ctypes.data if stops.size else None, stops.size, ps.ctypes.data, pf.ctypes.data, op.ctypes.data,
+        float(length_penalty), int(early_stopping), *((None,) * 4 if sa is None else (a.ctypes.data for a in sa)),
+        cand.ctypes.data, cacc.ctypes.data, cstop.ctypes.data, par.ctypes.data, tok.ctypes.data, sc.ctypes.data, src.ctypes.data,
+        dn.ctypes.data, _lib.MI_HOST), "mi_gpt_beam_pool_select")
+    return dict(cand=cand[:K], cand_acc=cacc[:K], cand_stop=cstop[:K].astype(bool), parents=par, tokens=tok, scores=sc,
+                pool_scores=ps, pool_finished=pf.astype(bool), pool_src=src, open=bool(op[0]), done=bool(dn[0]))
 
 
 def _attn_inputs(q, K, V, slots: bool):
@@ -913,16 +949,28 @@ class IndexGPT:
         return n
 
     def generate_beam(self, prompts, max_new, beams: int, *, stop_tokens=None, repeat_value=None, penalty_range=None,
-                      repeat_penality=None):
+                      repeat_penality=None, pool: bool = False, length_penalty: float = 0.0, early_stopping: bool = False,
+                      sampling=None):
         """Beam search (include/mi355tts.h, "beam search"; always the beam entry, beams = 1 included): every sentence runs
         ``beams`` hypotheses over one shared KV cache and its best one is returned.  prompts / max_new as generate_batch.
         Returns a list of (tokens, hidden, score) — score = the hypothesis' cumulative log-probability — and the
-        (nb, mel_codes) penalty matrix."""
+        (nb, mel_codes) penalty matrix.
+
+        ``pool=True`` is the second beam mode ("beam search with a finished pool"): finished hypotheses are kept aside, the
+        best of the pool is returned (score = its cumulative log-probability / length ** length_penalty), and with
+        ``sampling`` (one Sampling or a list of nb) the candidates are drawn.  The penalty matrix is then returned as given."""
         c = self.cfg
         nb = len(prompts)
-        beams = _check_beams(beams, nb, c)
+        if not pool and (length_penalty != 0.0 or early_stopping):
+            raise ValueError("length_penalty and early_stopping belong to pool=True")
+        samp = _batch_sampling(sampling, nb)
+        if samp is not None and not pool:
+            raise ValueError("beams and sampling do not combine without pool=True: that beam search is deterministic")
+        beams = _check_beams(beams, nb, c, sampling=samp, pool=bool(pool))
         if nb < 1 or nb * beams > c.max_batch or len(max_new) != nb:
             raise ValueError(f"{nb} sentences x {beams} beams; this engine was created with max_batch = {c.max_batch}")
+        if samp is not None and any(x is None for x in samp):
+            raise ValueError("pool mode samples every sentence of the call or none")
         ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
         rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
         cat = np.ascontiguousarray(np.concatenate(ps, axis=0))
@@ -935,11 +983,17 @@ class IndexGPT:
         hid = np.zeros((nb, cap, c.hidden), np.float32)
         n = np.zeros((nb,), np.int32)
         sc = np.zeros((nb,), np.float32)
-        _lib.check(_lib.load().mi_gpt_generate_beam(
-            self._h, nb, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None, stops.size,
-            float(c.repeat_penalty if repeat_value is None else repeat_value),
-            int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, beams, toks.ctypes.data,
-            hid.ctypes.data, cap, _lib.i32p(n), sc.ctypes.data, _lib.MI_HOST), "mi_gpt_generate_beam")
+        head = (self._h, nb, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None, stops.size,
+                float(c.repeat_penalty if repeat_value is None else repeat_value),
+                int(c.penalty_range if penalty_range is None else penalty_range), pen.ctypes.data, beams)
+        tail = (toks.ctypes.data, hid.ctypes.data, cap, _lib.i32p(n), sc.ctypes.data, _lib.MI_HOST)
+        if pool:
+            sa = None if samp is None else _sampling_arrays(samp)
+            _lib.check(_lib.load().mi_gpt_generate_beam_pool(
+                *head, float(length_penalty), int(early_stopping), *((None,) * 4 if sa is None else (a.ctypes.data for a in sa)),
+                *tail), "mi_gpt_generate_beam_pool")
+        else:
+            _lib.check(_lib.load().mi_gpt_generate_beam(*head, *tail), "mi_gpt_generate_beam")
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy(), float(sc[b])) for b in range(nb)], pen
 
     def generate(self, conds_latent, text_ids, *, max_generate_length=None, **kw):

@@ -94,7 +94,7 @@ def build_engines(args, vocab):
     fast = not args.small
     state = lambda spec: weights.synth_state(spec, args.seed, fast=fast)
     cond = IndexCond(ccfg, state(weights.cond_spec(ccfg)))
-    gpt = IndexGPT(gcfg, state(weights.gpt_spec(gcfg)), dtype=args.dtype)
+    gpt = IndexGPT(gcfg, state(weights.gpt_spec(gcfg)), dtype=args.dtype, weights=args.gpt_weights)
     voc = BigVGANVocoder(vcfg, state(weights.bigvgan_spec(vcfg)), dtype=args.dtype)
     return (gcfg, ccfg, vcfg), (cond, gpt, voc)
 
@@ -112,6 +112,8 @@ def parse_args(argv=None):
     ap.add_argument("--tokenizer", default=os.path.join(ROOT, "tests", "golden", "indextts_sp.model"),
                     help="sentencepiece model; default: the small fixture model of this repo")
     ap.add_argument("--dtype", default="f16", choices=["f32", "f16", "bf16"])
+    ap.add_argument("--gpt-weights", default=None, choices=["q8"], help="q8: the GPT's linear weights as per-channel uint8, dequantised in the "
+                    "kernels (needs --dtype f16; about half the f16 handle's weight bytes)")
     ap.add_argument("--device-type", default="cpu", choices=["cpu", "cuda"], help="cuda: per-sentence tensors stay in HBM between the engine calls")
     ap.add_argument("--small", action="store_true", help="reduced synthetic models (smoke runs)")
     ap.add_argument("--max-generate-length", type=int, default=None)

@@ -251,6 +251,25 @@ mi_gpt*     mi_gpt_create(const int32_t* cfg, int n_cfg, const float* weights, i
 mi_gpt*     mi_gpt_create_mem(const int32_t* cfg, int n_cfg, const float* weights, int64_t n_weights, int dtype, int device,
                               int mem);
 void        mi_gpt_destroy(mi_gpt* h);
+/* Per-channel uint8 weights, dequantised in the kernels.  The six matrix kinds of the blob (c_attn, attn.c_proj, c_fc, mlp.c_proj of
+ * every layer and lm_head.1, stored as (n, k) rows) are held as bytes; everything else (embeddings, position tables, LayerNorm vectors,
+ * biases: fp32; KV cache: the engine dtype) is as in mi_gpt_create.  The format, per output row n, all in float32:
+ *     rmin = min(0, min_k w[n,k]), rmax = max(0, max_k w[n,k]); scale[n] = (rmax - rmin) / 255 (an all-zero row: scale 1, zp 0);
+ *     zp[n] = clip(rint(-rmin / scale), 0, 255); q[n,k] = clip(rint(w[n,k] / scale) + zp, 0, 255); dq[n,k] = float32(q - zp) * scale
+ * (rint: round half to even).  It restates the weight side of the reference's int8 export (IndexTTS/Optimize_ONNX.py:
+ * quantize_dynamic(per_channel=True, weight_type=QUInt8, MatMulConstBOnly=True), reduce_range off); parity with onnxruntime's own bytes
+ * is not pinned by any test.  Unlike that export the activations are NOT quantised: weights 8-bit, activations 16-bit.  The kernels
+ * compute act(scale[n] * sum_k (q - zp) x'[k] + bias[n]) + res[n] with (q - zp) exact and the sum in fp32; prompt passes of two or
+ * more rows read an f16 copy f16(dq) of the matrix in use, written into one scratch of the handle.
+ *   mi_gpt_quantize_u8   the rule above on the host (no GPU needed): w (n, k) -> q (n, k), scale (n), zp (n).
+ *   mi_gpt_create_q8     mi_gpt_create_mem on the same canonical fp32 blob (host or device by `mem`), quantised at creation: the same
+ *                        bytes whichever `mem`.  dtype must be MI_F16; MI_F32 and MI_BF16 are refused (NULL, mi_last_error names the
+ *                        cause), as are a hidden or inner that is not a multiple of 16.  "gpt_mfma_min" and MI355TTS_GPT_NO_MFMA apply.
+ *   mi_gpt_weight_bytes  device bytes the handle holds for the six matrix kinds.  A q8 handle: sum n * k (bytes) + 4 * sum n (scales)
+ *                        + sum n (zero points) + 2 * max n * k (the prompt scratch); any other handle: sum n * k elements of its dtype. */
+int         mi_gpt_quantize_u8(const float* w, int n, int k, uint8_t* q, float* scale, uint8_t* zp);
+mi_gpt*     mi_gpt_create_q8(const int32_t* cfg, int n_cfg, const float* weights, int64_t n_weights, int dtype, int device, int mem);
+int64_t     mi_gpt_weight_bytes(mi_gpt* h);
 /* graph B: text_ids (n) -> text_hidden_state (n + 2, hidden): start id 0 / end id 1 added, + position rows. */
 int         mi_gpt_text_embed(mi_gpt* h, const int32_t* text_ids, int n, float* out, int mem);
 /* graph C: mel embedding of gpt_id + mel position row gen_len -> (hidden). (the caller keeps gen_len + 1) */
@@ -500,6 +519,16 @@ int         mi_gpt_linear_batch(const float* w, const float* bias, const float* 
                                 int nb, const float* res, int act, int out_f32, int qkv, const int32_t* hist, int max_seq,
                                 float* kc, float* vc, float* out, int mem);
 int         mi_gpt_linear_batch_rows(int nb);       /* P above; < 0 (MI_EINVAL) outside 1..64 */
+/* the same two entries on uint8 weights (the format of mi_gpt_create_q8): q (n, k) bytes, scale (n) fp32, zp (n) bytes in place of w,
+ * following `mem`; dtype is the activation type and must be MI_F16; k a multiple of 16, at most 8192 in decode, and the fused LayerNorm
+ * takes k <= 4096.  Same NaN presets, same launchers as the engine (csrc/gpt_q8.hip). */
+int         mi_gpt_linear_decode_q8(const uint8_t* q, const float* scale, const uint8_t* zp, const float* bias, const float* x,
+                                    int dtype, int n, int k, const float* ln_w, const float* ln_b, const float* pre_w,
+                                    const float* pre_b, float* pre_out, const float* res, int act, int out_f32, int qkv, int hist,
+                                    int max_seq, float* kc, float* vc, float* out, int mem);
+int         mi_gpt_linear_batch_q8(const uint8_t* q, const float* scale, const uint8_t* zp, const float* bias, const float* x,
+                                   const float* x_dead, int dtype, int n, int k, int nb, const float* res, int act, int out_f32,
+                                   int qkv, const int32_t* hist, int max_seq, float* kc, float* vc, float* out, int mem);
 
 /* ---- sentence queue: any number of sentences through the handle's slots, a slot refilled as soon as its sentence stops ---------
  * A decode step costs little more for 16 live slots than for 1, and 64 cost far less than four times 16,

@@ -677,6 +677,38 @@ mi_gpt* mi_gpt_create_mem(const int32_t* cfg, int n_cfg, const float* weights, i
     return rc == MI_OK ? h : nullptr;
 }
 
+mi_gpt* mi_gpt_create_q8(const int32_t* cfg, int n_cfg, const float* weights, int64_t n_weights, int dtype, int device, int mem) {
+    mi_gpt* h = nullptr;
+    int rc = guard([&] {
+        MI_REQUIRE(weights != nullptr && (mem == MI_HOST || mem == MI_DEVICE), "mi_gpt_create_q8: null weights / bad mem kind");
+        GptCfg c = parse_gpt_cfg(cfg, n_cfg);
+        MI_REQUIRE(n_weights == gpt_param_count(c), "gpt: weight blob size does not match the config");
+        // quantised on the host from the fp32 blob, wherever it lives: the same bytes whichever mem
+        std::vector<float> hw;
+        if (mem == MI_DEVICE) hw = read_back(weights, n_weights, device);
+        Gpt* impl = new Gpt(c, mem == MI_DEVICE ? hw.data() : weights, n_weights, dtype, device, GPT_W_Q8);
+        h = new mi_gpt; h->impl = impl;
+    });
+    return rc == MI_OK ? h : nullptr;
+}
+
+int64_t mi_gpt_weight_bytes(mi_gpt* h) {
+    int64_t n = -1;
+    int rc = guard([&] {
+        MI_REQUIRE(h && h->impl, "mi_gpt_weight_bytes: null handle");
+        n = h->impl->weight_bytes();
+    });
+    return rc == MI_OK ? n : (int64_t)rc;
+}
+
+int mi_gpt_quantize_u8(const float* w, int n, int k, uint8_t* q, float* scale, uint8_t* zp) {
+    return guard([&] {
+        MI_REQUIRE(w && q && scale && zp, "mi_gpt_quantize_u8: null argument");
+        MI_REQUIRE(n >= 1 && k >= 1 && (int64_t)n * k <= ((int64_t)1 << 40), "mi_gpt_quantize_u8: n and k must be positive");
+        gpt_quantize_u8(w, n, k, q, scale, zp);
+    });
+}
+
 void mi_gpt_destroy(mi_gpt* h) {
     if (!h) return;
     delete h->impl;                          // synchronises the stream: nothing of an open session is in flight afterwards
@@ -1366,6 +1398,12 @@ struct LinUnit {
         bufs.emplace_back(new DevBuf);
         return (const float*)stage_in(*bufs.back(), p, n * 4, mem, s);
     }
+    // n bytes of the caller, on the device
+    const void* bytes(const void* p, size_t n) {
+        if (mem == MI_DEVICE) return p;
+        bufs.emplace_back(new DevBuf);
+        return stage_in(*bufs.back(), p, n, mem, s);
+    }
     // (rows, cols) fp32 of the caller -> rows [0, rows) of a device array of `dt` with alloc_rows >= rows rows
     void* typed(const float* p, long rows, int cols, int dt, long alloc_rows = 0) {
         DevBuf& d = buf((size_t)std::max(rows, alloc_rows) * cols * dtype_size(dt));
@@ -1489,15 +1527,31 @@ int mi_gpt_attn_prompt_packed(const float* qkv, const float* kc, const float* vc
 
 int mi_gpt_linear_batch_rows(int nb) { return nb >= 1 && nb <= GPT_MAX_BATCH ? gpt_padded_rows(nb) : MI_EINVAL; }
 
-int mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int dtype, int n, int k, const float* ln_w,
-                         const float* ln_b, const float* pre_w, const float* pre_b, float* pre_out, const float* res, int act,
-                         int out_f32, int qkv, int hist, int max_seq, float* kc, float* vc, float* out, int mem) {
-    return guard([&] {
-        const std::string who = "mi_gpt_linear_decode";
-        LinUnit u(who, dtype, mem);
-        MI_REQUIRE(w && x && out, who + ": null argument");
-        MI_REQUIRE(n >= 1 && n <= (1 << 20) && k >= 1 && k <= 16384, who + ": n must be in [1, 2^20], k in [1, 16384]");
+// uint8 weights of a unit entry: null q = the fp32 matrix w, rounded to dtype
+struct LinQ8 { const uint8_t* q; const float* scale; const uint8_t* zp; };
+
+// the weights of a unit entry on the device, as the launchers take them
+static GptLin lin_unit_weights(LinUnit& u, const std::string& who, const float* w, const LinQ8& q8, const float* bias, int dtype,
+                               int n, int k) {
+    if (!q8.q) {
+        MI_REQUIRE(w, who + ": null argument");
         MI_REQUIRE(k % 8 == 0, who + ": k must be a multiple of 8");
+        return GptLin{dtype, u.typed(w, n, k, dtype), u.f32(bias, n), n, k};
+    }
+    MI_REQUIRE(q8.scale && q8.zp, who + ": null argument");
+    MI_REQUIRE(dtype == MI_F16, who + ": uint8 weights run with MI_F16 activations");
+    MI_REQUIRE(k % 16 == 0, who + ": k must be a multiple of 16");
+    return GptLin{dtype, u.bytes(q8.q, (size_t)n * k), u.f32(bias, n), n, k, GPT_W_Q8, u.f32(q8.scale, n), (const uint8_t*)u.bytes(q8.zp, n)};
+}
+
+static int linear_decode_unit(const std::string& who, const float* w, const LinQ8& q8, const float* bias, const float* x, int dtype,
+                              int n, int k, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b,
+                              float* pre_out, const float* res, int act, int out_f32, int qkv, int hist, int max_seq, float* kc,
+                              float* vc, float* out, int mem) {
+    return guard([&] {
+        LinUnit u(who, dtype, mem);
+        MI_REQUIRE(x && out, who + ": null argument");
+        MI_REQUIRE(n >= 1 && n <= (1 << 20) && k >= 1 && k <= 16384, who + ": n must be in [1, 2^20], k in [1, 16384]");
         MI_REQUIRE(!ln_w == !ln_b && !pre_w == !pre_b, who + ": a LayerNorm needs both its vectors");
         MI_REQUIRE(act == ACT_NONE || act == ACT_GELU_TANH, who + ": act must be 0 or 1 (gelu_new)");
         if (qkv) {
@@ -1507,7 +1561,7 @@ int mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int 
         }
         const int odt = out_f32 ? MI_F32 : dtype;
         const size_t nc = qkv ? (size_t)k * max_seq : 0;
-        const GptLin l{dtype, u.typed(w, n, k, dtype), u.f32(bias, n), n, k};
+        const GptLin l = lin_unit_weights(u, who, w, q8, bias, dtype, n, k);
         const void* xd = ln_w ? (const void*)u.f32(x, k) : u.typed(x, 1, k, dtype);
         void* kd = qkv ? u.typed(kc, (long)(nc / 64), 64, dtype) : nullptr;
         void* vd = qkv ? u.typed(vc, (long)(nc / 64), 64, dtype) : nullptr;
@@ -1523,16 +1577,30 @@ int mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int 
     });
 }
 
-int mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const float* x_dead, int dtype, int n, int k, int nb,
-                        const float* res, int act, int out_f32, int qkv, const int32_t* hist, int max_seq, float* kc, float* vc,
-                        float* out, int mem) {
+int mi_gpt_linear_decode(const float* w, const float* bias, const float* x, int dtype, int n, int k, const float* ln_w,
+                         const float* ln_b, const float* pre_w, const float* pre_b, float* pre_out, const float* res, int act,
+                         int out_f32, int qkv, int hist, int max_seq, float* kc, float* vc, float* out, int mem) {
+    return linear_decode_unit("mi_gpt_linear_decode", w, LinQ8{nullptr, nullptr, nullptr}, bias, x, dtype, n, k, ln_w, ln_b, pre_w, pre_b,
+                              pre_out, res, act, out_f32, qkv, hist, max_seq, kc, vc, out, mem);
+}
+
+int mi_gpt_linear_decode_q8(const uint8_t* q, const float* scale, const uint8_t* zp, const float* bias, const float* x, int dtype, int n,
+                            int k, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b, float* pre_out,
+                            const float* res, int act, int out_f32, int qkv, int hist, int max_seq, float* kc, float* vc, float* out,
+                            int mem) {
+    if (!q) return guard([&] { MI_REQUIRE(false, "mi_gpt_linear_decode_q8: null argument"); });
+    return linear_decode_unit("mi_gpt_linear_decode_q8", nullptr, LinQ8{q, scale, zp}, bias, x, dtype, n, k, ln_w, ln_b, pre_w, pre_b,
+                              pre_out, res, act, out_f32, qkv, hist, max_seq, kc, vc, out, mem);
+}
+
+static int linear_batch_unit(const std::string& who, const float* w, const LinQ8& q8, const float* bias, const float* x,
+                             const float* x_dead, int dtype, int n, int k, int nb, const float* res, int act, int out_f32, int qkv,
+                             const int32_t* hist, int max_seq, float* kc, float* vc, float* out, int mem) {
     return guard([&] {
-        const std::string who = "mi_gpt_linear_batch";
         LinUnit u(who, dtype, mem);
-        MI_REQUIRE(w && x && out, who + ": null argument");
+        MI_REQUIRE(x && out, who + ": null argument");
         MI_REQUIRE(nb >= 1 && nb <= GPT_MAX_BATCH, who + ": nb must be in [1, 64]");
         MI_REQUIRE(n >= 1 && n <= (1 << 20) && k >= 1 && k <= 16384, who + ": n must be in [1, 2^20], k in [1, 16384]");
-        MI_REQUIRE(k % 8 == 0, who + ": k must be a multiple of 8");
         MI_REQUIRE(act == ACT_NONE || act == ACT_GELU_TANH, who + ": act must be 0 or 1 (gelu_new)");
         if (qkv) {
             MI_REQUIRE(n % 3 == 0 && n == 3 * k && k % 64 == 0, who + ": qkv needs n == 3 * k (a multiple of 3), k a multiple of 64");
@@ -1542,7 +1610,7 @@ int mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const
         }
         const int odt = out_f32 ? MI_F32 : dtype, P = gpt_padded_rows(nb);
         const size_t sstride = qkv ? (size_t)k * max_seq : 0, nc = (size_t)nb * sstride;
-        const GptLin l{dtype, u.typed(w, n, k, dtype), u.f32(bias, n), n, k};
+        const GptLin l = lin_unit_weights(u, who, w, q8, bias, dtype, n, k);
         char* xd = (char*)u.typed(x, nb, k, dtype, P);
         const size_t row = (size_t)k * dtype_size(dtype);
         if (x_dead) {
@@ -1560,6 +1628,21 @@ int mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const
         if (qkv) { u.give(kc, kd, nc, dtype); u.give(vc, vd, nc, dtype); }
         MI_HIP(hipStreamSynchronize(u.s));
     });
+}
+
+int mi_gpt_linear_batch(const float* w, const float* bias, const float* x, const float* x_dead, int dtype, int n, int k, int nb,
+                        const float* res, int act, int out_f32, int qkv, const int32_t* hist, int max_seq, float* kc, float* vc,
+                        float* out, int mem) {
+    return linear_batch_unit("mi_gpt_linear_batch", w, LinQ8{nullptr, nullptr, nullptr}, bias, x, x_dead, dtype, n, k, nb, res, act, out_f32,
+                             qkv, hist, max_seq, kc, vc, out, mem);
+}
+
+int mi_gpt_linear_batch_q8(const uint8_t* q, const float* scale, const uint8_t* zp, const float* bias, const float* x,
+                           const float* x_dead, int dtype, int n, int k, int nb, const float* res, int act, int out_f32, int qkv,
+                           const int32_t* hist, int max_seq, float* kc, float* vc, float* out, int mem) {
+    if (!q) return guard([&] { MI_REQUIRE(false, "mi_gpt_linear_batch_q8: null argument"); });
+    return linear_batch_unit("mi_gpt_linear_batch_q8", nullptr, LinQ8{q, scale, zp}, bias, x, x_dead, dtype, n, k, nb, res, act, out_f32,
+                             qkv, hist, max_seq, kc, vc, out, mem);
 }
 
 // The ConvGemm of mi_bench_conv_gemm's arguments, its operands from buf(which, bytes): device memory to launch it, aligned dummies

@@ -24,8 +24,11 @@ enum { GS_HIST = 0, GS_TOKEN = 1, GS_GEN_LEN = 2, GS_NDEC = 3, GS_RESET = 4, GS_
 // Never 1: gemv_b_kernel stages whole template widths of x rows, and its narrowest width is 2
 inline int gpt_padded_rows(int mb) { return mb <= 2 ? 2 : mb <= 4 ? 4 : mb <= 8 ? 8 : (mb + 15) / 16 * 16; }
 
-// a decode-step linear layer as its launchers see it: weights (n, k) of `dtype`, fp32 bias (n) or null, both on the device
-struct GptLin { int dtype; const void* w; const float* bias; int n, k; };
+// a decode-step linear layer as its launchers see it: weights (n, k), fp32 bias (n) or null, both on the device.  wfmt says what w
+// holds: GPT_W_DTYPE = elements of `dtype`; GPT_W_Q8 = uint8 rows with one fp32 scale and one uint8 zero point per row
+// (w ~ float(q - zp) * scale, gpt_q8.hip), `dtype` then being the activation type alone
+enum { GPT_W_DTYPE = 0, GPT_W_Q8 = 1 };
+struct GptLin { int dtype; const void* w; const float* bias; int n, k; int wfmt = GPT_W_DTYPE; const float* scale = nullptr; const uint8_t* zp = nullptr; };
 
 struct GptSampleRec;      // gpt_pick.h
 struct GptPoolCfg;        // gpt_pool.h
@@ -36,8 +39,11 @@ struct Gpt {
     int dtype, device;
     hipStream_t stream = nullptr;
 
-    struct GLin { DevBuf w, b; int n = 0, k = 0; };
-    GptLin lin(const GLin& l) const { return {dtype, l.w.p, l.b.as<float>(), l.n, l.k}; }
+    int wfmt = GPT_W_DTYPE;   // what the six matrix kinds (c_attn, attn.c_proj, c_fc, mlp.c_proj, lm_head.1) are stored as
+    struct GLin { DevBuf w, b, sc, zp; int n = 0, k = 0; };      // sc / zp: GPT_W_Q8 only
+    GptLin lin(const GLin& l) const { return {dtype, l.w.p, l.b.as<float>(), l.n, l.k, wfmt, l.sc.as<float>(), l.zp.as<uint8_t>()}; }
+    DevBuf wdq;               // GPT_W_Q8: the 16-bit copy of the matrix a prompt pass is about to use (the largest of the six)
+    int64_t weight_bytes() const;                      // device bytes held for the six matrix kinds (mi_gpt_weight_bytes)
     struct Layer { DevBuf ln1_w, ln1_b, ln2_w, ln2_b; GLin qkv, proj, fc, fc2; };
     std::vector<Layer> L;
     DevBuf text_emb, text_pos, mel_emb, mel_pos;       // fp32 tables
@@ -97,7 +103,7 @@ struct Gpt {
     // instantiation failure turns graphs off for the handle and the steps run eagerly.
     template <typename F> void replay(hipGraphExec_t& exec, int n, F&& step);
 
-    Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev);
+    Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev, int wfmt = GPT_W_DTYPE);
     ~Gpt();
 
     void text_embed(const int32_t* ids_dev, int n, float* out_dev);                 // graph B (n + 2 rows)
@@ -226,6 +232,20 @@ void launch_gpt_gemv_b(const GptLin& l, const void* x, int nb, int max_rows, voi
 //   nb <= 16 rows (a 16-slot group of a wider batch passes its own bases); of = the output is fp32
 void launch_gpt_gemv_b16(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
                          const int* st, int max_seq, size_t slot_stride, hipStream_t s);
+
+// The same launches on GPT_W_Q8 layers (gpt_q8.hip; the three above route to them): K a multiple of 16, MI_F16 activations.
+// launch_gpt_gemv_wide_q8 is the 17..64-row matrix-core launch and returns false when the options or K rule it out (the caller then
+// goes group by group); launch_gpt_dequant_q8 writes the layer's (n, k) matrix as f16(float(q - zp) * scale) to `out`.
+void launch_gpt_gemv_q8(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b,
+                        float* pre_out, void* out, int odt, int act, const float* res, void* kcl, void* vcl, const int* st,
+                        int max_seq, hipStream_t s);
+void launch_gpt_gemv_b16_q8(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
+                            const int* st, int max_seq, size_t slot_stride, hipStream_t s);
+bool launch_gpt_gemv_wide_q8(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl,
+                             void* vcl, const int* st, int max_seq, size_t slot_stride, hipStream_t s);
+void launch_gpt_dequant_q8(const GptLin& l, void* out, hipStream_t s);
+// per-row asymmetric uint8 quantisation of (n, k) fp32 rows on the host (the rule is stated in include/mi355tts.h)
+void gpt_quantize_u8(const float* w, int n, int k, uint8_t* q, float* scale, uint8_t* zp);
 
 // The four attention launches of the GPT, each defined beside its kernel and called by the engine and by the unit entries of
 // capi.hip (mi_gpt_attn_*): arrays of `dtype` on the device, st = GS_* state words, kc / vc = one layer's cache.

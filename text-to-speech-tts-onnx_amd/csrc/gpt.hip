@@ -21,6 +21,7 @@
 #include "gpt_attn.h"
 #include "gpt_pick.h"
 #include "gpt_vec.h"
+#include "gpt_lin.h"
 #include "mfma.h"
 #include "lds_dma.h"         // buf_rsrc
 #include "wave_reduce.h"
@@ -55,10 +56,6 @@ int64_t gpt_param_count(const GptCfg& c) {
 // ---------------------------------------------------------------------------------------------------------------
 // Pack16 / ld16 / dot_pack: gpt_vec.h
 
-__device__ inline float gelu_new(float x) {
-    return 0.5f * x * (1.f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Decode-step linear layer of ONE sentence: out[n] = act(dot(w[n, :], x') + bias[n]) (+ res[n]), one wave per R
 // output rows, lane l holds k = l*V + it*64*V .. +V of the row (V = elements per 16 bytes), fp32 FMAs, DPP reduction.
@@ -77,19 +74,7 @@ __device__ inline float gelu_new(float x) {
 //     (f5_kernels.hip) — ln_f in front of the lm_head's final_norm, Export_IndexTTS.py:286-288 — and block 0 stores
 //     that intermediate row to `pre_out` (graph E's last_hidden_state output);
 //   * QKV: rows [hidden, 3*hidden) go straight into the K / V cache row st[GS_HIST] of this layer.
-#ifndef GPT_NT
-#define GPT_NT 1
-#endif
-#if GPT_NT
-#define GPT_WLOAD ldnt16
-#else
-#define GPT_WLOAD ld16
-#endif
-template <typename T> __device__ inline Pack16<T> ldnt16(const T* p) {
-    Pack16<T> r;
-    *reinterpret_cast<u32x4*>(&r) = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    return r;
-}
+// GPT_WLOAD (the non-temporal 16-byte weight load), gelu_new, reduce_multi, Mfma16, skinny_store: gpt_lin.h
 
 template <typename T, int R, int KI, int WAVES, bool LN, bool QKV>
 __global__ __launch_bounds__(WAVES * 64) void gemv_d_kernel(const T* __restrict__ w, const void* __restrict__ xin,
@@ -289,31 +274,10 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_d_kernel(const T* __restrict_
     }
 }
 
-// NV per-lane partial sums -> full sums: after the call, lane l holds the total of value index
-//   idx = sum_s ((l >> (5 - s)) & 1) << (log2(NV) - 1 - s)   (and every lane sharing those bits holds the same total).
-// log2(NV) halving exchange steps (NV - 1 shuffles) + the remaining butterfly, instead of 6 * NV shuffles.
-template <int NV> __device__ inline float reduce_multi(float (&v)[NV], int lane) {
-    int off = 32;
-#pragma unroll
-    for (int n = NV; n > 1; n >>= 1) {
-        const bool hi = (lane & off) != 0;
-#pragma unroll
-        for (int i = 0; i < n / 2; ++i) {
-            const float send = hi ? v[i] : v[i + n / 2];
-            const float keep = hi ? v[i + n / 2] : v[i];
-            v[i] = keep + __shfl_xor(send, off, 64);
-        }
-        off >>= 1;
-    }
-    for (; off > 0; off >>= 1) v[0] += __shfl_xor(v[0], off, 64);
-    return v[0];
-}
-
 // batched decode step: out[b][n] = act(dot(w[n, :], x[b, :]) + bias[n]) (+ res[b][n]) for BB slots at once — every
 // weight row is streamed once for all sentences.  QKV: k / v rows of slot b go to that slot's cache row st[b].hist.
 // 8 waves per block share the x rows through LDS in 1024-element K chunks (read straight from L2 by every wave they
 // cost BB x the weight traffic); a chunk's weight loads are issued before the barrier that publishes the x chunk.
-constexpr int GB_KC = 1024;
 template <typename T, int R, int BB, bool QKV>
 __global__ __launch_bounds__(512) void gemv_b_kernel(const T* __restrict__ w, const T* __restrict__ x,
                                                      const float* __restrict__ bias, const float* res, void* out,
@@ -408,47 +372,6 @@ __global__ __launch_bounds__(512) void gemv_b_kernel(const T* __restrict__ w, co
 // k = 16g .. 16g+15 for BOTH operands (the contraction is order-free), so a lane's two 16-byte loads are adjacent and
 // the four groups cover one full 128-byte line of the row.  The KS partial tiles meet in LDS.  x (<= 16 x K) is read
 // from L2 by every wave: as many bytes as the weights, but they never leave the chip.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <typename T> struct Mfma16;
-template <> struct Mfma16<f16> {
-    using Frag = f16x8;
-    static __device__ __forceinline__ f32x4_t mma(Frag a, Frag b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma16<bf16> {
-    using Frag = bf16x8;
-    static __device__ __forceinline__ f32x4_t mma(Frag a, Frag b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
-// epilogue of one lane's four D values of a skinny tile: rows n4 .. n4+3 of sentence b (bias, activation, residual; QKV: the
-// k / v rows go to cache row st[b].hist of slot b)
-template <typename T, bool QKV>
-__device__ __forceinline__ void skinny_store(f32x4_t acc, int b, int n4, const float* __restrict__ bias, const float* res,
-                                             void* out, int out_f32, int act, int N, T* __restrict__ kc, T* __restrict__ vc,
-                                             const int* __restrict__ st, int max_seq, size_t slot_stride) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int n = n4 + r;
-        if (n >= N) continue;
-        float v = acc[r] + (bias ? bias[n] : 0.f);
-        if (act == ACT_GELU_TANH) v = gelu_new(v);
-        if (res) v += res[(size_t)b * N + n];
-        bool to_cache = false;
-        if (QKV) {
-            const int hidden = N / 3;
-            if (n >= hidden) {
-                const int c = n - hidden, which = c / hidden, cc = c % hidden;
-                const int pos = st[b * GS_WORDS + GS_HIST];
-                if (pos < max_seq)
-                    (which ? vc : kc)[(size_t)b * slot_stride + kv_cache_offset(cc, pos, max_seq)] = (T)v;
-                to_cache = true;
-            }
-        }
-        if (!to_cache) {
-            if (out_f32) ((float*)out)[(size_t)b * N + n] = v; else ((T*)out)[(size_t)b * N + n] = (T)v;
-        }
-    }
-}
-
 template <typename T, bool QKV, int UNR>
 __global__ __launch_bounds__(512) void gemm_skinny_kernel(const T* __restrict__ w, const T* __restrict__ x,
                                                           const float* __restrict__ bias, const float* res, void* out,
@@ -720,15 +643,34 @@ __global__ __launch_bounds__(256) void kv_import_kernel(T* __restrict__ kc, T* _
 // ---------------------------------------------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------------------------------------------
-static void up_glin(Gpt::GLin& l, const float*& p, int n, int k, int dt, hipStream_t s) {
+static void up_glin(Gpt::GLin& l, const float*& p, int n, int k, int dt, int wfmt, hipStream_t s) {
     l.n = n; l.k = k;
-    upload_as(l.w, p, (size_t)n * k, dt, s); p += (size_t)n * k;
+    if (wfmt == GPT_W_Q8) {
+        std::vector<uint8_t> q((size_t)n * k), zp(n);
+        std::vector<float> sc(n);
+        gpt_quantize_u8(p, n, k, q.data(), sc.data(), zp.data());
+        l.w.ensure(q.size()); l.zp.ensure(n);
+        MI_HIP(hipMemcpyAsync(l.w.p, q.data(), q.size(), hipMemcpyHostToDevice, s));
+        MI_HIP(hipMemcpyAsync(l.zp.p, zp.data(), n, hipMemcpyHostToDevice, s));
+        upload_f32(l.sc, sc.data(), n, s);
+        MI_HIP(hipStreamSynchronize(s));       // the staging vectors are locals
+    } else {
+        upload_as(l.w, p, (size_t)n * k, dt, s);
+    }
+    p += (size_t)n * k;
     upload_f32(l.b, p, n, s); p += n;
 }
 static void up_vec(DevBuf& b, const float*& p, size_t n, hipStream_t s) { upload_f32(b, p, n, s); p += n; }
 
-Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c), dtype(dt), device(dev) {
+Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev, int wf) : cfg(c), dtype(dt), device(dev), wfmt(wf) {
     MI_REQUIRE(dt == MI_F32 || dt == MI_F16 || dt == MI_BF16, "gpt: dtype");
+    if (wf == GPT_W_Q8) {
+        MI_REQUIRE(dt != MI_F32, "gpt: uint8 weights need 16-bit activations (MI_F16); MI_F32 is refused");
+        MI_REQUIRE(dt == MI_F16, "gpt: uint8 weights run with MI_F16 activations; MI_BF16 is refused (the kernels' byte -> f16 form has no bf16 twin)");
+        MI_REQUIRE(c.hidden % 16 == 0 && c.inner % 16 == 0, "gpt: uint8 weights need hidden and inner to be multiples of 16 (16 weights per 16-byte load)");
+    } else {
+        MI_REQUIRE(wf == GPT_W_DTYPE, "gpt: weight format");
+    }
     MI_REQUIRE(nw == gpt_param_count(c), "gpt: weight blob size does not match the config");
     MI_HIP(hipSetDevice(dev));
     MI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -742,16 +684,17 @@ Gpt::Gpt(const GptCfg& c, const float* w, int64_t nw, int dt, int dev) : cfg(c),
     L.resize(c.layers);
     for (auto& l : L) {
         up_vec(l.ln1_w, p, h, s); up_vec(l.ln1_b, p, h, s);
-        up_glin(l.qkv, p, 3 * h, h, dt, s);
-        up_glin(l.proj, p, h, h, dt, s);
+        up_glin(l.qkv, p, 3 * h, h, dt, wf, s);
+        up_glin(l.proj, p, h, h, dt, wf, s);
         up_vec(l.ln2_w, p, h, s); up_vec(l.ln2_b, p, h, s);
-        up_glin(l.fc, p, n, h, dt, s);
-        up_glin(l.fc2, p, h, n, dt, s);
+        up_glin(l.fc, p, n, h, dt, wf, s);
+        up_glin(l.fc2, p, h, n, dt, wf, s);
     }
     up_vec(lnf_w, p, h, s); up_vec(lnf_b, p, h, s);
     up_vec(fn_w, p, h, s); up_vec(fn_b, p, h, s);
-    up_glin(head, p, c.mel_codes, h, dt, s);
+    up_glin(head, p, c.mel_codes, h, dt, wf, s);
     MI_REQUIRE(p - w == nw, "gpt: blob walk mismatch");
+    if (wf == GPT_W_Q8) wdq.ensure((size_t)std::max({3 * h * h, n * h, c.mel_codes * h}) * 2);
 
     const size_t es = dtype_size(dt), S = c.max_seq, MB = c.max_batch;
     MBp = gpt_padded_rows(c.max_batch);
@@ -781,6 +724,14 @@ Gpt::~Gpt() {
     if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
 }
 
+int64_t Gpt::weight_bytes() const {
+    int64_t t = 0;
+    auto one = [&](const GLin& l) { t += (int64_t)l.w.bytes + (int64_t)l.sc.bytes + (int64_t)l.zp.bytes; };
+    for (const auto& l : L) { one(l.qkv); one(l.proj); one(l.fc); one(l.fc2); }
+    one(head);
+    return t + (int64_t)wdq.bytes;
+}
+
 void Gpt::set_state(const std::vector<int32_t>& words, int slot) {
     MI_REQUIRE(words.size() == GS_WORDS && slot >= 0 && slot < cfg.max_batch, "gpt: state slot");
     MI_HIP(hipMemcpyAsync(state.as<int32_t>() + (size_t)slot * GS_WORDS, words.data(), GS_WORDS * 4, hipMemcpyHostToDevice, stream));
@@ -804,6 +755,10 @@ void Gpt::linear(const GLin& l, const void* x, int rows, void* out, int odt, int
     MI_REQUIRE(rows > 1, "gpt: linear() is the multi-row path");
     ConvGemm g;
     g.dtype = dtype; g.out_dtype = odt; g.x = x; g.w = l.w.p; g.bias = l.b.as<float>(); g.out = out; g.res = res;
+    if (wfmt == GPT_W_Q8) {                    // the matrix about to be used, as a 16-bit engine would hold it (stream order keeps wdq safe)
+        launch_gpt_dequant_q8(lin(l), wdq.p, stream);
+        g.w = wdq.p;
+    }
     g.B = 1; g.T_in = rows; g.M = rows; g.N = l.n; g.Cin = l.k; g.taps = 1;
     g.x_bstride = (long)rows * l.k; g.x_rstride = l.k; g.out_bstride = (long)rows * l.n; g.out_rstride = l.n; g.act = act;
     launch_conv_gemm(g, stream);
@@ -871,6 +826,7 @@ static void gemv_d_dispatch(const GptLin& l, const void* x, const float* ln_w, c
 void launch_gpt_gemv(const GptLin& l, const void* x, const float* ln_w, const float* ln_b, const float* pre_w, const float* pre_b,
                      float* pre_out, void* out, int odt, int act, const float* res, void* kcl, void* vcl, const int* st,
                      int max_seq, hipStream_t s) {
+    if (l.wfmt == GPT_W_Q8) { launch_gpt_gemv_q8(l, x, ln_w, ln_b, pre_w, pre_b, pre_out, out, odt, act, res, kcl, vcl, st, max_seq, s); return; }
     MI_REQUIRE(l.k % 8 == 0, "gemv: K must be a multiple of 8");
     const int of = odt == MI_F32;
     MI_REQUIRE(of || odt == l.dtype, "gemv: output dtype");
@@ -1008,7 +964,9 @@ void launch_gpt_gemv_b(const GptLin& l, const void* x, int nb, int max_rows, voi
     if (nb <= 16) { launch_gpt_gemv_b16(l, x, nb, out, of, act, res, kcl, vcl, st, max_seq, sstride, stream); return; }
     const size_t es = dtype_size(dtype);
     const int KS = l.k > 2048 ? 8 : 4;
-    if (opt(OPT_GPT_MFMA) && dtype != MI_F32 && nb >= opt(OPT_GPT_MFMA_MIN) && l.k % (KS * 64) == 0) {
+    if (l.wfmt == GPT_W_Q8) {                   // the wide matrix-core kernel, or group by group below
+        if (launch_gpt_gemv_wide_q8(l, x, nb, out, of, act, res, kcl, vcl, st, max_seq, sstride, stream)) return;
+    } else if (opt(OPT_GPT_MFMA) && dtype != MI_F32 && nb >= opt(OPT_GPT_MFMA_MIN) && l.k % (KS * 64) == 0) {
         ProfScope ps(FAM_CONV_GEMM, stream, (double)l.n * l.k * es, 2.0 * l.n * l.k * nb);
         // the launch is bound by the bytes a CU has in flight (x is read by every wave): one tile per block while that still
         // is one round of blocks, so the four-way split's x traffic spreads over twice the CUs
@@ -1036,6 +994,7 @@ void launch_gpt_gemv_b(const GptLin& l, const void* x, int nb, int max_rows, voi
 // up to 16 rows: the batched GEMV at the template width that holds nb, or the matrix-core kernel.  st = the state words of row 0
 void launch_gpt_gemv_b16(const GptLin& l, const void* x, int nb, void* out, int of, int act, const float* res, void* kcl, void* vcl,
                          const int* st, int max_seq, size_t sstride, hipStream_t stream) {
+    if (l.wfmt == GPT_W_Q8) { launch_gpt_gemv_b16_q8(l, x, nb, out, of, act, res, kcl, vcl, st, max_seq, sstride, stream); return; }
     const int dtype = l.dtype;
     const int BB = nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 8 ? 8 : 16;
     const int R = l.n >= 4096 ? 2 : 1;

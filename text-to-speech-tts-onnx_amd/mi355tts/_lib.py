@@ -201,6 +201,15 @@ def load() -> C.CDLL:
         L.mi_gpt_linear_batch.restype = C.c_int
         L.mi_gpt_linear_batch_rows.argtypes = [C.c_int]
         L.mi_gpt_linear_batch_rows.restype = C.c_int
+    if hasattr(L, "mi_gpt_create_q8"):          # per-channel uint8 weights (csrc/gpt_q8.hip)
+        L.mi_gpt_create_q8.argtypes = [C.POINTER(C.c_int32), C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int]
+        L.mi_gpt_create_q8.restype = C.c_void_p
+        L.mi_gpt_weight_bytes.argtypes = [vp]; L.mi_gpt_weight_bytes.restype = C.c_int64
+        L.mi_gpt_quantize_u8.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]; L.mi_gpt_quantize_u8.restype = C.c_int
+        L.mi_gpt_linear_decode_q8.argtypes = [vp, vp] + L.mi_gpt_linear_decode.argtypes
+        L.mi_gpt_linear_decode_q8.restype = C.c_int
+        L.mi_gpt_linear_batch_q8.argtypes = [vp, vp] + L.mi_gpt_linear_batch.argtypes
+        L.mi_gpt_linear_batch_q8.restype = C.c_int
     L.mi_gpt_bench_pick.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_double)]
     L.mi_gpt_bench_pick.restype = C.c_int
     L.mi_bench_conv_gemm.argtypes = [C.c_int] * 9 + [C.POINTER(C.c_double)]

@@ -331,17 +331,37 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def _q8_arrays(q8, what):
+    """(q (n, k) uint8, scale (n) float32, zp (n) uint8), contiguous"""
+    q, scale, zp = q8
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    if q.ndim != 2:
+        raise ValueError(f"{what}: q must be (n, k)")
+    scale = np.ascontiguousarray(scale, dtype=np.float32)
+    zp = np.ascontiguousarray(zp, dtype=np.uint8)
+    if scale.shape != (q.shape[0],) or zp.shape != (q.shape[0],):
+        raise ValueError(f"{what}: scale and zp must have one entry per row of q")
+    return q, scale, zp
+
+
 def linear_decode(w, x, *, bias=None, ln=None, pre=None, res=None, act: bool = False, out_f32: bool = True, cache=None,
-                  hist: int = 0, dtype: str = "f32"):
+                  hist: int = 0, dtype: str = "f32", q8=None):
     """One decode-step linear launch of ONE sentence (unit entry mi_gpt_linear_decode, csrc/gpt.hip gemv_d_kernel):
     act(w x' + bias) + res for w (n, k), x (k).  ``ln`` = (gain, shift): x stays float32 and x' = LayerNorm(x); ``pre`` = (gain,
     shift) of a LayerNorm in front of that one, whose row is returned too.  ``cache`` = (K, V), one layer's caches
     (k / 64, max_seq, 64): the QKV form (n = 3 k) — columns [k, 3k) go to row ``hist`` of copies of K and V, not to the output.
+    ``q8`` = (q, scale, zp) with ``w`` None: per-channel uint8 weights (mi_gpt_linear_decode_q8, csrc/gpt_q8.hip), dtype "f16".
     Returns a dict: "out" (n) float32, NaN where the launch wrote nothing; "pre_out" (k) with ``pre``; "K", "V" with ``cache``."""
-    w = _f32(w)
-    if w.ndim != 2:
-        raise ValueError("w must be (n, k)")
-    n, k = w.shape
+    if q8 is not None:
+        if w is not None:
+            raise ValueError("give w or q8, not both")
+        q8 = _q8_arrays(q8, "linear_decode")
+        n, k = q8[0].shape
+    else:
+        w = _f32(w)
+        if w.ndim != 2:
+            raise ValueError("w must be (n, k)")
+        n, k = w.shape
     x = _f32(x, (k,), "x")
     bias, res = _f32(bias, (n,), "bias"), _f32(res, (n,), "res")
     lw, lb = (_f32(ln[0], (k,), "ln gain"), _f32(ln[1], (k,), "ln shift")) if ln is not None else (None, None)
@@ -355,10 +375,12 @@ def linear_decode(w, x, *, bias=None, ln=None, pre=None, res=None, act: bool = F
         if K.shape != V.shape or K.ndim != 3 or K.shape[2] != 64:
             raise ValueError("cache = (K, V), each (heads, max_seq, 64)")
         S = K.shape[1]
-    _lib.check(_lib.load().mi_gpt_linear_decode(_ptr(w), _ptr(bias), _ptr(x), _lib.DTYPES[dtype], n, k, _ptr(lw), _ptr(lb), _ptr(pw),
-                                                _ptr(pb), _ptr(pre_out), _ptr(res), int(bool(act)), int(bool(out_f32)),
-                                                int(cache is not None), int(hist), S, _ptr(K), _ptr(V), _ptr(out), _lib.MI_HOST),
-               "mi_gpt_linear_decode")
+    rest = (_ptr(bias), _ptr(x), _lib.DTYPES[dtype], n, k, _ptr(lw), _ptr(lb), _ptr(pw), _ptr(pb), _ptr(pre_out), _ptr(res),
+            int(bool(act)), int(bool(out_f32)), int(cache is not None), int(hist), S, _ptr(K), _ptr(V), _ptr(out), _lib.MI_HOST)
+    if q8 is not None:
+        _lib.check(_lib.load().mi_gpt_linear_decode_q8(*(_ptr(a) for a in q8), *rest), "mi_gpt_linear_decode_q8")
+    else:
+        _lib.check(_lib.load().mi_gpt_linear_decode(_ptr(w), *rest), "mi_gpt_linear_decode")
     r = {"out": out}
     if pre is not None:
         r["pre_out"] = pre_out
@@ -376,16 +398,23 @@ def linear_batch_rows(nb: int) -> int:
 
 
 def linear_batch(w, x, *, bias=None, res=None, act: bool = False, out_f32: bool = True, cache=None, hist=None, x_dead=None,
-                 dtype: str = "f32"):
+                 dtype: str = "f32", q8=None):
     """One batched decode-step linear launch (unit entry mi_gpt_linear_batch, csrc/gpt.hip gemv_b_kernel / gemm_skinny_kernel /
     gemm_skinny_wide_kernel by the engine's dispatch): row b of x (nb, k) is slot b.  ``cache`` = (K, V), (nb, k / 64, max_seq, 64)
     with ``hist`` (nb): the QKV form.  ``x_dead`` (k): what the device x array holds in its rows nb .. linear_batch_rows(nb) - 1.
+    ``q8`` = (q, scale, zp) with ``w`` None: per-channel uint8 weights (mi_gpt_linear_batch_q8), dtype "f16".
     Returns a dict: "out" (linear_batch_rows(nb), n) float32 — rows >= nb are never written and come back NaN; "K", "V"."""
-    w = _f32(w)
+    if q8 is not None:
+        if w is not None:
+            raise ValueError("give w or q8, not both")
+        q8 = _q8_arrays(q8, "linear_batch")
+    else:
+        w = _f32(w)
     x = _f32(x)
-    if w.ndim != 2 or x.ndim != 2 or x.shape[1] != w.shape[1]:
+    wshape = q8[0].shape if q8 is not None else w.shape
+    if len(wshape) != 2 or x.ndim != 2 or x.shape[1] != wshape[1]:
         raise ValueError("w must be (n, k), x (nb, k)")
-    (n, k), nb = w.shape, x.shape[0]
+    (n, k), nb = wshape, x.shape[0]
     bias, res, x_dead = _f32(bias, (n,), "bias"), _f32(res, (nb, n), "res"), _f32(x_dead, (k,), "x_dead")
     K = V = h = None
     S = 1
@@ -396,9 +425,12 @@ def linear_batch(w, x, *, bias=None, res=None, act: bool = False, out_f32: bool 
             raise ValueError("cache = (K, V), each (nb, heads, max_seq, 64), with one hist entry per row")
         S = K.shape[2]
     out = np.zeros((linear_batch_rows(nb), n), np.float32)
-    _lib.check(_lib.load().mi_gpt_linear_batch(_ptr(w), _ptr(bias), _ptr(x), _ptr(x_dead), _lib.DTYPES[dtype], n, k, nb, _ptr(res),
-                                               int(bool(act)), int(bool(out_f32)), int(cache is not None), _ptr(h), S, _ptr(K), _ptr(V),
-                                               _ptr(out), _lib.MI_HOST), "mi_gpt_linear_batch")
+    rest = (_ptr(bias), _ptr(x), _ptr(x_dead), _lib.DTYPES[dtype], n, k, nb, _ptr(res), int(bool(act)), int(bool(out_f32)),
+            int(cache is not None), _ptr(h), S, _ptr(K), _ptr(V), _ptr(out), _lib.MI_HOST)
+    if q8 is not None:
+        _lib.check(_lib.load().mi_gpt_linear_batch_q8(*(_ptr(a) for a in q8), *rest), "mi_gpt_linear_batch_q8")
+    else:
+        _lib.check(_lib.load().mi_gpt_linear_batch(_ptr(w), *rest), "mi_gpt_linear_batch")
     r = {"out": out}
     if cache is not None:
         r["K"], r["V"] = K, V
@@ -622,9 +654,14 @@ def stream_synthesize(gpt, voc, prompts, max_new, voices, voice_of, *, chunk: in
 
 class IndexGPT:
     def __init__(self, cfg: IndexGPTConfig, state: Optional[dict] = None, *, blob: Optional[np.ndarray] = None,
-                 blob_device=None, dtype: str = "f32", device: int = 0):
+                 blob_device=None, dtype: str = "f32", device: int = 0, weights: Optional[str] = None):
+        """``weights="q8"``: the six matrix kinds held as per-channel uint8 and dequantised in the kernels (mi_gpt_create_q8;
+        dtype "f16"), quantised at creation from the same fp32 state or blob; None: weights of ``dtype``."""
+        if weights not in (None, "q8"):
+            raise ValueError('weights must be None or "q8"')
         self.cfg = cfg
         self.dtype = dtype
+        self.weights = weights
         self.device = device
         self._h = None
         L = _lib.load()
@@ -637,10 +674,10 @@ class IndexGPT:
                 raise ValueError("blob_device must be a contiguous float32 CUDA tensor on the engine's device")
             ci = np.asarray(cfg.to_int_array(), dtype=np.int32)
             torch.cuda.current_stream(t.device).synchronize()
-            self._h = L.mi_gpt_create_mem(_lib.i32p(ci), len(ci), t.data_ptr(), t.numel(), _lib.DTYPES[dtype], device,
-                                          _lib.MI_DEVICE)
+            create = L.mi_gpt_create_q8 if weights == "q8" else L.mi_gpt_create_mem
+            self._h = create(_lib.i32p(ci), len(ci), t.data_ptr(), t.numel(), _lib.DTYPES[dtype], device, _lib.MI_DEVICE)
             if not self._h:
-                raise _lib.MiError("mi_gpt_create_mem: " + L.mi_last_error().decode())
+                raise _lib.MiError(("mi_gpt_create_q8: " if weights == "q8" else "mi_gpt_create_mem: ") + L.mi_last_error().decode())
             return
         if blob is None:
             if state is None:
@@ -651,9 +688,14 @@ class IndexGPT:
         expect = L.mi_gpt_param_count(_lib.i32p(ci), len(ci))
         if expect != blob.size:
             raise _lib.MiError(f"weight blob has {blob.size} floats, config needs {expect}")
-        self._h = L.mi_gpt_create(_lib.i32p(ci), len(ci), _lib.f32p(blob), blob.size, _lib.DTYPES[dtype], device)
-        if not self._h:
-            raise _lib.MiError("mi_gpt_create: " + L.mi_last_error().decode())
+        if weights == "q8":
+            self._h = L.mi_gpt_create_q8(_lib.i32p(ci), len(ci), blob.ctypes.data, blob.size, _lib.DTYPES[dtype], device, _lib.MI_HOST)
+            if not self._h:
+                raise _lib.MiError("mi_gpt_create_q8: " + L.mi_last_error().decode())
+        else:
+            self._h = L.mi_gpt_create(_lib.i32p(ci), len(ci), _lib.f32p(blob), blob.size, _lib.DTYPES[dtype], device)
+            if not self._h:
+                raise _lib.MiError("mi_gpt_create: " + L.mi_last_error().decode())
         # the reference initialises repeat_penality once and carries it across sentences (:685)
         self.repeat_penality = np.ones((1, cfg.mel_codes), np.float32)
 
@@ -661,6 +703,13 @@ class IndexGPT:
         if getattr(self, "_h", None):
             _lib.load().mi_gpt_destroy(self._h)
             self._h = None
+
+    def weight_bytes(self) -> int:
+        """device bytes held for the six matrix kinds (q8: bytes + scales + zero points + the prompt scratch)"""
+        n = _lib.load().mi_gpt_weight_bytes(self._h)
+        if n < 0:
+            raise _lib.MiError("mi_gpt_weight_bytes: " + _lib.load().mi_last_error().decode())
+        return int(n)
 
     def __del__(self):
         try:

@@ -339,6 +339,48 @@ def pack_gpt(cfg: IndexGPTConfig, state: Dict[str, np.ndarray]) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([st[name].reshape(-1) for name, _, _ in gpt_spec(cfg)]))
 
 
+# per-channel uint8 weights of the GPT's six matrix kinds (the rule is stated in include/mi355tts.h, mi_gpt_create_q8; the C twin is
+# mi_gpt_quantize_u8).  Every step is one float32 operation, so the two agree bit for bit.
+GPT_Q8_KINDS = ("attn.c_attn.weight", "attn.c_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight", "lm_head.1.weight")
+
+
+def quantize_u8(w):
+    """(n, k) rows -> (q (n, k) uint8, scale (n) float32, zp (n) uint8): asymmetric, the range of a row widened to hold 0"""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.ndim != 2 or w.size == 0:
+        raise ValueError("quantize_u8 takes (n, k) rows")
+    rmin = np.minimum(w.min(axis=1), np.float32(0))
+    rmax = np.maximum(w.max(axis=1), np.float32(0))
+    flat = rmax == rmin                          # an all-zero row
+    scale = np.where(flat, np.float32(1), (rmax - rmin) / np.float32(255)).astype(np.float32)
+    zpf = np.where(flat, np.float32(0), np.clip(np.rint(-rmin / scale), 0, 255)).astype(np.float32)
+    q = np.clip(np.rint(w / scale[:, None]) + zpf[:, None], 0, 255).astype(np.uint8)
+    return q, scale, zpf.astype(np.uint8)
+
+
+def dequantize_u8(q, scale, zp):
+    """float32(q - zp) * scale, one fp32 multiply per element"""
+    d = (np.asarray(q, np.int32) - np.asarray(zp, np.int32)[:, None]).astype(np.float32)
+    return d * np.asarray(scale, np.float32)[:, None]
+
+
+def gpt_q8_dequantized_blob(cfg: IndexGPTConfig, blob: np.ndarray) -> np.ndarray:
+    """The packed, folded blob of pack_gpt with its six matrix kinds replaced by dequantize_u8(quantize_u8(.)), everything else
+    untouched: what a q8 engine's weights are worth, as a blob any other engine can be built from."""
+    blob = np.array(blob, dtype=np.float32, copy=True).reshape(-1)
+    off = 0
+    for name, shape, _ in gpt_spec(cfg):
+        n = int(np.prod(shape))
+        if name.endswith(GPT_Q8_KINDS):
+            rows = shape[1] if name != "inference_model.lm_head.1.weight" else shape[0]     # folded: (out, in) rows
+            w = blob[off:off + n].reshape(rows, n // rows)
+            blob[off:off + n] = dequantize_u8(*quantize_u8(w)).reshape(-1)
+        off += n
+    if off != blob.size:
+        raise ValueError("blob size does not match the config")
+    return blob
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # IndexTTS graph A: conditioning encoder + perceiver (indexTTS.gpt.*) and ECAPA speaker encoder + cond layers (indexTTS.bigvgan.*)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of a batched decode step of the IndexTTS GPT against the number of slots, up to 64, in one run.
 
-    python tools/gpt_slots_bench.py [--nb 1,8,16,17,32,48,64] [--max-batch 64] [--tokens 256] [--rows 100] [--dtype f16] [--small]
+    python tools/gpt_slots_bench.py [--nb 1,8,16,17,32,48,64] [--max-batch 64] [--tokens 256] [--rows 100] [--dtype f16] [--weights q8] [--small]
 
 Full IndexTTS-1.5 size (24 x 1280, 8194 mel codes), synthetic weights, ONE handle with --max-batch slots.  For every nb:
 generate_batch with nb prompts of --rows rows, --tokens tokens per call, no stop token, so every sentence decodes exactly
@@ -13,6 +13,8 @@ The family split (linears / attention / rest = the row norms; the token choice c
 (eager launches timed by events; --prof-tokens tokens, the max_new = 1 call's share subtracted): per-launch event times, so their
 sum exceeds the replayed graph's step — read it as shares.  One JSON line per nb.
 --max-batch 16 with --nb 1,8,16 runs on a library built from an older commit (MI355TTS_LIB) as well: the yardstick P.
+--weights q8: the handle holds its six matrix kinds as per-channel uint8 (IndexGPT(weights="q8"), --dtype f16).  Every line carries
+the handle's mi_gpt_weight_bytes where the library has it.
 """
 import argparse
 import json
@@ -59,6 +61,7 @@ def main():
     ap.add_argument("--prof-tokens", type=int, default=33)
     ap.add_argument("--rows", type=int, default=100)
     ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--weights", default=None, choices=["q8"], help="q8: per-channel uint8 weights, dequantised in the kernels")
     ap.add_argument("--small", action="store_true", help="the reduced model (a functional check of this tool, not a measurement)")
     a = ap.parse_args()
     nbs = [int(x) for x in a.nb.split(",")]
@@ -72,7 +75,8 @@ def main():
     assert max(nbs) <= a.max_batch and n_tok >= 2 and 2 <= a.prof_tokens <= n_tok
     assert n_text >= 0 and n_text + 2 <= cfg.max_text_pos and a.rows + n_tok - 1 <= cfg.max_seq and n_tok <= cfg.max_mel_pos
     st = W.synth_state(W.gpt_spec(cfg), 9527, fast=not a.small)
-    eng = IndexGPT(cfg, st, dtype=a.dtype)
+    eng = IndexGPT(cfg, st, dtype=a.dtype, **({"weights": a.weights} if a.weights else {}))
+    wbytes = eng.weight_bytes() if hasattr(_lib.load(), "mi_gpt_weight_bytes") else None
     mel0 = eng.mel_embed(cfg.start_mel_token, 0)[0]
     prompts = []
     for i in range(max(nbs)):
@@ -86,7 +90,7 @@ def main():
         step = (t - t1) / (n_tok - 1)
         full, one = profiled(lambda: run(a.prof_tokens)), profiled(lambda: run(1))
         fam = {f: (full[f] - one[f]) / (a.prof_tokens - 1) for f in FAMILIES}
-        print(json.dumps({"dtype": a.dtype, "max_batch": a.max_batch, "nb": nb, "rows": a.rows, "tokens": n_tok,
+        print(json.dumps({"dtype": a.dtype, "weights": a.weights or a.dtype, "weight_bytes": wbytes, "max_batch": a.max_batch, "nb": nb, "rows": a.rows, "tokens": n_tok,
                           "seconds": round(t, 4), "spread": round(sp, 4), "prompt_seconds": round(t1, 4),
                           "prompt_spread": round(sp1, 4), "ms_per_step": round(step * 1e3, 4),
                           "codes_per_s": round(nb * n_tok / t, 1),

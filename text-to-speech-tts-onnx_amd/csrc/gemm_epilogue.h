@@ -6,6 +6,7 @@
 #include "mfma.h"
 #include "x3_split.h"
 #include "wave_reduce.h"
+#include "lds_dma.h"        // store16
 
 namespace mi {
 
@@ -56,6 +57,9 @@ struct ConvGemmDev {
     int* sat = nullptr;                          // fp16-pair producers raise bit 0 when an operand met the fp16 range limit
     const int* lens = nullptr; int len_mul = 1, len_add = 0;   // ragged batches (ConvGemm::lens): the LENS instantiations only
     long bias_bstride = 0;                       // ... and their per-item bias rows (ConvGemm::bias_bstride), floats; 0: one row for all items
+    // gemm_x3d.hip (the WTS instantiations of the epilogues below), launch-uniform: bit 0 = the 16-byte output stores are write-through
+    // (store16, lds_dma.h); bit 1 = fp32 rows (O / FF2's residual stream, Q) leave as whole 128-byte lines per store instruction
+    int epi_wt = 0;
 };
 
 // Shared epilogue: 32x32 accumulator tiles -> bias / activation / gate / residual / alpha / accumulate -> HBM,
@@ -228,10 +232,12 @@ __device__ __forceinline__ bool gemm_tile_dead(const ConvGemmDev& p, int m0, int
 // K = 1024 GEMM).  Here each wave parks 32*RT rows x WN columns of fp32 results (bias / activation / gate applied) in
 // its own slice of the now idle operand ring, then reads them back row-wise and leaves with 16-byte stores (residual
 // and accumulate operands are fetched with 16-byte loads in the same layout).  Wave-local: no block barrier.
-template <typename TO, int TM, int TN, int WM, int WN>
+// WTS: the launch may ask for write-through stores (ConvGemmDev::epi_wt); every other instantiation compiles the stores it always had.
+template <typename TO, int TM, int TN, int WM, int WN, bool WTS = false>
 __device__ __forceinline__ void gemm_epilogue_lds(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int m0, int n0, int b, int g,
                                                   int wm, int wn, int lr, int lk, float* stage, int m_end = -1) {
     const int Mlim = m_end >= 0 ? m_end : p.M;
+    const bool wt = WTS && (p.epi_wt & 1);
     constexpr int CH = sizeof(TO) == 2 ? 8 : 4;            // columns per lane: one 16-byte store
     constexpr int LPR = WN / CH;                            // lanes per output row
     constexpr int RPI = 64 / LPR;                           // rows per wave instruction
@@ -324,7 +330,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(f32x16 (&acc)[TM][TN], const C
                 Pk o;
 #pragma unroll
                 for (int q = 0; q < CH; ++q) o.v[q] = from_f32<TO>(x[q]);
-                if (okv[gi]) *reinterpret_cast<Pk*>(outp + ixv[gi]) = o;
+                if (okv[gi]) store16(outp + ixv[gi], o, wt);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -376,12 +382,13 @@ __device__ __forceinline__ void ln_rows32(const ConvGemmDev& p, long row0, long 
 // LN: consumer side of the AdaLN fold (see below): the accumulators carry W (x o (1 + scale)); bias and the LayerNorm's
 // mean / rstd enter on the row-wise read-back as rstd * acc - (mean * rstd) * ln_p[col] + ln_c[col]
 // PRE (with LN): (rstd, mean * rstd) of the wave's rows were fetched by the caller (at the start of the tile, under its main loop)
-template <typename TO, int TMQ = 2, bool LN = false, bool PRE = false>
+template <typename TO, int TMQ = 2, bool LN = false, bool PRE = false, bool WTS = false>
 __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], const ConvGemmDev& p, int m0, int n0, int b,
                                                       int wm, int wn, int lr, int lk, float* stage,
                                                       const float* pre_rs = nullptr, const float* pre_mr = nullptr, int m_end = -1) {
     // m_end >= 0: rows of this launch at or beyond m_end are not this caller's (gemm_x3d.hip: a 144-row tile ends inside a 32-row block)
     const int Mlim = m_end >= 0 ? m_end : p.M;
+    const bool wt = WTS && (p.epi_wt & 1), lines = WTS && (p.epi_wt & 2);
     const int lane = lk * 32 + lr;
     const int dm = p.heads * 64;
     const int nbase = n0 + wn * 64;
@@ -500,8 +507,8 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                         }
                         bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 2 * p.k_ld + mv[gi]) * 64 + c8;
                         if (okv[gi]) {
-                            *reinterpret_cast<u32x4*>(kp) = pl[0];
-                            *reinterpret_cast<u32x4*>(kp + p.k_ld * 64) = pl[1];
+                            store16(kp, pl[0], wt);
+                            store16(kp + p.k_ld * 64, pl[1], wt);
                         }
                         continue;
                     }
@@ -510,9 +517,9 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
                     for (int q = 0; q < 4; ++q) x3_split_pair(x[2 * q], x[2 * q + 1], p1[q], p2[q], p3[q]);
                     bf16* kp = kvo + ((((long)b + biv[gi]) * p.heads + hh) * 3 * p.k_ld + mv[gi]) * 64 + c8;
                     if (okv[gi]) {
-                        *reinterpret_cast<u32x4*>(kp) = u32x4{p1[0], p1[1], p1[2], p1[3]};
-                        *reinterpret_cast<u32x4*>(kp + p.k_ld * 64) = u32x4{p2[0], p2[1], p2[2], p2[3]};
-                        *reinterpret_cast<u32x4*>(kp + 2 * p.k_ld * 64) = u32x4{p3[0], p3[1], p3[2], p3[3]};
+                        store16(kp, u32x4{p1[0], p1[1], p1[2], p1[3]}, wt);
+                        store16(kp + p.k_ld * 64, u32x4{p2[0], p2[1], p2[2], p2[3]}, wt);
+                        store16(kp + 2 * p.k_ld * 64, u32x4{p3[0], p3[1], p3[2], p3[3]}, wt);
                     }
                     continue;
                 }
@@ -521,10 +528,36 @@ __device__ __forceinline__ void gemm_epilogue_qkv_lds(f32x16 (&acc)[TMQ][2], con
 #pragma unroll
                     for (int q = 0; q < 8; ++q) qkv_sat |= (fabsf(x[q]) * 1.4426950408889634f >= 65504.f || x[q] != x[q]) ? 1u : 0u;
                 }
+                if constexpr (WTS && sizeof(TO) == 4) if (lines && which == 0) {
+                    // fp32 Q rows as whole lines (see gemm_epilogue_resid_ln): back into the lane's own staging slots, stored below
+                    *reinterpret_cast<float4*>(&stage[rr * 64 + c8]) = make_float4(x[0], x[1], x[2], x[3]);
+                    *reinterpret_cast<float4*>(&stage[rr * 64 + c8 + 4]) = make_float4(x[4], x[5], x[6], x[7]);
+                    continue;
+                }
                 Pk o8;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) o8.v[q] = from_f32<TO>(x[q]);
-                if (okv[gi]) *reinterpret_cast<Pk*>(base + (((long)b + biv[gi]) * p.heads + hh) * Mb * 64 + (long)mv[gi] * 64 + c8) = o8;
+                if (okv[gi]) {
+                    TO* qp = base + (((long)b + biv[gi]) * p.heads + hh) * Mb * 64 + (long)mv[gi] * 64 + c8;
+                    if constexpr (WTS && sizeof(TO) == 4) {          // fp32 rows: the lane's 32 bytes as two 16-byte stores
+                        store16(qp, make_float4(x[0], x[1], x[2], x[3]), wt);
+                        store16(qp + 4, make_float4(x[4], x[5], x[6], x[7]), wt);
+                    } else {
+                        *reinterpret_cast<Pk*>(qp) = o8;
+                    }
+                }
+            }
+        }
+        if constexpr (WTS && sizeof(TO) == 4) if (lines && which == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < 8 * TMQ; ++k) {                    // 32 TMQ x 64 floats, 256 per instruction: four 256-byte rows
+                const int e = k * 256 + lane * 4, rr = e >> 6, cc = e & 63;
+                int m = mloc0 + rr, bi = bi0;
+                if (m >= Mb) { m -= Mb; ++bi; }
+                const float4 t = *reinterpret_cast<const float4*>(&stage[e]);
+                if (mrow + rr < Mlim) store16(base + (((long)b + bi) * p.heads + hh) * Mb * 64 + (long)m * 64 + cc, t, wt);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -632,10 +665,11 @@ template <typename TO> __device__ __forceinline__ void ln_act8(float (&x)[8], in
 // CONSUMER with a plain epilogue (FF1): v = act(rstd * acc - (mean * rstd) * ln_p[col] + ln_c[col]).  The wave tile is TM
 // 32-row blocks x WN = 32 * TN columns, first row `mw` of this launch, first column `nc0`; it leaves as rows of TO (16-bit
 // engines: p.out) or as panel planes of NP planes (fp32 engines: p.out_planes), one 16-byte store per lane and plane.
-template <typename TO, int TM, int TN, int NP, bool PRE = false>
+template <typename TO, int TM, int TN, int NP, bool PRE = false, bool WTS = false>
 __device__ __forceinline__ void gemm_epilogue_ln_in(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int mw, int nc0, int lr, int lk, float* stage,
                                                     const float* pre_rs = nullptr, const float* pre_mr = nullptr, int m_end = -1) {
     const int Mlim = m_end >= 0 ? m_end : p.M;
+    const bool wt = WTS && (p.epi_wt & 1);
     constexpr int WN = 32 * TN, LPR = WN / 8, RPI = 64 / LPR, NIT = 32 / RPI;
     const int lane = lk * 32 + lr;
     const int c8 = (lane % LPR) * 8, rl0 = lane / LPR;
@@ -683,7 +717,7 @@ __device__ __forceinline__ void gemm_epilogue_ln_in(f32x16 (&acc)[TM][TN], const
                 if (m < Mlim) {
                     unsigned char* dst = (unsigned char*)p.out_planes + x3p_slot_offset(m, col >> 3, p.N >> 5, NP);
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
+                    for (int q = 0; q < NP; ++q) store16(dst + q * X3P_PLANE, pl[q], wt);
                 }
             } else {
                 Pk o;
@@ -701,9 +735,13 @@ __device__ __forceinline__ void gemm_epilogue_ln_in(f32x16 (&acc)[TM][TN], const
 // PRODUCER (O / FF2 projections): x_new = res + gate * (acc + bias) -> fp32 rows in p.out (the residual stream); the same rows
 // o (1 + ln_scale) -> the next GEMM's A operand (TA = float: panel planes of NP planes; else rows of TA, [M][N]); partial
 // (sum, M2 about the block mean) of x_new per 32-column block -> ln_stats_out (wave_reduce.h).  Wave tile as above.
-template <typename TA, int TM, int TN, int NP>
+// WTS with epi_wt bit 1: the fp32 rows go back into the lane's own staging slots and leave after the block's statistics, 16 bytes
+// per lane in row order, so that a store instruction writes 1 KB of whole lines (8 rows of a 32-column tile, 4 of a 64-column
+// one) — a lane's two stores of its 32 bytes write every line in halves, which write-through stores send on as halves.
+template <typename TA, int TM, int TN, int NP, bool WTS = false>
 __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int mw, int nc0, int lr, int lk, float* stage, int m_end = -1) {
     const int Mlim = m_end >= 0 ? m_end : p.M;
+    const bool wt = WTS && (p.epi_wt & 1), lines = WTS && (p.epi_wt & 2);
     constexpr int WN = 32 * TN, LPR = WN / 8, RPI = 64 / LPR, NIT = 32 / RPI;
     const int lane = lk * 32 + lr;
     const int c8 = (lane % LPR) * 8, rl0 = lane / LPR;
@@ -751,9 +789,12 @@ __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], co
             const float4 t1 = *reinterpret_cast<const float4*>(&stage[rr * WN + c8 + 4]);
             float x[8] = {t0.x + r0[it].x, t0.y + r0[it].y, t0.z + r0[it].z, t0.w + r0[it].w,
                           t1.x + r1[it].x, t1.y + r1[it].y, t1.z + r1[it].z, t1.w + r1[it].w};
-            if (ok[it]) {
-                *reinterpret_cast<float4*>(outp + ix[it]) = make_float4(x[0], x[1], x[2], x[3]);
-                *reinterpret_cast<float4*>(outp + ix[it] + 4) = make_float4(x[4], x[5], x[6], x[7]);
+            if (lines) {
+                *reinterpret_cast<float4*>(&stage[rr * WN + c8]) = make_float4(x[0], x[1], x[2], x[3]);
+                *reinterpret_cast<float4*>(&stage[rr * WN + c8 + 4]) = make_float4(x[4], x[5], x[6], x[7]);
+            } else if (ok[it]) {
+                store16(outp + ix[it], make_float4(x[0], x[1], x[2], x[3]), wt);
+                store16(outp + ix[it] + 4, make_float4(x[4], x[5], x[6], x[7]), wt);
             }
             // partial statistics of the 32-column block this lane's quad covers (8 columns per lane, 4 lanes): fixed order
             float s1, s2;
@@ -768,7 +809,7 @@ __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], co
                 if (ok[it]) {
                     unsigned char* dst = (unsigned char*)p.ln_out + x3p_slot_offset(m, col >> 3, p.N >> 5, NP);
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
+                    for (int q = 0; q < NP; ++q) store16(dst + q * X3P_PLANE, pl[q], wt);
                 }
             } else {
                 Pk o;
@@ -781,6 +822,17 @@ __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], co
                 if constexpr (std::is_same<TA, f16>::value) sat |= ok[it] ? f16_range_word(x) : 0u;
             }
         }
+        if (lines) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < WN / 8; ++k) {                     // 32 x WN floats, 256 per instruction
+                const int e = k * 256 + lane * 4, rr = e / WN, cc = e - rr * WN;
+                const int m = mw + i * 32 + rr;
+                const float4 t = *reinterpret_cast<const float4*>(&stage[e]);
+                if (m < Mlim) store16(outp + (long)m * p.out_rstride + nc0 + cc, t, wt);
+            }
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -790,10 +842,11 @@ __device__ __forceinline__ void gemm_epilogue_resid_ln(f32x16 (&acc)[TM][TN], co
 // Epilogue with the OUTPUT as panel planes of the [M][N] result (the A operand of the next linear layer; FF1 -> FF2):
 // bias + activation on the accumulators, the 64x64 wave tile through LDS, then every lane takes 8 consecutive columns of
 // a row (one 16-byte k-slot of the next GEMM), splits them three ways and stores 16 bytes per plane.
-template <int TM, int TN, int NP>
+template <int TM, int TN, int NP, bool WTS = false>
 __device__ __forceinline__ void x3p_epilogue_planes(f32x16 (&acc)[TM][TN], const ConvGemmDev& p, int m0, int n0, int wm, int wn,
                                                     int lr, int lk, float* stage, int m_end = -1) {
     const int Mlim = m_end >= 0 ? m_end : p.M;
+    const bool wt = WTS && (p.epi_wt & 1);
     const int lane = lk * 32 + lr;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -833,7 +886,7 @@ __device__ __forceinline__ void x3p_epilogue_planes(f32x16 (&acc)[TM][TN], const
         if (m < Mlim) {
             unsigned char* dst = planes + x3p_slot_offset(m, s8, nch_out, NP);
 #pragma unroll
-            for (int q = 0; q < NP; ++q) *reinterpret_cast<u32x4*>(dst + q * X3P_PLANE) = pl[q];
+            for (int q = 0; q < NP; ++q) store16(dst + q * X3P_PLANE, pl[q], wt);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

@@ -297,8 +297,8 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
                 h1[0][0][r] = (rb == G::NRB - 1 && r >= 8) ? 0.f : t;     // (rows 144 .. 159 were never staged: see below)
             }
             float* st = half_stage + wave * 1024;
-            if constexpr (FOLD) gemm_epilogue_resid_ln<float, 1, 1, 2>(h1, p, m0 + rb * 32, n0 + cb * 64 + hf * 32, lr, lk, st, m_end);
-            else gemm_epilogue_lds<float, 1, 1, 32, 32>(h1, p, m0, n0, 0, 0, rb, cb * 2 + hf, lr, lk, st, m_end);
+            if constexpr (FOLD) gemm_epilogue_resid_ln<float, 1, 1, 2, true>(h1, p, m0 + rb * 32, n0 + cb * 64 + hf * 32, lr, lk, st, m_end);
+            else gemm_epilogue_lds<float, 1, 1, 32, 32, true>(h1, p, m0, n0, 0, 0, rb, cb * 2 + hf, lr, lk, st, m_end);
         }
         return;
     }
@@ -321,13 +321,13 @@ __global__ __launch_bounds__(768) void linear_x3d_kernel(const ConvGemmDev p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if constexpr (FOLD) {
-            if constexpr (EPK == 1) gemm_epilogue_qkv_lds<float, 1, true, true>(h, p, m0, n0, 0, rb, cb, lr, lk, blk, prs, pmr, m_end);
-            else if constexpr (EPK == 2) gemm_epilogue_ln_in<float, 1, 2, 2, true>(h, p, m0 + rb * 32, n0 + cb * 64, lr, lk, blk, prs, pmr, m_end);
-            else gemm_epilogue_resid_ln<float, 1, 2, 2>(h, p, m0 + rb * 32, n0 + cb * 64, lr, lk, blk, m_end);
+            if constexpr (EPK == 1) gemm_epilogue_qkv_lds<float, 1, true, true, true>(h, p, m0, n0, 0, rb, cb, lr, lk, blk, prs, pmr, m_end);
+            else if constexpr (EPK == 2) gemm_epilogue_ln_in<float, 1, 2, 2, true, true>(h, p, m0 + rb * 32, n0 + cb * 64, lr, lk, blk, prs, pmr, m_end);
+            else gemm_epilogue_resid_ln<float, 1, 2, 2, true>(h, p, m0 + rb * 32, n0 + cb * 64, lr, lk, blk, m_end);
         } else {
-            if constexpr (EPK == 1) gemm_epilogue_qkv_lds<float, 1>(h, p, m0, n0, 0, rb, cb, lr, lk, blk, nullptr, nullptr, m_end);
-            else if constexpr (EPK == 2) x3p_epilogue_planes<1, 2, 2>(h, p, m0, n0, rb, cb, lr, lk, blk, m_end);
-            else gemm_epilogue_lds<float, 1, 2, 32, 64>(h, p, m0, n0, 0, 0, rb, cb, lr, lk, blk, m_end);
+            if constexpr (EPK == 1) gemm_epilogue_qkv_lds<float, 1, false, false, true>(h, p, m0, n0, 0, rb, cb, lr, lk, blk, nullptr, nullptr, m_end);
+            else if constexpr (EPK == 2) x3p_epilogue_planes<1, 2, 2, true>(h, p, m0, n0, rb, cb, lr, lk, blk, m_end);
+            else gemm_epilogue_lds<float, 1, 2, 32, 64, true>(h, p, m0, n0, 0, 0, rb, cb, lr, lk, blk, m_end);
         }
     }
 #endif
@@ -368,6 +368,13 @@ void launch_linear_x3d(const ConvGemmDev& e_in, int tw, int rgn, int cgn, int ba
     const dim3 grid((unsigned)(((tiles + 7) / 8) * 8));
     const bool fold = e.ln_stats_in || e.ln_stats_out;
     const int epk = e.epi == EPI_QKV_ROPE ? 1 : fold ? (e.ln_stats_in ? 2 : 3) : (e.out_planes ? 2 : 3);
+    // store policy of this launch's role (MI355TTS_EPI_WT, options.h): bit 0 QKV, 1 FF1, 2 O / FF2, 3 rows / planes out; bit 5: the
+    // fp32 rows of O / FF2 as whole lines with plain stores.  A role that stores write-through always sends whole lines: Q in
+    // halves measured 1.1 us per launch slower than Q in lines, O / FF2 was built in lines only (profiles/r21/INDEX.md)
+    const long wtm = opt(OPT_EPI_WT);
+    const bool role_wt = (wtm >> (epk == 1 ? 0 : !fold ? 3 : epk == 2 ? 1 : 2)) & 1;
+    const bool lines = (epk == 1 && role_wt) || (fold && epk == 3 && (role_wt || (wtm & 32)));
+    e.epi_wt = (role_wt ? 1 : 0) | (lines ? 2 : 0);
 #define X3D_GO(TW_, FOLD_, EPK_, LABEL)                                                                                           \
     do {                                                                                                                          \
         prof_set_kernel("linear_x3d_kernel<" #TW_ ", " LABEL ">", "", "");                                                        \

@@ -33,6 +33,28 @@ __device__ __forceinline__ void dma16_buf(RSRC rsrc, int voff, unsigned lds_dst)
 #endif
 }
 
+// 16-byte store to global memory, write-through when `wt` (wave-uniform) is set: global_store_dwordx4 ... sc1, the policy of
+// gemm_sk.hip's __builtin_amdgcn_raw_buffer_store_b128(..., 16) without a descriptor (the 64-bit address is the VGPR pair the plain
+// store would use, so the register budget does not move).  A plain store leaves its line dirty in the XCD's L2 until the kernel
+// boundary writes it back with every CU idle; an sc1 store sends the bytes on at once and drops the line, so a layer's output
+// leaves under the epilogue's LDS hops instead of behind the last wave (MI355X_MICROARCH.md: store flavours, "boundary",
+// "publish-large").  Only worth it when a wave instruction covers whole 128-byte lines.  Nothing in the storing launch may read
+// the bytes back; the next launch sees them at the stream's kernel boundary as it does plain stores.  Inline asm: the compiler
+// has no sc1 on an ordinary store; gfx9 stores read their data at issue, so no wait is owed before the registers are reused.
+template <typename V>
+__device__ __forceinline__ void store16(void* dst, const V& v, bool wt) {
+    static_assert(sizeof(V) == 16, "store16: one dwordx4");
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (wt) {
+        u32x4 w;
+        __builtin_memcpy(&w, &v, 16);
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(w));
+    } else {
+        *reinterpret_cast<V*>(dst) = v;
+    }
+#endif
+}
+
 // counted waits: at most N of this wave's operations of that counter still in flight.  vmcnt: vector-memory loads (LDS-DMA
 // included) return in order, so "all but the N youngest have landed" is exact.  lgkmcnt: LDS operations complete in order, but
 // scalar memory loads share the counter and return OUT of order — a wait_lgkm<N > 0>() is exact only where no scalar load can be

@@ -61,6 +61,10 @@ namespace mi {
     X(GEMM_X3P_GRID, "gemm_x3p_grid", "MI355TTS_X3P_GRID", ENV_INT, 0, STORE, 0, 0) /* A/B: 0 = automatic, else GR (1, 2, 4, 8) */ \
     X(GEMM_X3D, "gemm_x3d", "MI355TTS_X3D", ENV_INT, 1, STORE, 0, 0) /* 0 off, 1 automatic */                           \
     X(GEMM_X3D_MIN_EFF, "gemm_x3d_min_eff", "MI355TTS_X3D_MIN_EFF", ENV_INT, 90, STORE, 0, 0) /* per cent of useful tile area */ \
+    /* gemm_x3d.hip epilogues: which roles store write-through (store16, lds_dma.h).  Bit 0 QKV, 1 FF1, 2 O / FF2, 3 rows / planes */ \
+    /* out, 4 attention (reserved: its 8-byte stores stay plain), 5 the fp32 rows of O / FF2 as whole lines with plain stores (A/B). */ \
+    /* Default 14: the roles whose period fell in every alternation (profiles/r21/INDEX.md); QKV rose by 0.3 - 1.0 us and stays plain */ \
+    X(EPI_WT, nullptr, "MI355TTS_EPI_WT", ENV_INT, 14, CLAMP, 0, 63)                                                    \
     /* 256x256 eight-phase kernel (gemm_ph8.hip) for 16-bit linear layers with at least min_tiles tiles of 256x256 */   \
     X(GEMM_PH8, "gemm_ph8", "MI355TTS_PH8", ENV_INT, 1, STORE, 0, 0)                                                    \
     X(GEMM_PH8_MIN_TILES, "gemm_ph8_min_tiles", "MI355TTS_PH8_MIN", ENV_INT, 200, STORE, 0, 0)                          \

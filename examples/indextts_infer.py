@@ -24,8 +24,8 @@ sampling flags.
 `--num-beams N --beam-pool [--length-penalty x] [--early-stopping]` is upstream's own beam search: finished hypotheses are kept
 in a pool, the search goes on while a running one can still beat them, and the best of the pool goes to the vocoder.  With
 `--beam-pool` the sampling flags ARE accepted together with `--num-beams` (beam sampling: `--num-beams 3 --beam-pool --top-k 30
---top-p 0.8` is what upstream runs).  Every sentence starts from a fresh penalty vector; not with --queue, --takes or
---device-type cuda.
+--top-p 0.8` is what upstream runs).  Every sentence starts from a fresh penalty vector; not with --takes or --device-type
+cuda.
 `--queue` decodes the whole text at once instead of sentence by sentence: every sentence is embedded, `generate_queue` runs them
 through `--slots` batch slots (default 8, 1..64) — a slot is refilled as soon as its sentence stops and the prompts admitted
 together share one pass over the weights — and `run_latent_ragged` vocodes them in one forward, in order, with the same gap.
@@ -33,7 +33,10 @@ Every queued sentence starts from a FRESH penalty vector: the sentences run conc
 sentence to the next that the sentence-by-sentence forms keep (like the reference) does not exist there.  Sampling flags apply
 (one seed per sentence: sample-seed + its index); takes do not go through the queue.  `--queue --num-beams N` is beam search
 through the queue: every sentence runs as a group of N slots, the queue schedules the `--slots` // N groups, and with `--stream`
-a sentence's audio leaves whole, as soon as its group is retired, while the other groups decode.
+a sentence's audio leaves whole, as soon as its group is retired, while the other groups decode.  `--queue --num-beams N
+--beam-pool [--top-k 30 --top-p 0.8 --sample-seed s] [--length-penalty x] [--early-stopping] [--stream]` is upstream's decode
+configuration through the queue: the groups run the pool-mode search (one seed per sentence: sample-seed + its index), and a
+sentence's result is what `--beam-pool` gives for it alone.
 With `--queue`, `--prompt a.wav,b.wav,...` is a dialogue: graph A runs once per file, sentence i is spoken by voice i mod V (or by
 `--voice-of 0,1,1,0,...`, one index per sentence), every sentence's prompt carries its own voice's conditioning rows, and ONE
 `run_latent_voices` call vocodes all of them in order, whatever the mix of voices.  One prompt file is the one-voice case of the
@@ -160,8 +163,8 @@ def parse_args(argv=None):
     if not 1 <= args.takes <= MAX_SLOTS:
         ap.error(f"--takes must be in 1..{MAX_SLOTS} (the engine's batch slots)")
     args.sampled = args.takes > 1 or any(v is not None for v in (args.temperature, args.top_k, args.top_p, args.sample_seed))
-    if args.beam_pool and (args.queue or args.takes > 1 or args.device_type == "cuda"):
-        ap.error("--beam-pool decodes sentence by sentence through the host-array beam call: no --queue, no --takes, --device-type cpu")
+    if args.beam_pool and (args.takes > 1 or args.device_type == "cuda"):
+        ap.error("--beam-pool decodes through the host-array beam calls (sentence by sentence, or --queue): no --takes, --device-type cpu")
     if not args.beam_pool and (args.length_penalty != 0.0 or args.early_stopping):
         ap.error("--length-penalty and --early-stopping belong to --beam-pool")
     if not math.isfinite(args.length_penalty):
@@ -219,12 +222,14 @@ def main():
             budgets.append(max(gcfg.max_generate_length - int(prompt_len[0]), 0))
         t_dec = time.time()
         q_sampling = [dataclasses.replace(take_sampling[0], seed=take_sampling[0].seed + i) for i in range(len(prompts))] if sampled else None
-        q_beams = args.num_beams if args.num_beams > 1 else None     # a sentence in a group of N slots, the queue over slots // N groups
+        # a sentence in a group of N slots, the queue over slots // N groups; --beam-pool: the groups run the pool-mode search
+        q_beams = args.num_beams if args.num_beams > 1 or args.beam_pool else None
+        q_pool = dict(pool=True, length_penalty=args.length_penalty, early_stopping=args.early_stopping) if args.beam_pool else {}
         if args.stream:
             chunks, t_first = {}, None
             for i, first_sample, chunk, last in stream_synthesize(gpt, voc, prompts, budgets, [c for c, _ in speakers], voice_of,
                                                                   chunk=args.chunk, halo=args.halo, stop_tokens=stops, sampling=q_sampling,
-                                                                  beams=q_beams):
+                                                                  beams=q_beams, **q_pool):
                 if t_first is None:
                     t_first = time.time() - t_dec
                 assert first_sample == sum(c.size for c in chunks.get(i, []))
@@ -239,7 +244,7 @@ def main():
             results = []
         else:
             results, q_stats = gpt.generate_queue(prompts, budgets, stop_tokens=stops, sampling=q_sampling, beams=q_beams,
-                                                  return_stats=True)
+                                                  return_stats=True, **q_pool)
             results = [r[:2] for r in results]                       # (tokens, hidden[, score])
             n_codes = sum(h.shape[0] for _, h in results)
             print(f"Decode Speed: {n_codes / max(time.time() - t_dec, 1e-9):.3f} tokens/s ({n_codes} tokens, {len(prompts)} sentences in "

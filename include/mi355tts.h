@@ -444,8 +444,9 @@ int         mi_gpt_beam_select(const float* logits, const float* pen, const floa
  *   Property: B = 1, deterministic, length_penalty = 0 gives the tokens of mi_gpt_generate wherever rounding cannot decide a
  *      selection.
  * Scores hold to a tolerance and choices wherever rounding cannot decide, as above; sampled results are the same bits from
- * every launch, slot, batch and graph replay.  Not offered yet: pool mode through the sentence queue, and streaming of it (a
- * group's retirement there needs the frozen list).
+ * every launch, slot, batch and graph replay.  Pool mode through the sentence queue, as a session and streamed:
+ * mi_gpt_generate_queue_beam_pool / mi_gpt_queue_begin_beam_pool, below beside "beam search through the sentence queue" (a
+ * group's retirement there follows the frozen list).
  *
  * MI_EINVAL, before anything is launched and with the handle still usable: what mi_gpt_generate_beam rejects; K > 64 or
  * K > mel_codes; length_penalty not finite; early_stopping outside {0, 1}; an invalid sampling record; top_k not 0 and below K;
@@ -637,6 +638,44 @@ int         mi_gpt_generate_queue_beam(mi_gpt* h, int n, const float* prompts, c
 int         mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
                                     const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
                                     int32_t* tokens, float* hidden, int cap, float* scores /* (n) or NULL */, int mem);
+
+/* ---- pool mode through the sentence queue: the groups above running "beam search with a finished pool" (selections 1-9, ties,
+ * Philox counters, K = (n_stop + 1) * B exactly as defined there), deterministic or sampled.  This is upstream IndexTTS' own
+ * decode configuration (num_beams = 3, do_sample, top_k = 30, top_p = 0.8, length_penalty = 0) with slot refill, packed prompt
+ * passes, sessions and streaming.
+ *
+ * mi_gpt_generate_queue_beam_pool: the arguments of mi_gpt_generate_queue_beam, then length_penalty, early_stopping and four HOST
+ * arrays of n sampling parameters (all four NULL: deterministic), as mi_gpt_generate_beam_pool takes them.  Validation is the
+ * union of the two entries': lengths per sentence; num_beams 1..8, at most mel_codes, at most max_batch; K <= 64 and <= mel_codes;
+ * length_penalty finite; early_stopping 0 or 1; valid sampling records, all four arrays or none; top_k 0 or >= K; at most 16384
+ * mel codes with sampling.  All of it runs before anything is launched: MI_EINVAL, the handle still usable and no session open.
+ * There is no repeat_penality argument: every sentence starts from ones, as in the other queue entries.
+ *   Contract: per sentence the result (tokens, rows, n_out, score) is what mi_gpt_generate_beam_pool gives for that sentence
+ *   alone from a penalty vector of ones.  The decode steps are the same launches; the prompt pass differs from the one-by-one
+ *   pass in GEMM tiling only.  A sampled sentence's result depends on its seed alone: not on its group, its pass or n.
+ * Policy: the one above, a unit being a group.  max_new bounds the SELECTIONS a sentence runs (the prompt pass's selection 0
+ * included), which is what the schedule counts; the length a sentence returns is that of pool entry 0 and is usually smaller.
+ * So stats, and mi_gpt_queue_schedule(..., beams = B) as their host model, take lengths[i] = the selections sentence i ran, not
+ * its returned length.  A pass that admits k groups makes each group's pool empty (in stream order behind the retirement of the
+ * tenant before) and runs selection 0 of all k in one launch; every group retiring in a round leaves in one launch along its
+ * frozen list, ahead of the pass that refills it.  A sentence with max_new == 0 takes no group: n_out 0, score 0.
+ *
+ * mi_gpt_queue_begin_beam_pool: the same arguments without n_out and stats; the session mi_gpt_queue_advance / mi_gpt_queue_end
+ * drive, exactly as mi_gpt_queue_begin_beam's: count[i] is 0 until sentence i is retired, then its n_out with done[i] = 1, its
+ * tokens, rows and score leaving in that round.  While it is open the MI_ESTATE rules above hold (mi_gpt_generate_beam_pool and
+ * these two entries included).                                                                                              */
+int         mi_gpt_generate_queue_beam_pool(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows,
+                                            const int32_t* max_new, const int32_t* stop_ids, int n_stop, float repeat_value,
+                                            int penalty_range, int num_beams, float length_penalty, int early_stopping,
+                                            const float* temperature, const int32_t* top_k, const float* top_p,
+                                            const uint64_t* seeds /* host, n; all four or none */, int32_t* tokens, float* hidden,
+                                            int cap, int32_t* n_out, float* scores /* (n) or NULL */, int mem,
+                                            int32_t* stats /* host, 2 ints or NULL */);
+int         mi_gpt_queue_begin_beam_pool(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                         const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                                         float length_penalty, int early_stopping, const float* temperature, const int32_t* top_k,
+                                         const float* top_p, const uint64_t* seeds, int32_t* tokens, float* hidden, int cap,
+                                         float* scores /* (n) or NULL */, int mem);
 
 /* Tests and tools, no handle, no GPU: the schedule the policy above gives n sentences that will produce lengths[i] tokens each
  * (host arrays of n; 1 <= lengths[i] <= max_new[i], or 0 where max_new[i] is 0) on a handle of `slots` slots and max_seq packed

@@ -968,7 +968,7 @@ static int gpt_queue_run(mi_gpt* h, const GptQueueArgs& a, int32_t* n_out, int32
         Gpt& e = *h->impl;
         GptQueue q(e, a);
         GptModeScope mode(e, q.sampled());
-        GptBeamScope group(e, q.beams());
+        GptBeamScope group(e, q.beams(), q.pool());
         while (q.round()) {}
         q.settle();
         q.report(n_out, nullptr, nullptr, stats);
@@ -1012,6 +1012,27 @@ int mi_gpt_queue_begin_beam(mi_gpt* h, int n, const float* prompts, const int32_
                               tokens, hidden, cap, mem, nullptr, nullptr, nullptr, nullptr, true, num_beams, scores});
 }
 
+// pool mode through the queue: the beam entries' arguments, the search's parameters and the four sampling arrays (all or none)
+int mi_gpt_generate_queue_beam_pool(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                    const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                                    float length_penalty, int early_stopping, const float* temperature, const int32_t* top_k,
+                                    const float* top_p, const uint64_t* seeds, int32_t* tokens, float* hidden, int cap,
+                                    int32_t* n_out, float* scores, int mem, int32_t* stats) {
+    return gpt_queue_run(h, {"mi_gpt_generate_queue_beam_pool", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value,
+                             penalty_range, tokens, hidden, cap, mem, temperature, top_k, top_p, seeds, true, num_beams, scores, true,
+                             length_penalty, early_stopping}, n_out, stats);
+}
+
+int mi_gpt_queue_begin_beam_pool(mi_gpt* h, int n, const float* prompts, const int32_t* prompt_rows, const int32_t* max_new,
+                                 const int32_t* stop_ids, int n_stop, float repeat_value, int penalty_range, int num_beams,
+                                 float length_penalty, int early_stopping, const float* temperature, const int32_t* top_k,
+                                 const float* top_p, const uint64_t* seeds, int32_t* tokens, float* hidden, int cap, float* scores,
+                                 int mem) {
+    return gpt_queue_open(h, {"mi_gpt_queue_begin_beam_pool", n, prompts, prompt_rows, max_new, stop_ids, n_stop, repeat_value,
+                              penalty_range, tokens, hidden, cap, mem, temperature, top_k, top_p, seeds, true, num_beams, scores, true,
+                              length_penalty, early_stopping});
+}
+
 int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* finished, int32_t* stats) {
     return guard([&] {
         const std::string who = "mi_gpt_queue_advance";
@@ -1022,7 +1043,7 @@ int mi_gpt_queue_advance(mi_gpt* h, int32_t* count, int32_t* done, int32_t* fini
         GptQueue& q = *h->session;
         if (!q.ended()) {
             GptModeScope mode(e, q.sampled());
-            GptBeamScope group(e, q.beams());
+            GptBeamScope group(e, q.beams(), q.pool());
             if (q.round()) q.publish_live();
             q.settle();
         }

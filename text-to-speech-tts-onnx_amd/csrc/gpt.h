@@ -94,6 +94,14 @@ struct Gpt {
     void decode_pool_eager(int nb, int B);
     void decode_pool_steps(int nb, int B, int n);
     void pool_gather(int nb, int B, int32_t* tokens, float* hidden, int cap);          // pool entry 0 of every group
+    // the sentence queue in pool mode: `pool` set beside `beams` makes forward_packed run the pool-mode selection 0; the
+    // session's parameters; one group's pool made empty in stream order (rec: the sentence's record, null = deterministic);
+    // selection 0 of the k groups of the pass just run, one launch; retirement of the table's groups along their frozen
+    // lists (pool entry 0's tokens, rows and score), one launch
+    int pool = 0;
+    void pool_set_cfg(const GptPoolCfg& cf);
+    void pool_reset_group(int group, int B, const GptSampleRec* rec);
+    void pool_select_segs(int k, int B);              // (pool_out_rows: below, beside beam_out_rows)
     hipGraphExec_t step_graph[2] = {nullptr, nullptr};      // by mode
     bool use_graph = true;
     long graph_epoch = 0;     // option_epoch() the captured graphs were taken under
@@ -127,6 +135,7 @@ struct Gpt {
     struct OutTable { OutSeg e[GPT_MAX_BATCH]; };
     void copy_out_rows(const OutTable& tab, int n, int32_t* tokens_dst, float* hidden_dst);
     void beam_out_rows(const OutTable& tab, int n, int B, int32_t* tokens_dst, float* hidden_dst, float* score_dst);   // gpt_beam.hip
+    void pool_out_rows(const OutTable& tab, int n, int B, int32_t* tokens_dst, float* hidden_dst, float* score_dst);   // gpt_beam_pool.hip
     // one layer's K / V cache of a slot (bytes; slots are slot_cache_elems() elements apart)
     struct LayerKV { char *k, *v; };
     LayerKV layer_cache(int layer, int slot = 0) {

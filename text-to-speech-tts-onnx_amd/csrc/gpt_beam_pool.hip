@@ -10,6 +10,8 @@
 //                           stop test, next running hypotheses, pool merge, `open`; then the move of the running hypotheses
 //                           as in beam_step_body.
 //   gpt_pool_gather_kernel  pool entry 0 along its frozen ancestor list.
+// and for pool groups in the sentence queue (gpt_queue.hip): gpt_pool_first_segs_kernel (selection 0 of every group a packed pass
+// admitted), gpt_pool_reset_kernel (one group's pool made empty at admission), gpt_pool_out_kernel (retirement by table).
 //
 // The pool lives in device memory per group (GptPoolDev): an entry is a score, a flag, a length and a physical row that holds
 // its frozen ancestor list, its last token and its last last_hidden_state row; the merge permutes the small words and never
@@ -647,6 +649,40 @@ __global__ __launch_bounds__(1024) void gpt_pool_step_kernel(const float* __rest
                    max_pos, xb, B, pd, (size_t)(group0 + blockIdx.x) * B);
 }
 
+// The sentence queue in pool mode: selection 0 of every group a packed prompt pass admitted, in one launch — the form of
+// gpt_beam_first_segs_kernel (gpt_beam.hip).  Workgroup q serves segment q of the pass's table (Gpt::Seg as an int4: first packed
+// row, rows, slot, pad); the group is slot / B and `rows` is the segment's.  A segment whose slot does not name a whole group
+// inside the handle's slots is left alone (block-uniform).
+__global__ __launch_bounds__(1024) void gpt_pool_first_segs_kernel(const int4* __restrict__ segs, const float* __restrict__ logits,
+                                                                   float* pen0, float* pen1, const float* __restrict__ last,
+                                                                   int* st, int* toks, float* __restrict__ hid, int* anc0,
+                                                                   int* anc1, float* scores, int codes, int hidden,
+                                                                   const float* __restrict__ rep_dev, int max_tok,
+                                                                   const float* __restrict__ emb, const float* __restrict__ pos,
+                                                                   int max_pos, float* __restrict__ xb, int B, GptPoolDev pd,
+                                                                   int max_batch) {
+    const int4 g = segs[blockIdx.x];
+    const int group = g.z / B;
+    if (g.z < 0 || (group + 1) * B > max_batch) return;
+    pool_step_body(logits, pen0, pen1, last, st, toks, hid, anc0, anc1, scores, codes, hidden, min(max(g.y, 0), max_tok), rep_dev,
+                   max_tok, emb, pos, max_pos, xb, B, pd, (size_t)group * B);
+}
+
+// The pool of the group whose first slot is s0 made empty for the sentence the queue admits into it (Gpt::pool_begin's state, for
+// one group, in stream order): scores -1e9, no entry finished, entry j in physical row j, `open`, and the sentence's record.
+__global__ __launch_bounds__(64) void gpt_pool_reset_kernel(float* __restrict__ score, int* __restrict__ meta,
+                                                            GptSampleRec* __restrict__ recs, int s0, int B, GptSampleRec rec) {
+    const int j = threadIdx.x;
+    if (j >= B) return;
+    score[s0 + j] = -1.0e9f;
+    int* mw = meta + (size_t)(s0 + j) * GPT_POOL_META;
+#pragma unroll
+    for (int q = 0; q < GPT_POOL_META; ++q) mw[q] = 0;
+    mw[PM_ROW] = j;
+    mw[PM_OPEN] = 1;
+    recs[s0 + j] = rec;
+}
+
 // pool entry 0 of every group along its frozen ancestor list; its last token and row are the entry's own
 __global__ __launch_bounds__(256) void gpt_pool_gather_kernel(GptPoolDev pd, const int* __restrict__ toks,
                                                               const float* __restrict__ hid, int32_t* __restrict__ tokens,
@@ -665,6 +701,34 @@ __global__ __launch_bounds__(256) void gpt_pool_gather_kernel(GptPoolDev pd, con
     if (hidden_out)
         for (int c = threadIdx.x; c < hidden; c += 256)
             hidden_out[((size_t)blockIdx.y * cap + n) * hidden + c] = own ? pd.hid[row * hidden + c] : hid[(src * max_tok + n) * hidden + c];
+}
+
+// Retirement of the queue's pool groups by table, in the form of gpt_beam_out_kernel (gpt_beam.hip) with the gather above as
+// its source: entry q = (slot = the group's first slot, sentence, count, dst_row).  Pool entry 0 of the group leaves: token n
+// and last_hidden_state row n below its last along the frozen list pool_anc of its physical row, the last token and row from
+// PM_TOK / pool_hid of that row; they go to row dst_row + n of the destination arrays and its score (0 when the pool holds no
+// finished entry) to score_dst[sentence].  One block per (row of the longest entry, entry); indices are clamped as above.
+__global__ __launch_bounds__(256) void gpt_pool_out_kernel(Gpt::OutTable tab, GptPoolDev pd, const int* __restrict__ toks,
+                                                           const float* __restrict__ hid, int32_t* __restrict__ tokens_dst,
+                                                           float* __restrict__ hidden_dst, float* __restrict__ score_dst, int B,
+                                                           int max_tok, int hidden, int max_batch) {
+    const Gpt::OutSeg g = tab.e[blockIdx.y];
+    const int n = blockIdx.x;
+    if (g.slot < 0 || g.slot % B != 0 || g.slot + B > max_batch || g.sentence < 0) return;      // block-uniform
+    const size_t s0 = (size_t)g.slot;
+    const int* mw = pd.meta + s0 * GPT_POOL_META;
+    const int fin = mw[PM_FIN];
+    if (n == 0 && threadIdx.x == 0 && score_dst) score_dst[g.sentence] = fin ? pd.score[s0] : 0.f;
+    const int len = fin ? mw[PM_LEN] : 0;
+    if (n >= g.count || n >= len || n >= max_tok) return;
+    const size_t row = s0 + min(max(mw[PM_ROW], 0), B - 1);
+    const bool own = n == len - 1;
+    const size_t src = own ? row : s0 + min(max(pd.anc[row * max_tok + n], 0), B - 1);
+    const size_t dst = (size_t)(g.dst_row + n);
+    if (tokens_dst && threadIdx.x == 0) tokens_dst[dst] = own ? pd.meta[row * GPT_POOL_META + PM_TOK] : toks[src * max_tok + n];
+    if (hidden_dst)
+        for (int c = threadIdx.x; c < hidden; c += 256)
+            hidden_dst[dst * hidden + c] = own ? pd.hid[row * hidden + c] : hid[(src * max_tok + n) * hidden + c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -763,6 +827,49 @@ void Gpt::pool_gather(int nb, int B, int32_t* tokens, float* hidden, int cap) {
     const int rows = cap < cfg.max_seq ? cap : cfg.max_seq;
     hipLaunchKernelGGL(gpt_pool_gather_kernel, dim3(rows, nb), dim3(256), 0, stream, pool_dev(), toks.as<int>(), hid.as<float>(),
                        tokens, hidden, B, cfg.max_seq, cfg.hidden, cap);
+    MI_HIP(hipGetLastError());
+}
+
+// the call's parameters alone (a queue session has one GptPoolCfg; its groups are reset one by one, pool_reset_group)
+void Gpt::pool_set_cfg(const GptPoolCfg& cf) {
+    MI_REQUIRE(pool_cfg.p, "gpt beam pool: parameters before pool_ensure");
+    MI_HIP(hipMemcpyAsync(pool_cfg.p, &cf, sizeof(cf), hipMemcpyHostToDevice, stream));
+    MI_HIP(hipStreamSynchronize(stream));
+}
+
+void Gpt::pool_reset_group(int group, int B, const GptSampleRec* rec) {
+    MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX && group >= 0 && (group + 1) * B <= cfg.max_batch && pool_score.p, "gpt beam pool: group reset");
+    const GptSampleRec r = rec ? *rec : GptSampleRec{1.f, 1.f, 0, 0u, 0u, {0u, 0u, 0u}};
+    hipLaunchKernelGGL(gpt_pool_reset_kernel, dim3(1), dim3(64), 0, stream, pool_score.as<float>(), pool_meta.as<int>(),
+                       pool_rec.as<GptSampleRec>(), group * B, B, r);
+    MI_HIP(hipGetLastError());
+}
+
+// selection 0 of the k pool groups whose segments forward_packed left in segtab, one launch
+void Gpt::pool_select_segs(int k, int B) {
+    const GptCfg& c = cfg;
+    MI_REQUIRE(B >= 1 && B <= GPT_BEAM_MAX && B <= c.mel_codes && k >= 1 && k * B <= c.max_batch && pen_b.p && pool_score.p && segtab.p,
+               "gpt beam pool: selection launch over a pass's segments");
+    int* anc0 = anc.as<int>();
+    hipLaunchKernelGGL(gpt_pool_first_segs_kernel, dim3(k), dim3(1024), 0, stream, segtab.as<int4>(), logits.as<float>(),
+                       pen.as<float>(), pen_b.as<float>(), last.as<float>(), state.as<int>(), toks.as<int>(), hid.as<float>(), anc0,
+                       anc0 + (size_t)MBp * c.max_seq, score.as<float>(), c.mel_codes, c.hidden, rep_dev.as<float>(), c.max_seq,
+                       mel_emb.as<float>(), mel_pos.as<float>(), c.max_mel_pos, Xd.as<float>(), B, pool_dev(), c.max_batch);
+    MI_HIP(hipGetLastError());
+}
+
+void Gpt::pool_out_rows(const OutTable& tab, int n, int B, int32_t* tokens_dst, float* hidden_dst, float* score_dst) {
+    MI_REQUIRE(n >= 0 && n <= GPT_MAX_BATCH && B >= 1 && B <= GPT_BEAM_MAX && pool_score.p, "gpt beam pool: retirement table");
+    int rows = 1;                                                 // the score leaves in row 0's block
+    for (int q = 0; q < n; ++q) {
+        const OutSeg& g = tab.e[q];
+        MI_REQUIRE(g.slot >= 0 && g.slot % B == 0 && g.slot + B <= cfg.max_batch && g.count >= 0 && g.count <= cfg.max_seq &&
+                       g.sentence >= 0 && g.dst_row >= 0, "gpt beam pool: retirement entry");
+        rows = std::max(rows, (int)g.count);
+    }
+    if (n == 0 || (!tokens_dst && !hidden_dst && !score_dst)) return;
+    hipLaunchKernelGGL(gpt_pool_out_kernel, dim3(rows, n), dim3(256), 0, stream, tab, pool_dev(), toks.as<int>(), hid.as<float>(),
+                       tokens_dst, hidden_dst, score_dst, B, cfg.max_seq, cfg.hidden, cfg.max_batch);
     MI_HIP(hipGetLastError());
 }
 

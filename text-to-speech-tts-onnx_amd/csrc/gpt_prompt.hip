@@ -153,7 +153,8 @@ void Gpt::forward_packed(const Seg* segs, int k) {
     }
     if (total == 1) {                          // linear() is the multi-row path: a lone one-row prompt is the single-row pass
         forward_rows(1, 1, segs[0].slot);
-        if (beams) beam_select_first(segs[0].slot / beams, beams, 1);        // as mi_gpt_generate_beam's one-by-one pass
+        if (beams && pool) pool_select_first(segs[0].slot / beams, beams, 1);
+        else if (beams) beam_select_first(segs[0].slot / beams, beams, 1);   // as mi_gpt_generate_beam's one-by-one pass
         return;
     }
     if (!packed_ready) {
@@ -201,7 +202,9 @@ void Gpt::forward_packed(const Seg* segs, int k) {
         if (!beams) choose_token(segs[g].rows, slot, false);
     }
     // beam search: selection 0 of all admitted groups from the segment table the pass left on the device, one launch
-    if (beams) beam_select_segs(k, beams);
+    // (pool mode: the pool-mode selection, gpt_beam_pool.hip)
+    if (beams && pool) pool_select_segs(k, beams);
+    else if (beams) beam_select_segs(k, beams);
 }
 
 }  // namespace mi

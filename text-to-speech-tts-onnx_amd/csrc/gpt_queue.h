@@ -4,6 +4,7 @@
 #pragma once
 #include "gpt.h"
 #include "gpt_pick.h"
+#include "gpt_pool.h"
 #include <algorithm>
 
 namespace mi {
@@ -36,11 +37,12 @@ struct GptModeScope {
     ~GptModeScope() { e.sampled = 0; }
 };
 
-// the handle runs beam groups (forward_rows / forward_packed leave the token choice to selection 0) until the scope ends
+// the handle runs beam groups (forward_rows / forward_packed leave the token choice to selection 0; pool: to the pool-mode
+// selection 0) until the scope ends
 struct GptBeamScope {
     Gpt& e;
-    GptBeamScope(Gpt& g, int B) : e(g) { e.beams = B; }
-    ~GptBeamScope() { e.beams = 0; }
+    GptBeamScope(Gpt& g, int B, bool pool = false) : e(g) { e.beams = B; e.pool = B && pool ? 1 : 0; }
+    ~GptBeamScope() { e.beams = 0; e.pool = 0; }
 };
 
 // Steps 1-3 of the header's scheduling policy, decided here and nowhere else.  Plain host code: no HIP call, no Gpt.  A unit is a slot,
@@ -117,12 +119,17 @@ struct GptQueueArgs {
     bool beam = false;                   // the "_beam" entries: num_beams hypotheses per sentence, their scores (n) or null
     int num_beams = 0;
     float* scores = nullptr;
+    bool pool = false;                   // the "_beam_pool" entries: pool mode (the sampling arrays then belong to the beam sampling)
+    float length_penalty = 0.f;
+    int early_stopping = 0;
     bool per_round = false;              // sessions: tokens and rows leave after every round; blocking entry: at retirement only
 };
 
 // The loop of a session (mi_gpt_queue_begin / _advance / _end), which stops after every run of decode steps; the blocking entry is a
 // session driven to its end inside one call.  With beams (B != 0) the unit of the schedule is a group, B consecutive slots: group g =
 // slots gB .. gB + B - 1, S = min(max_batch / B, n) groups.  B == 0 launches exactly what the queue launched before groups existed.
+// Pool mode (B != 0 and `pool`): the groups run the pool-mode selection (gpt_beam_pool.hip); GS_NDEC counts the selections run,
+// which is what max_new bounds and the policy reads, and a sentence's length is PM_LEN of its group's pool entry 0.
 class GptQueue {
 public:
     // validation (all of it before anything is launched) and the start state: every slot finished, nothing admitted
@@ -137,18 +144,19 @@ public:
     // the end of an entry that ran rounds: the host mirror of slot 0's history, and the stream drained
     void settle();
     bool ended() const { return ended_; }
-    bool sampled() const { return any_samp; }
+    bool sampled() const { return any_samp && !pool_; }          // pool mode draws inside its selection, not with the sampler
     int beams() const { return B; }
+    bool pool() const { return pool_; }
 
 private:
     Gpt& e;
     QueuePolicy pol;
     int n, cap, mem, penalty_range, B, W;        // B: beams per sentence (0 = no beam search); W: slots per unit
-    bool any_samp, per_round, ended_ = false;
+    bool any_samp, per_round, pool_, ended_ = false;
     const float* prompts;
     int32_t* tokens;
     float *hidden, *scores;              // scores: beams only, the caller's (n) or null
-    std::vector<int32_t> stops, all, n_out, copied;
+    std::vector<int32_t> stops, all, n_out, copied, meta;      // meta: pool mode, the pool words of slots 0 .. S * W - 1
     std::vector<GptSampleRec> recs;
     std::vector<size_t> row0;
     std::vector<char> retired;
@@ -159,6 +167,8 @@ private:
 
     int32_t word(int unit, int w) const { return all[(size_t)unit * W * GS_WORDS + w]; }     // of the unit's first slot
     int held(int unit) const { return std::min(word(unit, GS_NDEC), pol.max_new[pol.owner[unit]]); }
+    int pool_len(int unit) const;        // pool mode: the tokens pool entry 0 of the unit holds (0: no finished entry)
+    void read_states();                  // the state words (pool mode: and the pool words) of the slots in use -> all (, meta)
     void admit(int unit, int sentence);
     void note(int slot, int sentence, int first, int count);
     void flush();

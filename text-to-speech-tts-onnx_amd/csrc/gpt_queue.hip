@@ -100,8 +100,8 @@ void gpt_queue_schedule(int n, const int32_t* prompt_rows, const int32_t* max_ne
 
 GptQueue::GptQueue(Gpt& g, const GptQueueArgs& a)
     : e(g), n(a.n), cap(a.cap), mem(a.mem), penalty_range(a.penalty_range), B(a.beam ? a.num_beams : 0), W(B ? B : 1),
-      any_samp(a.temperature || a.top_k || a.top_p || a.seeds), per_round(a.per_round), prompts(a.prompts), tokens(a.tokens),
-      hidden(a.hidden), scores(a.scores) {
+      any_samp(a.temperature || a.top_k || a.top_p || a.seeds), per_round(a.per_round), pool_(a.beam && a.pool), prompts(a.prompts),
+      tokens(a.tokens), hidden(a.hidden), scores(a.scores) {
     const GptCfg& c = e.cfg;
     const std::string who = a.who;
     if (a.beam) {                                                // mi_gpt_generate_beam's checks on num_beams
@@ -109,20 +109,42 @@ GptQueue::GptQueue(Gpt& g, const GptQueueArgs& a)
         MI_REQUIRE(B <= c.mel_codes, who + ": num_beams exceeds the mel codes");
         MI_REQUIRE(B <= c.max_batch, who + ": num_beams exceeds the handle's max_batch");
     }
+    if (pool_) {                                                 // mi_gpt_generate_beam_pool's checks on the search's parameters
+        MI_REQUIRE(std::isfinite(a.length_penalty), who + ": length_penalty must be finite");
+        MI_REQUIRE(a.early_stopping == 0 || a.early_stopping == 1, who + ": early_stopping must be 0 or 1");
+    }
     MI_REQUIRE(n >= 1 && n <= (1 << 20), who + ": n");
     MI_REQUIRE(prompts && a.prompt_rows && a.max_new && cap >= 1, who + ": null argument");
     stops = gpt_fetch_stops(a.stop_ids, a.n_stop, mem, who);
     MI_REQUIRE(!any_samp || (a.temperature && a.top_k && a.top_p && a.seeds), who + ": the four sampling arrays come together or not at all");
+    const int K = ((int)stops.size() + 1) * B;                   // pool mode: the candidates of a selection
+    if (pool_) {
+        MI_REQUIRE(K <= GPT_POOL_MAX_CAND && K <= c.mel_codes, who + ": (n_stop + 1) * num_beams must be <= 64 and <= mel_codes");
+        MI_REQUIRE(!any_samp || c.mel_codes <= GPT_SAMPLE_MAX_CODES, who + ": sampling supports at most 16384 mel codes");
+    }
     gpt_check_lengths(c, n, a.prompt_rows, a.max_new, cap, who);
     row0.resize(n);
     size_t rows_total = 0;
     for (int i = 0; i < n; ++i) { row0[i] = rows_total; rows_total += (size_t)a.prompt_rows[i]; }
-    GptModeScope mode(e, any_samp);                              // (checks that the handle can sample)
+    GptModeScope mode(e, any_samp && !pool_);                    // (checks that the handle can sample)
     recs.resize(any_samp ? n : 0);
-    for (int i = 0; i < (int)recs.size(); ++i) recs[i] = gpt_sample_rec(a.temperature[i], a.top_k[i], a.top_p[i], a.seeds[i]);
+    for (int i = 0; i < (int)recs.size(); ++i) {
+        recs[i] = gpt_sample_rec(a.temperature[i], a.top_k[i], a.top_p[i], a.seeds[i]);
+        MI_REQUIRE(!pool_ || a.top_k[i] == 0 || a.top_k[i] >= K, who + ": top_k must be 0 or at least (n_stop + 1) * num_beams");
+    }
     e.set_rep_value(a.repeat_value);
     pol.start(n, a.prompt_rows, a.max_new, c.max_batch / W, c.max_seq);
-    if (B) e.beam_ensure();
+    if (pool_) {
+        e.pool_ensure();
+        e.pool_set_cfg(GptPoolCfg{a.length_penalty, a.early_stopping, any_samp ? 1 : 0, 0});
+        meta.assign((size_t)pol.S * W * GPT_POOL_META, 0);
+        // a sentence with max_new == 0 takes no group: its score is 0 from the start
+        for (int i = 0; i < n && scores; ++i) {
+            if (a.max_new[i] != 0) continue;
+            if (mem == MI_HOST) scores[i] = 0.f;
+            else MI_HIP(hipMemsetAsync(scores + i, 0, 4, e.stream));
+        }
+    } else if (B) e.beam_ensure();
     // every slot the decode steps will run over starts as a finished one: a slot no sentence ever takes is a no-op
     all.assign((size_t)pol.S * W * GS_WORDS, 0);
     for (int b = 0; b < pol.S * W; ++b) all[(size_t)b * GS_WORDS + GS_DONE] = 1;
@@ -141,13 +163,15 @@ void GptQueue::note(int slot, int i, int first, int count) {
     copied[i] = first + count;
 }
 
-// The table's rows leave in one launch (beams: hypothesis 0's tokens and rows along its ancestors, and its score).  MI_DEVICE: straight
-// into the caller's arrays.  MI_HOST: packed into the staging buffers, one device-to-host copy per array, then placed by the host.
+// The table's rows leave in one launch (beams: hypothesis 0's tokens and rows along its ancestors, and its score; pool mode:
+// pool entry 0's along its frozen list).  MI_DEVICE: straight into the caller's arrays.  MI_HOST: packed into the staging buffers,
+// one device-to-host copy per array, then placed by the host.
 void GptQueue::flush() {
     if (n_tab == 0) return;
     const int h = e.cfg.hidden;
     auto launch = [&](const Gpt::OutTable& t, int32_t* tok, float* hid, float* sc) {
-        if (B) e.beam_out_rows(t, n_tab, B, tok, hid, sc);
+        if (pool_) e.pool_out_rows(t, n_tab, B, tok, hid, sc);
+        else if (B) e.beam_out_rows(t, n_tab, B, tok, hid, sc);
         else e.copy_out_rows(t, n_tab, tok, hid);
     };
     if (mem == MI_DEVICE) {
@@ -193,6 +217,20 @@ void GptQueue::flush() {
 //     row below GS_NDEC, so a stale row lies at an index >= ndec;
 //   - the KV cache: the pass rewrites the prompt's rows in the first slot, a decode step writes position P + n - 1 of its own
 //     slot before its attention reads it, and no key at or beyond the history is visited.
+// pool mode: the group's pool is made empty as well (Gpt::pool_reset_group: what pool_begin sets for every slot of a call, for
+// this group's B slots), in the same stream order: scores -1e9, every meta word 0 except PM_ROW = the slot's index in the group
+// and PM_OPEN = 1, and the sentence's sampling record.  The selection loads PM_FIN / PM_LEN / PM_ROW / PM_OPEN and the scores of
+// all B entries before it writes any, so these are reset; PM_LEN and PM_TOK go to 0 with them although no stale value of either
+// could reach a result (an entry's PM_LEN is used only when its PM_FIN is set, and both are written together when a candidate
+// enters).  What is not reset, and the write that precedes every read (checked against gpt_beam_pool.hip):
+//   - pool_anc: a candidate entering the pool at selection n writes entries [0, n) of its physical row and gets PM_LEN = n + 1;
+//     retirement reads entries below PM_LEN - 1 of the row of an entry whose PM_FIN is set, i.e. one this sentence froze; the
+//     selection itself never reads pool_anc;
+//   - pool_hid, PM_TOK: written whole for the physical row in that same freeze, read by retirement alone, for that row;
+//   - a physical row is reused only for an entry that left the pool: rows of kept entries are marked used before a free one
+//     is taken, and PM_ROW starts as the identity, so two entries never share a row;
+//   - pool_keys: scratch of one selection, every word [0, R * codes) it reads is written earlier in that selection;
+//   - PM_LEN: as above; PM_FIN = 0 until this sentence's own candidate sets both.
 void GptQueue::admit(int unit, int i) {
     const int slot = unit * W;
     const std::vector<int32_t> w = gpt_state_words(stops, penalty_range, pol.max_new[i], false);
@@ -203,7 +241,18 @@ void GptQueue::admit(int unit, int i) {
     MI_HIP(hipStreamSynchronize(e.stream));                      // `ws` is done with
     if (!B && slot == 0) e.history = 0;                          // as Gpt::set_state did for the greedy queue alone; settle() writes it for both
     e.reset_penalty(slot);
-    if (any_samp) e.set_sampling_slot(&recs[i], slot);
+    if (pool_) e.pool_reset_group(unit, B, any_samp ? &recs[i] : nullptr);
+    else if (any_samp) e.set_sampling_slot(&recs[i], slot);
+}
+
+int GptQueue::pool_len(int unit) const {
+    const int32_t* mw = meta.data() + (size_t)unit * W * GPT_POOL_META;
+    return mw[PM_FIN] ? std::min(std::max(mw[PM_LEN], 0), std::min(cap, e.cfg.max_seq)) : 0;
+}
+
+void GptQueue::read_states() {
+    if (pool_) MI_HIP(hipMemcpyAsync(meta.data(), e.pool_meta.p, meta.size() * 4, hipMemcpyDeviceToHost, e.stream));
+    gpt_read_states(e, all);                                     // (synchronises the stream: both copies have landed)
 }
 
 bool GptQueue::round() {
@@ -225,12 +274,12 @@ bool GptQueue::round() {
             e.forward_packed(segs, k);
             ++passes;
         }
-        if (ran) gpt_read_states(e, all);
+        if (ran) read_states();
         // 2. retire every finished unit: its tokens and rows go out, the unit is free
         for (int u = 0; u < pol.S; ++u) {
             const int i = pol.owner[u], b = u * W;
             if (i < 0 || !word(u, GS_DONE)) continue;
-            const int nt = n_out[i] = held(u);
+            const int nt = n_out[i] = pool_ ? pool_len(u) : held(u);   // pool mode: entry 0's length, not the selections run
             if (B || per_round) {
                 note(b, i, copied[i], nt - copied[i]);
             } else {                                             // the blocking greedy entry: one copy per array per sentence, no table kernel
@@ -247,10 +296,11 @@ bool GptQueue::round() {
         if (pol.idle()) { ended_ = true; return false; }
         const int cs = pol.run_length([&](int u) { return word(u, GS_NDEC); });
         MI_REQUIRE(cs >= 1, "gpt queue: a live slot is at its limit");
-        if (B) e.decode_beam_steps(pol.S, B, cs);
+        if (pool_) e.decode_pool_steps(pol.S, B, cs);
+        else if (B) e.decode_beam_steps(pol.S, B, cs);
         else e.decode_batch_steps(pol.S, cs);
         steps += cs;
-        gpt_read_states(e, all);
+        read_states();
         return true;
     }
 }

@@ -167,6 +167,15 @@ def load() -> C.CDLL:
         L.mi_gpt_queue_begin_beam.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int, C.c_float,
                                               C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int]
         L.mi_gpt_queue_begin_beam.restype = C.c_int
+    if hasattr(L, "mi_gpt_generate_queue_beam_pool"):      # pool mode through the queue (absent from an older MI355TTS_LIB)
+        L.mi_gpt_generate_queue_beam_pool.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int,
+                                                      C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp,
+                                                      C.c_int, C.POINTER(C.c_int32), vp, C.c_int, vp]
+        L.mi_gpt_generate_queue_beam_pool.restype = C.c_int
+        L.mi_gpt_queue_begin_beam_pool.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_int,
+                                                   C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp,
+                                                   C.c_int, vp, C.c_int]
+        L.mi_gpt_queue_begin_beam_pool.restype = C.c_int
     if hasattr(L, "mi_gpt_queue_schedule"):
         L.mi_gpt_queue_schedule.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         L.mi_gpt_queue_schedule.restype = C.c_int

@@ -437,15 +437,22 @@ def linear_batch(w, x, *, bias=None, res=None, act: bool = False, out_f32: bool 
     return r
 
 
-def _check_queue_beams(beams, cfg, sampling):
+def _check_queue_beams(beams, cfg, sampling, pool=False, length_penalty=0.0, early_stopping=False):
     """The ``beams`` keyword of the queue entries: None (no beam search) or an integer in [1, 8], not above the code count or the
-    engine's max_batch (one group must fit), and never together with ``sampling``."""
+    engine's max_batch (one group must fit), and together with ``sampling`` only in pool mode.  ``pool`` needs ``beams``, and
+    ``length_penalty`` / ``early_stopping`` belong to ``pool``."""
+    if not pool and (length_penalty != 0.0 or early_stopping):
+        raise ValueError("length_penalty and early_stopping belong to pool=True")
     if beams is None:
+        if pool:
+            raise ValueError("pool=True is a beam mode: give beams")
         return None
     if isinstance(beams, bool) or int(beams) != beams or not 1 <= beams <= MAX_BEAMS:
         raise ValueError(f"beams must be an integer in [1, {MAX_BEAMS}], got {beams}")
-    if sampling is not None:
-        raise ValueError("beams and sampling do not combine: beam search is deterministic")
+    if sampling is not None and not pool:
+        raise ValueError("beams and sampling do not combine without pool=True: that beam search is deterministic")
+    if pool and isinstance(sampling, (list, tuple)) and any(x is None for x in sampling) and any(x is not None for x in sampling):
+        raise ValueError("pool mode samples every sentence of the call or none")
     if beams > cfg.mel_codes:
         raise ValueError(f"beams = {beams} exceeds the {cfg.mel_codes} mel codes")
     if beams > cfg.max_batch:
@@ -453,9 +460,10 @@ def _check_queue_beams(beams, cfg, sampling):
     return int(beams)
 
 
-def _queue_beam_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, cap, beams):
-    """mi_gpt_generate_queue_beam on host arrays -> (tokens, hidden, counts, scores, stats).  What the entry rejects before
-    launching anything (MI_EINVAL) is a ValueError; the handle stays usable."""
+def _queue_beam_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_range, cap, beams, pool=None):
+    """mi_gpt_generate_queue_beam on host arrays -> (tokens, hidden, counts, scores, stats); with pool = (length_penalty,
+    early_stopping, sampling arrays or None) mi_gpt_generate_queue_beam_pool.  What the entry rejects before launching anything
+    (MI_EINVAL) is a ValueError; the handle stays usable."""
     n = int(rows.size)
     toks = np.zeros((n, cap), np.int32)
     hid = np.zeros((n, cap, cfg.hidden), np.float32)
@@ -463,13 +471,20 @@ def _queue_beam_call(handle, cfg, cat, rows, mx, stops, repeat_value, penalty_ra
     sc = np.zeros((n,), np.float32)
     stats = np.zeros((2,), np.int32)
     L = _lib.load()
-    rc = L.mi_gpt_generate_queue_beam(handle, n, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx),
-                                      stops.ctypes.data if stops.size else None, stops.size, repeat_value, penalty_range,
-                                      int(beams), toks.ctypes.data, hid.ctypes.data, cap, _lib.i32p(cnt), sc.ctypes.data,
-                                      _lib.MI_HOST, stats.ctypes.data)
+    head = (handle, n, cat.ctypes.data, _lib.i32p(rows), _lib.i32p(mx), stops.ctypes.data if stops.size else None, stops.size,
+            repeat_value, penalty_range, int(beams))
+    tail = (toks.ctypes.data, hid.ctypes.data, cap, _lib.i32p(cnt), sc.ctypes.data, _lib.MI_HOST, stats.ctypes.data)
+    if pool is None:
+        name = "mi_gpt_generate_queue_beam"
+        rc = L.mi_gpt_generate_queue_beam(*head, *tail)
+    else:
+        name = "mi_gpt_generate_queue_beam_pool"
+        lp, es, sa = pool
+        rc = L.mi_gpt_generate_queue_beam_pool(*head, float(lp), int(bool(es)),
+                                               *((None,) * 4 if sa is None else (a.ctypes.data for a in sa)), *tail)
     if rc == _lib.MI_EINVAL:
-        raise ValueError("mi_gpt_generate_queue_beam: " + L.mi_last_error().decode("utf-8", "replace"))
-    _lib.check(rc, "mi_gpt_generate_queue_beam")
+        raise ValueError(name + ": " + L.mi_last_error().decode("utf-8", "replace"))
+    _lib.check(rc, name)
     return toks, hid, cnt, sc, stats
 
 
@@ -497,11 +512,13 @@ class QueueSession:
     """An open sentence-queue session (include/mi355tts.h, mi_gpt_queue_begin / _advance / _end; made by
     ``IndexGPT.queue_session``).  ``tokens`` (n, cap) int32 and ``hidden`` (n, cap, hidden) float32 are numpy arrays, or torch
     tensors on the engine's device with device=True; after ``advance()`` the first count[i] entries of sentence i are valid and
-    final.  With ``beams`` (mi_gpt_queue_begin_beam) a sentence's count stays 0 until it is retired and is then all of it;
-    ``scores`` (n,) float32 holds hypothesis 0's score of every retired sentence (None without beams).  A context manager:
-    leaving it ends the session (also before everything has finished)."""
+    final.  With ``beams`` (mi_gpt_queue_begin_beam; with ``pool`` = (length_penalty, early_stopping) as well,
+    mi_gpt_queue_begin_beam_pool, where the sampling arrays belong to the beam sampling) a sentence's count stays 0 until it is
+    retired and is then all of it; ``scores`` (n,) float32 holds the score of every retired sentence's result (None without
+    beams).  A context manager: leaving it ends the session (also before everything has finished)."""
 
-    def __init__(self, gpt, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays, device, beams=None):
+    def __init__(self, gpt, cat, rows, mx, stops, repeat_value, penalty_range, cap, sampling_arrays, device, beams=None,
+                 pool=None):
         self._gpt = gpt
         self._open = False
         c = gpt.cfg
@@ -537,10 +554,16 @@ class QueueSession:
             name = "mi_gpt_queue_begin"
             rc = L.mi_gpt_queue_begin(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
                                       penalty_range, ptrs[2], ptrs[3], cap, mem, *(None if a is None else a.ctypes.data for a in sa))
-        else:
+        elif pool is None:
             name = "mi_gpt_queue_begin_beam"
             rc = L.mi_gpt_queue_begin_beam(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size, repeat_value,
                                            penalty_range, int(beams), ptrs[2], ptrs[3], cap, ptrs[4], mem)
+        else:
+            name = "mi_gpt_queue_begin_beam_pool"
+            rc = L.mi_gpt_queue_begin_beam_pool(gpt._h, n, ptrs[0], _lib.i32p(rows), _lib.i32p(mx), ptrs[1], stops.size,
+                                                repeat_value, penalty_range, int(beams), float(pool[0]), int(bool(pool[1])),
+                                                *(None if a is None else a.ctypes.data for a in sa), ptrs[2], ptrs[3], cap,
+                                                ptrs[4], mem)
         if rc == _lib.MI_EINVAL:
             raise ValueError(name + ": " + L.mi_last_error().decode("utf-8", "replace"))
         _lib.check(rc, name)
@@ -615,7 +638,8 @@ def stream_plan(emitted, count, done, chunk: int, halo: int):
 
 def stream_synthesize(gpt, voc, prompts, max_new, voices, voice_of, *, chunk: int = 32, halo: Optional[int] = None, **decode_kw):
     """Audio while the queue decodes: a generator over (sentence, first_sample, int16 chunk, last).  gpt = IndexGPT, voc = a
-    graph-F BigVGANVocoder, prompts / max_new / decode_kw (stop_tokens, repeat_value, penalty_range, sampling, beams) as
+    graph-F BigVGANVocoder, prompts / max_new / decode_kw (stop_tokens, repeat_value, penalty_range, sampling, beams, pool,
+    length_penalty, early_stopping) as
     ``IndexGPT.generate_queue``, voices / voice_of as ``BigVGANVocoder.run_latent_voices`` (one voice index per sentence).
     Every round is one ``QueueSession.advance()`` followed by ONE ``run_latent_windows_torch`` call over all windows
     ``stream_plan`` reports, of any sentences and voices, reading the rows from the session's device `hidden`.  The chunks of a
@@ -906,7 +930,8 @@ class IndexGPT:
         return [(toks[b, : n[b]].copy(), hid[b, : n[b]].copy()) for b in range(nb)], pen
 
     def generate_queue(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
-                       beams=None, return_stats: bool = False):
+                       beams=None, pool: bool = False, length_penalty: float = 0.0, early_stopping: bool = False,
+                       return_stats: bool = False):
         """Any number of sentences through the engine's max_batch slots (include/mi355tts.h, "sentence queue"): a slot is
         refilled as soon as its sentence stops, and the prompts admitted together run as one packed pass over the weights.
         prompts = list of (1, P_i, hidden) graph-D outputs, max_new = list of per-sentence limits.  Every sentence starts from a
@@ -914,12 +939,16 @@ class IndexGPT:
         ``Sampling`` for every sentence, or a list of n ``Sampling`` / None.  beams = B (1..8, not with sampling): beam search
         through the queue (mi_gpt_generate_queue_beam): a sentence runs as a group of B slots, the queue schedules the
         max_batch // B groups, and each result is (tokens, hidden, score) of the best hypothesis, as ``generate_beam`` gives for
-        the sentence alone.  Returns a list of (tokens, hidden) per sentence[, {"steps": decode steps launched, "passes": prompt
+        the sentence alone.  ``pool=True`` (with beams) is pool mode through the queue (mi_gpt_generate_queue_beam_pool): the
+        groups run "beam search with a finished pool" with ``length_penalty`` / ``early_stopping``, ``sampling`` (one ``Sampling``
+        or one per sentence) then draws the candidates, and each result is what ``generate_beam(..., pool=True)`` gives for the
+        sentence alone.  Returns a list of (tokens, hidden) per sentence[, {"steps": decode steps launched, "passes": prompt
         passes}]."""
         c = self.cfg
         n = len(prompts)
         if n < 1 or len(max_new) != n:
             raise ValueError(f"{n} prompts and {len(max_new)} limits: generate_queue needs one limit per sentence, n >= 1")
+        beams = _check_queue_beams(beams, c, sampling, bool(pool), length_penalty, early_stopping)
         samp = _batch_sampling(sampling, n)
         ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
         rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
@@ -927,11 +956,12 @@ class IndexGPT:
         mx = np.ascontiguousarray([int(m) for m in max_new], dtype=np.int32)
         cap = max(int(mx.max()), 1)
         stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
-        beams = _check_queue_beams(beams, c, sampling)
         if beams is not None:
+            pm = (length_penalty, early_stopping, None if samp is None else _sampling_arrays(samp)) if pool else None
             toks, hid, cnt, sc, stats = _queue_beam_call(self._h, c, cat, rows, mx, stops,
                                                          float(c.repeat_penalty if repeat_value is None else repeat_value),
-                                                         int(c.penalty_range if penalty_range is None else penalty_range), cap, beams)
+                                                         int(c.penalty_range if penalty_range is None else penalty_range), cap, beams,
+                                                         pm)
             res = [(toks[i, : cnt[i]].copy(), hid[i, : cnt[i]].copy(), float(sc[i])) for i in range(n)]
             return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
         sa = None if samp is None else _sampling_arrays(samp)
@@ -942,16 +972,19 @@ class IndexGPT:
         return (res, {"steps": int(stats[0]), "passes": int(stats[1])}) if return_stats else res
 
     def queue_session(self, prompts, max_new, *, stop_tokens=None, repeat_value=None, penalty_range=None, sampling=None,
-                      beams=None, device: bool = False) -> QueueSession:
+                      beams=None, pool: bool = False, length_penalty: float = 0.0, early_stopping: bool = False,
+                      device: bool = False) -> QueueSession:
         """``generate_queue`` as a session that hands out rows as they appear: arguments as there; returns a ``QueueSession``
         (a context manager) whose ``advance()`` runs one round.  device=True keeps tokens / hidden as torch tensors on the
         engine's device (``BigVGANVocoder.run_latent_windows_torch`` reads the rows where they lie).  beams = B: beam search, a
-        sentence's tokens, rows and score (``QueueSession.scores``) appearing all at once when it is retired.  While the session is open
+        sentence's tokens, rows and score (``QueueSession.scores``) appearing all at once when it is retired; pool / length_penalty
+        / early_stopping (and sampling with them) as in ``generate_queue``.  While the session is open
         the other decode entries of this engine raise (MI_ESTATE)."""
         c = self.cfg
         n = len(prompts)
         if n < 1 or len(max_new) != n:
             raise ValueError(f"{n} prompts and {len(max_new)} limits: queue_session needs one limit per sentence, n >= 1")
+        beams = _check_queue_beams(beams, c, sampling, bool(pool), length_penalty, early_stopping)
         samp = _batch_sampling(sampling, n)
         ps = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, c.hidden) for p in prompts]
         rows = np.ascontiguousarray([p.shape[0] for p in ps], dtype=np.int32)
@@ -960,9 +993,9 @@ class IndexGPT:
         cap = max(int(mx.max()), 1)
         stops = np.ascontiguousarray([c.stop_mel_token] if stop_tokens is None else list(stop_tokens), dtype=np.int32)
         sa = None if samp is None else _sampling_arrays(samp)
-        beams = _check_queue_beams(beams, c, sampling)
         return QueueSession(self, cat, rows, mx, stops, float(c.repeat_penalty if repeat_value is None else repeat_value),
-                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa, device, beams)
+                            int(c.penalty_range if penalty_range is None else penalty_range), cap, sa, device, beams,
+                            (length_penalty, early_stopping) if pool else None)
 
     def generate_batch_torch(self, prompts_cat, prompt_rows, max_new, tokens, hidden, *, stop_tokens=None,
                              repeat_value=None, penalty_range=None, sampling=None, beams: int = 1):

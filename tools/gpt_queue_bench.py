@@ -2,7 +2,7 @@
 """The sentence queue of the IndexTTS GPT against lock-step batches of the same sentences, in one run.
 
     python tools/gpt_queue_bench.py [--sentences 64] [--slots 16] [--rows 100] [--lo 60] [--hi 240] [--dtype f16] [--small]
-                                    [--beams B]
+                                    [--beams B [--pool [--sampled]]]
 
 Full IndexTTS-1.5 size (24 x 1280, 8194 mel codes), synthetic weights, --sentences prompts of --rows rows each, max_new seeded-
 uniform in [--lo, --hi], no stop token, so every sentence decodes exactly its limit.  Three measurements on one handle, each the
@@ -16,6 +16,11 @@ the steps the entry reports.  One JSON line per measurement and a summary line.
 --beams B: beam search.  (a) is generate_queue(beams=B): the queue over the --slots // B groups; (b) is generate_beam over
 index-order groups of --slots // B sentences; the host models are queue_schedule(..., beams=B) and lockstep_steps over
 --slots // B; (c) compares the packed pass with one selection-0 launch against generate_beam's one-by-one prompt passes.
+
+--beams B --pool [--sampled]: pool mode ("beam search with a finished pool"; --sampled: Sampling(1.0, 30, 0.8, 1001 + i) for
+sentence i, upstream IndexTTS' decode configuration).  (a) is generate_queue(beams=B, pool=True), (b) generate_beam(pool=True)
+over the same index-order groups, with the same prompts and limits.  Without stop ids a pool search runs max_new selections and
+returns max_new codes, so the host models are the ones above.
 """
 import argparse
 import json
@@ -30,7 +35,7 @@ import numpy as np  # noqa: E402
 
 from mi355tts import weights as W  # noqa: E402
 from mi355tts.config import IndexGPTConfig  # noqa: E402
-from mi355tts.indextts import IndexGPT, lockstep_steps, queue_schedule  # noqa: E402
+from mi355tts.indextts import IndexGPT, Sampling, lockstep_steps, queue_schedule  # noqa: E402
 
 
 def timed(fn):
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--beams", type=int, default=None, help="beam search with B hypotheses per sentence (1..8): groups of B slots")
+    ap.add_argument("--pool", action="store_true", help="with --beams: pool mode (generate_queue / generate_beam with pool=True)")
+    ap.add_argument("--sampled", action="store_true", help="with --pool: beam sampling, top_k 30, top_p 0.8, seed 1001 + index")
     ap.add_argument("--small", action="store_true", help="the reduced model (a functional check of this tool, not a measurement)")
     a = ap.parse_args()
     cfg = IndexGPTConfig.small() if a.small else IndexGPTConfig()
@@ -76,24 +83,35 @@ def main():
     if B is not None:
         assert 1 <= B <= 8 and B <= a.slots, "--beams must be in 1..8 and at most --slots"
         base["beams"] = B
+    assert not a.pool or B is not None, "--pool is a beam mode: give --beams"
+    assert not a.sampled or a.pool, "--sampled belongs to --pool"
     per = a.slots if B is None else a.slots // B       # sentences decoding together
     qkw = {} if B is None else {"beams": B}
+    samp = [Sampling(1.0, 30, 0.8, 1001 + i) for i in range(a.sentences)] if a.sampled else None
+    if a.pool:
+        base["pool"] = "sampled" if a.sampled else "deterministic"
+        qkw["pool"] = True
+
+    def skw(lo, hi):                                   # the sampling keyword of sentences lo .. hi - 1
+        return {"sampling": samp[lo:hi]} if a.sampled else {}
 
     stats = {}
 
     def run_queue():
-        _, s = eng.generate_queue(prompts, limits, stop_tokens=[], return_stats=True, **qkw)
+        _, s = eng.generate_queue(prompts, limits, stop_tokens=[], return_stats=True, **qkw, **skw(0, a.sentences))
         stats.update(s)
 
-    def batch(ps, ls):
+    def batch(ps, ls, lo=0):
         if B is None:
             eng.generate_batch(ps, ls, stop_tokens=[])
+        elif a.pool:
+            eng.generate_beam(ps, ls, B, stop_tokens=[], pool=True, **skw(lo, lo + len(ps)))
         else:
             eng.generate_beam(ps, ls, B, stop_tokens=[])
 
     def run_groups():
         for g in range(0, a.sentences, per):
-            batch(prompts[g:g + per], limits[g:g + per])
+            batch(prompts[g:g + per], limits[g:g + per], g)
 
     t_q, sp_q = timed(run_queue)
     q_steps, q_passes = queue_schedule(rows, limits, limits, a.slots, cfg.max_seq, beams=B or 1)
@@ -102,11 +120,11 @@ def main():
     print(json.dumps(ra), flush=True)
     t_b, sp_b = timed(run_groups)
     b_steps = lockstep_steps(limits, per)
-    rb = dict(base, what="b: generate_batch, index-order groups" if B is None else "b: generate_beam, index-order groups", seconds=round(t_b, 4), spread=round(sp_b, 4),
+    rb = dict(base, what="b: generate_batch, index-order groups" if B is None else "b: generate_beam, index-order groups" + (" (pool)" if a.pool else ""), seconds=round(t_b, 4), spread=round(sp_b, 4),
               codes_per_s=round(sum(limits) / t_b, 1), model_steps=b_steps, prompt_passes=a.sentences)
     print(json.dumps(rb), flush=True)
     k = min(per, a.sentences)
-    t_pp, sp_pp = timed(lambda: eng.generate_queue(prompts[:k], [1] * k, stop_tokens=[], **qkw))
+    t_pp, sp_pp = timed(lambda: eng.generate_queue(prompts[:k], [1] * k, stop_tokens=[], **qkw, **skw(0, k)))
     t_p1, sp_p1 = timed(lambda: batch(prompts[:k], [1] * k))
     rc = dict(base, what="c: prompt passes only", prompts=k, packed_seconds=round(t_pp, 5), packed_spread=round(sp_pp, 4),
               packed_passes=len(queue_schedule(rows[:k], [1] * k, [1] * k, a.slots, cfg.max_seq, beams=B or 1)[1]),
